@@ -10,11 +10,17 @@ Upper_Net), so by default they run as two concurrent branches of one HIP graph (
 one after the other; `ms_per_step_sequential` is always reported as well).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W          (one rank per GPU, RCCL gradient all-reduce)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, timed
-live with events on the launch stream) and, at N=1, `cpu_baseline` (the CPU oracle on the host cores).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  --full adds everything else this program measures or checks:
+the spread over repeated blocks, the per-stage split, the IMU-shared / bf16 / split3 / pipelined variants,
+`roofline` (dominant kernel, timed live with events on the launch stream), config 2 / 5, stage-1, UpperNetwlocal
+and, at N=1, `cpu_baseline` (the CPU oracle on the host cores) with `parity`.  --dump-outputs DIR writes what the
+timed step computed in its last timed step (per stage: losses, joints, parameters after Adam, gradients) as .npy.
 """
 import argparse
 import json
@@ -82,6 +88,32 @@ def clone_imu(imu, device):
     c = nets.IMUNet(15, 9, 512, 2, True, 0.1)
     c.load_state_dict(imu.state_dict())
     return c.to(device).eval()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, stages):
+    """--dump-outputs: what a caller of the timed step holds after its last step, one float32 DIR/<stage>_<name>.npy per array --
+    the two loss figures (L1 sum, sum of joint distances), the predicted joints, the parameters after Adam, the gradient of that
+    step and the BatchNorm running statistics.  Inputs and weights are seeded, so two builds can be compared array by array."""
+    import numpy as np
+    arrays = {}
+    for st in stages:
+        flat = st.net.flat()
+        arrays[st.stage + "_loss"] = st.loss2
+        arrays[st.stage + "_joints"] = st.last_pred
+        arrays[st.stage + "_params"] = flat.flat_p
+        arrays[st.stage + "_grads"] = flat.flat_g
+        arrays[st.stage + "_buffers"] = torch.cat([b.detach().reshape(-1).double() for b in st.net.buffers()])
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, over the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def profile_kernels(steps_fn, names, iters=3):
@@ -733,6 +765,20 @@ def split3_figures(device, imu, imu_in, out, with_parity=True):
     return res
 
 
+def headline(out):
+    """The contract's fields of the result line (all a plain run prints)."""
+    r5 = lambda v: round(v, 5) if isinstance(v, float) else v
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+            "data")
+    line = {k: r5(out[k]) for k in keep}
+    cfg = out["config"]
+    line["config"] = {"workload": "U+L step (Train_Upper + Train_Lower train_once bodies), B=64/GPU T=8 N=128, fp32, dropout live, "
+                                  + ("stages one after the other" if not cfg["stages_concurrent"] else "two concurrent HIP-graph branches"),
+                      "global_batch": cfg["global_batch"], "seq_len": cfg["seq_len"], "points": cfg["points"],
+                      "parallelism": cfg["parallelism"]}
+    return line
+
+
 def emit(out):
     """Everything measured goes out as ONE comment line (`# detail: {...}`, also written to gpurun_out/bench_detail.json when that
     directory can be written), THEN the contract's JSON line -- kept under 2 KB, so that a reader who only has the tail of stdout
@@ -747,14 +793,7 @@ def emit(out):
     except OSError:
         pass
     r5 = lambda v: round(v, 5) if isinstance(v, float) else v
-    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-            "data")
-    line = {k: r5(out[k]) for k in keep}
-    cfg = out["config"]
-    line["config"] = {"workload": "U+L step (Train_Upper + Train_Lower train_once bodies), B=64/GPU T=8 N=128, fp32, dropout live, "
-                                  + ("stages one after the other" if not cfg["stages_concurrent"] else "two concurrent HIP-graph branches"),
-                      "global_batch": cfg["global_batch"], "seq_len": cfg["seq_len"], "points": cfg["points"],
-                      "parallelism": cfg["parallelism"]}
+    line = headline(out)
     rf = out["roofline"]
     line["roofline"] = {k: r5(rf[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
     line["roofline"]["kernel"] = rf["kernel"].split(" ")[0]
@@ -815,6 +854,11 @@ def main():
     ap.add_argument("--no-split3-variant", action="store_true", help="skip the split3 (fp32-accurate bf16-pipe IMU_Net) figures")
     ap.add_argument("--no-config-extras", action="store_true", help="skip the config-2 / config-5 forward figures")
     ap.add_argument("--cpu-steps", type=int, default=12, help="timed U+L steps of the CPU baseline (~0.85 s each on 16 cores: ~10 s)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every extra figure and check (spread, stage split, variants, "
+                                                        "roofline, config 2 / 5, stage-1, wlocal, CPU baseline, parity); the --no-* "
+                                                        "options and --repeats apply here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step computed in its last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -899,9 +943,11 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (su, sl))
     # spread of the headline: the same K-step block timed REPEATS more times (the contract's block above stays `ms_per_step`)
     rep_dt = [dt]
-    if not args.trace_only:
+    if args.full and not args.trace_only:
         for _ in range(args.repeats):
             sync()
             t0r = time.perf_counter()
@@ -923,6 +969,38 @@ def main():
             torch.distributed.destroy_process_group()
         return
 
+    out = None
+    if rank == 0:
+        ms = dt / args.steps * 1e3
+        out = {"metric": "train frames/sec (Upper+Lower U+L step, B=64/GPU, T=8, 128 pts)", "value": world * B * T / (dt / args.steps),
+               "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "config": {"workload": "U+L step = Train_Upper.train_once body + Train_Lower.train_once body "
+                                      "(IMU_Net fwd in both, frozen Upper fwd in the Lower body), per-GPU B=64 T=8 N=128, "
+                                      "21 joints, Adam lr 3e-5, LSTM dropout 0.1 active; the two bodies (independent programs "
+                                      "in the reference) run " + ("one after the other" if args.sequential else
+                                                                  "as concurrent branches of one HIP graph"),
+                          "global_batch": world * B, "seq_len": T, "points": N, "parallelism": "dp%d" % world,
+                          "hip_graph": not args.no_graph, "stages_concurrent": not args.sequential},
+               "value_is": ("B*T / ms_per_step of the arrangement named in config.workload (%s); SURVEY 8-d's formula "
+                            "B*T / (t_upper + t_lower) is `frames_per_s_sequential`" %
+                            ("stages one after the other" if args.sequential else "the two bodies as concurrent branches of one HIP graph")),
+               "loss_upper": loss_u, "loss_lower": loss_l}
+    if not args.full:
+        if rank == 0:
+            # (the persistent rnn_slow launches of the timed steps bound their spins: one host read per buffer)
+            from mmego_amd import blocks as _blocks
+            out["persistent_launch_errors"] = _blocks.seq_xcd_errors()
+            if out["persistent_launch_errors"]:
+                raise RuntimeError("mmego_lstm_seq_xcd: %d launch(es) ran out of their bounded spin -- results invalid" % out["persistent_launch_errors"])
+            print(json.dumps(headline(out)))
+            sys.stdout.flush()
+        if dist_on:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
+
+    # ---- --full: every figure and check beyond the headline ------------------------------------------------------------------
     # per-stage split, stages one after the other (device time, events on the launch stream).  The steps run BACK TO BACK -- events
     # recorded around every stage, one host synchronisation behind the last -- and the medians are reported: with a host
     # synchronisation behind every step (r03: median of 5 isolated steps) the same code measured 5.67 and 5.84 ms in two runs on one
@@ -1092,28 +1170,13 @@ def main():
             finally:
                 imu.precision = imu_l.precision = "fp32"
 
-    out = None
     if rank == 0:
-        ms = dt / args.steps * 1e3
-        out = {"metric": "train frames/sec (Upper+Lower U+L step, B=64/GPU, T=8, 128 pts)", "value": world * B * T / (dt / args.steps),
-               "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-               "ms_per_step_min": rep_ms[0], "ms_per_step_median": rep_ms[len(rep_ms) // 2], "ms_per_step_max": rep_ms[-1],
-               "timed_blocks": len(rep_ms),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "config": {"workload": "U+L step = Train_Upper.train_once body + Train_Lower.train_once body "
-                                      "(IMU_Net fwd in both, frozen Upper fwd in the Lower body), per-GPU B=64 T=8 N=128, "
-                                      "21 joints, Adam lr 3e-5, LSTM dropout 0.1 active; the two bodies (independent programs "
-                                      "in the reference) run " + ("one after the other" if args.sequential else
-                                                                  "as concurrent branches of one HIP graph"),
-                          "global_batch": world * B, "seq_len": T, "points": N, "parallelism": "dp%d" % world,
-                          "hip_graph": not args.no_graph, "stages_concurrent": not args.sequential},
-               "value_is": ("B*T / ms_per_step of the arrangement named in config.workload (%s); SURVEY 8-d's formula "
-                            "B*T / (t_upper + t_lower) is `frames_per_s_sequential`" %
-                            ("stages one after the other" if args.sequential else "the two bodies as concurrent branches of one HIP graph")),
-               "ms_per_step_imu_shared": dt_shared / args.steps * 1e3,
-               "frames_per_s_imu_shared": world * B * T / (dt_shared / args.steps),
-               "ms_per_step_sequential": t_u + t_l, "frames_per_s_sequential": world * B * T / ((t_u + t_l) * 1e-3),
-               "t_upper_ms": t_u, "t_lower_ms": t_l, "loss_upper": loss_u, "loss_lower": loss_l}
+        out.update({"ms_per_step_min": rep_ms[0], "ms_per_step_median": rep_ms[len(rep_ms) // 2], "ms_per_step_max": rep_ms[-1],
+                    "timed_blocks": len(rep_ms),
+                    "ms_per_step_imu_shared": dt_shared / args.steps * 1e3,
+                    "frames_per_s_imu_shared": world * B * T / (dt_shared / args.steps),
+                    "ms_per_step_sequential": t_u + t_l, "frames_per_s_sequential": world * B * T / ((t_u + t_l) * 1e-3),
+                    "t_upper_ms": t_u, "t_lower_ms": t_l})
         out.update(bf16_extra)
         out.update(split3_extra)
         out.update(pipe_extra)
