@@ -12,6 +12,7 @@
 //                            (consumers: pooling, heads) and as bf16 (next step's / next layer's product operand).
 //                            The recurrent operands live in a fragment-major layout (see below).
 #include "common.h"
+#include "tile_order.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef unsigned short bf16_t;   // raw bf16 bits (the C ABI carries them as unsigned short)
@@ -79,9 +80,6 @@ extern "C" int mmego_cvt_bf16_tm(void* stream, const float* X, long ldx, int Bn,
 #define BK 64
 #define BLD 72
 
-// XCD-aware tile order: blocks b and b+8 share an XCD; hand each XCD a contiguous run of tile ids.
-__device__ __forceinline__ int bf_xcd_order(int id, int n) { return (n & 7) == 0 ? (id & 7) * (n >> 3) + (id >> 3) : id; }
-
 __device__ __forceinline__ bf16x8 lds_frag(const bf16_t* tile, int row, int k) {
   return *reinterpret_cast<const bf16x8*>(tile + row * BLD + k);
 }
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBfP p) {
   const int wm = w >> 1, wn = w & 1;
   // tile order: runs of 16 row-panels sweep the N tiles, so a W tile is shared by 16 consecutive blocks and the 16 A
   // panels stay in L2 for the whole sweep.
-  const int id = bf_xcd_order(blockIdx.x, (int)gridDim.x);
+  const int id = xcd_order(blockIdx.x, (int)gridDim.x);
   const int GM = 16;
   const int per_group = GM * p.tiles_n;
   const int group = id / per_group, in_group = id - group * per_group;
@@ -311,7 +309,7 @@ __global__ __launch_bounds__(256) void lstm_step_bf16_kernel(StepBfP p) {
   const int d = blockIdx.z, H = p.H, S = H >> 4;
   // blocks sharing a W_hh slice (same j0, different rows) are consecutive ids on one XCD
   const int nrb = gridDim.y, nb = gridDim.x * nrb;
-  const int id = bf_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
+  const int id = xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
   const int jb = id / nrb, j0 = jb * 32, r0 = (id % nrb) * ROWS;
   const int fr = lane & 31, fh = lane >> 5;
 
@@ -425,7 +423,7 @@ __global__ __launch_bounds__(256) void lstm_step_bf16_direct_kernel(StepBfP p) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int d = blockIdx.z, H = p.H, S = H >> 4, SQ = S >> 2;
   const int nrb = gridDim.y, nb = gridDim.x * nrb;
-  const int id = bf_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
+  const int id = xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
   const int jb = id / nrb, j0 = jb * 32, r0 = (id % nrb) * 64;
   const int fr = lane & 31, fh = lane >> 5;
   const int j = j0 + fr;
@@ -810,7 +808,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4 / WR, 4 /
   const int tid = threadIdx.x, lane = tid & 63, wr = tid >> 6;
   const int d = blockIdx.z, H = p.o.H;
   const int nrb = gridDim.y, nb = gridDim.x * nrb;
-  const int id = bf_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
+  const int id = xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
   // L2 blocking: consecutive workgroups on an XCD walk 4 x 4 super-tiles of (row block, hidden block), hidden-block groups
   // fastest, so 16 workgroups share 4 activation tiles and 4 weight tiles (8 x 0.4 MB at K = 1536, inside the 4-MB L2) and an
   // activation tile group stays resident across a whole sweep of W.  With (hidden block slow, row block fast) every row tile
@@ -949,9 +947,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // tile walk: where the grid is 8 x 32 workgroups and the tiles divide evenly, XCD x (workgroups x, x + 8, ...) takes a
   // contiguous run of tiles and its 32 workgroups work on 4 row blocks x all unit blocks at a time (they walk the same K chunks
   // at the same pace: an activation chunk is fetched into that L2 once for its 8 readers, a weight chunk once for 4)
-  const bool xcd_walk = G == 256 && ntiles % 256 == 0;
   const int niter = (ntiles + G - 1) / G;
-  auto tile_of = [&](int it) { return xcd_walk ? (int)(blockIdx.x & 7) * (ntiles >> 3) + it * 32 + (int)(blockIdx.x >> 3) : (int)blockIdx.x + it * G; };
+  auto tile_of = [&](int it) { return persistent_tile(blockIdx.x, it, G, ntiles); };
 
   // this wave's 8 pieces of a chunk: waves 0..3 carry the activation pieces, waves 4..7 the weight pieces
   const int q0 = w * 8;

@@ -16,6 +16,7 @@
 #include "../../include/mmego_hip.h"       // MmegoGemmDesc (mmego_gemm_group)
 
 #include "gemm_tile.h"
+#include "tile_order.h"
 
 struct GemmP {
   const float* A;
@@ -443,9 +444,8 @@ __global__ __launch_bounds__(256) void gemm128_nt_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
   // XCD-aware tile order: consecutive tiles along N (sharing the A row panel) stay on one XCD's L2
-  const int ntn = N / 128, ntm = M / 128, nwg = ntn * ntm;
-  int id = blockIdx.x;
-  if ((nwg & 7) == 0) id = (id & 7) * (nwg >> 3) + (id >> 3);
+  const int ntn = N / 128, ntm = M / 128;
+  const int id = xcd_order(blockIdx.x, ntn * ntm);
   const int m0 = (id / ntn) * 128, n0 = (id % ntn) * 128;
 
   const int lr = tid >> 2, lk = (tid & 3) * 4;

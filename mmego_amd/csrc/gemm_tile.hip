@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "gemm_tile.h"
+#include "tile_order.h"
 
 #define TLD_MAX 68
 // NOTE: staging registers are ext_vector f32x4 (not HIP's float4 struct): arrays of the struct type are left in
@@ -164,9 +165,6 @@ __device__ __forceinline__ void gemm_tile_body(const TileP& p, int m0, int n0, i
   MMEGO_STAMP_AT(sid, 3, tid == 0);
 }
 
-// XCD-aware tile order: blocks b and b+8 share an XCD; hand each XCD a contiguous run of tile ids
-__device__ __forceinline__ int xcd_order(int id, int n) { return (n & 7) == 0 ? (id & 7) * (n >> 3) + (id >> 3) : id; }
-
 // work unit u = (batch * nsplit + split) * tiles + tile
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KC, bool B_KC, int KCH>
 __global__ __launch_bounds__(256) void gemm_tile_kernel(TileP p) {
@@ -238,26 +236,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_big_kernel(TileP p, TileBigA
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 2, wn = w & 3;
-  int tm, tn, batch;
-  {
-    const int per_batch = g.tiles_m * g.tiles_n, n = (int)gridDim.x;
-    if ((n & 63) == 0 && (g.tiles_m & 3) == 0 && (g.tiles_n & 7) == 0) {
-      // XCD x (blocks x, x + 8, ...) walks blocks of 4 row panels x 8 column tiles: its A panels stay in its L2 for a round
-      const int x = blockIdx.x & 7, l = blockIdx.x >> 3, rounds = (n >> 3) >> 5;
-      const int blk = x * rounds + (l >> 5), within = l & 31;
-      const int nb_n = g.tiles_n >> 3, nb = (g.tiles_m >> 2) * nb_n;
-      batch = blk / nb;
-      const int rem = blk - batch * nb;
-      tm = (rem / nb_n) * 4 + (within & 3);
-      tn = (rem % nb_n) * 8 + (within >> 2);
-    } else {
-      batch = blockIdx.x / per_batch;
-      const int id = blockIdx.x - batch * per_batch;
-      tm = id / g.tiles_n;
-      tn = id - tm * g.tiles_n;
-    }
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
+  const TileMN t = panel_walk_or_row_major(blockIdx.x, gridDim.x, g.tiles_m, g.tiles_n);
+  const int batch = t.m / g.tiles_m;
+  const int m0 = (t.m - batch * g.tiles_m) * BM, n0 = t.n * BN;
   const int kbeg = p.nsplit > 1 ? (int)blockIdx.y * p.kchunk : 0;
   const int kend = p.nsplit > 1 ? min(p.K, kbeg + p.kchunk) : p.K;
   const float* Ab = p.A + (long)batch * p.sAb + (long)m0 * p.lda + kbeg;

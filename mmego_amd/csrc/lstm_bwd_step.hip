@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "tile_order.h"
 
 struct LstmBwdStepP {
   const float* dg[2]; long dgs;          // dgates of the step before in backward order: rows Bn, K = 4H contiguous
@@ -38,18 +39,9 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_dma_kernel(LstmBwdStepP p) 
   const bool loader = wave >= 4;
   const int H = p.H, K = 4 * H;
   const int nrb = p.Bn / 64, nht = H / HT, npairs = 2 * nht;
-  int pair, rb;
-  {
-    const int wg = blockIdx.x;
-    if ((npairs & 7) == 0) {                   // workgroups sharing a W_hh slice on one XCD (a contiguous run of hidden blocks)
-      const int xcd = wg & 7, q = wg >> 3;
-      pair = xcd * (npairs >> 3) + (q / nrb);
-      rb = q % nrb;
-    } else {
-      pair = wg / nrb;
-      rb = wg % nrb;
-    }
-  }
+  // workgroups sharing a W_hh slice on one XCD (a contiguous run of hidden blocks), where the pairs split evenly over the XCDs
+  const int id = (npairs & 7) == 0 ? xcd_order(blockIdx.x, npairs * nrb) : (int)blockIdx.x;
+  const int pair = id / nrb, rb = id - pair * nrb;
   const int d = pair / nht, ht = pair % nht;
   const int j0 = ht * HT, r0 = rb * 64;
   const int nk = K / KC;

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "tile_order.h"
 
 struct LstmStepP {
   const float* hprev[2]; long hps;
@@ -73,21 +74,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const bool loader = wave >= 4;
   const int H = p.H;
   const int nrb = (p.Bn + 63) / 64, nht = H / HT, npairs = p.ndir * nht;
-  int pair, rb;
-  {
-    const int wg = blockIdx.x;
-    if ((npairs & 7) == 0) {                   // workgroups sharing a W_hh slice on one XCD: each L2 holds 1/8 of W_hh
-      const int xcd = wg & 7, q = wg >> 3;
-      // an XCD takes a CONTIGUOUS run of hidden blocks: at HT = 16 a (row, gate) segment of xproj / c / h is 64 bytes, half a
-      // cache line, and the neighbouring hidden block's workgroup reads the other half -- on the same XCD the pair shares one
-      // L2 fill (the r02 order was strided: hidden blocks xcd, xcd + 8, ...)
-      pair = xcd * (npairs >> 3) + (q / nrb);
-      rb = q % nrb;
-    } else {
-      pair = wg / nrb;
-      rb = wg % nrb;
-    }
-  }
+  // workgroups sharing a W_hh slice on one XCD (each L2 holds 1/8 of W_hh), where the pairs split evenly over the XCDs.  An XCD
+  // takes a CONTIGUOUS run of hidden blocks: at HT = 16 a (row, gate) segment of xproj / c / h is 64 bytes, half a cache line, and
+  // the neighbouring hidden block's workgroup reads the other half -- on the same XCD the pair shares one L2 fill (the r02 order
+  // was strided: hidden blocks xcd, xcd + 8, ...)
+  const int id = (npairs & 7) == 0 ? xcd_order(blockIdx.x, npairs * nrb) : (int)blockIdx.x;
+  const int pair = id / nrb, rb = id - pair * nrb;
   const int d = pair / nht, ht = pair % nht;
   const int j0 = ht * HT, r0 = rb * 64;
   const bool first = p.first != 0;

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "tile_order.h"
 
 // Compile-time experiment mask (scripts/s3_experiments.py builds variant libraries with -DS3_EXP=<mask> to take a kernel's time apart
 // by elimination; 0 -- nothing of it exists -- in the product build).  1: piece products replaced by an XOR of the fragments,
@@ -307,9 +308,6 @@ __device__ __forceinline__ f32x16 s3_mma(const s3_u32x4 (&a)[3], const s3_u32x4 
   return acc;
 }
 
-// XCD-aware tile order: blocks b and b + 8 share an XCD; hand each XCD a contiguous run of tile ids.
-__device__ __forceinline__ int s3_xcd_order(int id, int n) { return (n & 7) == 0 ? (id & 7) * (n >> 3) + (id >> 3) : id; }
-
 // ---- C = A . W^T + bias -----------------------------------------------------------------------------------------------------------
 struct S3GemmP {
   const s3_u32x4* A;       // sfrag [Mrb][SK][3][64]
@@ -342,7 +340,7 @@ __global__ __launch_bounds__(WM * 128, 2) void s3_gemm_kernel(S3GemmP p) {
   const int wm = w >> 1, wn = w & 1;
   // tile order: runs of p.gm row panels sweep the N tiles, so that the workgroups resident on an XCD at one time share few A and few W
   // panels (64 resident 256 x 128 tiles as 4 row panels x 16 column tiles)
-  const int id = s3_xcd_order(blockIdx.x, (int)gridDim.x);
+  const int id = xcd_order(blockIdx.x, (int)gridDim.x);
   const int GM = p.gm;
   const int per_group = GM * p.tiles_n;
   const int group = id / per_group, in_group = id - group * per_group;
@@ -472,22 +470,8 @@ __global__ __launch_bounds__(512, 1) void s3_gemm_big_kernel(S3GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform by construction: addresses below stay scalar)
   const int wm = w >> 2, wn = w & 3;
-  int tm, tn;
-  {
-    const int n = (int)gridDim.x;
-    if ((n & 63) == 0 && (p.tiles_m & 3) == 0 && (p.tiles_n & 7) == 0) {
-      const int x = blockIdx.x & 7, l = blockIdx.x >> 3;          // XCD (round-robin dispatch), index inside the XCD's run
-      const int per_x = n >> 3, rounds = per_x >> 5;             // 32 tiles = 4 x 8 per round
-      const int blk = x * rounds + (l >> 5), within = l & 31;     // block of 4 row panels x 8 column tiles
-      const int bn_count = p.tiles_n >> 3;
-      tm = (blk / bn_count) * 4 + (within & 3);
-      tn = (blk % bn_count) * 8 + (within >> 2);
-    } else {
-      tm = blockIdx.x % p.tiles_m;
-      tn = blockIdx.x / p.tiles_m;
-    }
-  }
-  const int rbA0 = tm * TRB, rbW0 = tn * TCB;
+  const TileMN t = panel_walk_or_col_major(blockIdx.x, gridDim.x, p.tiles_m, p.tiles_n);
+  const int rbA0 = t.m * TRB, rbW0 = t.n * TCB;
   const int SKall = p.SK;
   const int s_first = (int)blockIdx.y * 2 * p.cps;               // this slab's 16-k steps: [s_first, s_first + SK)
   const int SK = min(SKall - s_first, 2 * p.cps);
@@ -759,7 +743,7 @@ __global__ __launch_bounds__(256, 1) void s3_step_kernel(S3StepP p) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int d = blockIdx.z, H = p.H, S = p.S;
   const int nrb = gridDim.y, nb = gridDim.x * nrb;
-  const int id = s3_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
+  const int id = xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
   const int jb = id / nrb, j0 = jb * 32, r0 = (id % nrb) * 64;
   const int fr = lane & 31, fh = lane >> 5;
   const int j = j0 + fr;
@@ -952,7 +936,7 @@ __global__ __launch_bounds__(256, 2) void s3_step16_kernel(S3StepP p) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int d = blockIdx.z, H = p.H, S = H >> 4;
   const int nrb = gridDim.y, nb = gridDim.x * nrb;
-  const int id = s3_xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
+  const int id = xcd_order(blockIdx.y * gridDim.x + blockIdx.x, nb);
   const int jb = id / nrb, j0 = jb * 16, r0 = (id % nrb) * 64;
   const int fr = lane & 31, fh = lane >> 5;
   const int ju = fr & 15, gsel = fr >> 4;              // unit inside the block; which gate of a pair this lane's column is

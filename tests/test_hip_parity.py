@@ -791,11 +791,12 @@ def test_topk_rows_is_the_stable_descending_sort(dev, F, N, keep):
     assert bool(torch.isnan(out2[:, 3:]).all())
 
 
-@pytest.mark.parametrize("rows,In,K", [(10240, 512, 4096), (10240, 1024, 4096), (5120, 1024, 2048), (640, 512, 4096)])
+@pytest.mark.parametrize("rows,In,K", [(10240, 512, 4096), (10240, 1024, 4096), (5120, 1024, 2048), (5120, 2048, 8192), (640, 512, 4096)])
 def test_input_gradient_product_in_k_slabs_on_320x256_tiles(dev, rows, In, K):
     """ops.grad_input_slabs (r06; stage-1 IMU_Net training's dX = dgates . W_ih in fp32): W^T + gemm_tile_big_kernel with K cut into
     256 / tiles slabs (grid.y; the deferred split-K format) + the streaming slab sum, against float64 -- no worse than the plain product
-    of ops.grad_input; the last shape (4 tiles: 64 slabs of 64 k would be too short) must decline and leave dX alone."""
+    of ops.grad_input; 5120 x 2048 is 16 x 8 tiles on 128 workgroups per slab, a grid the XCD panel walk does not fit (row-major
+    order); the last shape (4 tiles: 64 slabs of 64 k would be too short) must decline and leave dX alone."""
     from mmego_amd import ops
     g = torch.Generator().manual_seed(rows + In)
     dY = (torch.randn(rows, K, generator=g) * 0.1).to(dev)

@@ -233,11 +233,12 @@ def test_split3_bilstm_stack_against_the_fp32_step_kernels(dev, monkeypatch, Bn,
 
 def test_split3_projection_on_320x256_tiles_is_the_256x128_kernel_bit_for_bit(dev):
     """s3_gemm_big_kernel (split3.hip, r06: 320 x 256 tiles, LDS-DMA operands; mmego_split3_gemm's choice for rnn_fast's projections)
-    against s3_gemm_kernel<4, 2> (wm = 4) on the same pieces: tile-major and row-major outputs bit for bit, both K; a shape the
-    big tiles do not divide takes the old kernel either way."""
+    against s3_gemm_kernel<4, 2> (wm = 4) on the same pieces: tile-major and row-major outputs bit for bit, both K; 6400 rows are 20 x 16
+    tiles on 320 workgroups, a grid the XCD panel walk does not fit (column-major order); a shape the big tiles do not divide takes the
+    old kernel either way."""
     from mmego_amd import blocks, hip
     g = torch.Generator().manual_seed(12)
-    for M, N, K in ((10240, 4096, 512), (10240, 4096, 1024), (640, 512, 256)):
+    for M, N, K in ((10240, 4096, 512), (10240, 4096, 1024), (6400, 4096, 512), (640, 512, 256)):
         A = torch.randn(M, K, generator=g).to(dev)
         W = (torch.randn(N, K, generator=g) * 0.05).to(dev)
         bias = torch.randn(N, generator=g).to(dev)
