@@ -530,13 +530,9 @@ extern "C" int mmego_lstm_step_bf16(void* stream, int ndir, int Bn, int H, int f
   hipStream_t st = (hipStream_t)stream;
   if (Bn <= 2048 && H % 256 == 0) {
     const int lds = 4 * 2 * 4 * 16 * 64 * (int)sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)lstm_step_bf16_direct_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lstm_step_bf16_direct_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
+    int e = mmego_allow_lds<lstm_step_bf16_direct_kernel<8>>(lds);
+    if (!e) e = mmego_allow_lds<lstm_step_bf16_direct_kernel<4>>(lds);
+    if (e) return e;
     dim3 grid(H / 32, cdiv(Bn, 64), ndir);
     if (H % 512 == 0) lstm_step_bf16_direct_kernel<8><<<grid, 256, lds, st>>>(p);
     else lstm_step_bf16_direct_kernel<4><<<grid, 256, lds, st>>>(p);
@@ -713,12 +709,6 @@ extern "C" int mmego_fc_relu_bf16_frag_tm(void* stream, const float* X, long ldx
   MMEGO_REQUIRE(X && W && Y && Bn > 0 && T > 0 && Cin > 0 && Cin <= 16 && H > 0 && H % 16 == 0 && H <= 2048 && Bp >= Bn && Bp % 32 == 0);
   MMEGO_REQUIRE(T <= 65535 && (((uintptr_t)Y) & 15) == 0);
   const size_t lds = (size_t)(H * 16 + H) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)fc_relu_bf16_frag_tm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * 17 * 4);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   if (H % 128 == 0 && H <= 512) {
     const dim3 g(Bp / 32);
     hipStream_t st = (hipStream_t)stream;
@@ -731,6 +721,7 @@ extern "C" int mmego_fc_relu_bf16_frag_tm(void* stream, const float* X, long ldx
     MMEGO_LAUNCH_CHECK();
     return MMEGO_OK;
   }
+  if (int e = mmego_allow_lds<fc_relu_bf16_frag_tm_kernel>(lds)) return e;
   dim3 grid(Bp / 32, T);
   fc_relu_bf16_frag_tm_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(X, ldx, W, bias, Bn, T, Cin, H, Y, Bp, relu);
   MMEGO_LAUNCH_CHECK();
@@ -1153,13 +1144,9 @@ extern "C" int mmego_lstm_step_bf16_fused(void* stream, int ndir, int Bn, int H,
   //  128-row kernel there)
   if (ndir == 2 && Bn % 256 == 0 && H % 64 == 0 && k64) {
     constexpr int lds = 2 * 64 * 1024 + 8 * 4096;      // two ring stages + 4 KB per wave for the h_t fragments
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)lstm_step_bf16_fused256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lstm_step_bf16_fused256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
+    int e = mmego_allow_lds<lstm_step_bf16_fused256_kernel<true>>(lds);
+    if (!e) e = mmego_allow_lds<lstm_step_bf16_fused256_kernel<false>>(lds);
+    if (e) return e;
     MMEGO_REQUIRE((hout0 == nullptr) == (hout1 == nullptr));
     const int ntiles = 2 * (H / 64) * (Bn / 256);
     constexpr int maxwg = 256;

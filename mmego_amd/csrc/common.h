@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch_setup.h"
 
 #define MMEGO_OK 0
 #define MMEGO_EBADARG (-1)

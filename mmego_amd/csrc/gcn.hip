@@ -528,15 +528,10 @@ static int tconv_launch(hipStream_t st, TconvP& p, bool rec) {
   const bool act = rec || p.in_state;
   if ((long)grid.x * grid.y <= 512) {                      // small grid: four steps in flight per workgroup
     const size_t lds = (size_t)4 * 2 * 64 * GC_S * sizeof(float) + extra;
-    static bool attr = false;
-    if (!attr) {
-      const int mx = (int)((size_t)4 * 2 * 64 * GC_S * sizeof(float) + 4 * 256 * sizeof(float));
-      hipError_t e = hipFuncSetAttribute((const void*)tconv_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tconv_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tconv_kernel<4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-      if (e != hipSuccess) return (int)e;
-      attr = true;
-    }
+    int e = mmego_allow_lds<tconv_kernel<4, false>>(lds);
+    if (!e) e = mmego_allow_lds<tconv_kernel<4, true>>(lds);
+    if (!e) e = mmego_allow_lds<tconv_kernel<4, true, true>>(lds);
+    if (e) return e;
     if (rec) hipLaunchKernelGGL((tconv_kernel<4, true, true>), grid, dim3(1024), lds, st, p);
     else if (act) hipLaunchKernelGGL((tconv_kernel<4, true>), grid, dim3(1024), lds, st, p);
     else hipLaunchKernelGGL((tconv_kernel<4, false>), grid, dim3(1024), lds, st, p);
@@ -794,12 +789,7 @@ static int tconv_seq_launch(hipStream_t st, TconvSeqP& p, bool rec) {
   if (nk >= 4 && (long)grid.x * grid.y <= 256 && lds < 84 * 1024) lds = 84 * 1024;
 #define TS_LAUNCH(NK_, REC_)                                                                                          \
   do {                                                                                                                \
-    static size_t attr = 0;                                                                                           \
-    if (lds > 64 * 1024 && lds > attr) {                                                                              \
-      hipError_t e = hipFuncSetAttribute((const void*)tconv_seq_kernel<NK_, REC_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return (int)e;                                                                             \
-      attr = lds;                                                                                                     \
-    }                                                                                                                 \
+    if (int e = mmego_allow_lds<tconv_seq_kernel<NK_, REC_>>(lds)) return e;                                          \
     hipLaunchKernelGGL((tconv_seq_kernel<NK_, REC_>), grid, dim3(256), lds, st, p);                                   \
   } while (0)
   if (rec) {
@@ -936,13 +926,9 @@ extern "C" int mmego_tconv_wgrad(void* stream, const float* dY, long lddy, const
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)ns, (unsigned)(taps * ((Cin + 63) / 64) * ((Cout + 63) / 64)));
   const size_t lds = (size_t)2 * TW_K * TW_S * sizeof(float) + 2 * TW_K * sizeof(int);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)tconv_wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tconv_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  int e = mmego_allow_lds<tconv_wgrad_kernel<false>>(lds);
+  if (!e) e = mmego_allow_lds<tconv_wgrad_kernel<true>>(lds);
+  if (e) return e;
   if (Cin <= 32 && Cout <= 32) hipLaunchKernelGGL(tconv_wgrad_kernel<true>, grid, dim3(256), lds, st, p);
   else hipLaunchKernelGGL(tconv_wgrad_kernel<false>, grid, dim3(256), lds, st, p);
   MMEGO_LAUNCH_CHECK();

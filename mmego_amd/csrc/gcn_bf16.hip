@@ -201,12 +201,7 @@ static int tconv_bf16_launch(hipStream_t st, const TconvBfP& p) {
   const long XR = (long)((TV + 255) / 256) * 256 + 2 * halo;
   const long lds = 2L * COUT * KC * 2 + XR * (CIN + 8) * 2;
   if (lds > 160 * 1024) return -2;
-  static long attr = 0;
-  if (lds > attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)tconv_eval_bf16_kernel<CIN, COUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = lds;
-  }
+  if (int e = mmego_allow_lds<tconv_eval_bf16_kernel<CIN, COUT>>(lds)) return e;
   hipLaunchKernelGGL((tconv_eval_bf16_kernel<CIN, COUT>), dim3(p.B), dim3(512), lds, st, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
@@ -526,12 +521,7 @@ static int gcn_mix_bf16_launch(hipStream_t st, const GcnMixBfP& p) {
   constexpr int XS = KD + 8, YS = COUT + 8;
   constexpr long lds = K * 256 * 4 + (long)COUT * (KSY + KSR) * 16 * 2 + 128L * (XS > YS ? XS : YS) * 2;
   static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)gcn_mix_eval_bf16_kernel<CIN, COUT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  if (int e = mmego_allow_lds<gcn_mix_eval_bf16_kernel<CIN, COUT, K>>(lds)) return e;
   const long ntile = (p.F + GM_FPB - 1) / GM_FPB;
   const int per_cu = (int)(160 * 1024 / lds) < 4 ? (int)(160 * 1024 / lds) : 4;
   const long cap = 256L * (per_cu < 1 ? 1 : per_cu);

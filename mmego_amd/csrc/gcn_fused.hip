@@ -890,12 +890,7 @@ extern "C" int mmego_gcn_front(void* stream, const void* desc) {
   dim3 grid((unsigned)cdiv(p.F, GF_FPB));
 #define GF_LAUNCH(NCTW_, NK_)                                                                                         \
   do {                                                                                                                \
-    static size_t attr = 0;                                                                                           \
-    if (lds > 64 * 1024 && lds > attr) {                                                                              \
-      hipError_t e = hipFuncSetAttribute((const void*)gcn_front_kernel<NCTW_, NK_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return (int)e;                                                                             \
-      attr = lds;                                                                                                     \
-    }                                                                                                                 \
+    if (int e = mmego_allow_lds<gcn_front_kernel<NCTW_, NK_>>(lds)) return e;                                         \
     hipLaunchKernelGGL((gcn_front_kernel<NCTW_, NK_>), grid, dim3(GF_NT), lds, st, p);                                \
   } while (0)
   if (nk == 0 && nctw == 1) GF_LAUNCH(1, 0);

@@ -393,14 +393,8 @@ constexpr int GT_KCH = 32;
 
 template <int BM, int BN, bool A_KC, bool B_KC, int KCH>
 static int launch_plain_k(hipStream_t st, const TileP& p) {
-  static bool attr_set = false;
   const size_t lds = (size_t)((BM + BN) * (KCH + 4)) * sizeof(float);
-  if (!attr_set && lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tile_kernel<BM, BN, 2, 2, A_KC, B_KC, KCH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = mmego_allow_lds<gemm_tile_kernel<BM, BN, 2, 2, A_KC, B_KC, KCH>>(lds)) return e;
   const unsigned units = (unsigned)((p.M / BM) * (p.N / BN) * p.nsplit * p.nbatch);
   hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, 2, 2, A_KC, B_KC, KCH>), dim3(units), dim3(256), lds, st, p);
   hipError_t e = hipGetLastError();
@@ -429,15 +423,8 @@ static int launch_layout(hipStream_t st, const TileP& p) {
     if (big && (p.M % 320) == 0 && (p.N % 256) == 0 && (p.K % 32) == 0 && p.K >= 64 && slab_ok && !p.relu &&
         units >= 256 && (units % 256) == 0 && tiles < (1L << 30) && (p.lda % 4) == 0 && (p.ldw % 4) == 0 && (p.sAb % 4) == 0 && (p.sWb % 4) == 0 &&
         ((((uintptr_t)p.A) | ((uintptr_t)p.W)) & 15) == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
       constexpr int lds = 2 * (320 + 256) * 32 * (int)sizeof(float);        // 144 KB
-      static bool attr_set[64] = {};
-      if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tile_big_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-      }
+      if (int e = mmego_allow_lds<gemm_tile_big_kernel<0>>(lds)) return e;
       TileBigArgs g = {p.M / 320, p.N / 256};
       hipLaunchKernelGGL((gemm_tile_big_kernel<0>), dim3((unsigned)tiles, (unsigned)p.nsplit), dim3(512), lds, st, p, g);
       hipError_t e = hipGetLastError();
@@ -459,17 +446,8 @@ static int launch_layout(hipStream_t st, const TileP& p) {
       const int rest = units % slots;
       const bool halves = rest > 0 && rest <= slots / 2;
       const int nfull = halves ? units - rest : units, nhalf = halves ? 2 * rest : 0;
-      size_t lds = (size_t)(256 * (GT_KCH + 4)) * sizeof(float);
-      if (slots <= 256) {
-        static bool attr32 = false;
-        lds = 84 * 1024;
-        if (!attr32) {
-          hipError_t e = hipFuncSetAttribute((const void*)gemm_tile_persistent_kernel<A_KC, B_KC, GT_KCH>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (e != hipSuccess) return (int)e;
-          attr32 = true;
-        }
-      }
+      const size_t lds = slots <= 256 ? 84 * 1024 : (size_t)(256 * (GT_KCH + 4)) * sizeof(float);
+      if (int e = mmego_allow_lds<gemm_tile_persistent_kernel<A_KC, B_KC, GT_KCH>>(lds)) return e;
       // (second half of the grid starts with its half tiles: the walk's tail is staggered)
       hipLaunchKernelGGL((gemm_tile_persistent_kernel<A_KC, B_KC, GT_KCH>), dim3(slots), dim3(256), lds, st, p, nfull, nhalf, 1);
       hipError_t e = hipGetLastError();

@@ -860,12 +860,7 @@ extern "C" int mmego_local_group_l1(void* stream, const float* feats, long ldf, 
   const dim3 grid((unsigned)(nwg < F ? nwg : F));
 #define LG_LAUNCH(NK_)                                                                                                  \
   do {                                                                                                                  \
-    static size_t attr = 0;                                                                                             \
-    if (lds > 64 * 1024 && lds > attr) {                                                                                \
-      hipError_t e = hipFuncSetAttribute((const void*)local_group_l1_kernel<NK_, DD_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return (int)e;                                                                               \
-      attr = lds;                                                                                                       \
-    }                                                                                                                   \
+    if (int e = mmego_allow_lds<local_group_l1_kernel<NK_, DD_>>(lds)) return e;                                        \
     hipLaunchKernelGGL((local_group_l1_kernel<NK_, DD_>), grid, dim3(LG_NT), lds, st, p);                               \
   } while (0)
   if (N == 128 && D == 25) { constexpr int DD_ = 25; LG_LAUNCH(2); }       // (the reference's shape: constants folded)
@@ -899,12 +894,7 @@ extern "C" int mmego_local_front_eval(void* stream, const float* feats, long ldf
   const dim3 grid((unsigned)(F < 512 ? F : 512));
 #define LE_LAUNCH(NK_)                                                                                                  \
   do {                                                                                                                  \
-    static size_t attr = 0;                                                                                             \
-    if (lds > 64 * 1024 && lds > attr) {                                                                                \
-      hipError_t e = hipFuncSetAttribute((const void*)local_front_eval_kernel<NK_, DD_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return (int)e;                                                                               \
-      attr = lds;                                                                                                       \
-    }                                                                                                                   \
+    if (int e = mmego_allow_lds<local_front_eval_kernel<NK_, DD_>>(lds)) return e;                                      \
     hipLaunchKernelGGL((local_front_eval_kernel<NK_, DD_>), grid, dim3(LG_NT), lds, st, p);                             \
   } while (0)
   if (N == 128 && D == 25) { constexpr int DD_ = 25; LE_LAUNCH(2); }
@@ -931,12 +921,7 @@ extern "C" int mmego_pool8_bn_act(void* stream, const float* Z, long ldz, long r
   p8_grid(rows, &nblk, &rpw);
   Pool8P p = {Z, ldz, rows, 64, part, nblk, gamma, beta, (float)eps, rmean, rvar, (float)momentum, state, aw_w, aw_b, voxT, attn, rpw};
   const size_t lds = (size_t)(256 + 2 * 8 * 2 * 64 + 8 * 64 * P8_TS) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)pool8_bn_act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  if (int e = mmego_allow_lds<pool8_bn_act_kernel>(lds)) return e;
   hipLaunchKernelGGL(pool8_bn_act_kernel, dim3(nblk), dim3(P8_NT), lds, (hipStream_t)stream, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
@@ -955,12 +940,7 @@ extern "C" int mmego_pool8_backward(void* stream, const float* Z, long ldz, long
   p8_grid(rows, &nblk, &rpw);
   Pool8BwdP p = {Z, ldz, rows, state, attn, dvoxT, aw_w, dY, lddy, gpart, awpart, rpw};
   const size_t lds = (size_t)(2 * 8 * 2 * 64 + 8 * 65 + 3 + 8 * (64 * P8_TS + 8 * P8_TS + 8)) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)pool8_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  if (int e = mmego_allow_lds<pool8_bwd_kernel>(lds)) return e;
   hipLaunchKernelGGL(pool8_bwd_kernel, dim3(nblk), dim3(P8_NT), lds, (hipStream_t)stream, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
@@ -983,12 +963,7 @@ extern "C" int mmego_pool128_bn_act(void* stream, const float* Z, long ldz, long
   p8_grid(rows, &nblk, &rpw);
   Pool128P p = {Z, ldz, rows, part, nblk, gamma, beta, (float)eps, rmean, rvar, (float)momentum, state, aw_w, aw_b, vec, attn};
   const size_t lds = (size_t)(256 + 2 * 8 * 2 * 64 + 2 * 128 * P128_TS + 2 * (128 + 256 + 8)) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)pool128_bn_act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  if (int e = mmego_allow_lds<pool128_bn_act_kernel>(lds)) return e;
   hipLaunchKernelGGL(pool128_bn_act_kernel, dim3(nblk), dim3(P8_NT), lds, (hipStream_t)stream, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
@@ -1002,12 +977,7 @@ extern "C" int mmego_pool128_backward(void* stream, const float* Z, long ldz, lo
   p8_grid(rows, &nblk, &rpw);
   Pool128BwdP p = {Z, ldz, rows, state, attn, vec, dvec, aw_w, dY, lddy, gpart, awpart};
   const size_t lds = (size_t)(2 * 8 * 2 * 64 + 8 * 65 + 3 + 2 * 128 * P128_TS + 2 * (128 + 128 + 64 + 4)) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)pool128_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  if (int e = mmego_allow_lds<pool128_bwd_kernel>(lds)) return e;
   hipLaunchKernelGGL(pool128_bwd_kernel, dim3(nblk), dim3(P8_NT), lds, (hipStream_t)stream, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;

@@ -242,13 +242,7 @@ extern "C" int mmego_lstm64_forward(void* stream, int B, int T, const float* xpr
   MMEGO_REQUIRE((hprev0 != nullptr) == st_ && (hprev1 != nullptr) == st_ && (gates1 != nullptr) == st_);   // stashes: all or none
 #define L64_FWD_LAUNCH(F_, S_, D_)                                                                                    \
   do {                                                                                                                \
-    static bool attr_set = false;                                                                                     \
-    if (!attr_set) {                                                                                                  \
-      hipError_t e = hipFuncSetAttribute((const void*)lstm64_fwd_kernel<F_, S_, D_>,                                  \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-      if (e != hipSuccess) return (int)e;                                                                             \
-      attr_set = true;                                                                                                \
-    }                                                                                                                 \
+    if (int e = mmego_allow_lds<lstm64_fwd_kernel<F_, S_, D_>>(lds)) return e;                                        \
     hipLaunchKernelGGL((lstm64_fwd_kernel<F_, S_, D_>), dim3(cdiv(B, 16), 2), dim3(256), lds, (hipStream_t)stream, p); \
   } while (0)
   if (full) {

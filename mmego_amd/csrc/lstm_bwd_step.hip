@@ -200,12 +200,7 @@ int lstm_bwd_step_dma_try(void* stream, int Bn, int H, const float* dg0, const f
   p.dc[0] = dc0; p.dc[1] = dc1; p.dgo[0] = dgo0; p.dgo[1] = dgo1;
   p.Bn = Bn; p.H = H;
   constexpr int lds = 3 * (64 + 32) * 64 * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)lstm_bwd_step_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = mmego_allow_lds<lstm_bwd_step_dma_kernel>(lds)) return e;
   const int grid = 2 * (Bn / 64) * (H / 32);
   hipLaunchKernelGGL(lstm_bwd_step_dma_kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, p);
   MMEGO_LAUNCH_CHECK();

@@ -191,20 +191,7 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_xcd_kernel(LstmSeqP p) {
 // must all be resident).  From the kernel's real occupancy -- hipOccupancyMaxActiveBlocksPerMultiprocessor x CU count, queried per
 // device -- not from an assumed two workgroups per CU; 0 on a device or partition that cannot hold one launch (the caller then keeps
 // the launch-per-timestep form), 2 on a whole MI355X (256 CUs x 2).
-extern "C" int mmego_lstm_seq_xcd_slots(void) {
-  static int slots[64];
-  static bool have[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (!have[dev]) {
-    int cus = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_seq_xcd_kernel, 256, 0) != hipSuccess) per_cu = 0;
-    slots[dev] = (int)(((long)cus * per_cu) / 256);
-    have[dev] = true;
-  }
-  return slots[dev];
-}
+extern "C" int mmego_lstm_seq_xcd_slots(void) { return mmego_resident_blocks<lstm_seq_xcd_kernel, 256>() / 256; }
 
 // 1 when mmego_lstm_seq_xcd takes the shape on the current device
 extern "C" int mmego_lstm_seq_xcd_ok(int Bn, int H, int T) {

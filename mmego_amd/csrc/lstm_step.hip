@@ -462,33 +462,19 @@ extern "C" int mmego_lstm_step(void* stream, int ndir, int Bn, int H, int first,
   } else if (Bn >= 128) {
     // HT = 32 by default (the HT = 16 two-workgroups-per-CU variant: shorter product loop, 37.9 k against 41.1 k cycles, but its
     // prologue -- twice the workgroups fetching first chunks -- costs more)
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
+    const int ncu = mmego_cu_count();
     const int grid32 = ndir * (H / 32) * cdiv(Bn, 64);
     // (both directions in one launch, Bn = H = 512: 26.7 us with HT 16 against 24.3 us with HT 32 per step.)  A launch that
     // would fill at most HALF the chip with HT = 32 -- one direction of the pair, launched on its own stream -- takes HT = 16:
     // then each direction's grid covers every CU once and the two directions' workgroups share the CUs out of phase
-    const bool ht16 = 2 * grid32 <= ncu;
-    static bool attr32 = false, attr16 = false;
+    const bool ht16 = 2 * grid32 <= (ncu > 0 ? ncu : 256);
     if (ht16) {
       const size_t lds = (size_t)3 * (64 + 64) * 32 * sizeof(float);
-      if (!attr16) {
-        hipError_t e = hipFuncSetAttribute((const void*)lstm_step_dma_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr16 = true;
-      }
+      if (int e = mmego_allow_lds<lstm_step_dma_kernel<16>>(lds)) return e;
       hipLaunchKernelGGL(lstm_step_dma_kernel<16>, dim3(2 * grid32), dim3(512), lds, (hipStream_t)stream, p);
     } else {
       const size_t lds = (size_t)3 * (64 + 128) * 32 * sizeof(float);
-      if (!attr32) {
-        hipError_t e = hipFuncSetAttribute((const void*)lstm_step_dma_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr32 = true;
-      }
+      if (int e = mmego_allow_lds<lstm_step_dma_kernel<32>>(lds)) return e;
       hipLaunchKernelGGL(lstm_step_dma_kernel<32>, dim3(grid32), dim3(512), lds, (hipStream_t)stream, p);
     }
   } else {
@@ -498,13 +484,7 @@ extern "C" int mmego_lstm_step(void* stream, int ndir, int Bn, int H, int first,
 #define SMALL_LAUNCH(SK_, F_)                                                                                        \
   do {                                                                                                               \
     const size_t lds = (size_t)2 * (64 + 16) * (SK_ + 4) * sizeof(float);                                            \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      hipError_t e = hipFuncSetAttribute((const void*)lstm_step_small_kernel<SK_, F_>,                               \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-      if (e != hipSuccess) return (int)e;                                                                            \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
+    if (int e = mmego_allow_lds<lstm_step_small_kernel<SK_, F_>>(lds)) return e;                                     \
     hipLaunchKernelGGL((lstm_step_small_kernel<SK_, F_>), dim3(grid), dim3(256), lds, (hipStream_t)stream, p);       \
   } while (0)
     if (H == 512 && full) {              // whole row blocks at IMU_Net's width: all eight chunks' loads up front

@@ -673,14 +673,10 @@ static int mlp_bwd_layer_launch(hipStream_t st, MlpBwdP& p) {
   mt_grid(p.rows, &nblk, &p.rows_per_wg);
   p.g_nblk = nblk;
   const size_t lds = (size_t)((MTB_NG * 3 + 1) * 64 * MT_S + 10 * 64) * sizeof(float) + sizeof(double) * 8 * 2 * 64;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)mlp_bwd_layer_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)mlp_bwd_layer_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)mlp_bwd_layer_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
+  int e = mmego_allow_lds<mlp_bwd_layer_kernel<false, false>>(lds);
+  if (!e) e = mmego_allow_lds<mlp_bwd_layer_kernel<false, true>>(lds);
+  if (!e) e = mmego_allow_lds<mlp_bwd_layer_kernel<true, false>>(lds);
+  if (e) return e;
   // the fast form: complete workgroups only, 32-bit byte offsets inside a workgroup's rows
   const long ldmax = p.lddy > p.ldz ? (p.lddy > p.ldxin ? p.lddy : p.ldxin) : (p.ldz > p.ldxin ? p.ldz : p.ldxin);
   const bool full = !p.gidx && p.rows % p.rows_per_wg == 0 && p.rows_per_wg * 4 * (ldmax > p.lddx ? ldmax : p.lddx) < (1L << 31);

@@ -779,12 +779,7 @@ extern "C" int mmego_attn_pool_forward(void* stream, const float* X, const float
     return MMEGO_OK;
   }
   if (vec_ok && tile <= 96 * 1024) {
-    static size_t attr_bytes = 0;
-    if (tile > 64 * 1024 && tile > attr_bytes) {
-      hipError_t e = hipFuncSetAttribute((const void*)attn_pool_fwd_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_bytes = 96 * 1024;
-    }
+    if (int e = mmego_allow_lds<attn_pool_fwd_lds_kernel>(tile)) return e;
     hipLaunchKernelGGL(attn_pool_fwd_lds_kernel, dim3((unsigned)G), dim3(256), tile, (hipStream_t)stream, X, w, b, P, C, vec, attn);
     MMEGO_LAUNCH_CHECK();
     return MMEGO_OK;

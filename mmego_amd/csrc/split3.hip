@@ -268,12 +268,7 @@ extern "C" int mmego_split3_fc_relu(void* stream, const float* X, long ldx, cons
   MMEGO_REQUIRE(X && W && Y && Bn > 0 && T > 0 && Cin > 0 && Cin <= 16 && H > 0 && H % 16 == 0 && H <= 2048 && Bp >= Bn && Bp % 32 == 0);
   MMEGO_REQUIRE(T <= 65535 && (((uintptr_t)Y) & 15) == 0);
   const size_t lds = (size_t)(H * 16 + H) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)s3_fc_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * 17 * 4);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int e = mmego_allow_lds<s3_fc_relu_kernel>(lds)) return e;
   dim3 grid(Bp / 32, T);
   s3_fc_relu_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(X, ldx, W, bias, Bn, T, Cin, H, reinterpret_cast<s3_u32x4*>(Y), Bp, relu);
   MMEGO_LAUNCH_CHECK();
@@ -618,17 +613,11 @@ static int s3_gemm_launch(void* stream, const unsigned short* A, const unsigned 
       p.Cf = Cf; p.C = C; p.ldc = ldc; p.bias = bias; p.Mrb = Mrb; p.Nrb = Nrb; p.SK = K / 16; p.M = M;
       p.tiles_m = Mrb / trb; p.tiles_n = Nrb / 8; p.gm = 4; p.cps = cps; p.slab = slab;
       constexpr int lds = 2 * 54 * 1024;
-      static bool attr_set[64] = {};
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MMEGO_EBADARG;
-      if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)s3_gemm_big_kernel<6, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)s3_gemm_big_kernel<9, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)s3_gemm_big_kernel<6, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)s3_gemm_big_kernel<9, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-      }
+      int e = mmego_allow_lds<s3_gemm_big_kernel<6, 10>>(lds);
+      if (!e) e = mmego_allow_lds<s3_gemm_big_kernel<9, 10>>(lds);
+      if (!e) e = mmego_allow_lds<s3_gemm_big_kernel<6, 8>>(lds);
+      if (!e) e = mmego_allow_lds<s3_gemm_big_kernel<9, 8>>(lds);
+      if (e) return e;
       const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)nsplit);
       hipStream_t st = (hipStream_t)stream;
       if (trb == 10) {
@@ -1110,12 +1099,7 @@ extern "C" int mmego_split3_step(void* stream, int ndir, int Bn, int H, int firs
   const int sq = H / 64;
 #define S3_STEP_LAUNCH(SQ_, NP_, F_)                                                                                        \
   {                                                                                                                         \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute((const void*)s3_step_kernel<SQ_, NP_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-      if (e != hipSuccess) return (int)e;                                                                                   \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    if (int e = mmego_allow_lds<s3_step_kernel<SQ_, NP_, F_>>(lds)) return e;                                               \
     s3_step_kernel<SQ_, NP_, F_><<<grid, 256, lds, st>>>(p);                                                               \
   }
 #define S3_STEP_NP(SQ_, F_)                 \
@@ -1158,12 +1142,7 @@ extern "C" int mmego_split3_proj(void* stream, const unsigned short* A, const un
   const int sq = K / 64;
 #define S3_PROJ_LAUNCH(SQ_, NP_)                                                                                            \
   {                                                                                                                         \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute((const void*)s3_step_kernel<SQ_, NP_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-      if (e != hipSuccess) return (int)e;                                                                                   \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    if (int e = mmego_allow_lds<s3_step_kernel<SQ_, NP_, 2>>(lds)) return e;                                                \
     s3_step_kernel<SQ_, NP_, 2><<<grid, 256, lds, st>>>(p);                                                                 \
   }
   if (sq == 16) { if (nprod == 6) S3_PROJ_LAUNCH(16, 6) else S3_PROJ_LAUNCH(16, 9) }
@@ -1200,12 +1179,7 @@ extern "C" int mmego_split3_step16(void* stream, int ndir, int Bn, int H, int fi
   const int sq = H / 64;
 #define S3_STEP_LAUNCH(SQ_, NP_, F_)                                                                                        \
   {                                                                                                                         \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute((const void*)s3_step16_kernel<SQ_, NP_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-      if (e != hipSuccess) return (int)e;                                                                                   \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    if (int e = mmego_allow_lds<s3_step16_kernel<SQ_, NP_, F_>>(lds)) return e;                                             \
     s3_step16_kernel<SQ_, NP_, F_><<<grid, 256, lds, st>>>(p);                                                             \
   }
 #define S3_STEP_NP(SQ_, F_)                 \
