@@ -290,6 +290,13 @@ int mmego_transform2h(void* stream, float* pts, long F, int P, int C, const floa
 /* out = R^T in + t (transpose=1, add_t=1: Utils.py:274-281) or out = R in (its backward). */
 int mmego_rotate_points(void* stream, const float* in, float* out, long F, int P, const float* R, const float* t,
                         int transpose, int add_t);
+/* Backward of mmego_transform2h with respect to the head pose: dR [F,3,3], dR[f][i][k] = sum_n g_i (p - t)_k and dt [F,3] =
+ * -R^T sum_n g over the frame's P points.  pts (row stride ldp >= 3): the UNTRANSFORMED points -- p - t is never recovered as R^T p',
+ * R need not be orthonormal.  g (row stride ldg) and g2 (may be NULL, row stride ldg2): gradients with respect to the transformed xyz
+ * columns of the F*P rows; their sum is used (Upper_Net: PointNet's first layer and the xyz columns of GlobalPointNet's input).
+ * accumulate != 0: added to what dR / dt hold.  One wave per frame, a fixed summation order: two runs give the same bits. */
+int mmego_transform2h_backward(void* stream, const float* pts, long ldp, long F, int P, const float* R, const float* t,
+                               const float* g, long ldg, const float* g2, long ldg2, int accumulate, float* dR, float* dt);
 /* which=0: y[F,87] -> q[F,14,3,3], joints[F,15,3] (Upper_Net.py:122-144,354-364);
  * which=1: y[F,42] -> q[F,6,3,3], joints[F,8,3] (Lower_Net.py:12-37,125-136).  body [B,20,3]; frame n
  * uses body row n % B (quirk Q2).  Joints are in the head frame.
@@ -303,6 +310,11 @@ int mmego_head_fk_forward(void* stream, int which, const float* y, const float* 
                           unsigned long long* seed_ctr);
 int mmego_head_fk_backward(void* stream, int which, const float* y, const float* body, int B, long F, const float* dj,
                            float* dy, const float* Rw);
+/* mmego_head_fk_backward with the head pose's own gradients of world = Rw^T joint + tw: dj is the gradient wrt the WORLD-frame joints,
+ * joints_h [F,nslots,3] the forward's head-frame joints; dtw [F,3] = sum_slots dj, dRw [F,3,3], dRw[k][i] = sum_slots joint_k dj_i
+ * (slots added in index order).  dy as from mmego_head_fk_backward, bit for bit. */
+int mmego_head_fk_backward_pose(void* stream, int which, const float* y, const float* body, int B, long F, const float* dj,
+                                float* dy, const float* Rw, const float* joints_h, float* dRw, float* dtw);
 /* mmego_head_fk_forward -> mmego_l1_loss (scale, loss[2], gradient = sign) -> mmego_head_fk_backward as ONE launch.  The loss is a
  * fixed-order sum: per-workgroup partial pairs in scratch (2 * ceil(F/64) + 1 doubles; the last double's storage is a ticket that must
  * be 0 before the first call and is left 0), added in index order by the workgroup that finishes last.  map [nslots]: target joint of
@@ -312,6 +324,11 @@ int mmego_head_fk_loss(void* stream, int which, const float* y, const float* bod
                        const float* Rw, const float* tw, float* world, long long* counters, int ncount,
                        unsigned long long* seed_ctr, const float* target, const int* map, int ntgt, double scale, float* loss,
                        float* dy, double* scratch);
+/* mmego_head_fk_loss with dRw [F,3,3], dtw [F,3] (see mmego_head_fk_backward_pose) from the same launch; everything else bit for bit. */
+int mmego_head_fk_loss_pose(void* stream, int which, const float* y, const float* body, int B, long F, float* q, float* joints_h,
+                            const float* Rw, const float* tw, float* world, long long* counters, int ncount,
+                            unsigned long long* seed_ctr, const float* target, const int* map, int ntgt, double scale, float* loss,
+                            float* dy, double* scratch, float* dRw, float* dtw);
 /* y[F,9] -> R[F,3,3] (eps rule of IMU_Net.py:7-18), t[F,3]. */
 int mmego_imu_head(void* stream, const float* y, long F, float* R, float* t);
 /* IMU_Net.fc2 (Net/IMU_Net.py:84) and mmego_imu_head in one launch: y = X [F][K] . W[9][K]^T + b (row-wise dot products, fixed

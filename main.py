@@ -6,7 +6,8 @@
   python main.py --infer [--vis]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
-available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
+--finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -45,7 +46,27 @@ def build_parser():
                         "products as piece products: DESIGN.md 7c)")
     p.add_argument("--resume", type=str, help="continue --train from a checkpoint written by this framework (the model .pth "
                                                "or its .train_state.pth: weights, Adam state, epoch, RNGs)")
+    p.add_argument("--finetune_imu", action="store_true",
+                   help="--train --network Upper_Net only: train the IMU_Net as well, end to end through the pose loss (Train_Upper.py:162 "
+                        "without its .detach()); the IMU_Net is saved beside the Upper_Net checkpoint, in an IMU_Net folder")
+    p.add_argument("--imu_lr", type=float, help="learning rate of the IMU_Net under --finetune_imu (default: --lr / Config.lr)")
     return p
+
+
+def check_finetune(parser, args, world):
+    """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
+    if not args.finetune_imu:
+        if args.imu_lr is not None:
+            parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
+        return
+    if not (args.train and args.network == "Upper_Net"):
+        parser.error("--finetune_imu goes with --train --network Upper_Net only (Lower_Net produces no head-pose gradients yet)")
+    if args.gt_head_pose:
+        parser.error("--finetune_imu needs an IMU_Net to train; --gt_head_pose takes the head pose from the recording instead")
+    if world > 1:
+        parser.error("--finetune_imu is not data parallel yet (WORLD_SIZE=%d): the IMU_Net gradients have no all-reduce" % world)
+    if args.resume:
+        parser.error("--finetune_imu cannot be combined with --resume yet: the IMU_Net's optimiser state is not part of a train state")
 
 
 def apply_overrides(args):
@@ -70,6 +91,8 @@ def apply_overrides(args):
         for c in both:
             c.gt_head_pose = True
     Config.resume_path = args.resume
+    Config.finetune_imu = bool(args.finetune_imu)
+    Config.imu_lr = args.imu_lr
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:
@@ -77,7 +100,9 @@ def apply_overrides(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_finetune(parser, args, int(os.environ.get("WORLD_SIZE", "1")))
     apply_overrides(args)
     if args.seed is not None:
         import numpy as np

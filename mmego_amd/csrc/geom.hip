@@ -99,6 +99,48 @@ __global__ __launch_bounds__(256) void rotate_points_kernel(const float* __restr
   out[i * 3] = o0; out[i * 3 + 1] = o1; out[i * 3 + 2] = o2;
 }
 
+// Backward of p' = R (p - t) with respect to R and t: dR[f][i][k] = sum_n g_i (p - t)_k, dt[f] = -R^T sum_n g, where g is the gradient
+// with respect to the transformed xyz -- the sum of ga and (optional) gb, the two consumers of those columns in Upper_Net.  pts are the
+// UNTRANSFORMED points (p - t is not recovered as R^T p': nothing makes R orthonormal).  One wave per frame: lane j adds points j,
+// j + 64, ... in that order, then a butterfly over the lanes -- a fixed order, so two runs give the same bits.  accumulate: the results
+// are added to what dR / dt hold (the world transform's share of the same gradients).
+__global__ __launch_bounds__(64) void transform2h_bwd_kernel(const float* __restrict__ pts, long ldp, int P, const float* __restrict__ R,
+                                                             const float* __restrict__ t, const float* __restrict__ ga, long lda,
+                                                             const float* __restrict__ gb, long ldb, int accumulate,
+                                                             float* __restrict__ dR, float* __restrict__ dt) {
+  const long f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float t0 = t[f * 3], t1 = t[f * 3 + 1], t2 = t[f * 3 + 2];
+  float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s[3] = {0.f, 0.f, 0.f};
+  for (int p = lane; p < P; p += 64) {
+    const long i = f * P + p;
+    const float* x = pts + i * ldp;
+    const float d[3] = {__fsub_rn(x[0], t0), __fsub_rn(x[1], t1), __fsub_rn(x[2], t2)};        // (the forward's p - t)
+    float g[3] = {ga[i * lda], ga[i * lda + 1], ga[i * lda + 2]};
+    if (gb) { g[0] += gb[i * ldb]; g[1] += gb[i * ldb + 1]; g[2] += gb[i * ldb + 2]; }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      s[r] += g[r];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a[r * 3 + k] += g[r] * d[k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 9; ++j) a[j] = wave_sum(a[j]);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) s[j] = wave_sum(s[j]);
+  if (lane == 0) {
+    const float* Rf = R + f * 9;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) dR[f * 9 + j] = accumulate ? dR[f * 9 + j] + a[j] : a[j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float v = -(Rf[k] * s[0] + Rf[3 + k] * s[1] + Rf[6 + k] * s[2]);
+      dt[f * 3 + k] = accumulate ? dt[f * 3 + k] + v : v;
+    }
+  }
+}
+
 // ---- 6-D -> rotation (Gram-Schmidt), two eps rules -------------------------------------------------
 // mode 0: F.normalize, v / max(|v|, 1e-12)  (Upper/Lower heads);  mode 1: v / max(|v|, 1e-8) (IMU_Net)
 struct Rot6 {
@@ -287,10 +329,14 @@ __global__ __launch_bounds__(64) void head_fk_fwd_kernel(const float* __restrict
 
 // dj: [F, nslots, 3] gradient wrt head-frame joints  ->  dy [F, ny]
 // Rw (optional): dj is the gradient wrt the WORLD-frame joints; the head-frame gradient Rw dj is formed first.
-template <int WHICH>
+// POSE (needs Rw): the head pose's own gradients of world = Rw^T joint + tw as well, from the same data: dtw [F, 3] = sum_slots dj,
+// dRw [F, 3, 3], dRw[k][i] = sum_slots joint_k dj_i (joints [F, nslots, 3]: the forward's head-frame joints).  A frame's thread adds
+// its slots in index order; the <WHICH, false> instantiation is the kernel without these outputs, statement by statement.
+template <int WHICH, bool POSE = false>
 __global__ __launch_bounds__(64) void head_fk_bwd_kernel(const float* __restrict__ y, const float* __restrict__ body, int B, long F,
                                                          const float* __restrict__ dj, float* __restrict__ dy,
-                                                         const float* __restrict__ Rw) {
+                                                         const float* __restrict__ Rw, const float* __restrict__ joints = nullptr,
+                                                         float* __restrict__ dRw = nullptr, float* __restrict__ dtw = nullptr) {
   using P = FkC<WHICH>;
   long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
@@ -304,6 +350,23 @@ __global__ __launch_bounds__(64) void head_fk_bwd_kernel(const float* __restrict
   for (int s = 0; s < P::nslots; ++s)
 #pragma unroll
     for (int i = 0; i < 3; ++i) g[s][i] = dj[(f * P::nslots + s) * 3 + i];
+  if (POSE) {
+    float pr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < P::nslots; ++s) {
+      const float* jp = joints + (f * P::nslots + s) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        pt[i] += g[s][i];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pr[k * 3 + i] += jp[k] * g[s][i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) dRw[f * 9 + i] = pr[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dtw[f * 3 + i] = pt[i];
+  }
   if (Rw) {
     const float* Rf = Rw + f * 9;
 #pragma unroll
@@ -349,7 +412,8 @@ __global__ __launch_bounds__(64) void head_fk_bwd_kernel(const float* __restrict
 // same value whichever workgroup is last -- and resets the ticket for the next launch (graph replays).  Same arithmetic, statement by statement, as
 // head_fk_fwd_kernel -> l1_loss_kernel -> head_fk_bwd_kernel (bit-identical results; tests/test_hip_parity.py).  Replaces three
 // dependent launches at the turning point of a training step (Train_Upper.py:165-182, Train_Lower.py:199-224).
-template <int WHICH>
+// POSE: dRw [F, 3, 3], dtw [F, 3] as in head_fk_bwd_kernel<WHICH, true> (the loss gradient is the sign computed here).
+template <int WHICH, bool POSE = false>
 __global__ __launch_bounds__(64) void head_fk_loss_kernel(const float* __restrict__ y, const float* __restrict__ body, int B, long F,
                                                           float* __restrict__ q, float* __restrict__ joints,
                                                           const float* __restrict__ Rw, const float* __restrict__ tw,
@@ -357,7 +421,8 @@ __global__ __launch_bounds__(64) void head_fk_loss_kernel(const float* __restric
                                                           unsigned long long* seed_ctr, const float* __restrict__ target,
                                                           const int* __restrict__ map, int ntgt, float scale,
                                                           float* __restrict__ loss, float* __restrict__ dy, double* part,
-                                                          unsigned* ticket) {
+                                                          unsigned* ticket, float* __restrict__ dRw = nullptr,
+                                                          float* __restrict__ dtw = nullptr) {
   using P = FkC<WHICH>;
   const long f = (long)blockIdx.x * 64 + threadIdx.x;
   if (f == 0) {
@@ -391,6 +456,7 @@ __global__ __launch_bounds__(64) void head_fk_loss_kernel(const float* __restric
     float* qf = q + f * P::nrot * 9;
     float l[P::nslots][3];
     float g[P::nslots][3];
+    float pr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f};      // (POSE only)
     {
       float R[P::nrot][9];
 #pragma unroll
@@ -429,6 +495,15 @@ __global__ __launch_bounds__(64) void head_fk_loss_kernel(const float* __restric
       const float v0 = dx > 0.f ? scale : (dx < 0.f ? -scale : 0.f);
       const float v1 = dyy > 0.f ? scale : (dyy < 0.f ? -scale : 0.f);
       const float v2 = dz > 0.f ? scale : (dz < 0.f ? -scale : 0.f);
+      if (POSE) {
+        const float v[3] = {v0, v1, v2};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          pt[i] += v[i];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) pr[k * 3 + i] += l[s_][k] * v[i];
+        }
+      }
       g[s_][0] = dot3_nofma(Rr[0], Rr[1], Rr[2], v0, v1, v2);       // world -> head frame (head_fk_bwd_kernel's first step)
       g[s_][1] = dot3_nofma(Rr[3], Rr[4], Rr[5], v0, v1, v2);
       g[s_][2] = dot3_nofma(Rr[6], Rr[7], Rr[8], v0, v1, v2);
@@ -458,6 +533,12 @@ __global__ __launch_bounds__(64) void head_fk_loss_kernel(const float* __restric
     for (int s_ = 0; s_ < P::nseed; ++s_)
 #pragma unroll
       for (int i = 0; i < 3; ++i) dyf[P::seed_off[s_] + i] = g[P::seed_slot[s_]][i];
+    if (POSE) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) dRw[f * 9 + i] = pr[i];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) dtw[f * 3 + i] = pt[i];
+    }
   }
   acc = wave_sum_d(acc);
   dist = wave_sum_d(dist);
@@ -808,6 +889,15 @@ extern "C" int mmego_transform2h_pair(void* stream, float* pts, long F, int P, i
   return MMEGO_OK;
 }
 
+extern "C" int mmego_transform2h_backward(void* stream, const float* pts, long ldp, long F, int P, const float* R, const float* t,
+                                          const float* g, long ldg, const float* g2, long ldg2, int accumulate, float* dR, float* dt) {
+  MMEGO_REQUIRE(F > 0 && F < (1L << 31) && P > 0 && ldp >= 3 && ldg >= 3 && (!g2 || ldg2 >= 3) && pts && R && t && g && dR && dt);
+  hipLaunchKernelGGL(transform2h_bwd_kernel, dim3((unsigned)F), dim3(64), 0, (hipStream_t)stream, pts, ldp, P, R, t, g, ldg, g2, ldg2,
+                     accumulate, dR, dt);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
 extern "C" int mmego_rotate_points(void* stream, const float* in, float* out, long F, int P, const float* R,
                                    const float* t, int transpose, int add_t) {
   MMEGO_REQUIRE(in && out && R && F > 0 && P > 0 && (!add_t || t));
@@ -840,6 +930,16 @@ extern "C" int mmego_head_fk_backward(void* stream, int which, const float* y, c
   return MMEGO_OK;
 }
 
+// mmego_head_fk_backward for a differentiable head pose: dj is the gradient wrt the WORLD-frame joints, and dRw / dtw come with dy.
+extern "C" int mmego_head_fk_backward_pose(void* stream, int which, const float* y, const float* body, int B, long F,
+                                           const float* dj, float* dy, const float* Rw, const float* joints_h, float* dRw, float* dtw) {
+  MMEGO_REQUIRE(F > 0 && B > 0 && (which == 0 || which == 1) && Rw && joints_h && dRw && dtw);
+  if (which == 0) hipLaunchKernelGGL((head_fk_bwd_kernel<0, true>), dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw);
+  else hipLaunchKernelGGL((head_fk_bwd_kernel<1, true>), dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
 // head_fk_forward + l1_loss + head_fk_backward as ONE launch (F <= 512 frames; map has the net's nslots entries: the target joint of
 // every predicted slot).  dy [F, ny]: gradient of the loss wrt the head output y.
 extern "C" int mmego_head_fk_loss(void* stream, int which, const float* y, const float* body, int B, long F, float* q, float* joints_h,
@@ -856,6 +956,21 @@ extern "C" int mmego_head_fk_loss(void* stream, int which, const float* y, const
   //  instructions beside a bf16-MFMA workgroup, DESIGN.md section 7d -- and the library is built without them: the request is gone.)
   if (which == 0) hipLaunchKernelGGL(head_fk_loss_kernel<0>, dim3(nb), dim3(64), 0, (hipStream_t)stream, y, body, B, F, q, joints_h, Rw, tw, world, counters, ncount, seed_ctr, target, map, ntgt, (float)scale, loss, dy, scratch, ticket);
   else hipLaunchKernelGGL(head_fk_loss_kernel<1>, dim3(nb), dim3(64), 0, (hipStream_t)stream, y, body, B, F, q, joints_h, Rw, tw, world, counters, ncount, seed_ctr, target, map, ntgt, (float)scale, loss, dy, scratch, ticket);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
+// mmego_head_fk_loss for a differentiable head pose: the same launch leaves dRw [F, 3, 3] and dtw [F, 3] as well.
+extern "C" int mmego_head_fk_loss_pose(void* stream, int which, const float* y, const float* body, int B, long F, float* q,
+                                       float* joints_h, const float* Rw, const float* tw, float* world, long long* counters, int ncount,
+                                       unsigned long long* seed_ctr, const float* target, const int* map, int ntgt, double scale,
+                                       float* loss, float* dy, double* scratch, float* dRw, float* dtw) {
+  MMEGO_REQUIRE((which == 0 || which == 1) && y && body && q && joints_h && Rw && tw && world && target && map && loss && dy && scratch);
+  MMEGO_REQUIRE(B > 0 && F > 0 && F <= 65536 && ntgt > 0 && ncount >= 0 && ncount <= 4096 && (ncount == 0 || counters) && dRw && dtw);
+  const int nb = cdiv(F, 64);
+  unsigned* ticket = reinterpret_cast<unsigned*>(scratch + 2 * nb);
+  if (which == 0) hipLaunchKernelGGL((head_fk_loss_kernel<0, true>), dim3(nb), dim3(64), 0, (hipStream_t)stream, y, body, B, F, q, joints_h, Rw, tw, world, counters, ncount, seed_ctr, target, map, ntgt, (float)scale, loss, dy, scratch, ticket, dRw, dtw);
+  else hipLaunchKernelGGL((head_fk_loss_kernel<1, true>), dim3(nb), dim3(64), 0, (hipStream_t)stream, y, body, B, F, q, joints_h, Rw, tw, world, counters, ncount, seed_ctr, target, map, ntgt, (float)scale, loss, dy, scratch, ticket, dRw, dtw);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }

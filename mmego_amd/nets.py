@@ -129,10 +129,11 @@ class _NetBase(nn.Module):
     # -- kinematics head, optionally with the trainer's loss and the start of backward in the same launch ----------------
     loss_hook = None      # (target [B,T,21,3], joint map int32, loss buffer [2], scale): set by train_step.StageStep around a step
 
-    def _head_fk(self, ar, which, y, body, B, F, q, jh, R, t, l, tick, stash):
+    def _head_fk(self, ar, which, y, body, B, F, q, jh, R, t, l, tick, stash, pose=None):
         """mmego_head_fk_forward; with a loss hook (training step, <= 512 frames) mmego_head_fk_loss instead: kinematics, head-to-world
         transform, L1(sum) loss, its gradient and the kinematics' backward in one launch -- dy lands in the arena and
-        _backward_impl skips its first launch (bit-identical to the three separate launches)."""
+        _backward_impl skips its first launch (bit-identical to the three separate launches).
+        pose = (dRw, dtw) (a differentiable head pose): the fused launch leaves the world transform's pose gradients there as well."""
         hook = self.loss_hook
         self._dy_ready = False
         if hook is not None and stash and _FUSED_HEAD_LOSS:
@@ -143,7 +144,11 @@ class _NetBase(nn.Module):
             scr = ar.get("fkloss.scratch%d" % nb, (2 * nb + 1,), dtype=torch.float64)
             if fresh:
                 scr.zero_()          # (the ticket starts at 0; every launch leaves it 0.  One-time, outside any captured graph: warm-up)
-            hip.call("head_fk_loss", which, y, body, B, F, q, jh, R, t, l, *tick, target, jmap, target.shape[-2], float(scale), loss2, dy, scr)
+            if pose is not None:
+                hip.call("head_fk_loss_pose", which, y, body, B, F, q, jh, R, t, l, *tick, target, jmap, target.shape[-2], float(scale), loss2,
+                         dy, scr, *pose)
+            else:
+                hip.call("head_fk_loss", which, y, body, B, F, q, jh, R, t, l, *tick, target, jmap, target.shape[-2], float(scale), loss2, dy, scr)
             self._dy_ready = True
         else:
             hip.call("head_fk_forward", which, y, body, B, F, q, jh, R, t, l, *tick)
@@ -183,6 +188,45 @@ class _Bridge(torch.autograd.Function):
         ctx.net._backward_impl(grads[0])
         ctx.net.flat().bind_grads()
         return (None, None, None) + (None,) * len(ctx.net._flat.params)
+
+
+def _pose_wants_grad(*ts):
+    return torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in ts)
+
+
+def _refuse_pose_grad(who, **named):
+    """Nets whose backward owes its inputs nothing yet: a differentiable input must not lose its gradient silently."""
+    bad = [k for k, v in named.items() if isinstance(v, torch.Tensor) and v.requires_grad]
+    if bad and torch.is_grad_enabled():
+        raise NotImplementedError("%s: %s require%s grad, but this net's backward produces no input gradients (only UpperNet "
+                                  "differentiates its head pose R, t); detach them" % (who, ", ".join(bad), "s" if len(bad) == 1 else ""))
+
+
+class _PoseBridge(torch.autograd.Function):
+    """_Bridge of UpperNet with the head pose as differentiable inputs: backward returns dR, dt beside the parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, net, args, R, t, *params):
+        ctx.net = net
+        x, h0, c0, body = args
+        outs = net._forward_impl(x, h0, c0, body, R, t, pose_grad=True)
+        ctx.mark_non_differentiable(*outs[1:])
+        ctx.pose_like = (R.shape, R.dtype, t.shape, t.dtype)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if not ctx.net.training:
+            raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
+                                      "the reference detaches frozen nets (Train_Lower.py:195-196)")
+        ctx.net._backward_impl(grads[0])
+        ctx.net.flat().bind_grads()
+        dR, dt = ctx.net.pose_grads()
+        rs, rd, ts, td = ctx.pose_like
+        # (copies: the arena's buffers are rewritten by the next step, and autograd may keep what it is handed as .grad)
+        dR = dR.clone().view(rs).to(rd) if ctx.needs_input_grad[2] else None
+        dt = dt.clone().view(ts).to(td) if ctx.needs_input_grad[3] else None
+        return (None, None, dR, dt) + (None,) * len(ctx.net._flat.params)
 
 
 # =====================================================================================================
@@ -226,7 +270,9 @@ class MLPHead(nn.Module):
 
 class UpperNet(_NetBase):
     """forward(x[B,T,N,6], h0_g[6,B,64], c0_g[6,B,64], initial_body[B,20,3], R[B,T,3,3], t[B,T,3])
-    -> (l[B,T,15,3], q[B,T,14,3,3], global_weights[B*T,N,1], hn_g, cn_g).  MUTATES x (Q1)."""
+    -> (l[B,T,15,3], q[B,T,14,3,3], global_weights[B*T,N,1], hn_g, cn_g).  MUTATES x (Q1).
+    R, t that require grad receive their gradients from backward (both transforms: head frame in front, world frame behind);
+    x, initial_body, h0_g, c0_g are not differentiable."""
 
     def __init__(self):
         super().__init__()
@@ -237,15 +283,26 @@ class UpperNet(_NetBase):
     def forward(self, x, h0_g, c0_g, initial_body, R, t):
         _require_gpu(x, "UpperNet")
         args = (x, h0_g, c0_g, initial_body, R, t)
+        if _pose_wants_grad(R, t):
+            self.flat()
+            return _PoseBridge.apply(self, args[:4], R, t, *self._flat.params)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self.flat()
             return _Bridge.apply(self, 1, args, *self._flat.params)
         return self._forward_impl(*args, stash=False)
 
+    def pose_grads(self):
+        """(dR [F,3,3], dt [F,3]) of the last backward behind a pose_grad forward: arena buffers, rewritten by the next one."""
+        if getattr(self, "_pose", None) is None:
+            raise RuntimeError("UpperNet.pose_grads: the last forward did not ask for the head pose's gradients")
+        return self._pose[2], self._pose[3]
+
     # -- pipelines ---------------------------------------------------------------------------------
-    def _forward_impl(self, x, h0, c0, body, R, t, stash=True, x_src=None):
+    def _forward_impl(self, x, h0, c0, body, R, t, stash=True, x_src=None, pose_grad=False):
         """x_src (optional, x's shape): the minibatch is read from there and x receives the transformed copy (one launch for a
-        trainer's 'fresh batch' copy and the transform)."""
+        trainer's 'fresh batch' copy and the transform).
+        pose_grad: _backward_impl also forms d loss / d R and d loss / d t (pose_grads()).  The head-frame transform's share needs
+        the UNTRANSFORMED points: x_src when given (the caller leaves it alone until backward has run), else a copy taken here."""
         self.flat()
         training = self.training
         ar = self.arena("train" if stash else "eval")
@@ -260,6 +317,16 @@ class UpperNet(_NetBase):
         c0 = _f32c(c0) if c0 is not None else None
         vec = ar.get("vec", (F, 64))
         attn = torch.empty((F, N, 1), dtype=torch.float32, device=x.device)
+        self._pose = None
+        if pose_grad:
+            if not stash:
+                raise ValueError("UpperNet: pose_grad needs a forward that keeps its activations (stash=True)")
+            if x_src is not None:
+                raw = x_src.view(rows, Cx)
+            else:
+                raw = ar.get("pts_raw", (rows, Cx))
+                ops.copy2d(x.view(rows, Cx), raw)
+            self._pose = (raw, t, ar.get("dR", (F, 3, 3)), ar.get("dt", (F, 3)))
         if not training and not stash and self._front_fusable(Cx, N):
             # eval mode: transform, PointNet, concat, GlobalPointNet and the attention pooling as ONE launch (front.hip); the
             # per-point 28- / 64-channel tensors never exist in memory
@@ -325,7 +392,9 @@ class UpperNet(_NetBase):
         jh = ar.get("jh", (F, 15, 3))
         l = torch.empty((B, T, 15, 3), dtype=torch.float32, device=vec.device)
         tick = self._flat.tick_args(self.seed_counter()) if training else (None, 0, None)   # BatchNorm counters + dropout seed
-        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash)    # kinematics + head-to-world transform (+ loss), one launch
+        pose = getattr(self, "_pose", None)
+        # kinematics + head-to-world transform (+ loss), one launch
+        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash, pose=pose[2:] if (stash and pose is not None) else None)
         if stash:
             self._saved = (B, T, N, R, body, c0, attn)
         return l, q, attn, hn, cn
@@ -338,8 +407,12 @@ class UpperNet(_NetBase):
         dl = _f32c(dl)
         y, h1 = ar.get("y", (F, 87)), ar.get("h1", (F, 128))
         dy = ar.get("dy", (F, 87))
+        pose = getattr(self, "_pose", None)
         if not getattr(self, "_dy_ready", False):
-            hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
+            if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
+                hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
+            else:
+                hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
         dh1 = ar.get("dh1", (F, 128))
         leaves = []          # weight gradients of the head and of the BiLSTM stack: leaves, issued together behind the stack
         blocks.linear_backward(dy, h1, self.mlpHead.fc2, G, dh1, relu_input=True, leaves=leaves)
@@ -362,7 +435,12 @@ class UpperNet(_NetBase):
                 blocks.attn_pool_backward(ar, "gpool", g3, gpn.attn, attn, dvec, F, N, 64, dg3, G)
                 dfeats = blocks.mlp3_backward(ar, "gp", gpn, feats, g3, dg3, G, True)
             pts = ar.get("pts", (rows, 6))
-            blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, False)
+            dpts = blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, pose is not None)
+        if pose is not None:
+            # the head-frame transform's share, added to the world transform's: the transformed xyz feed PointNet's first layer (dpts)
+            # and the first columns of GlobalPointNet's input (dfeats); range, velocity and intensity do not depend on the pose
+            raw, t, dR, dt = pose
+            hip.call("transform2h_backward", raw, raw.stride(0), F, N, R, t, dfeats, dfeats.stride(0), dpts, dpts.stride(0), 1, dR, dt)
 
 
 # =====================================================================================================
@@ -468,6 +546,7 @@ class LowerNet(_NetBase):
         cut its choice depends on the torch build; replaying the recorded choice lets the HIP path be compared with the
         reference's outputs (goldens G5 / G9) at the 1e-3 cm bar instead of through the oracle alone."""
         _require_gpu(x, "LowerNet")
+        _refuse_pose_grad("LowerNet", upper_l=upper_l, R=R, t=t)
         args = (upper_l, x, initial_body, R, t, pin_select_idx)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self.flat()

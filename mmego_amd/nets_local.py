@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import blocks, hip, ops
 from .blocks import LstmParams
-from .nets import GlobalModule, PointNet, _Bridge, _Mlp3, _NetBase, _f32c, _require_gpu
+from .nets import GlobalModule, PointNet, _Bridge, _Mlp3, _NetBase, _f32c, _refuse_pose_grad, _require_gpu
 
 N_ANCHOR, N_GROUP = 27, 8
 _LOCAL_FUSED = True      # the anchor branch on the fused kernels of local.hip
@@ -115,6 +115,7 @@ class UpperNetwlocal(_NetBase):
 
     def forward(self, x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t):
         _require_gpu(x, "UpperNetwlocal")
+        _refuse_pose_grad("UpperNetwlocal", R=R, t=t)
         args = (x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self.flat()

@@ -28,6 +28,8 @@ _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_
 
 class _Base:
     """Shared set-up: directories, frozen IMU_Net (or ground-truth head pose), datasets."""
+    finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
+    _imu_opt_shared = None
 
     def __init__(self, cfg, make_dirs=True):
         self.cfg = cfg
@@ -57,7 +59,8 @@ class _Base:
         return "a" if getattr(self.cfg, "resume_path", None) else "w"     # --resume continues the logs instead of truncating them
 
     def _load_imu(self):
-        imu = IMUNet(15, 6 + 3, 512, 2, True, 0.1).to(self.device).eval()
+        # (--finetune_imu: built without dropout -- same state_dict keys -- because its training forward has none, as in stage 1)
+        imu = IMUNet(15, 6 + 3, 512, 2, True, 0 if getattr(self.cfg, "finetune_imu", False) else 0.1).to(self.device).eval()
         if self.cfg.gt_head_pose:
             print("[mmego_amd] head pose from the recording (R_R0R, ground-truth head joint); IMU_Net not used")
             return None
@@ -121,7 +124,11 @@ class _StageTrainer(_Base):
         super().__init__(Config)
         cfg = self.cfg
         self.num_epochs, self.save_slot, self.learning_rate = cfg.epochs, 50, cfg.lr
+        self.finetune_imu = bool(getattr(cfg, "finetune_imu", False))
+        if self.finetune_imu and (self.stage != "upper" or cfg.gt_head_pose or self.world > 1 or getattr(cfg, "resume_path", None)):
+            raise SystemExit("--finetune_imu: Upper_Net stage with an IMU_Net checkpoint only; not data parallel, not with --resume")
         self.model_IMU = self._load_imu()
+        self._imu_opt_shared = None
         self.train_data = PosePC(batch_length=self.frame_no)
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -144,10 +151,18 @@ class _StageTrainer(_Base):
         st = self._steps.get(B)
         if st is None:
             pg = self.pg
-            pipelined = self.model_IMU is not None and os.environ.get("MMEGO_PIPELINE_IMU", "1") != "0"
+            # (--finetune_imu: the plain StageStep -- the IMU_Net is trained, there is no frozen forward to run ahead)
+            pipelined = (self.model_IMU is not None and not self.finetune_imu and os.environ.get("MMEGO_PIPELINE_IMU", "1") != "0")
+            imu_lr = getattr(self.cfg, "imu_lr", None)
             st = StageStep(self.stage, self.model, None if pipelined else self.model_IMU,
                            upper_frozen=getattr(self, "Upper_net", None), lr=self.learning_rate, process_group=pg,
-                           use_graph=not pipelined)
+                           use_graph=not pipelined, finetune_imu=self.finetune_imu,
+                           imu_lr=self.learning_rate if imu_lr is None else imu_lr)
+            if self.finetune_imu:                                       # one IMU_Net optimiser state for all batch sizes, too
+                if self._imu_opt_shared is not None:
+                    st.imu_opt = self._imu_opt_shared
+                else:
+                    self._imu_opt_shared = st.imu_opt
             if self._opt_shared is not None:
                 st.opt = self._opt_shared                               # one optimiser state for all batch sizes
             else:
@@ -164,6 +179,8 @@ class _StageTrainer(_Base):
 
     def train_once(self):
         self.model.train()
+        if self.finetune_imu:
+            self.model_IMU.train()                                      # (.eval() again for the epoch evaluation: eval_model)
         nsel = self.model_out_joints
         if self._log is None:
             self._log = torch.zeros((64, 2), dtype=torch.float32, device=self.device)
@@ -242,10 +259,22 @@ class _StageTrainer(_Base):
             #  checkpoint consistent with "epoch finished", which is what --resume continues from)
             if (epoch + 1) % self.save_slot == 0 or epoch + 1 == self.num_epochs or stop:
                 self.save_models(epoch, self.model, self._optimizer(), early)
+                if self.finetune_imu:
+                    self.save_imu(epoch)
             if stop:
                 print("Early stopping")
                 break
         return out
+
+    def save_imu(self, epoch):
+        """--finetune_imu: the trained IMU_Net beside the Upper_Net checkpoint, same file name, in an IMU_Net folder."""
+        if self.rank != 0:
+            return None
+        folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), "IMU_Net")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
+        torch.save(self.model_IMU.state_dict(), path)
+        return path
 
 
 class UpperTrainer(_StageTrainer):
@@ -279,6 +308,9 @@ class UpperTrainer(_StageTrainer):
         per-minibatch sums land in a device-side log, and the host reads that log ONCE per epoch.  Returns the reference's tuple
         (eval_loss, eval_loss_l, eval_accu, dis_l, accu_ll[15], angle_ll[14]): means over minibatches of per-minibatch means."""
         self.model.eval()
+        if self.finetune_imu:
+            self.model_IMU.eval()
+            self.model_IMU.weights_changed()          # (the fused Adam writes through raw pointers: no derived copy of old weights)
         m = _epoch_eval(self, self.test_data, self.batchsize, True, self._rng, self.model_IMU, self.model, None)
         eval_loss = float(np.mean(m[:, 29]))                                 # L1(sum) / B / T per minibatch
         return (eval_loss, np.asarray([eval_loss / self.cfg.joint_num_upper]), float(np.mean(m[:, :15].mean(axis=1))),

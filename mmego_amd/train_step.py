@@ -137,17 +137,43 @@ def needs_exclusive(nets):
     return any(getattr(m, a, "fp32") != "fp32" for m in nets if m is not None for a in ("precision", "train_precision"))
 
 
+def _refuse_finetune(who, stages):
+    """The multi-stage engines run FROZEN IMU_Nets (shared, prefetched or beside another stage); a stage that trains its own does not fit."""
+    if any(getattr(st, "finetune_imu", False) for st in stages):
+        raise ValueError("%s: a stage with finetune_imu=True trains its IMU_Net, which is then no frozen, shareable forward; run it as a "
+                         "plain StageStep" % who)
+
+
 class StageStep:
     """One training stage's per-minibatch body with static buffers (graph friendly).
 
     ``imu_net=None`` takes the head pose from the recording (R_gt, ground-truth head joint) instead of the
-    frozen IMU_Net -- the shipped reference snapshot has no IMU_Net checkpoint."""
+    frozen IMU_Net -- the shipped reference snapshot has no IMU_Net checkpoint.
+
+    ``finetune_imu`` (Upper stage): the IMU_Net is trained too, through the pose loss -- Train_Upper.py:162 without its .detach().
+    Per minibatch: IMU_Net training forward -> R, t -> Upper_Net forward + loss + backward, which now leaves d loss / d R and
+    d loss / d t (UpperNet.pose_grads) -> IMU_Net backward -> two Adam steps (Upper_Net at ``lr``, IMU_Net at ``imu_lr`` with stage
+    1's weight decay).  The body is still one HIP graph."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
-                 use_graph=True, pose=None):
+                 use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001):
         assert stage in ("upper", "lower")
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
+        self.finetune_imu = bool(finetune_imu)
+        self.imu_opt = None
+        if self.finetune_imu:
+            from .nets import UpperNet
+            if stage != "upper" or type(net) is not UpperNet:
+                raise ValueError("StageStep: finetune_imu trains IMU_Net through Upper_Net's head-pose gradients; Lower_Net and "
+                                 "UpperNetwlocal produce none")
+            if imu_net is None or pose is not None:
+                raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
+            if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
+                raise ValueError("StageStep: finetune_imu is not data parallel yet (no all-reduce of the IMU_Net gradients)")
+            if imu_net.rnn_fast.dropout > 0.0 or imu_net.rnn_slow.dropout > 0.0:
+                raise ValueError("StageStep: finetune_imu needs an IMU_Net built with dropout=0 (its training forward has no dropout)")
+            self.imu_opt = FusedAdam(imu_net.flat(), lr=lr if imu_lr is None else imu_lr, weight_decay=imu_weight_decay)
         self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay)
         self.pg = process_group
         self.use_graph = use_graph
@@ -185,6 +211,15 @@ class StageStep:
             ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
         x_src = s["x_src"] if via_transform else None
         with torch.no_grad():
+            if self.finetune_imu:
+                from . import imu_train
+                R, t = imu_train.forward_train(self.imu, s["imu"])
+                # (without x_src the net keeps its own copy of the untransformed points)
+                l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src, pose_grad=True)[0]
+                if not getattr(self.net, "_dy_ready", False):
+                    hip.call("l1_loss", l, s["target"], self.jmap, 15, 21, B * T, 1.0, self.loss2, s["dl"])
+                self.last_pred = l
+                return
             if self.pose is not None:
                 R, t = self.pose
             elif self.imu is not None:
@@ -217,6 +252,9 @@ class StageStep:
     def _body_backward(self):
         with torch.no_grad():
             self.net._backward_impl(self.static["dl"])
+            if self.finetune_imu:
+                from . import imu_train
+                imu_train.backward(self.imu, *self.net.pose_grads())
 
     def bind(self, x, imu, body, target, R_gt=None):
         """Register the (device-resident) minibatch buffers; contents may be overwritten between steps."""
@@ -234,7 +272,7 @@ class StageStep:
     def _mutable_state(self):
         """What a body changes besides gradients/activations: BatchNorm running statistics + step counters and the dropout
         counter of the trained net (the frozen nets run in eval mode)."""
-        return list(self.net.buffers()) + [self.net.seed_counter()]
+        return list(self.net.buffers()) + [self.net.seed_counter()] + ([self.imu.seed_counter()] if self.finetune_imu else [])
 
     def warm_up(self):
         """Run the body once WITHOUT side effects (sizes the arenas, sets kernel attributes before graph capture): the
@@ -261,6 +299,8 @@ class StageStep:
             self._body()
         allreduce_grads(self.net._flat, self.pg)
         self.opt.step()
+        if self.finetune_imu:
+            self.imu_opt.step()
         return self.loss
 
 
@@ -319,6 +359,7 @@ class SharedImuStages:
 
     def __init__(self, imu_net, stages, imu_in, use_graph=True):
         self.imu, self.stages, self.imu_in = imu_net, list(stages), imu_in
+        _refuse_finetune("SharedImuStages", self.stages)
         B, T = imu_in.shape[0], imu_in.shape[1]
         dev = imu_in.device
         self.R, self.t = torch.empty(B, T, 3, 3, device=dev), torch.empty(B, T, 3, device=dev)
@@ -368,6 +409,7 @@ class ConcurrentStages:
 
     def __init__(self, stages, use_graph=True, unguarded=False):
         self.stages = list(stages)
+        _refuse_finetune("ConcurrentStages", self.stages)
         # unguarded: keep the concurrent branches even when a net runs bf16-MFMA kernels (bench.py's comparison figure and the
         # reproducers of scripts/ only; see needs_exclusive)
         self.unguarded = unguarded
@@ -509,6 +551,7 @@ class PipelinedStages:
 
     def __init__(self, stages, imu_nets, imu_next, use_graph=True, unguarded=False):
         self.stages, self.imus, self.imu_next = list(stages), list(imu_nets), imu_next
+        _refuse_finetune("PipelinedStages", self.stages)
         if len(self.stages) != len(self.imus) or any(st.imu is not None for st in self.stages):
             raise ValueError("PipelinedStages: one IMU_Net per stage, and the stages themselves must be built with imu_net=None")
         if len({id(m) for m in self.imus}) != len(self.imus):
