@@ -12,15 +12,10 @@
 //                            (consumers: pooling, heads) and as bf16 (next step's / next layer's product operand).
 //                            The recurrent operands live in a fragment-major layout (see below).
 #include "common.h"
+#include "bf16_pack.h"
+#include "lds_dma.h"
+#include "lstm_cell.h"
 #include "tile_order.h"
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef unsigned short bf16_t;   // raw bf16 bits (the C ABI carries them as unsigned short)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// round to nearest even, NaN stays NaN: v_cvt_pk_bf16_f32 on gfx950 (the integer form -- add 0x7fff + lsb, shift, a branch for NaN --
-// was five VALU instructions and a branch per value)
-__device__ __forceinline__ unsigned int f2bf_bits(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
 
 // ---- fp32 -> bf16 ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cvt_bf16_kernel(const float* __restrict__ X, long ldx, long rows, long cols4,
@@ -30,8 +25,8 @@ __global__ __launch_bounds__(256) void cvt_bf16_kernel(const float* __restrict__
     const long r = i / cols4, c = (i - r * cols4) * 4;
     const f32x4 v = *reinterpret_cast<const f32x4*>(X + r * ldx + c);
     uint2 o;
-    o.x = f2bf_bits(v[0]) | (f2bf_bits(v[1]) << 16);
-    o.y = f2bf_bits(v[2]) | (f2bf_bits(v[3]) << 16);
+    o.x = f2bf(v[0]) | (f2bf(v[1]) << 16);
+    o.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
     *reinterpret_cast<uint2*>(Y + r * ldy + c) = o;
   }
 }
@@ -57,8 +52,8 @@ __global__ __launch_bounds__(256) void cvt_bf16_tm_kernel(const float* __restric
     const long b = r / T, t = r - b * T;
     const f32x4 v = *reinterpret_cast<const f32x4*>(X + r * ldx + c);
     uint2 o;
-    o.x = f2bf_bits(v[0]) | (f2bf_bits(v[1]) << 16);
-    o.y = f2bf_bits(v[2]) | (f2bf_bits(v[3]) << 16);
+    o.x = f2bf(v[0]) | (f2bf(v[1]) << 16);
+    o.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
     *reinterpret_cast<uint2*>(Y + (t * Bp + b) * (cols4 * 4) + c) = o;
   }
 }
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBfP p) {
           float v = acc[mi][ni][i] + bv;
           if (p.relu) v = fmaxf(v, 0.f);
           if (p.C) p.C[(long)row * p.ldc + col] = v;
-          if (p.Cb) p.Cb[(long)row * p.ldcb + col] = (bf16_t)f2bf_bits(v);
+          if (p.Cb) p.Cb[(long)row * p.ldcb + col] = (bf16_t)f2bf(v);
         }
       }
     }
@@ -255,9 +250,6 @@ struct StepBfP {
   int Bn, H, first;
 };
 
-__device__ __forceinline__ float bf_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float bf_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 __device__ __forceinline__ long frag_off(int r, int k, int H) {
   return ((((long)(r >> 5) * (H >> 4) + (k >> 4)) * 64) + ((k >> 3) & 1) * 32 + (r & 31)) * 8 + (k & 7);
 }
@@ -271,12 +263,11 @@ __device__ __forceinline__ const f32x4* xp_tile(const StepBfP& p, int d, int rb,
 // cell update of one (row, j) and the three stores of h_t
 __device__ __forceinline__ void bf_cell(const StepBfP& p, int d, int row, int j, float pi, float pf, float pg, float po,
                                         float cprev) {
-  const float gi = bf_sigmoid(pi), gf = bf_sigmoid(pf), gg = bf_tanh(pg), go = bf_sigmoid(po);
-  const float cn = gf * cprev + gi * gg;
-  const float hn = go * bf_tanh(cn);
+  const LstmCell u = lstm_cell_fwd(pi, pf, pg, po, cprev);
+  const float cn = u.c, hn = u.h;
   p.c[d][(long)row * p.H + j] = cn;
   p.hout[d][(long)row * p.hos + j] = hn;
-  const bf16_t hb = (bf16_t)f2bf_bits(hn);
+  const bf16_t hb = (bf16_t)f2bf(hn);
   if (p.houtb[d]) p.houtb[d][(long)row * p.hbs + j] = hb;
   p.hfrag[d][frag_off(row, j, p.H)] = hb;
 }
@@ -566,10 +557,10 @@ __global__ __launch_bounds__(256) void cvt_bf16_frag_tm_kernel(const float* __re
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(X + r * ldx + k);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(X + r * ldx + k + 4);
     u32x4 o;
-    o[0] = f2bf_bits(v0[0]) | (f2bf_bits(v0[1]) << 16);
-    o[1] = f2bf_bits(v0[2]) | (f2bf_bits(v0[3]) << 16);
-    o[2] = f2bf_bits(v1[0]) | (f2bf_bits(v1[1]) << 16);
-    o[3] = f2bf_bits(v1[2]) | (f2bf_bits(v1[3]) << 16);
+    o[0] = f2bf(v0[0]) | (f2bf(v0[1]) << 16);
+    o[1] = f2bf(v0[2]) | (f2bf(v0[3]) << 16);
+    o[2] = f2bf(v1[0]) | (f2bf(v1[1]) << 16);
+    o[3] = f2bf(v1[2]) | (f2bf(v1[3]) << 16);
     *reinterpret_cast<u32x4*>(Y + (long)t * Bp * C + frag_off(b, k, C)) = o;
   }
 }
@@ -625,10 +616,10 @@ __global__ __launch_bounds__(256) void fc_relu_bf16_frag_tm_kernel(const float* 
       y[j] = live ? (relu ? fmaxf(a, 0.f) : a) : 0.f;
     }
     u32x4 o;
-    o[0] = f2bf_bits(y[0]) | (f2bf_bits(y[1]) << 16);
-    o[1] = f2bf_bits(y[2]) | (f2bf_bits(y[3]) << 16);
-    o[2] = f2bf_bits(y[4]) | (f2bf_bits(y[5]) << 16);
-    o[3] = f2bf_bits(y[6]) | (f2bf_bits(y[7]) << 16);
+    o[0] = f2bf(y[0]) | (f2bf(y[1]) << 16);
+    o[1] = f2bf(y[2]) | (f2bf(y[3]) << 16);
+    o[2] = f2bf(y[4]) | (f2bf(y[5]) << 16);
+    o[3] = f2bf(y[6]) | (f2bf(y[7]) << 16);
     dst[(long)k16 * 64] = o;
   }
 }
@@ -693,10 +684,10 @@ __global__ __launch_bounds__(256) void fc_relu_bf16_frag_tm_mfma_kernel(const fl
 #pragma unroll
         for (int q = 0; q < 8; ++q) y[q] = live ? tl[prow * 33 + pc * 16 + pc8 * 8 + q] : 0.f;
         u32x4 o;
-        o[0] = f2bf_bits(y[0]) | (f2bf_bits(y[1]) << 16);
-        o[1] = f2bf_bits(y[2]) | (f2bf_bits(y[3]) << 16);
-        o[2] = f2bf_bits(y[4]) | (f2bf_bits(y[5]) << 16);
-        o[3] = f2bf_bits(y[6]) | (f2bf_bits(y[7]) << 16);
+        o[0] = f2bf(y[0]) | (f2bf(y[1]) << 16);
+        o[1] = f2bf(y[2]) | (f2bf(y[3]) << 16);
+        o[2] = f2bf(y[4]) | (f2bf(y[5]) << 16);
+        o[3] = f2bf(y[6]) | (f2bf(y[7]) << 16);
         dst[(long)(((wave * NCTW + j) * 2 + pc)) * 64] = o;
       }
       __builtin_amdgcn_wave_barrier();
@@ -859,11 +850,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4 / WR, 4 /
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const float cprev = p.o.first ? 0.f : cn[i];
-      const float gi = bf_sigmoid(acc[mi][0][i] + bv[0]), gf = bf_sigmoid(acc[mi][1][i] + bv[1]);
-      const float gg = bf_tanh(acc[mi][2][i] + bv[2]), go = bf_sigmoid(acc[mi][3][i] + bv[3]);
-      cn[i] = gf * cprev + gi * gg;
-      hn[i] = go * bf_tanh(cn[i]);
+      const LstmCell u = lstm_cell_fwd(acc[mi][0][i] + bv[0], acc[mi][1][i] + bv[1], acc[mi][2][i] + bv[2], acc[mi][3][i] + bv[3],
+                                       p.o.first ? 0.f : cn[i]);
+      cn[i] = u.c;
+      hn[i] = u.h;
     }
     if (rb * 32 + 32 <= p.o.Bn) {                          // whole row block: no predicate per element
 #pragma unroll
@@ -871,12 +861,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4 / WR, 4 /
         const int row = rb * 32 + 8 * (i >> 2) + 4 * fh + (i & 3);
         p.o.c[d][(long)row * H + j] = cn[i];
         if (p.o.hout[d]) p.o.hout[d][(long)row * p.o.hos + j] = hn[i];
-        p.o.hfrag[d][frag_off(row, j, H)] = (bf16_t)f2bf_bits(hn[i]);
+        p.o.hfrag[d][frag_off(row, j, H)] = (bf16_t)f2bf(hn[i]);
       }
     } else {
       unsigned short hb[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) hb[i] = f2bf_bits(hn[i]);
+      for (int i = 0; i < 16; ++i) hb[i] = f2bf(hn[i]);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int row = rb * 32 + 8 * (i >> 2) + 4 * fh + (i & 3);
@@ -918,10 +908,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4 / WR, 4 /
 // 512 of K and 30 us more per launch in the cell update: the loop is not bound by LDS traffic either; every second workgroup started
 // 7-27 us late so that store bursts meet product loops -- slower by about a third of the delay.  What the numbers say together: the loop
 // runs at ~0.7 of the MFMA rate the clock under this load allows, and 130 us of a 335-us launch are the eight cell updates.
-#define GLDS16B(gptr, lptr)                                                                                 \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                   \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-
 template <bool HOUT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void lstm_step_bf16_fused256_kernel(FusedStepP p, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem256[];
@@ -955,7 +941,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned char* g0 = (q0 < 32 ? ab : wb) + ((blk0 * S + s0) << 10) + lane * 16;
     const long blk_stride = (long)S << 10;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) GLDS16B(g0 + (i >> 2) * blk_stride + ((i & 3) << 10), st + ((q0 + i) << 10));
+    for (int i = 0; i < 8; ++i) GLDS16(g0 + (i >> 2) * blk_stride + ((i & 3) << 10), st + ((q0 + i) << 10));
   };
   // the c tile [256 rows][64 units] fp32 of a workgroup as 64 pieces of 4 rows (lane l: row 4 piece + l / 16, 16 B at column 4 (l % 16))
   auto issue_c = [&](int tile, int stage) {
@@ -963,7 +949,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float* cb = p.o.c[d] + ((long)rbw * 256 + (lane >> 4)) * H + jb * 64 + (lane & 15) * 4;
     unsigned char* st = smem256 + stage * STAGE;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) GLDS16B(cb + (long)(q0 + i) * 4 * H, st + ((q0 + i) << 10));
+    for (int i = 0; i < 8; ++i) GLDS16(cb + (long)(q0 + i) * 4 * H, st + ((q0 + i) << 10));
   };
 
   const int fr = lane & 31, fh = lane >> 5;
@@ -1013,8 +999,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       // all but the youngest 63 operations done covers them, and waits for no more of those stores than it must
       // (younger than those pieces: the cell update's stores, counted by the constants its loops run on -- EPI_YOUNGER above; the
       // wait may leave at most that many operations outstanding, and the counter holds 63)
-      if (c == 0 && it > 0) __builtin_amdgcn_s_waitcnt(0x0F70 | (EPI_WAIT & 15) | ((EPI_WAIT >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);                                        // vmcnt(0)
+      if (c == 0 && it > 0) wait_vmcnt<EPI_WAIT>();
+      else wait_vmcnt<0>();
       F256_BARRIER();                          // everyone's pieces of chunk c are in LDS; everyone has finished the other stage
       if (c + 1 < NC) issue(tile, c + 1, stage ^ 1);
       else if (!first) issue_c(tile, stage ^ 1);
@@ -1038,7 +1024,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     // `stage` now holds the c tile (its DMAs were issued a whole chunk ago); the other stage is free once everyone has passed
     // this barrier: the next tile's first chunk goes there now, and the ring continues from that stage
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vmcnt<0>();
     F256_BARRIER();
     const float* cs = reinterpret_cast<const float*>(smem256 + stage * STAGE);
     stage ^= 1;
@@ -1066,11 +1052,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       float cn[16], hn[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float cprev = first ? 0.f : cv[mi][i];
-        const float gi = bf_sigmoid(acc[mi][0][i] + bv[0]), gf = bf_sigmoid(acc[mi][1][i] + bv[1]);
-        const float gg = bf_tanh(acc[mi][2][i] + bv[2]), go = bf_sigmoid(acc[mi][3][i] + bv[3]);
-        cn[i] = gf * cprev + gi * gg;
-        hn[i] = go * bf_tanh(cn[i]);
+        const LstmCell u = lstm_cell_fwd(acc[mi][0][i] + bv[0], acc[mi][1][i] + bv[1], acc[mi][2][i] + bv[2], acc[mi][3][i] + bv[3],
+                                         first ? 0.f : cv[mi][i]);
+        cn[i] = u.c;
+        hn[i] = u.h;
       }
       // addresses = a wave-uniform row base (scalar arithmetic) + one per-lane offset that does not depend on i
       // addresses = a wave-uniform row base + one per-lane offset that does not depend on i
@@ -1083,7 +1068,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (HOUT) hwave[(long)(8 * (i >> 2) + (i & 3)) * p.o.hos + hl] = hn[i];
         // piece (mi, fr >> 4) of the wave's four; inside it [k half][row % 32][8 k]
         *reinterpret_cast<bf16_t*>(hst + ((((mi * 2 + (fr >> 4)) * 64 + ((fr >> 3) & 1) * 32 + 4 * fh + 8 * (i >> 2) + (i & 3)) * 8 + (fr & 7)) << 1)) =
-            __builtin_bit_cast(bf16_t, (__bf16)hn[i]);      // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN (f2bf_bits' branch per element gone)
+            (bf16_t)f2bf(hn[i]);
       }
     }
     {

@@ -60,6 +60,7 @@ __device__ __forceinline__ bool dropout_keep(unsigned key, unsigned i, float p) 
 // In-kernel clock stamps: compiled ONLY into the diagnostic probe (scripts/clock_probe.hip defines MMEGO_STAMP); the
 // product library contains no stamp.  Slot s of workgroup b holds {s_memtime, s_memrealtime} taken by one lane.
 #ifdef MMEGO_STAMP
+#include "lds_dma.h"
 #define MMEGO_STAMP_SLOTS 4
 __device__ unsigned long long mmego_stamp_buf[8192 * MMEGO_STAMP_SLOTS * 2];
 __device__ unsigned int mmego_stamp_hw[8192 * 2];   // {HW_ID, XCC_ID} of the stamping wave (where the workgroup ran)
@@ -68,7 +69,7 @@ __device__ unsigned int mmego_stamp_hw[8192 * 2];   // {HW_ID, XCC_ID} of the st
     __builtin_amdgcn_sched_barrier(0);                                                               \
     if (cond) {                                                                                      \
       unsigned long long t_ = __builtin_amdgcn_s_memtime(), r_ = __builtin_amdgcn_s_memrealtime();   \
-      __builtin_amdgcn_s_waitcnt(0xC07F);                                                            \
+      wait_lgkmcnt0();                                                                               \
       mmego_stamp_buf[(((id) & 8191) * MMEGO_STAMP_SLOTS + (slot)) * 2] = t_;                  \
       mmego_stamp_buf[(((id) & 8191) * MMEGO_STAMP_SLOTS + (slot)) * 2 + 1] = r_;              \
       if ((slot) == 0) {                                                                             \

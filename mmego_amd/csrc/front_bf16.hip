@@ -14,20 +14,12 @@
 // puts the four point columns BEHIND them (k 24..27); the weight columns of that layer are permuted to match when they are staged.
 // The softmax pooling accumulates per lane (its point, its 16 features) and is reduced over the points once per frame.
 #include "common.h"
+#include "bf16_pack.h"
 
-typedef unsigned short bf16_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-// (a float -> __bf16 conversion is v_cvt_pk_bf16_f32 on gfx950: round to nearest even, NaN stays NaN -- one instruction for two
-// values where the integer form took five per value)
-typedef float lo_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 lo_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned int frb_bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ unsigned int frb_bf2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector((lo_f32x2){lo, hi}, lo_bf16x2));
-}
 __device__ __forceinline__ uint2 frb_pack4(float a, float b, float c, float d) {
-  return make_uint2(frb_bf2(a, b), frb_bf2(c, d));
+  return make_uint2(f2bf2(a, b), f2bf2(c, d));
 }
 
 #define FR_SLAB 16
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(256) void upper_front_eval_bf16_kernel(FrontP p) {
       for (int u = 0; u < Cp[L] * Kp[L] / 256; ++u) {
         const int i = tid + 256 * u, n = i / Kp[L], k = i - n * Kp[L];
         FR_PIN(w[u0 + u]);
-        shw[Wo[L] + n * Sw[L] + k] = (bf16_t)frb_bf((n < Cn[L] && k < Kn[L]) ? scale[So[L] + n] * w[u0 + u] : 0.f);
+        shw[Wo[L] + n * Sw[L] + k] = (bf16_t)f2bf((n < Cn[L] && k < Kn[L]) ? scale[So[L] + n] * w[u0 + u] : 0.f);
       }
       u0 += Cp[L] * Kp[L] / 256;
     }

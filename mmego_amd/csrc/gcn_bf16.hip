@@ -20,19 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef unsigned short bf16_t;   // raw bf16 bits (the C ABI carries them as unsigned short)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// (a float -> __bf16 conversion is v_cvt_pk_bf16_f32 on gfx950: round to nearest even, NaN stays NaN -- one instruction for two
-// values where the integer form took five per value)
-typedef float lo_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 lo_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned int f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ unsigned int f2bf2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector((lo_f32x2){lo, hi}, lo_bf16x2));
-}
+#include "bf16_pack.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------
 struct TconvBfP {

@@ -16,6 +16,7 @@
 #include "../../include/mmego_hip.h"       // MmegoGemmDesc (mmego_gemm_group)
 
 #include "gemm_tile.h"
+#include "lstm_cell.h"
 #include "tile_order.h"
 
 struct GemmP {
@@ -274,8 +275,8 @@ __device__ __forceinline__ void gemm32kq_body(const GemmP& p, const int bx, cons
     }
   }
   if (p.cb_dg[0]) {
-    // LSTM cell backward on the tile (the expressions of lstm_cell_bwd_kernel, imu_train.hip: same bits): whole tiles only (the
-    // launcher checks), N = H; every load of the thread's four elements before its first store
+    // LSTM cell backward on the tile (lstm_cell_bwd of lstm_cell.h with libm tanhf, as lstm_cell_bwd_kernel of imu_train.hip: same
+    // bits): whole tiles only (the launcher checks), N = H; every load of the thread's four elements before its first store
     const int col = tid & 31, H = p.N, d = batch;
     float dh[4], gi[4], gf[4], gg[4], go[4], cc[4], cp[4], dcin[4];
 #pragma unroll
@@ -290,25 +291,19 @@ __device__ __forceinline__ void gemm32kq_body(const GemmP& p, const int bx, cons
       cp[e] = p.cb_cprev[d] ? p.cb_cprev[d][i] : 0.f;
       dcin[e] = p.cb_dc[d][i];
     }
-    float o0[4], o1[4], o2[4], o3[4], dco[4];
+    LstmCellGrad o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       asm volatile("" : "+v"(gi[e]), "+v"(gf[e]), "+v"(gg[e]), "+v"(go[e]), "+v"(cc[e]), "+v"(cp[e]), "+v"(dcin[e]), "+v"(dh[e]));
-      const float tc = tanhf(cc[e]);
-      const float dcv = dcin[e] + dh[e] * go[e] * (1.f - tc * tc);
-      o0[e] = dcv * gg[e] * gi[e] * (1.f - gi[e]);
-      o1[e] = dcv * cp[e] * gf[e] * (1.f - gf[e]);
-      o2[e] = dcv * gi[e] * (1.f - gg[e] * gg[e]);
-      o3[e] = dh[e] * tc * go[e] * (1.f - go[e]);
-      dco[e] = dcv * gf[e];
+      o[e] = lstm_cell_bwd(gi[e], gf[e], gg[e], go[e], tanhf(cc[e]), cp[e], dcin[e], dh[e]);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int row = (tid >> 5) + 8 * e;
       const long r = m0 + row, j = n0 + col;
       float* dg = p.cb_dg[d] + r * p.cb_dgs + j;
-      dg[0] = o0[e]; dg[H] = o1[e]; dg[2 * H] = o2[e]; dg[3 * H] = o3[e];
-      p.cb_dc[d][r * H + j] = dco[e];
+      dg[0] = o[e].di; dg[H] = o[e].df; dg[2 * H] = o[e].dg; dg[3 * H] = o[e].dout;
+      p.cb_dc[d][r * H + j] = o[e].dcprev;
     }
     return;
   }

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "gemm_tile.h"
+#include "lds_dma.h"
 #include "tile_order.h"
 
 #define TLD_MAX 68
@@ -260,8 +261,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tile_big_kernel(TileP p, TileBigA
 #define GTB_DMA(kt, stage)                                                                                                  \
   if (!((GTB_EXP & 1) && (kt) > 1)) {                                                                                       \
     _Pragma("unroll") for (int j = 0; j < 9; ++j)                                                                           \
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gp[j] + (long)(kt) * KCH),            \
-                                       (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + (w + 8 * j) * 8 * KCH), 16, 0, 0); \
+      GLDS16(gp[j] + (long)(kt) * KCH, smem + (stage) * STAGE + (w + 8 * j) * 8 * KCH);                                     \
   }
   const int nk = (kend - kbeg) / KCH;
   const int r = lane & 31, h = lane >> 5, key = (r >> 1) & 7;

@@ -2,6 +2,7 @@
 // Reference: Processor/Train/Train_IMU.py:21-34 (GeodesicLoss), :138-141 (loss), Net/IMU_Net.py:7-47 (6-D head).
 // The recurrent products of the backward pass (dh_{t-1} = dgates . W_hh, dW = dgates^T . [x, h]) are mmego_gemm calls.
 #include "common.h"
+#include "lstm_cell.h"
 
 struct CellBwdP {
   const float* dout[2]; long dos;
@@ -24,14 +25,13 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(CellBwdP p) {
     const float gi = gs[0], gf = gs[p.H], gg = gs[2 * p.H], go = gs[3 * p.H];
     const float c = p.cst[d][i];
     const float cprev = p.cprev[d] ? p.cprev[d][i] : 0.f;
-    const float tc = tanhf(c);
-    const float dcv = p.dc[d][i] + dh * go * (1.f - tc * tc);
+    const LstmCellGrad o = lstm_cell_bwd(gi, gf, gg, go, tanhf(c), cprev, p.dc[d][i], dh);
     float* dg = p.dgates[d] + row * p.dgs + j;
-    dg[0] = dcv * gg * gi * (1.f - gi);
-    dg[p.H] = dcv * cprev * gf * (1.f - gf);
-    dg[2 * p.H] = dcv * gi * (1.f - gg * gg);
-    dg[3 * p.H] = dh * tc * go * (1.f - go);
-    p.dc[d][i] = dcv * gf;
+    dg[0] = o.di;
+    dg[p.H] = o.df;
+    dg[2 * p.H] = o.dg;
+    dg[3 * p.H] = o.dout;
+    p.dc[d][i] = o.dcprev;
   }
 }
 

@@ -12,6 +12,7 @@
 //                     the recurrence, so a workgroup keeps W_hh (64 KB) in LDS, 16 rows of h in LDS and c
 //                     in registers and walks all T steps with no inter-workgroup traffic.
 #include "common.h"
+#include "lstm_cell.h"
 #include <stddef.h>
 #include "../../include/mmego_hip.h"       // MmegoLstm64Fwd / MmegoLstm64Bwd (the _multi entry points)
 
@@ -32,10 +33,8 @@ struct Lstm64P {
   float* drop_y; float* drop_mask; float drop_p; const unsigned long long* seed_ctr; unsigned salt;
 };
 
-// rcp / v_exp_f32-based activations: a few ulp from the libm forms at a fraction of their instruction count (the step loop
-// of this kernel issued ~490 VALU instructions per 64 MFMAs, most of them libm expf and 64-bit address arithmetic)
-__device__ __forceinline__ float l64_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float l64_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+// (the cell update runs on the fast activations of lstm_cell.h: the step loop of this kernel issued ~490 VALU instructions per 64
+// MFMAs, most of them libm expf and 64-bit address arithmetic)
 
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load / store
 // (vmcnt(0)), which would put the prefetch of the next step's inputs and this step's stash stores back on the critical path.
@@ -48,9 +47,8 @@ __device__ __forceinline__ float l64_tanh(float x) { return 1.0f - 2.0f * __buil
 // loads and stores in flight.  Explicit global address space keeps them global_load / global_store (vmcnt only).
 typedef const float __attribute__((address_space(1)))* l64_gcptr;
 typedef float __attribute__((address_space(1)))* l64_gptr;
-typedef float l64_f4 __attribute__((ext_vector_type(4)));
-typedef l64_f4 __attribute__((address_space(1)))* l64_gptr4;
-typedef const l64_f4 __attribute__((address_space(1)))* l64_gcptr4;
+typedef f32x4 __attribute__((address_space(1)))* l64_gptr4;
+typedef const f32x4 __attribute__((address_space(1)))* l64_gcptr4;
 
 // FULL: B is a multiple of the 16 rows of a workgroup, so every `live` test is a compile-time true; STASH / DROP: the backward
 // stashes (gates, cell states, h_{t-1}: all or none) / the fused inter-layer dropout.  Template parameters so that the step loop is
@@ -157,12 +155,9 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
     L64_LDS_BARRIER();  // everyone has finished reading hs for this step
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      float gi = l64_sigmoid(acc[0][reg] + (xp[0][reg] + bh[0]));
-      float gf = l64_sigmoid(acc[1][reg] + (xp[1][reg] + bh[1]));
-      float gg = l64_tanh(acc[2][reg] + (xp[2][reg] + bh[2]));
-      float go = l64_sigmoid(acc[3][reg] + (xp[3][reg] + bh[3]));
-      float cn = gf * creg[reg] + gi * gg;
-      float hn = go * l64_tanh(cn);
+      const LstmCell u = lstm_cell_fwd(acc[0][reg] + (xp[0][reg] + bh[0]), acc[1][reg] + (xp[1][reg] + bh[1]),
+                                       acc[2][reg] + (xp[2][reg] + bh[2]), acc[3][reg] + (xp[3][reg] + bh[3]), creg[reg]);
+      const float cn = u.c, hn = u.h;
       creg[reg] = cn;
       hreg[reg] = hn;
       hs[j * 16 + fq * 4 + reg] = hn;
@@ -175,7 +170,7 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
           p.drop_y[off] = hn * mk;
         }
         if (stash) {
-          *(l64_gptr4)gq[reg] = (l64_f4){gi, gf, gg, go};       // one 16-B store (was four dword stores 256 B apart)
+          *(l64_gptr4)gq[reg] = (f32x4){u.i, u.f, u.g, u.o};      // one 16-B store (was four dword stores 256 B apart)
           *cq[reg] = cn;
         }
       }
@@ -306,7 +301,7 @@ __device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
     _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) {                                                      \
       const int row_ = r0 + fq * 4 + reg;                                                                      \
       if (FULL || row_ < B) {                                                                                  \
-        const l64_f4 gv_ = *(l64_gcptr4)(g_gates + ((long)tq_ * B + row_) * 256 + 4 * j);                      \
+        const f32x4 gv_ = *(l64_gcptr4)(g_gates + ((long)tq_ * B + row_) * 256 + 4 * j);                       \
         DST[reg][0] = g_dout[((long)row_ * T + tq_) * p.dos + d * 64 + j];                                     \
         DST[reg][1] = gv_.x; DST[reg][2] = gv_.y; DST[reg][3] = gv_.z; DST[reg][4] = gv_.w;                    \
         const l64_gcptr cp_ = ((step) > 0) ? g_cst + ((long)tp_ * B + row_) * 64 + j : g_c0 + (long)row_ * 64 + j; \
@@ -337,15 +332,12 @@ __device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
       if (FULL || row < B) {
         float dh = gin[reg][0] + dhrec[reg];
         float gi = gin[reg][1], gf = gin[reg][2], gg = gin[reg][3], go = gin[reg][4];
-        float c = ccur[reg];
-        float cprev = gin[reg][5];
-        float tc = l64_tanh(c);
-        float dc = dcreg[reg] + dh * go * (1.f - tc * tc);
-        dg4[0][reg] = dc * gg * gi * (1.f - gi);
-        dg4[1][reg] = dc * cprev * gf * (1.f - gf);
-        dg4[2][reg] = dc * gi * (1.f - gg * gg);
-        dg4[3][reg] = dh * tc * go * (1.f - go);
-        dcreg[reg] = dc * gf;
+        const LstmCellGrad o = lstm_cell_bwd(gi, gf, gg, go, fast_tanh(ccur[reg]), gin[reg][5], dcreg[reg], dh);   // (tanh: the forward's fast form)
+        dg4[0][reg] = o.di;
+        dg4[1][reg] = o.df;
+        dg4[2][reg] = o.dg;
+        dg4[3][reg] = o.dout;
+        dcreg[reg] = o.dcprev;
         l64_gptr dst = (l64_gptr)p.dgates[d] + ((long)row * T + tt) * p.dgs + j;
 #pragma unroll
         for (int g = 0; g < 4; ++g) dst[g * 64] = dg4[g][reg];

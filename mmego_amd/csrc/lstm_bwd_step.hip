@@ -15,6 +15,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_dma.h"
+#include "lstm_cell.h"
 #include "tile_order.h"
 
 struct LstmBwdStepP {
@@ -25,10 +27,6 @@ struct LstmBwdStepP {
   float* dc[2]; float* dgo[2];
   int Bn, H;
 };
-
-#define BGLDS16(gptr, lptr)                                                                                 \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                   \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 __global__ __launch_bounds__(512) void lstm_bwd_step_dma_kernel(LstmBwdStepP p) {
   constexpr int HT = 32, KC = 64;
@@ -63,21 +61,21 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_dma_kernel(LstmBwdStepP p) 
 #define B2_CHUNK(kt)                                                                                        \
   do {                                                                                                      \
     float* st_ = smem + ((kt) % 3) * STAGE;                                                                 \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) BGLDS16(ag[i] + (kt) * KC, st_ + 4 * (lw + 4 * i) * KC);  \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j) BGLDS16(wg_[j] + (kt) * KC, st_ + 64 * KC + 4 * (lw + 4 * j) * KC); \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) GLDS16(ag[i] + (kt) * KC, st_ + 4 * (lw + 4 * i) * KC);   \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) GLDS16(wg_[j] + (kt) * KC, st_ + 64 * KC + 4 * (lw + 4 * j) * KC); \
   } while (0)
     constexpr int PC = 6;                      // DMAs per loader wave and chunk
     B2_CHUNK(0);
     if (nk > 1) B2_CHUNK(1);
     if (nk > 2) B2_CHUNK(2);
-    if (nk > 2) __builtin_amdgcn_s_waitcnt(0x0F70 | ((2 * PC) & 15) | (((2 * PC) >> 4) << 14));
-    else if (nk > 1) __builtin_amdgcn_s_waitcnt(0x0F70 | (PC & 15) | ((PC >> 4) << 14));
-    else __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (nk > 2) wait_vmcnt<2 * PC>();
+    else if (nk > 1) wait_vmcnt<PC>();
+    else wait_vmcnt<0>();
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();              // (1) chunk 0 is in LDS
     for (int kt = 0; kt + 1 < nk; ++kt) {      // B_kt: chunk kt+1 has landed; stage kt % 3 may be refilled
-      if (kt + 2 < nk) __builtin_amdgcn_s_waitcnt(0x0F70 | (PC & 15) | ((PC >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      if (kt + 2 < nk) wait_vmcnt<PC>();
+      else wait_vmcnt<0>();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
       if (kt + 3 < nk) B2_CHUNK(kt + 3);
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_dma_kernel(LstmBwdStepP p) 
       B2_MM(pa, pb);
       __builtin_amdgcn_sched_barrier(0);
       if (kt + 1 < nk) {
-        __builtin_amdgcn_s_waitcnt(0xC07F);    // this wave's reads of stage kt are done (the builtin: the compiler's wait-count pass sees it)
+        wait_lgkmcnt0();                       // this wave's reads of stage kt are done
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();          // B_kt: chunk kt+1 has landed, stage kt may be refilled
         so = (so == 2 * STAGE) ? 0 : so + STAGE;
@@ -157,29 +155,22 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_dma_kernel(LstmBwdStepP p) 
 #undef B2_RD
 #undef B2_MM
   }
-  // LSTM cell backward on the tile (the expressions of lstm_cell_bwd_kernel, imu_train.hip)
-  float o0[2][4], o1[2][4], o2[2][4], o3[2][4], dco[2][4];
+  // LSTM cell backward on the tile (lstm_cell_bwd of lstm_cell.h with libm tanhf, as lstm_cell_bwd_kernel of imu_train.hip)
+  LstmCellGrad o[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const float dhv = dh[i][reg] + acc[i][reg];
-      const float tc = tanhf(cc[i][reg]);
-      const float dcv = dcin[i][reg] + dhv * go[i][reg] * (1.f - tc * tc);
-      o0[i][reg] = dcv * gg[i][reg] * gi[i][reg] * (1.f - gi[i][reg]);
-      o1[i][reg] = dcv * cp[i][reg] * gf[i][reg] * (1.f - gf[i][reg]);
-      o2[i][reg] = dcv * gi[i][reg] * (1.f - gg[i][reg] * gg[i][reg]);
-      o3[i][reg] = dhv * tc * go[i][reg] * (1.f - go[i][reg]);
-      dco[i][reg] = dcv * gf[i][reg];
-    }
+    for (int reg = 0; reg < 4; ++reg)
+      o[i][reg] = lstm_cell_bwd(gi[i][reg], gf[i][reg], gg[i][reg], go[i][reg], tanhf(cc[i][reg]), cp[i][reg], dcin[i][reg],
+                                dh[i][reg] + acc[i][reg]);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const long r = r0 + rowbase + 16 * i + 4 * fq + reg;
       float* dgp = p.dgo[d] + r * p.dgs + jj;
-      dgp[0] = o0[i][reg]; dgp[H] = o1[i][reg]; dgp[2 * H] = o2[i][reg]; dgp[3 * H] = o3[i][reg];
-      p.dc[d][r * H + jj] = dco[i][reg];
+      dgp[0] = o[i][reg].di; dgp[H] = o[i][reg].df; dgp[2 * H] = o[i][reg].dg; dgp[3 * H] = o[i][reg].dout;
+      p.dc[d][r * H + jj] = o[i][reg].dcprev;
     }
 }
 

@@ -26,10 +26,11 @@
 // only become resident after that (their tags are long overwritten) leave after LQ_SPIN_CHECK retries.
 // The last workgroup to finish resets the counters, so a launch leaves them as it found them (graph replays need no memset node).
 // Arithmetic: the products accumulate in another order than the step kernels' (k split over lane groups and four chains), so results
-// agree with them to fp32 rounding, not bit for bit; gate non-linearities and the cell update are the step kernels' expressions.
+// agree with them to fp32 rounding, not bit for bit; gate non-linearities and the cell update are lstm_cell.h's, as in the step kernels.
 #include <stdlib.h>
 
 #include "common.h"
+#include "lstm_cell.h"
 
 #define LQ_H 512
 #define LQ_RS (LQ_H + 4)                  // LDS row stride of the h tile (floats): 16-byte aligned, rows on distinct bank groups
@@ -44,10 +45,6 @@ struct LstmSeqP {
   unsigned long long* xbuf;              // [2 stages][8 groups][16 rows][512] (value bits | tag << 32), zero before the first launch
   int Bn, T;
 };
-
-// (the step kernels' forms: lstm_step.hip)
-__device__ __forceinline__ float lq_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float lq_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 __global__ __launch_bounds__(256, 2) void lstm_seq_xcd_kernel(LstmSeqP p) {
   __shared__ __attribute__((aligned(16))) float hs[16 * LQ_RS];       // h_{t-1} of the group's 16 rows
@@ -160,12 +157,9 @@ __global__ __launch_bounds__(256, 2) void lstm_seq_xcd_kernel(LstmSeqP p) {
       for (int q = 0; q < 4; ++q) pre[q] = gs[q][crow][cu];
     }
     // ---- cell update of (row, unit): PyTorch gate order i, f, g, o
-    const float gi = lq_sigmoid(pre[0] + (xp[0] + bh[0]));
-    const float gf = lq_sigmoid(pre[1] + (xp[1] + bh[1]));
-    const float gg = lq_tanh(pre[2] + (xp[2] + bh[2]));
-    const float go = lq_sigmoid(pre[3] + (xp[3] + bh[3]));
-    creg = gf * creg + gi * gg;
-    const float hval = go * lq_tanh(creg);
+    const LstmCell u = lstm_cell_fwd(pre[0] + (xp[0] + bh[0]), pre[1] + (xp[1] + bh[1]), pre[2] + (xp[2] + bh[2]), pre[3] + (xp[3] + bh[3]), creg);
+    creg = u.c;
+    const float hval = u.h;
     if (live) oq[(xrow + t) * p.os] = hval;
     if (s + 1 < T) {
       // (value, tag) in one 8-byte store; stage s & 1 was last read at step s - 1, which every workgroup of the group has left:

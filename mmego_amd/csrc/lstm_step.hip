@@ -15,6 +15,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_dma.h"
+#include "lstm_cell.h"
 #include "tile_order.h"
 
 struct LstmStepP {
@@ -32,14 +34,6 @@ struct LstmStepP {
 #endif
 };
 
-// rcp / v_exp_f32 based activations (as in lstm.hip): a few ulp from the libm forms at a fraction of their instruction count
-// (libm expf is ~15 VALU instructions; the cell update evaluates 40 of them per lane)
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
-#define GLDS16(gptr, lptr)                                                                                  \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                   \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 #ifdef MMEGO_STAMP
 #define D2_DBG(bit) (p.dbg & (bit))
 #else
@@ -115,16 +109,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       if (nk > 1) D2_CHUNK(1);
       if (nk > 2) D2_CHUNK(2);
       if (D2_DBG(1)) { }
-      else if (nk > 2) __builtin_amdgcn_s_waitcnt(0x0F70 | ((2 * PC) & 15) | (((2 * PC) >> 4) << 14));
-      else if (nk > 1) __builtin_amdgcn_s_waitcnt(0x0F70 | (PC & 15) | ((PC >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      else if (nk > 2) wait_vmcnt<2 * PC>();
+      else if (nk > 1) wait_vmcnt<PC>();
+      else wait_vmcnt<0>();
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();              // (1) chunk 0 is in LDS
     for (int kt = 0; kt + 1 < nk; ++kt) {      // B_kt: chunk kt+1 has landed; stage kt % 3 may be refilled
       if (D2_DBG(1)) { }
-      else if (kt + 2 < nk) __builtin_amdgcn_s_waitcnt(0x0F70 | (PC & 15) | ((PC >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      else if (kt + 2 < nk) wait_vmcnt<PC>();
+      else wait_vmcnt<0>();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
       if (kt + 3 < nk) D2_CHUNK(kt + 3);
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       if (kt + 1 < nk) {
         // this wave's reads of stage kt are done (fragments in registers).  The BUILTIN, not inline asm: the compiler's
         // wait-count pass must know that set q has landed, or it makes q's MFMAs wait for the p reads issued just before them.
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();          // B_kt: chunk kt+1 has landed, stage kt may be refilled
         so = (so == 2 * STAGE) ? 0 : so + STAGE;
@@ -220,17 +214,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const int lrow = rowbase + i * 16 + fq * 4 + reg;
-      const float gi = fast_sigmoid(acc[i][0][reg]);
-      const float gf = fast_sigmoid(acc[i][1][reg]);
-      const float gg = fast_tanh(acc[i][2][reg]);
-      const float go = fast_sigmoid(acc[i][3][reg]);
-      const float cn = gf * cprev[i][reg] + gi * gg;
-      OUT[lrow * CLD + hb + fr] = cn;
-      OUT[64 * CLD + lrow * CLD + hb + fr] = go * fast_tanh(cn);
+      const LstmCell u = lstm_cell_fwd(acc[i][0][reg], acc[i][1][reg], acc[i][2][reg], acc[i][3][reg], cprev[i][reg]);
+      OUT[lrow * CLD + hb + fr] = u.c;
+      OUT[64 * CLD + lrow * CLD + hb + fr] = u.h;
       if (p.gst[d] && (r0 + lrow) < p.Bn) {
         float* gs = p.gst[d] + (long)(r0 + lrow) * 4 * H + j0 + hb + fr;
-        gs[0] = gi; gs[H] = gf; gs[2 * H] = gg; gs[3 * H] = go;
-        p.cst[d][(long)(r0 + lrow) * H + j0 + hb + fr] = cn;
+        gs[0] = u.i; gs[H] = u.f; gs[2 * H] = u.g; gs[3 * H] = u.o;
+        p.cst[d][(long)(r0 + lrow) * H + j0 + hb + fr] = u.c;
       }
     }
   MMEGO_STAMP_AT(blockIdx.x, 3, tid == 0);
@@ -383,8 +373,9 @@ __global__ __launch_bounds__(256) void lstm_step_small_kernel(LstmStepP p) {
 
 // ---- the FIRST timestep of a sequence (h = c = 0): no product, gates = xproj + b_hh -- an elementwise pass ------------------
 // (Through the step kernels it cost their whole fixed part -- operand staging skipped, but workgroup set-up, the LDS output tile
-// and its barriers kept: 5.8-6.4 us per launch at Bn = 512; eight such launches per U+L step.)  Same expressions as the step
-// kernels' cell update with c_{t-1} = 0: same bits.  One thread per row and four hidden units.
+// and its barriers kept: 5.8-6.4 us per launch at Bn = 512; eight such launches per U+L step.)  The activations of lstm_cell.h but
+// not lstm_cell_fwd: the f c_{t-1} term is not formed at all (one operation per element less than the cell with c_{t-1} = 0; the same
+// bits up to the sign of a zero c).  One thread per row and four hidden units.
 __global__ __launch_bounds__(256) void lstm_first_step_kernel(LstmStepP p) {
   const int d = blockIdx.y, H = p.H, H4 = H >> 2;
   const long n = (long)p.Bn * H4;
@@ -409,7 +400,7 @@ __global__ __launch_bounds__(256) void lstm_first_step_kernel(LstmStepP p) {
       gf[u] = fast_sigmoid(x[1][u] + b[1][u]);
       gg[u] = fast_tanh(x[2][u] + b[2][u]);
       go[u] = fast_sigmoid(x[3][u] + b[3][u]);
-      cn[u] = gi[u] * gg[u];                     // (= gf * 0 + gi * gg of the step kernels)
+      cn[u] = gi[u] * gg[u];                     // (gf * 0 + gi * gg of lstm_cell_fwd without its first term)
       hn[u] = go[u] * fast_tanh(cn[u]);
     }
     *reinterpret_cast<f32x4*>(p.c[d] + row * H + j) = cn;

@@ -6,10 +6,7 @@
 // one ds_read_b128 per operand and 16 k where the fp32 kernel issues sixteen ds_read_b32 and eight MFMAs.  Biases, ReLU and the
 // output stay fp32.
 #include "common.h"
-
-typedef unsigned short bf16_t;
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-__device__ __forceinline__ bf16_t m3b_bf(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }   // v_cvt_pk_bf16_f32: RNE
+#include "bf16_pack.h"
 
 #define M3_ROWS 64
 #define M3_S32 40     // row stride (bf16 elements) of tiles with k <= 32: 80 B, 16-byte aligned rows on distinct bank groups
@@ -88,21 +85,21 @@ __global__ __launch_bounds__(256) void mlp3_eval_bf16_kernel(Mlp3P p) {
       const int i = tid + 256 * u, n = i >> 5, k = i & 31;
       M3_PIN(w1[u]);
       const float wf = fold ? S1s[n] * w1[u] : w1[u];
-      W1s[n * M3_S32 + k] = m3b_bf((n < p.C1 && k < p.Cin) ? wf : 0.f);
+      W1s[n * M3_S32 + k] = (bf16_t)f2bf((n < p.C1 && k < p.Cin) ? wf : 0.f);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = tid + 256 * u, n = i >> 5, k = i & 31;
       M3_PIN(w2[u]);
       const float wf = fold ? S2s[n] * w2[u] : w2[u];
-      W2s[n * M3_S32 + k] = m3b_bf((n < p.C2 && k < p.C1) ? wf : 0.f);
+      W2s[n * M3_S32 + k] = (bf16_t)f2bf((n < p.C2 && k < p.C1) ? wf : 0.f);
     }
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int i = tid + 256 * u, n = i >> 6, k = i & 63;
       M3_PIN(w3[u]);
       const float wf = fold ? S3s[n] * w3[u] : w3[u];
-      W3s[n * M3_S64 + k] = m3b_bf((n < p.C3 && k < p.C2) ? wf : 0.f);
+      W3s[n * M3_S64 + k] = (bf16_t)f2bf((n < p.C3 && k < p.C2) ? wf : 0.f);
     }
   }
 #undef M3_PIN
@@ -144,7 +141,7 @@ __global__ __launch_bounds__(256) void mlp3_eval_bf16_kernel(Mlp3P p) {
     }
     __syncthreads();                                      // previous iteration's readers of Xs / Y1s / Y2s are done
 #pragma unroll
-    for (int j = 0; j < 8; ++j) Xs[(xr + 8 * j) * M3_S32 + xk] = m3b_bf(xv[j]);
+    for (int j = 0; j < 8; ++j) Xs[(xr + 8 * j) * M3_S32 + xk] = (bf16_t)f2bf(xv[j]);
     __syncthreads();
     M3_FETCH(t + gridDim.x < ntiles ? t + gridDim.x : t);
     __builtin_amdgcn_sched_barrier(0);
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(256) void mlp3_eval_bf16_kernel(Mlp3P p) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int row = rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        Y1s[row * M3_S32 + (lane & 31)] = m3b_bf(fmaxf(acc[reg] + bv, 0.f));
+        Y1s[row * M3_S32 + (lane & 31)] = (bf16_t)f2bf(fmaxf(acc[reg] + bv, 0.f));
       }
     }
     __syncthreads();
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(256) void mlp3_eval_bf16_kernel(Mlp3P p) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int row = rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        Y2s[row * M3_S64 + col] = m3b_bf(fmaxf(acc[reg] + bv, 0.f));
+        Y2s[row * M3_S64 + col] = (bf16_t)f2bf(fmaxf(acc[reg] + bv, 0.f));
       }
     }
     __syncthreads();

@@ -31,6 +31,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "bf16_pack.h"
+#include "lds_dma.h"
+#include "lstm_cell.h"
 #include "tile_order.h"
 
 // Compile-time experiment mask (scripts/s3_experiments.py builds variant libraries with -DS3_EXP=<mask> to take a kernel's time apart
@@ -41,25 +44,20 @@
 #define S3_EXP 0
 #endif
 
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 s3_bf16x8;
-typedef unsigned short s3_bf16_t;
-typedef unsigned int s3_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned s3_bits(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }   // RNE: v_cvt_pk_bf16_f32
 __device__ __forceinline__ float s3_up(unsigned b) { return __uint_as_float(b << 16); }
 
 // a -> (a1, a2, a3) as bf16 bit patterns; a1 + a2 + a3 == a exactly for every finite a with 2^-110 <= |a| <= 3.38e38 and for 0
 __device__ __forceinline__ void s3_split(float a, unsigned& p1, unsigned& p2, unsigned& p3) {
-  p1 = s3_bits(a);
+  p1 = f2bf(a);
   const bool fin = (p1 & 0x7f80u) != 0x7f80u;           // a1 neither inf nor NaN
   const float r1 = fin ? a - s3_up(p1) : 0.f;
-  p2 = s3_bits(r1);
+  p2 = f2bf(r1);
   const float r2 = r1 - s3_up(p2);
-  p3 = s3_bits(r2);
+  p3 = f2bf(r2);
 }
 
 // 8 values -> the three 16-byte pieces of one lane
-__device__ __forceinline__ void s3_split8(const float (&y)[8], s3_u32x4& o1, s3_u32x4& o2, s3_u32x4& o3) {
+__device__ __forceinline__ void s3_split8(const float (&y)[8], u32x4& o1, u32x4& o2, u32x4& o3) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     unsigned a1, a2, a3, b1, b2, b3;
@@ -75,7 +73,7 @@ __device__ __forceinline__ void s3_split8(const float (&y)[8], s3_u32x4& o1, s3_
 // Output row r (of Rp, a multiple of 32) takes input row r (tm == 0; rows >= rows_in are zero) or, time-major (tm != 0: r = t Bp + b),
 // input row b T + t (b < Bn, else zero).
 __global__ __launch_bounds__(256) void s3_cvt_kernel(const float* __restrict__ X, long ldx, int rows_in, int SK, int tm, int Bn, int T,
-                                                      int Bp, s3_u32x4* __restrict__ Y, long nblk) {
+                                                      int Bp, u32x4* __restrict__ Y, long nblk) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = (int)(idx & 63);
   const long blk = idx >> 6;
@@ -101,9 +99,9 @@ __global__ __launch_bounds__(256) void s3_cvt_kernel(const float* __restrict__ X
     y[e] = live ? v0[e] : 0.f;
     y[4 + e] = live ? v1[e] : 0.f;
   }
-  s3_u32x4 o1, o2, o3;
+  u32x4 o1, o2, o3;
   s3_split8(y, o1, o2, o3);
-  s3_u32x4* dst = Y + blk * 192 + lane;
+  u32x4* dst = Y + blk * 192 + lane;
   dst[0] = o1;
   dst[64] = o2;
   dst[128] = o3;
@@ -121,7 +119,7 @@ extern "C" int mmego_split3_cvt(void* stream, const float* X, long ldx, long row
   const long nthr = nblk * 64;
   MMEGO_REQUIRE(nthr / 256 + 1 < (1L << 31));
   s3_cvt_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, (hipStream_t)stream>>>(X, ldx, (int)rows_in, K / 16, tm, Bn, T, Bp,
-                                                                                  reinterpret_cast<s3_u32x4*>(Y), nblk);
+                                                                                  reinterpret_cast<u32x4*>(Y), nblk);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -132,7 +130,7 @@ extern "C" int mmego_split3_cvt(void* stream, const float* X, long ldx, long row
 // For the weight-gradient products of stage-1 training (dW = dY^T X: both operands are read along the row axis).
 // shift / T (T > 0): the k axis reads row r + shift of X where that row belongs to the same T-row sequence as r (rows b T + t), zero
 // otherwise: h_{t-1} (shift -1) or h_{t+1} (shift +1, the reverse direction) of a BiLSTM layer's outputs without a shifted copy.
-__global__ __launch_bounds__(256) void s3_cvt_t_kernel(const float* __restrict__ X, long ldx, int C, int SK, s3_u32x4* __restrict__ Y, long nblk,
+__global__ __launch_bounds__(256) void s3_cvt_t_kernel(const float* __restrict__ X, long ldx, int C, int SK, u32x4* __restrict__ Y, long nblk,
                                                         int shift, int T) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = (int)(idx & 63);
@@ -156,9 +154,9 @@ __global__ __launch_bounds__(256) void s3_cvt_t_kernel(const float* __restrict__
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] = ok[e] ? y[e] : 0.f;
-  s3_u32x4 o1, o2, o3;
+  u32x4 o1, o2, o3;
   s3_split8(y, o1, o2, o3);
-  s3_u32x4* dst = Y + blk * 192 + lane;
+  u32x4* dst = Y + blk * 192 + lane;
   dst[0] = o1;
   dst[64] = o2;
   dst[128] = o3;
@@ -172,21 +170,21 @@ extern "C" int mmego_split3_cvt_t(void* stream, const float* X, long ldx, long R
   const long nblk = (Cp / 32) * (R / 16);
   const long nthr = nblk * 64;
   MMEGO_REQUIRE(nthr / 256 + 1 < (1L << 31));
-  s3_cvt_t_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, (hipStream_t)stream>>>(X, ldx, C, (int)(R / 16), reinterpret_cast<s3_u32x4*>(Y), nblk, shift, T);
+  s3_cvt_t_kernel<<<(unsigned)((nthr + 255) / 256), 256, 0, (hipStream_t)stream>>>(X, ldx, C, (int)(R / 16), reinterpret_cast<u32x4*>(Y), nblk, shift, T);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
 
 // sfrag -> fp32 row-major (a1 + a2 + a3 in that order of addition: exact for a split of an fp32 value).  Test / debug aid.
-__global__ __launch_bounds__(256) void s3_join_kernel(const s3_u32x4* __restrict__ Y, int SK, long nblk, float* __restrict__ X, long ldx) {
+__global__ __launch_bounds__(256) void s3_join_kernel(const u32x4* __restrict__ Y, int SK, long nblk, float* __restrict__ X, long ldx) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = (int)(idx & 63);
   const long blk = idx >> 6;
   if (blk >= nblk) return;
   const long rb = blk / SK;
   const int s = (int)(blk - rb * SK);
-  const s3_u32x4* src = Y + blk * 192 + lane;
-  const s3_u32x4 o1 = src[0], o2 = src[64], o3 = src[128];
+  const u32x4* src = Y + blk * 192 + lane;
+  const u32x4 o1 = src[0], o2 = src[64], o3 = src[128];
   float* xr = X + (rb * 32 + (lane & 31)) * ldx + 16 * s + 8 * (lane >> 5);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -198,7 +196,7 @@ __global__ __launch_bounds__(256) void s3_join_kernel(const s3_u32x4* __restrict
 extern "C" int mmego_split3_join(void* stream, const unsigned short* Y, long Rp, int K, float* X, long ldx) {
   MMEGO_REQUIRE(X && Y && Rp > 0 && Rp % 32 == 0 && K > 0 && K % 16 == 0 && ldx >= K);
   const long nblk = (Rp / 32) * (K / 16);
-  s3_join_kernel<<<(unsigned)((nblk * 64 + 255) / 256), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const s3_u32x4*>(Y), K / 16, nblk, X, ldx);
+  s3_join_kernel<<<(unsigned)((nblk * 64 + 255) / 256), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const u32x4*>(Y), K / 16, nblk, X, ldx);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -210,7 +208,7 @@ extern "C" int mmego_split3_join(void* stream, const unsigned short* Y, long Rp,
 // another summation order: same result to fp32 rounding).
 __global__ __launch_bounds__(256) void s3_fc_relu_kernel(const float* __restrict__ X, long ldx, const float* __restrict__ W,
                                                           const float* __restrict__ bias, int Bn, int T, int Cin, int H,
-                                                          s3_u32x4* __restrict__ Y, int Bp, int relu) {
+                                                          u32x4* __restrict__ Y, int Bp, int relu) {
   extern __shared__ __attribute__((aligned(16))) float s3_wsm[];      // [H][16] + bias [H]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // (W padded to 16 columns; loads unconditional on clamped addresses, 16 in flight: under `k < Cin ? W[..] : 0` every load was a round
@@ -240,7 +238,7 @@ __global__ __launch_bounds__(256) void s3_fc_relu_kernel(const float* __restrict
   __syncthreads();
   const bool live = b < Bn;
   const int SK = H >> 4;
-  s3_u32x4* dst = Y + ((long)t * (Bp >> 5) + rb) * SK * 192 + lane;
+  u32x4* dst = Y + ((long)t * (Bp >> 5) + rb) * SK * 192 + lane;
   for (int k16 = wave; k16 < SK; k16 += 4) {
     const int n0 = k16 * 16 + half * 8;
     float y[8];
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(256) void s3_fc_relu_kernel(const float* __restrict
       }
       y[j] = live ? (relu ? fmaxf(a, 0.f) : a) : 0.f;
     }
-    s3_u32x4 o1, o2, o3;
+    u32x4 o1, o2, o3;
     s3_split8(y, o1, o2, o3);
     dst[(long)k16 * 192] = o1;
     dst[(long)k16 * 192 + 64] = o2;
@@ -270,7 +268,7 @@ extern "C" int mmego_split3_fc_relu(void* stream, const float* X, long ldx, cons
   const size_t lds = (size_t)(H * 16 + H) * sizeof(float);
   if (int e = mmego_allow_lds<s3_fc_relu_kernel>(lds)) return e;
   dim3 grid(Bp / 32, T);
-  s3_fc_relu_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(X, ldx, W, bias, Bn, T, Cin, H, reinterpret_cast<s3_u32x4*>(Y), Bp, relu);
+  s3_fc_relu_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(X, ldx, W, bias, Bn, T, Cin, H, reinterpret_cast<u32x4*>(Y), Bp, relu);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -278,16 +276,16 @@ extern "C" int mmego_split3_fc_relu(void* stream, const float* X, long ldx, cons
 // ---- the piece products of one (A tile, B tile) pair at one 16-k step --------------------------------------------------------
 // small terms first, a1 b1 last (the accumulator is fp32 either way; this order keeps the partial sums' rounding smallest)
 template <int NPROD>
-__device__ __forceinline__ f32x16 s3_mma(const s3_u32x4 (&a)[3], const s3_u32x4 (&b)[3], f32x16 acc) {
+__device__ __forceinline__ f32x16 s3_mma(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
   if (S3_EXP & 1) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const s3_u32x4 v = a[q] ^ b[q];
+      const u32x4 v = a[q] ^ b[q];
       acc[q] = __uint_as_float(__float_as_uint(acc[q]) ^ v[0] ^ v[1] ^ v[2] ^ v[3]);
     }
     return acc;
   }
-#define S3_MM(i, j) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s3_bf16x8, a[i]), __builtin_bit_cast(s3_bf16x8, b[j]), acc, 0, 0, 0)
+#define S3_MM(i, j) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[i]), __builtin_bit_cast(bf16x8, b[j]), acc, 0, 0, 0)
   if (NPROD == 9) {
     S3_MM(2, 2);
     S3_MM(1, 2);
@@ -305,8 +303,8 @@ __device__ __forceinline__ f32x16 s3_mma(const s3_u32x4 (&a)[3], const s3_u32x4 
 
 // ---- C = A . W^T + bias -----------------------------------------------------------------------------------------------------------
 struct S3GemmP {
-  const s3_u32x4* A;       // sfrag [Mrb][SK][3][64]
-  const s3_u32x4* W;       // sfrag [Nrb][SK][3][64]
+  const u32x4* A;       // sfrag [Mrb][SK][3][64]
+  const u32x4* W;       // sfrag [Nrb][SK][3][64]
   float* Cf;               // tile-major fp32 [Mrb][Nrb][1024] or null
   float* C; long ldc;      // row-major fp32 or null
   const float* bias;       // [32 Nrb] or null
@@ -329,8 +327,8 @@ __global__ __launch_bounds__(WM * 128, 2) void s3_gemm_kernel(S3GemmP p) {
   constexpr int NLA = RBA * 384 / NT;          // 16-byte loads per thread and chunk
   constexpr int NLW = 4 * 384 / NT;
   static_assert(RBA * 384 % NT == 0 && 4 * 384 % NT == 0, "tile images must divide over the threads");
-  __shared__ s3_u32x4 As[RBA * 384];
-  __shared__ s3_u32x4 Bs[4 * 384];
+  __shared__ u32x4 As[RBA * 384];
+  __shared__ u32x4 Bs[4 * 384];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w >> 1, wn = w & 1;
   // tile order: runs of p.gm row panels sweep the N tiles, so that the workgroups resident on an XCD at one time share few A and few W
@@ -357,7 +355,7 @@ __global__ __launch_bounds__(WM * 128, 2) void s3_gemm_kernel(S3GemmP p) {
     gw[j] = min(rbW0 + i / 384, p.Nrb - 1) * SK * 192 + i % 384;
   }
   const int c0 = (int)blockIdx.y * p.cps;
-  s3_u32x4 ra[NLA], rw[NLW];
+  u32x4 ra[NLA], rw[NLW];
 #pragma unroll
   for (int j = 0; j < NLA; ++j) ra[j] = p.A[ga[j] + c0 * 384];
 #pragma unroll
@@ -388,7 +386,7 @@ __global__ __launch_bounds__(WM * 128, 2) void s3_gemm_kernel(S3GemmP p) {
     }
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) {
-      s3_u32x4 a[MI][3], b[2][3];
+      u32x4 a[MI][3], b[2][3];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -461,7 +459,7 @@ __global__ __launch_bounds__(WM * 128, 2) void s3_gemm_kernel(S3GemmP p) {
 template <int NPROD, int TRB>
 __global__ __launch_bounds__(512, 1) void s3_gemm_big_kernel(S3GemmP p) {
   constexpr int TCB = 8, NBLK = (TRB + TCB) * 3, MI = TRB / 2;   // 1-KB blocks per step and stage; accumulator row blocks per wave
-  extern __shared__ __attribute__((aligned(16))) s3_u32x4 s3_big[];   // [2 stages][NBLK][64]
+  extern __shared__ __attribute__((aligned(16))) u32x4 s3_big[];   // [2 stages][NBLK][64]
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform by construction: addresses below stay scalar)
   const int wm = w >> 2, wn = w & 3;
@@ -472,7 +470,7 @@ __global__ __launch_bounds__(512, 1) void s3_gemm_big_kernel(S3GemmP p) {
   const int SK = min(SKall - s_first, 2 * p.cps);
   // this wave's transfers: blocks i = w + 8 j of a stage (i < NBLK); block i < 3 TRB: A row block i / 3, piece i % 3; else W.
   // Source = a wave-uniform block address (scalar registers) + 16 lane.
-  const s3_u32x4* gp[7];
+  const u32x4* gp[7];
 #pragma unroll
   for (int j = 0; j < 7; ++j) {
     const int i = min(w + 8 * j, NBLK - 1);
@@ -484,8 +482,7 @@ __global__ __launch_bounds__(512, 1) void s3_gemm_big_kernel(S3GemmP p) {
   {                                                                                                                   \
     _Pragma("unroll") for (int j = 0; j < 7; ++j)                                                                     \
       if (w + 8 * j < NBLK && !(S3_EXP & 16))                                                                         \
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gp[j] + (long)((S3_EXP & 2) ? 0 : (s)) * 192 + lane), \
-                                         (__attribute__((address_space(3))) void*)(s3_big + ((stage) * NBLK + w + 8 * j) * 64), 16, 0, 0); \
+        GLDS16(gp[j] + (long)((S3_EXP & 2) ? 0 : (s)) * 192 + lane, s3_big + ((stage) * NBLK + w + 8 * j) * 64);       \
   }
   f32x16 acc[MI][2];
 #pragma unroll
@@ -506,7 +503,7 @@ __global__ __launch_bounds__(512, 1) void s3_gemm_big_kernel(S3GemmP p) {
   // wait, barrier in front of row block 3 -- was 1.5-2.5 % slower; git history.)
   // A-fragment slots: row block mi of a step of parity par sits in slot (par + mi) & 1 for odd MI, mi & 1 for even MI -- either way the
   // next step's first fragments, requested in front of the last row block's MFMAs, go to the slot those MFMAs do not read.
-  s3_u32x4 b[2][2][3], a[2][3];
+  u32x4 b[2][2][3], a[2][3];
 #define S3_SLOT(par, mi) ((MI & 1) ? (((par) + (mi)) & 1) : ((mi) & 1))
 #define S3_BIG_RD_B(slot, stage)                                                                                      \
   if (!(S3_EXP & 32)) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                \
@@ -609,7 +606,7 @@ static int s3_gemm_launch(void* stream, const unsigned short* A, const unsigned 
     if (trb) {
       MMEGO_REQUIRE((long)(nsplit - 1) * cps < K / 32);          // (no empty slab)
       S3GemmP p;
-      p.A = reinterpret_cast<const s3_u32x4*>(A); p.W = reinterpret_cast<const s3_u32x4*>(W);
+      p.A = reinterpret_cast<const u32x4*>(A); p.W = reinterpret_cast<const u32x4*>(W);
       p.Cf = Cf; p.C = C; p.ldc = ldc; p.bias = bias; p.Mrb = Mrb; p.Nrb = Nrb; p.SK = K / 16; p.M = M;
       p.tiles_m = Mrb / trb; p.tiles_n = Nrb / 8; p.gm = 4; p.cps = cps; p.slab = slab;
       constexpr int lds = 2 * 54 * 1024;
@@ -638,7 +635,7 @@ static int s3_gemm_launch(void* stream, const unsigned short* A, const unsigned 
   }
   MMEGO_REQUIRE(wm == 1 || wm == 2 || wm == 4);
   S3GemmP p;
-  p.A = reinterpret_cast<const s3_u32x4*>(A); p.W = reinterpret_cast<const s3_u32x4*>(W);
+  p.A = reinterpret_cast<const u32x4*>(A); p.W = reinterpret_cast<const u32x4*>(W);
   p.Cf = Cf; p.C = C; p.ldc = ldc; p.bias = bias; p.Mrb = Mrb; p.Nrb = Nrb; p.SK = K / 16; p.M = M;
   p.tiles_m = cdiv(Mrb, 2 * wm); p.tiles_n = cdiv(Nrb, 4);
   p.gm = 4;         // (r05: 4 / 8 / 16 / 32 row panels per sweep group measured 194 / 193 / 197 / 205 us at K = 512, 369 / 373 / 377 / 387 at 1024)
@@ -703,18 +700,16 @@ extern "C" int mmego_split3_slab_sum(void* stream, const float* ws, int nsplit, 
 
 // ---- one BiLSTM timestep -------------------------------------------------------------------------------------------------------------
 struct S3StepP {
-  const s3_u32x4* hprev[2]; long hrb;   // h_{t-1} pieces: block (rb, s, p) at hprev[d] + (rb * hrb + s * 3 + p) * 64; hrb = blocks between row blocks
-  const s3_u32x4* whh[2];               // W_hh pieces, sfrag with rows [hidden block jb][gate][32 units], SK = H / 16
+  const u32x4* hprev[2]; long hrb;   // h_{t-1} pieces: block (rb, s, p) at hprev[d] + (rb * hrb + s * 3 + p) * 64; hrb = blocks between row blocks
+  const u32x4* whh[2];               // W_hh pieces, sfrag with rows [hidden block jb][gate][32 units], SK = H / 16
   const float* xpf; long mt0[2];        // x . W_ih^T + b_ih + b_hh, tile-major; mt0[d] = first row tile of direction d's timestep
   float* hout[2]; long hos;             // h_t fp32 row-major (may be null)
-  s3_u32x4* hnext[2]; long hnrb;        // h_t pieces, addressed like hprev
+  u32x4* hnext[2]; long hnrb;        // h_t pieces, addressed like hprev
   float* c[2];
   int Bn, H, first, dbase;             // dbase: direction of slot 0 (a single-direction launch of the reverse direction: 1)
   int S;                               // 16-k steps of the product: H / 16 for a timestep, K / 16 for mmego_split3_proj
 };
 
-__device__ __forceinline__ float s3_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float s3_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // The small-batch step of the bf16 mode (lstm_step_bf16_direct_kernel, bf16.hip) on piece products.  Workgroup = 64 rows x 32 hidden
 // units x 4 gates of one direction (Bn = H = 512: 8 x 16 x 2 = 256 workgroups, one per CU); wave w takes k quarter w of the whole tile,
@@ -753,13 +748,13 @@ __global__ __launch_bounds__(256, 1) void s3_step_kernel(S3StepP p) {
     for (int n = 0; n < 4; ++n)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[mi][n][i] = 0.f;
-  const s3_u32x4* ap[2];
+  const u32x4* ap[2];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) ap[mi] = p.hprev[d] + ((long)min((r0 >> 5) + mi, last_rb) * p.hrb + (long)w * SQ * 3) * 64 + lane;
-  const s3_u32x4* wp = p.whh[d] + ((long)jb * 4 * S + w * SQ) * 192 + lane;
+  const u32x4* wp = p.whh[d] + ((long)jb * 4 * S + w * SQ) * 192 + lane;
   const int gstride = S * 192;                        // between the gates' row blocks
   constexpr int NR = SQ >= 4 ? 4 : SQ;                // ring of fragment sets: requests run NR - 1 steps (48 (NR - 1) MFMAs) ahead
-  s3_u32x4 a[NR][2][3], b[NR][4][3];
+  u32x4 a[NR][2][3], b[NR][4][3];
 #define S3_LOAD(slot, s)                                                                    \
     {                                                                                       \
       _Pragma("unroll") for (int q = 0; q < 3; ++q) a[slot][0][q] = ap[0][((S3_EXP & 2 ? 0 : (s)) * 3 + q) * 64];        \
@@ -862,18 +857,20 @@ __global__ __launch_bounds__(256, 1) void s3_step_kernel(S3StepP p) {
     }
     return;
   }
-  // cell update of this lane's 8 (row, unit j) elements; PyTorch gate order i, f, g, o
-  s3_bf16_t* img = reinterpret_cast<s3_bf16_t*>(s3_red);            // [2 rb][2 s][3 p][64 lanes][8] bf16 = 12 KB
+  // cell update of this lane's 8 (row, unit j) elements; PyTorch gate order i, f, g, o.  The expressions of lstm_cell_fwd (lstm_cell.h)
+  // written out: through the call the register allocator places the accumulator-register copies of two forms (<4, 6> and <8, 9>: every
+  // VGPR taken) differently, and this kernel is held to the machine code it was measured with
+  bf16_t* img = reinterpret_cast<bf16_t*>(s3_red);            // [2 rb][2 s][3 p][64 lanes][8] bf16 = 12 KB
 #pragma unroll
   for (int ii = 0; ii < 8; ++ii) {
     const int rl = own_r0 + 8 * (ii >> 2) + 4 * fh + (ii & 3);      // row inside the workgroup's 64
     const int row = r0 + rl;
-    const float gi = s3_sigmoid(pre[0][ii] + xp[0][ii >> 2][ii & 3]);
-    const float gf = s3_sigmoid(pre[1][ii] + xp[1][ii >> 2][ii & 3]);
-    const float gg = s3_tanh(pre[2][ii] + xp[2][ii >> 2][ii & 3]);
-    const float go = s3_sigmoid(pre[3][ii] + xp[3][ii >> 2][ii & 3]);
+    const float gi = fast_sigmoid(pre[0][ii] + xp[0][ii >> 2][ii & 3]);
+    const float gf = fast_sigmoid(pre[1][ii] + xp[1][ii >> 2][ii & 3]);
+    const float gg = fast_tanh(pre[2][ii] + xp[2][ii >> 2][ii & 3]);
+    const float go = fast_sigmoid(pre[3][ii] + xp[3][ii >> 2][ii & 3]);
     const float cn = gf * (FIRST ? 0.f : cprev[ii]) + gi * gg;
-    const float hn = row < p.Bn ? go * s3_tanh(cn) : 0.f;
+    const float hn = row < p.Bn ? go * fast_tanh(cn) : 0.f;
     if (row < p.Bn) {
       p.c[d][(long)row * H + j] = cn;
       if (p.hout[d]) p.hout[d][(long)row * p.hos + j] = hn;
@@ -882,14 +879,14 @@ __global__ __launch_bounds__(256, 1) void s3_step_kernel(S3StepP p) {
     s3_split(hn, q1, q2, q3);
     // element (row rl, k = fr of the workgroup's 32 units): block (rl / 32, fr / 16), lane (rl % 32) + 32 ((fr / 8) & 1), e = fr % 8
     const int o = ((((rl >> 5) * 2 + (fr >> 4)) * 3) * 64 + (rl & 31) + 32 * ((fr >> 3) & 1)) * 8 + (fr & 7);
-    img[o] = (s3_bf16_t)q1;
-    img[o + 512] = (s3_bf16_t)q2;
-    img[o + 1024] = (s3_bf16_t)q3;
+    img[o] = (bf16_t)q1;
+    img[o + 512] = (bf16_t)q2;
+    img[o + 1024] = (bf16_t)q3;
   }
   __syncthreads();
   {
     // 768 16-byte pieces: image index i = ((rb_l * 2 + s_l) * 3 + p) * 64 + lane
-    const s3_u32x4* im4 = reinterpret_cast<const s3_u32x4*>(img);
+    const u32x4* im4 = reinterpret_cast<const u32x4*>(img);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
       const int i = u * 256 + tid;
@@ -941,13 +938,13 @@ __global__ __launch_bounds__(256, 2) void s3_step16_kernel(S3StepP p) {
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[mi][n][i] = 0.f;
-  const s3_u32x4* ap[2];
+  const u32x4* ap[2];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) ap[mi] = p.hprev[d] + ((long)min((r0 >> 5) + mi, last_rb) * p.hrb + (long)w * SQ * 3) * 64 + lane;
-  const s3_u32x4* wp = p.whh[d] + ((long)jb * 2 * S + w * SQ) * 192 + lane;
+  const u32x4* wp = p.whh[d] + ((long)jb * 2 * S + w * SQ) * 192 + lane;
   const int gstride = S * 192;
   constexpr int NR = SQ >= 3 ? 3 : SQ;
-  s3_u32x4 a[NR][2][3], b[NR][2][3];
+  u32x4 a[NR][2][3], b[NR][2][3];
 #define S3_LOAD16(slot, s)                                                                  \
     {                                                                                       \
       _Pragma("unroll") for (int q = 0; q < 3; ++q) a[slot][0][q] = ap[0][((s) * 3 + q) * 64];              \
@@ -1031,18 +1028,16 @@ __global__ __launch_bounds__(256, 2) void s3_step16_kernel(S3StepP p) {
       mine[n][r] = gsel ? pre[n][4 + r] : pre[n][r];
       theirs[n][r] = __shfl_xor(gsel ? pre[n][r] : pre[n][4 + r], 16, 64);
     }
-  s3_bf16_t* img = reinterpret_cast<s3_bf16_t*>(s3_red16);          // [2 rb][3 p][64 lanes][8] bf16 = 6 KB
+  bf16_t* img = reinterpret_cast<bf16_t*>(s3_red16);          // [2 rb][3 p][64 lanes][8] bf16 = 6 KB
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int rl = own_r0 + 8 * gsel + 4 * fh + r;
     const int row = r0 + rl;
     // PyTorch gate order i, f, g, o = columns (n, gsel) = (0, 0), (0, 1), (1, 0), (1, 1)
-    const float gi = s3_sigmoid(gsel ? theirs[0][r] : mine[0][r]);
-    const float gf = s3_sigmoid(gsel ? mine[0][r] : theirs[0][r]);
-    const float gg = s3_tanh(gsel ? theirs[1][r] : mine[1][r]);
-    const float go = s3_sigmoid(gsel ? mine[1][r] : theirs[1][r]);
-    const float cn = gf * (FIRST ? 0.f : cprev[r]) + gi * gg;
-    const float hn = row < p.Bn ? go * s3_tanh(cn) : 0.f;
+    const LstmCell u = lstm_cell_fwd(gsel ? theirs[0][r] : mine[0][r], gsel ? mine[0][r] : theirs[0][r], gsel ? theirs[1][r] : mine[1][r],
+                                     gsel ? mine[1][r] : theirs[1][r], FIRST ? 0.f : cprev[r]);
+    const float cn = u.c;
+    const float hn = row < p.Bn ? u.h : 0.f;
     if (row < p.Bn) {
       p.c[d][(long)row * H + j0 + ju] = cn;
       if (p.hout[d]) p.hout[d][(long)row * p.hos + j0 + ju] = hn;
@@ -1050,14 +1045,14 @@ __global__ __launch_bounds__(256, 2) void s3_step16_kernel(S3StepP p) {
     unsigned q1, q2, q3;
     s3_split(hn, q1, q2, q3);
     const int o = (((rl >> 5) * 3) * 64 + (rl & 31) + 32 * ((ju >> 3) & 1)) * 8 + (ju & 7);
-    img[o] = (s3_bf16_t)q1;
-    img[o + 512] = (s3_bf16_t)q2;
-    img[o + 1024] = (s3_bf16_t)q3;
+    img[o] = (bf16_t)q1;
+    img[o + 512] = (bf16_t)q2;
+    img[o + 1024] = (bf16_t)q3;
   }
   __syncthreads();
   {
     // 384 16-byte pieces: image index i = (rb_l * 3 + p) * 64 + lane
-    const s3_u32x4* im4 = reinterpret_cast<const s3_u32x4*>(img);
+    const u32x4* im4 = reinterpret_cast<const u32x4*>(img);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int i = u * 256 + tid;
@@ -1086,11 +1081,11 @@ extern "C" int mmego_split3_step(void* stream, int ndir, int Bn, int H, int firs
   MMEGO_REQUIRE(hnext0 && (ndir == 1 || hnext1) && ((((uintptr_t)hnext0) | ((uintptr_t)hnext1)) & 15) == 0 && hnext0 != hprev0);
   MMEGO_REQUIRE(xpf && (((uintptr_t)xpf) & 15) == 0 && mt0_0 >= 0 && mt0_1 >= 0 && c0 && (ndir == 1 || c1) && hrb > 0 && hnrb > 0);
   S3StepP p;
-  p.hprev[0] = reinterpret_cast<const s3_u32x4*>(hprev0); p.hprev[1] = reinterpret_cast<const s3_u32x4*>(hprev1); p.hrb = hrb;
-  p.whh[0] = reinterpret_cast<const s3_u32x4*>(whh0); p.whh[1] = reinterpret_cast<const s3_u32x4*>(whh1);
+  p.hprev[0] = reinterpret_cast<const u32x4*>(hprev0); p.hprev[1] = reinterpret_cast<const u32x4*>(hprev1); p.hrb = hrb;
+  p.whh[0] = reinterpret_cast<const u32x4*>(whh0); p.whh[1] = reinterpret_cast<const u32x4*>(whh1);
   p.xpf = xpf; p.mt0[0] = mt0_0; p.mt0[1] = mt0_1;
   p.hout[0] = hout0; p.hout[1] = hout1; p.hos = hos;
-  p.hnext[0] = reinterpret_cast<s3_u32x4*>(hnext0); p.hnext[1] = reinterpret_cast<s3_u32x4*>(hnext1); p.hnrb = hnrb;
+  p.hnext[0] = reinterpret_cast<u32x4*>(hnext0); p.hnext[1] = reinterpret_cast<u32x4*>(hnext1); p.hnrb = hnrb;
   p.c[0] = c0; p.c[1] = c1;
   p.Bn = Bn; p.H = H; p.first = first; p.dbase = dbase; p.S = H / 16;
   const int lds = 4 * 2 * 4 * 16 * 64 * (int)sizeof(float);
@@ -1131,8 +1126,8 @@ extern "C" int mmego_split3_proj(void* stream, const unsigned short* A, const un
   MMEGO_REQUIRE(A && W0 && W1 && C && M > 0 && M <= 2048 && H > 0 && H % 32 == 0 && (K == 256 || K == 512 || K == 1024) && ldc >= 8 * H);
   MMEGO_REQUIRE((nprod == 6 || nprod == 9) && ((((uintptr_t)A) | ((uintptr_t)W0) | ((uintptr_t)W1)) & 15) == 0);
   S3StepP p = {};
-  p.hprev[0] = p.hprev[1] = reinterpret_cast<const s3_u32x4*>(A); p.hrb = (long)(K / 16) * 3;
-  p.whh[0] = reinterpret_cast<const s3_u32x4*>(W0); p.whh[1] = reinterpret_cast<const s3_u32x4*>(W1);
+  p.hprev[0] = p.hprev[1] = reinterpret_cast<const u32x4*>(A); p.hrb = (long)(K / 16) * 3;
+  p.whh[0] = reinterpret_cast<const u32x4*>(W0); p.whh[1] = reinterpret_cast<const u32x4*>(W1);
   p.xpf = bias;
   p.hout[0] = C; p.hout[1] = C + 4 * H; p.hos = ldc;
   p.Bn = M; p.H = H; p.first = 0; p.dbase = 0; p.S = K / 16;
@@ -1166,11 +1161,11 @@ extern "C" int mmego_split3_step16(void* stream, int ndir, int Bn, int H, int fi
   MMEGO_REQUIRE(hnext0 && (ndir == 1 || hnext1) && ((((uintptr_t)hnext0) | ((uintptr_t)hnext1)) & 15) == 0 && hnext0 != hprev0);
   MMEGO_REQUIRE(xpf && (((uintptr_t)xpf) & 15) == 0 && mt0_0 >= 0 && mt0_1 >= 0 && c0 && (ndir == 1 || c1) && hrb > 0 && hnrb > 0);
   S3StepP p;
-  p.hprev[0] = reinterpret_cast<const s3_u32x4*>(hprev0); p.hprev[1] = reinterpret_cast<const s3_u32x4*>(hprev1); p.hrb = hrb;
-  p.whh[0] = reinterpret_cast<const s3_u32x4*>(whh0); p.whh[1] = reinterpret_cast<const s3_u32x4*>(whh1);
+  p.hprev[0] = reinterpret_cast<const u32x4*>(hprev0); p.hprev[1] = reinterpret_cast<const u32x4*>(hprev1); p.hrb = hrb;
+  p.whh[0] = reinterpret_cast<const u32x4*>(whh0); p.whh[1] = reinterpret_cast<const u32x4*>(whh1);
   p.xpf = xpf; p.mt0[0] = mt0_0; p.mt0[1] = mt0_1;
   p.hout[0] = hout0; p.hout[1] = hout1; p.hos = hos;
-  p.hnext[0] = reinterpret_cast<s3_u32x4*>(hnext0); p.hnext[1] = reinterpret_cast<s3_u32x4*>(hnext1); p.hnrb = hnrb;
+  p.hnext[0] = reinterpret_cast<u32x4*>(hnext0); p.hnext[1] = reinterpret_cast<u32x4*>(hnext1); p.hnrb = hnrb;
   p.c[0] = c0; p.c[1] = c1;
   p.Bn = Bn; p.H = H; p.first = first; p.dbase = dbase; p.S = H / 16;
   const int lds = 4 * 2 * 2 * 16 * 64 * (int)sizeof(float);

@@ -25,12 +25,11 @@
 #include "common.h"
 #include "gcn_stats.h"
 
-typedef float vx_f4 __attribute__((ext_vector_type(4)));
 #define VX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // (mean, M2) of one column of a 16 x 16 accumulator tile over its first nvalid rows: lane (r = lane & 15: column, q = lane >> 4:
 // rows 4q .. 4q+3).  Every lane returns the column's record.
-__device__ __forceinline__ float2 vx_tile_record(const vx_f4& z, int nvalid, int q) {
+__device__ __forceinline__ float2 vx_tile_record(const f32x4& z, int nvalid, int q) {
   float s = 0.f;
 #pragma unroll
   for (int v = 0; v < 4; ++v) s += (4 * q + v < nvalid) ? z[v] : 0.f;
@@ -64,20 +63,20 @@ __global__ __launch_bounds__(128) void vox_l1_fwd_kernel(const float* __restrict
   const int rowc = min(r0 + r, R - 1);
   const float* A = X + (long)rowc * ldx + wave * kh + 4 * q;
   const float* B = W + (long)(c0 + r) * K + wave * kh + 4 * q;
-  vx_f4 ra[D], rb[D];
+  f32x4 ra[D], rb[D];
 #pragma unroll
   for (int u = 0; u < D; ++u) {
-    ra[u] = *reinterpret_cast<const vx_f4*>(A + 16 * u);
-    rb[u] = *reinterpret_cast<const vx_f4*>(B + 16 * u);
+    ra[u] = *reinterpret_cast<const f32x4*>(A + 16 * u);
+    rb[u] = *reinterpret_cast<const f32x4*>(B + 16 * u);
   }
   __builtin_amdgcn_sched_barrier(0);
-  vx_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    const vx_f4 a = ra[i % D], b = rb[i % D];
+    const f32x4 a = ra[i % D], b = rb[i % D];
     if (i + D < NCH) {
-      ra[i % D] = *reinterpret_cast<const vx_f4*>(A + 16 * (i + D));
-      rb[i % D] = *reinterpret_cast<const vx_f4*>(B + 16 * (i + D));
+      ra[i % D] = *reinterpret_cast<const f32x4*>(A + 16 * (i + D));
+      rb[i % D] = *reinterpret_cast<const f32x4*>(B + 16 * (i + D));
     }
     __builtin_amdgcn_sched_barrier(0);                   // (the requests stay HERE, D chunks ahead of their use: the scheduler sinks them otherwise)
 #pragma unroll
@@ -114,11 +113,11 @@ __global__ __launch_bounds__(64 * (COUT / 16)) void vox_mid_fwd_kernel(const flo
   __shared__ __attribute__((aligned(16))) float at[16 * LDA];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
   const int r0 = blockIdx.x * 16, c0 = wave * 16;
-  vx_f4 wb[CIN / 16];
+  f32x4 wb[CIN / 16];
   {
     const float* B = W + (long)(c0 + r) * CIN + 4 * q;
 #pragma unroll
-    for (int kc = 0; kc < CIN / 16; ++kc) wb[kc] = *reinterpret_cast<const vx_f4*>(B + 16 * kc);
+    for (int kc = 0; kc < CIN / 16; ++kc) wb[kc] = *reinterpret_cast<const f32x4*>(B + 16 * kc);
   }
   const float bv = bias[c0 + r];
   bn_from_records<NT>(bn, CIN, R, red, st, blockIdx.x == 0);      // st: mean, a, b, invstd
@@ -131,10 +130,10 @@ __global__ __launch_bounds__(64 * (COUT / 16)) void vox_mid_fwd_kernel(const flo
     if (row < R) Yin[(long)row * CIN + c] = a;
   }
   __syncthreads();
-  vx_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kc = 0; kc < CIN / 16; ++kc) {
-    const vx_f4 a = *reinterpret_cast<const vx_f4*>(&at[r * LDA + 16 * kc + 4 * q]);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&at[r * LDA + 16 * kc + 4 * q]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc = VX_MFMA(a[j], wb[kc][j], acc);
   }
@@ -238,7 +237,7 @@ __global__ __launch_bounds__(64 * (CIN / 16)) void vox_mid_bwd_kernel(const floa
   __shared__ __attribute__((aligned(16))) float dzt[16 * LDZ];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
   const int r0 = blockIdx.x * 16, c0 = wave * 16;
-  vx_f4 wb[COUT / 16];                                 // W[16 kc + 4 q + j][c0 + r]: coalesced over r
+  f32x4 wb[COUT / 16];                                 // W[16 kc + 4 q + j][c0 + r]: coalesced over r
 #pragma unroll
   for (int kc = 0; kc < COUT / 16; ++kc)
 #pragma unroll
@@ -256,10 +255,10 @@ __global__ __launch_bounds__(64 * (CIN / 16)) void vox_mid_bwd_kernel(const floa
     if (row < R) dZ[(long)row * COUT + c] = dz;
   }
   __syncthreads();
-  vx_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kc = 0; kc < COUT / 16; ++kc) {
-    const vx_f4 a = *reinterpret_cast<const vx_f4*>(&dzt[r * LDZ + 16 * kc + 4 * q]);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&dzt[r * LDZ + 16 * kc + 4 * q]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc = VX_MFMA(a[j], wb[kc][j], acc);
   }
@@ -294,7 +293,7 @@ __global__ __launch_bounds__(256) void vox_l1_bwd_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
   const int r0 = blockIdx.x * 16;
   const int n0 = (blockIdx.y * 4 + wave) * TPW * 16;
-  vx_f4 wb[2][NK];
+  f32x4 wb[2][NK];
   const float* Wl = W + (long)(4 * q) * K + n0 + r;
 #pragma unroll
   for (int kc = 0; kc < NK; ++kc)
@@ -313,9 +312,9 @@ __global__ __launch_bounds__(256) void vox_l1_bwd_kernel(const float* __restrict
     if (row < R && blockIdx.y == 0) dZ[(long)row * C + c] = dz;
   }
   __syncthreads();
-  vx_f4 a[NK];
+  f32x4 a[NK];
 #pragma unroll
-  for (int kc = 0; kc < NK; ++kc) a[kc] = *reinterpret_cast<const vx_f4*>(&dzt[r * LDZ + 16 * kc + 4 * q]);
+  for (int kc = 0; kc < NK; ++kc) a[kc] = *reinterpret_cast<const f32x4*>(&dzt[r * LDZ + 16 * kc + 4 * q]);
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     if (t + 1 < TPW) {
@@ -324,7 +323,7 @@ __global__ __launch_bounds__(256) void vox_l1_bwd_kernel(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) wb[(t + 1) & 1][kc][j] = Wl[(long)(16 * kc + j) * K + 16 * (t + 1)];
     }
-    vx_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kc = 0; kc < NK; ++kc)
 #pragma unroll
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(256) void vox_dw_kernel(VoxDwP p) {
   const float* B = L.In + 16 * nt + r;
   const long lda = L.Cout, ldb = L.ldin;
   constexpr int D = 4;
-  vx_f4 ra[D], rb[D];
+  f32x4 ra[D], rb[D];
 #pragma unroll
   for (int u = 0; u < D; ++u)
 #pragma unroll
@@ -365,12 +364,12 @@ __global__ __launch_bounds__(256) void vox_dw_kernel(VoxDwP p) {
       ra[u][j] = A[(long)row * lda];
       rb[u][j] = B[(long)row * ldb];
     }
-  vx_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int i0 = 0; i0 < nch; i0 += D) {
 #pragma unroll
     for (int u = 0; u < D; ++u) {
-      vx_f4 a = ra[u];
-      const vx_f4 b = rb[u];
+      f32x4 a = ra[u];
+      const f32x4 b = rb[u];
       const int nx = min(i0 + D + u, nch - 1);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {

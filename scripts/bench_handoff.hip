@@ -10,6 +10,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "../mmego_amd/csrc/lds_dma.h"
+
 #define H 512
 #define ROWS 64
 #define NWG_DIR 128
@@ -21,7 +23,7 @@ __global__ __launch_bounds__(256) void handoff_b_kernel(float* hbuf, unsigned* c
   for (int s = 0; s < steps; ++s) {
     float* hcur = hbuf + ((size_t)(s & 1) * 2 + d) * ROWS * H;
     __hip_atomic_store(&hcur[(tid >> 2) * H + slice * 4 + (tid & 3)], (float)(s + 1) + acc * 1e-30f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0);                         // this thread's store has been acknowledged
+    wait_vmcnt<0>();                                       // this thread's store has been acknowledged
     __syncthreads();
     if (tid == 0) {
       __hip_atomic_fetch_add(&counters[d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void handoff_c_kernel(float* hbuf, unsigned* c
   for (int s = 0; s < steps; ++s) {
     float* hcur = hbuf + ((size_t)(s & 1) * 8 + g) * 16 * H;                      // [16 rows][512]
     __hip_atomic_store(&hcur[(tid >> 4) * H + slice * 16 + (tid & 15)], (float)(s + 1) + acc * 1e-30f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0);
+    wait_vmcnt<0>();
     __syncthreads();
     if (tid == 0) {
       __hip_atomic_fetch_add(&counters[g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../mmego_amd/csrc/lds_dma.h"
+
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 template <int PATH>
@@ -35,8 +37,7 @@ __global__ __launch_bounds__(1024) void stream_kernel(const f4* __restrict__ buf
         // a wave's transfer = 64 lanes x 16 B = 1 KB into its own LDS slot u (8 slots x 1 KB per wave)
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(region + i0 + (long)u * nthr + tid),
-                                           (__attribute__((address_space(3))) void*)(lds + (w * 8 + u) * 64), 16, 0, 0);
+          GLDS16(region + i0 + (long)u * nthr + tid, lds + (w * 8 + u) * 64);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
