@@ -114,10 +114,11 @@ def test_linear_pair_and_batched_bias(dev):
 
 def test_fused_eval_mlp_and_bn_fold(dev):
     """mmego_bn_fold_linear + mmego_mlp3_eval (eval-mode PointNet stages in one kernel) against conv -> BatchNorm(eval) -> ReLU
-    in fp64, for the three channel plans of the path, ragged row counts and column-slice inputs / outputs."""
+    in fp64, for the three channel plans of the path, ragged row counts and column-slice inputs / outputs; the last row count has more
+    64-row tiles than the launch has workgroups (2048): workgroups 0 and 1 walk on to a second tile, the last one ragged."""
     from mmego_amd import hip
     g = torch.Generator().manual_seed(11)
-    for rows, dims in ((1000, (28, 32, 48, 64)), (77, (6, 8, 16, 24)), (4099, (6, 16, 32, 61))):
+    for rows, dims in ((1000, (28, 32, 48, 64)), (77, (6, 8, 16, 24)), (4099, (6, 16, 32, 61)), (2048 * 64 + 64 + 13, (6, 8, 16, 24))):
         Cin = dims[0]
         xbuf = torch.randn(rows, Cin + 5, generator=g).to(dev)
         x = xbuf[:, 3:3 + Cin]                                            # column slice (row stride Cin + 5)

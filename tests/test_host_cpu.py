@@ -131,15 +131,17 @@ def test_product_does_not_import_oracle():
 
 def test_shared_device_helpers_are_defined_once():
     """The LDS-DMA request and every s_waitcnt immediate live in csrc/lds_dma.h, the fast activations in lstm_cell.h, the fp32 -> bf16
-    conversions in bf16_pack.h: no kernel file or probe spells one out again (the tests compare the kernels that share them bit for
-    bit).  No exception: common.h's stamp macro calls wait_lgkmcnt0() as well."""
+    conversions in bf16_pack.h, the bodies of the eval MLP and of the Upper front end in mlp3_eval.h and front_eval.h: no kernel file or
+    probe spells one out again (the tests compare the kernels that share them bit for bit).  No exception: common.h's stamp macro calls wait_lgkmcnt0() as well."""
     import glob
     csrc = os.path.join(ROOT, "mmego_amd", "csrc")
     files = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(ROOT, "scripts", "*.hip"))
     assert len(files) >= 40
     only_in = {r"__builtin_amdgcn_global_load_lds": "lds_dma.h", r"__builtin_amdgcn_s_waitcnt\(": "lds_dma.h",
                r"__builtin_amdgcn_rcpf\(1\.0f \+ __expf": "lstm_cell.h", r"(?<!sizeof)\(__bf16\)": "bf16_pack.h",     # (a cast, not sizeof(__bf16))
-               r"__builtin_convertvector": "bf16_pack.h"}
+               r"__builtin_convertvector": "bf16_pack.h",
+               # the eval MLP and the Upper front end are written once for fp32 and bf16 operands: their staging macros occur nowhere else
+               r"define M3_FETCH": "mlp3_eval.h", r"define FR_PIN": "front_eval.h"}
     seen = set()
     for path in files:
         src = open(path).read()
