@@ -336,7 +336,10 @@ struct MlpBwdP {
 };
 
 // 512 threads = 2 groups of 4 waves, each group one 64-row tile of a 128-row round (three tiles of LDS per group)
-// FULL: every workgroup of the launch owns rows_per_wg complete rows (rows % rows_per_wg == 0: every shape of the training step).  In-kernel
+// FULL: every workgroup of the launch owns rows_per_wg complete rows (rows % rows_per_wg == 0: every shape of the benchmark's training step;
+// any other batch -- a shorter last batch of an epoch -- takes the ragged form, and LocalPointNet's first layer the gather form.  All
+// three forms of this kernel and both forms of mlp_fwd_layer_kernel run alone against float64 in tests/test_mlp_train_gpu.py: the ragged
+// forms at 3 .. 257, 1920, 4173 and 66 381 rows, the forms against each other bit for bit on shared rows in test_forms_agree_*).  In-kernel
 // stamps (scripts/mlp_bwd_probe.hip) put the two 128-row rounds of a workgroup at ~15 k cycles EACH whatever the channel count -- 8 or
 // 64 -- with ~1400 instructions per wave and round, a third of them 64-bit row x stride address arithmetic, row clamps and per-element
 // predicates: the kernel is bound by instruction issue (two waves per SIMD), not by memory or the matrix pipe (regrouping its loads,
