@@ -297,6 +297,19 @@ int mmego_rotate_points(void* stream, const float* in, float* out, long F, int P
  * accumulate != 0: added to what dR / dt hold.  One wave per frame, a fixed summation order: two runs give the same bits. */
 int mmego_transform2h_backward(void* stream, const float* pts, long ldp, long F, int P, const float* R, const float* t,
                                const float* g, long ldg, const float* g2, long ldg2, int accumulate, float* dR, float* dt);
+/* Backward of Lower_Net's two head-frame transforms p' = R (p - t) (Lower_Net.py:191-192,205) with respect to R, t and the predicted
+ * joints, in one launch.  Points share (skipped when pts is NULL): pts [F*N] UNTRANSFORMED rows (row stride ldp), idx [F,P] the
+ * forward's selection (int64, indices into the frame's N rows), g (row stride ldg) and g2 (may be NULL, row stride ldg2) gradients
+ * with respect to the transformed xyz of the F*P selected rows (BasePointNet's input gradient and the xyz columns of p_vec's).
+ * Joints share (skipped when joints is NULL): joints [F,V,3] as the caller gave them, gj (row stride ldgj >= 3V) and gj2 (may be NULL,
+ * row stride ldgj2) gradients with respect to the transformed joints, one row of 3V columns per frame (fc0's input columns and
+ * data_bn's input gradient).  dR [F,3,3], dR[f][i][k] = sum g_i (p - t)_k and dt [F,3] = -R^T sum g over both shares (both NULL: not
+ * wanted); djoints [F,V,3] = R^T gj (may be NULL).  accumulate != 0: added to what dR / dt hold (the world transform's share).
+ * One wave per frame, a fixed summation order (points, then joints, in index order; then the lanes): two runs give the same bits. */
+int mmego_lower_inputs_backward(void* stream, const float* pts, long ldp, long F, int N, const long long* idx, int P, const float* R,
+                                const float* t, const float* g, long ldg, const float* g2, long ldg2, const float* joints, int V,
+                                const float* gj, long ldgj, const float* gj2, long ldgj2, int accumulate, float* dR, float* dt,
+                                float* djoints);
 /* which=0: y[F,87] -> q[F,14,3,3], joints[F,15,3] (Upper_Net.py:122-144,354-364);
  * which=1: y[F,42] -> q[F,6,3,3], joints[F,8,3] (Lower_Net.py:12-37,125-136).  body [B,20,3]; frame n
  * uses body row n % B (quirk Q2).  Joints are in the head frame.
@@ -725,6 +738,11 @@ int mmego_slab_reduce(void* stream, int n, const void* descs);
  * GCN.py:310: the skeleton input is detached, Train_Lower.py:196); state [4][C]. */
 int mmego_bn_param_grads(void* stream, const float* dY, long lddy, const float* X, long ldx, const float* state, long rows, int C,
                          float* dgamma, float* dbeta);
+/* Input gradient of a train-mode BatchNorm from its finished parameter gradients: dX[r][c] = a[c] (dY[r][c] - dbeta[c] / rows -
+ * xhat[r][c] dgamma[c] / rows), with dgamma / dbeta as mmego_bn_param_grads left them (the two column sums the formula needs: read,
+ * not written).  data_bn when the predicted skeleton is differentiable (Lower_Net input gradients). */
+int mmego_bn_input_grad(void* stream, const float* dY, long lddy, const float* X, long ldx, const float* state, long rows, int C,
+                        const float* dgamma, const float* dbeta, float* dX, long lddx);
 
 /* ---- optimiser (optim.hip) -------------------------------------------------------------------------
  * torch.optim.Adam step (coupled L2 weight decay) over one flat buffer; state = 3 doubles on the device

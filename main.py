@@ -7,7 +7,8 @@
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
---finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+--finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients), --finetune_upper [--upper_lr F]
+(stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -50,17 +51,37 @@ def build_parser():
                    help="--train --network Upper_Net only: train the IMU_Net as well, end to end through the pose loss (Train_Upper.py:162 "
                         "without its .detach()); the IMU_Net is saved beside the Upper_Net checkpoint, in an IMU_Net folder")
     p.add_argument("--imu_lr", type=float, help="learning rate of the IMU_Net under --finetune_imu (default: --lr / Config.lr)")
+    p.add_argument("--finetune_upper", action="store_true",
+                   help="--train --network Lower_Net only: train the Upper_Net as well (Train_Lower.py:195-196 without its .detach()), on "
+                        "the sum of the two stages' losses; the Upper_Net is saved beside the Lower_Net checkpoint, in an Upper_Net folder")
+    p.add_argument("--upper_lr", type=float, help="learning rate of the Upper_Net under --finetune_upper (default: --lr / Config.lr)")
     return p
+
+
+def check_finetune_upper(parser, args, world):
+    """--finetune_upper fits one arrangement only; everything else is refused before any work starts.  (--gt_head_pose is fine: the
+    head pose is not what is trained.)"""
+    if not args.finetune_upper:
+        if args.upper_lr is not None:
+            parser.error("--upper_lr is the Upper_Net's learning rate under --finetune_upper; without that flag the Upper_Net is frozen")
+        return
+    if not (args.train and args.network == "Lower_Net") or args.infer:
+        parser.error("--finetune_upper goes with --train --network Lower_Net only (joint stage-3 training of Upper_Net and Lower_Net)")
+    if world > 1:
+        parser.error("--finetune_upper is not data parallel yet (WORLD_SIZE=%d): the Upper_Net gradients have no all-reduce" % world)
+    if args.resume:
+        parser.error("--finetune_upper cannot be combined with --resume yet: the Upper_Net's optimiser state is not part of a train state")
 
 
 def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
+    check_finetune_upper(parser, args, world)
     if not args.finetune_imu:
         if args.imu_lr is not None:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
         return
     if not (args.train and args.network == "Upper_Net"):
-        parser.error("--finetune_imu goes with --train --network Upper_Net only (Lower_Net produces no head-pose gradients yet)")
+        parser.error("--finetune_imu goes with --train --network Upper_Net only (training the IMU_Net through Lower_Net's head-pose gradients is not offered on the command line)")
     if args.gt_head_pose:
         parser.error("--finetune_imu needs an IMU_Net to train; --gt_head_pose takes the head pose from the recording instead")
     if world > 1:
@@ -93,6 +114,8 @@ def apply_overrides(args):
     Config.resume_path = args.resume
     Config.finetune_imu = bool(args.finetune_imu)
     Config.imu_lr = args.imu_lr
+    Config.finetune_upper = bool(args.finetune_upper)
+    Config.upper_lr = args.upper_lr
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

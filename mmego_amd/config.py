@@ -46,6 +46,8 @@ class _Common:
     # can be taken from the recording instead (R = loader R_R0R, t = ground-truth head joint).
     gt_head_pose = False
     data_parallel = False       # set by main.py when launched under torch.distributed.run
+    finetune_upper = False      # --finetune_upper: stage 3 trains the Upper_Net too (train_step.StageStep)
+    upper_lr = None             # --upper_lr: its learning rate (None: lr)
 
 
 class Config(_Common):

@@ -19,7 +19,8 @@
 //   graph_dA_fused finalize + apply of the BatchNorm behind the einsum while the frame's rows are loaded, then both gradients of
 //                  the einsum (bn reduce + finalize + apply + graph_dA: 4 launches -> 1 with tconv's epilogue)
 //   slab_reduce    every split-K / split-row partial product of a backward pass summed by ONE launch at its end (fixed order)
-//   bn_param_grads data_bn's d(gamma), d(beta) alone (its input gradient is never used: the skeleton input is detached)
+//   bn_param_grads data_bn's d(gamma), d(beta) alone (the skeleton input is detached by default ...
+//   bn_input_grad  ... and data_bn's input gradient from those two sums when Lower_Net's inputs are differentiable)
 // All reductions have a fixed order: results are bit-identical from run to run and between the graph / eager engines.
 #include <stdlib.h>
 #include "gcn_stats.h"
@@ -837,6 +838,21 @@ __global__ __launch_bounds__(256) void bn_param_grads_kernel(const float* __rest
   }
 }
 
+// dX = a (dY - dbeta / rows - xhat dgamma / rows): the input gradient of the BatchNorm whose parameter gradients bn_param_grads_kernel
+// has just written (they ARE the two column sums; read here, never written: the parameter gradients keep their bits)
+__global__ __launch_bounds__(256) void bn_input_grad_kernel(const float* __restrict__ dY, long lddy, const float* __restrict__ X, long ldx,
+                                                            const float* __restrict__ st, long rows, int C, const float* __restrict__ dgamma,
+                                                            const float* __restrict__ dbeta, float* __restrict__ dX, long lddx) {
+  const long total = rows * C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / C;
+    const int c = (int)(i - r * C);
+    const float c1 = (float)((double)dbeta[c] / (double)rows), c2 = (float)((double)dgamma[c] / (double)rows);
+    const float xh = (X[r * ldx + c] - st[c]) * st[C + c];
+    dX[r * lddx + c] = st[2 * C + c] * (dY[r * lddy + c] - c1 - xh * c2);
+  }
+}
+
 // =============================================================================================================================
 // C ABI
 // =============================================================================================================================
@@ -993,6 +1009,16 @@ extern "C" int mmego_bn_param_grads(void* stream, const float* dY, long lddy, co
   MMEGO_REQUIRE(dY && X && state && dgamma && dbeta && rows > 0 && C > 0);
   hipLaunchKernelGGL(bn_param_grads_kernel, dim3(cdiv(C, 16)), dim3(256), 0, (hipStream_t)stream, dY, lddy, X, ldx, state, rows, C,
                      dgamma, dbeta);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
+extern "C" int mmego_bn_input_grad(void* stream, const float* dY, long lddy, const float* X, long ldx, const float* state, long rows, int C,
+                                   const float* dgamma, const float* dbeta, float* dX, long lddx) {
+  MMEGO_REQUIRE(dY && X && state && dgamma && dbeta && dX && rows > 0 && C > 0 && lddy >= C && ldx >= C && lddx >= C);
+  const long total = rows * C;
+  hipLaunchKernelGGL(bn_input_grad_kernel, dim3((unsigned)(total < 256L * 1024 ? cdiv(total, 256) : 1024)), dim3(256), 0, (hipStream_t)stream,
+                     dY, lddy, X, ldx, state, rows, C, dgamma, dbeta, dX, lddx);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }

@@ -141,6 +141,78 @@ __global__ __launch_bounds__(64) void transform2h_bwd_kernel(const float* __rest
   }
 }
 
+// Backward of Lower_Net's two head-frame transforms p' = R (p - t) in one launch: the P selected radar points of a frame (rows
+// idx[f][0..P) of its N UNTRANSFORMED points: the forward's selection) and its V predicted joints (as the caller gave them).
+// g / g2: gradient sources with respect to the transformed xyz of the F*P selected rows; gj / gj2: with respect to the transformed
+// joints, one row of 3V columns per frame; every source has a row stride of its own, the second of each pair is optional.
+// dR[f][i][k] = sum g_i (p - t)_k and dt[f] = -R^T sum g over both shares, d joints[f][v] = R^T gj[v].  One wave per frame: lane j adds
+// points j, j + 64, ... then joints j, j + 64, ... in that order, then a butterfly over the lanes -- a fixed order, so two runs give the
+// same bits.  p - t is the forward's difference, never R^T p' (nothing makes R orthonormal).  A share whose pointer is null is skipped;
+// accumulate: the results are added to what dR / dt hold (the world transform's share of the same gradients).
+__global__ __launch_bounds__(64) void lower_inputs_bwd_kernel(const float* __restrict__ pts, long ldp, int N, const long long* __restrict__ idx,
+                                                              int P, const float* __restrict__ R, const float* __restrict__ t,
+                                                              const float* __restrict__ g, long ldg, const float* __restrict__ g2, long ldg2,
+                                                              const float* __restrict__ joints, int V, const float* __restrict__ gj, long ldgj,
+                                                              const float* __restrict__ gj2, long ldgj2, int accumulate,
+                                                              float* __restrict__ dR, float* __restrict__ dt, float* __restrict__ djoints) {
+  const long f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* Rf = R + f * 9;
+  const float t0 = t[f * 3], t1 = t[f * 3 + 1], t2 = t[f * 3 + 2];
+  float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s[3] = {0.f, 0.f, 0.f};
+  if (pts) {
+    for (int p = lane; p < P; p += 64) {
+      const long i = f * P + p;
+      long long n = idx[i];
+      n = n < 0 ? 0 : (n >= N ? N - 1 : n);                       // (the forward's indices are in range; never read outside the frame)
+      const float* x = pts + (f * N + n) * ldp;
+      const float d[3] = {__fsub_rn(x[0], t0), __fsub_rn(x[1], t1), __fsub_rn(x[2], t2)};        // (the forward's p - t)
+      float gv[3] = {g[i * ldg], g[i * ldg + 1], g[i * ldg + 2]};
+      if (g2) { gv[0] += g2[i * ldg2]; gv[1] += g2[i * ldg2 + 1]; gv[2] += g2[i * ldg2 + 2]; }
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        s[r] += gv[r];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a[r * 3 + k] += gv[r] * d[k];
+      }
+    }
+  }
+  if (joints) {
+    for (int v = lane; v < V; v += 64) {
+      const float* u = joints + (f * V + v) * 3;
+      const float d[3] = {__fsub_rn(u[0], t0), __fsub_rn(u[1], t1), __fsub_rn(u[2], t2)};
+      const float* q = gj + f * ldgj + 3 * v;
+      float gv[3] = {q[0], q[1], q[2]};
+      if (gj2) { const float* q2 = gj2 + f * ldgj2 + 3 * v; gv[0] += q2[0]; gv[1] += q2[1]; gv[2] += q2[2]; }
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        s[r] += gv[r];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a[r * 3 + k] += gv[r] * d[k];
+      }
+      if (djoints) {
+        float* o = djoints + (f * V + v) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = Rf[k] * gv[0] + Rf[3 + k] * gv[1] + Rf[6 + k] * gv[2];
+      }
+    }
+  }
+  if (!dR) return;                                                  // (uniform: only the joints' own gradient was wanted)
+#pragma unroll
+  for (int j = 0; j < 9; ++j) a[j] = wave_sum(a[j]);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) s[j] = wave_sum(s[j]);
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) dR[f * 9 + j] = accumulate ? dR[f * 9 + j] + a[j] : a[j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float v = -(Rf[k] * s[0] + Rf[3 + k] * s[1] + Rf[6 + k] * s[2]);
+      dt[f * 3 + k] = accumulate ? dt[f * 3 + k] + v : v;
+    }
+  }
+}
+
 // ---- 6-D -> rotation (Gram-Schmidt), two eps rules -------------------------------------------------
 // mode 0: F.normalize, v / max(|v|, 1e-12)  (Upper/Lower heads);  mode 1: v / max(|v|, 1e-8) (IMU_Net)
 struct Rot6 {
@@ -894,6 +966,21 @@ extern "C" int mmego_transform2h_backward(void* stream, const float* pts, long l
   MMEGO_REQUIRE(F > 0 && F < (1L << 31) && P > 0 && ldp >= 3 && ldg >= 3 && (!g2 || ldg2 >= 3) && pts && R && t && g && dR && dt);
   hipLaunchKernelGGL(transform2h_bwd_kernel, dim3((unsigned)F), dim3(64), 0, (hipStream_t)stream, pts, ldp, P, R, t, g, ldg, g2, ldg2,
                      accumulate, dR, dt);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
+// Backward of Lower_Net's head-frame transforms (selected points and predicted joints) with respect to R, t and the joints.
+extern "C" int mmego_lower_inputs_backward(void* stream, const float* pts, long ldp, long F, int N, const long long* idx, int P,
+                                           const float* R, const float* t, const float* g, long ldg, const float* g2, long ldg2,
+                                           const float* joints, int V, const float* gj, long ldgj, const float* gj2, long ldgj2,
+                                           int accumulate, float* dR, float* dt, float* djoints) {
+  MMEGO_REQUIRE(F > 0 && F < (1L << 31) && R && t && (pts || joints) && (!dR == !dt) && (dR || djoints));
+  MMEGO_REQUIRE(!pts || (idx && g && N > 0 && P > 0 && ldp >= 3 && ldg >= 3 && (!g2 || ldg2 >= 3)));
+  MMEGO_REQUIRE(!joints || (gj && V > 0 && ldgj >= 3L * V && (!gj2 || ldgj2 >= 3L * V)));
+  MMEGO_REQUIRE(!djoints || joints);
+  hipLaunchKernelGGL(lower_inputs_bwd_kernel, dim3((unsigned)F), dim3(64), 0, (hipStream_t)stream, pts, ldp, N, idx, P, R, t, g, ldg, g2,
+                     ldg2, joints, V, gj, ldgj, gj2, ldgj2, accumulate, dR, dt, djoints);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }

@@ -198,8 +198,9 @@ def _refuse_pose_grad(who, **named):
     """Nets whose backward owes its inputs nothing yet: a differentiable input must not lose its gradient silently."""
     bad = [k for k, v in named.items() if isinstance(v, torch.Tensor) and v.requires_grad]
     if bad and torch.is_grad_enabled():
-        raise NotImplementedError("%s: %s require%s grad, but this net's backward produces no input gradients (only UpperNet "
-                                  "differentiates its head pose R, t); detach them" % (who, ", ".join(bad), "s" if len(bad) == 1 else ""))
+        raise NotImplementedError("%s: %s require%s grad, but this net's backward produces no input gradients (UpperNet differentiates "
+                                  "its head pose R, t; LowerNet its upper_l, R, t once differentiable_inputs = True); detach them"
+                                  % (who, ", ".join(bad), "s" if len(bad) == 1 else ""))
 
 
 class _PoseBridge(torch.autograd.Function):
@@ -227,6 +228,34 @@ class _PoseBridge(torch.autograd.Function):
         dR = dR.clone().view(rs).to(rd) if ctx.needs_input_grad[2] else None
         dt = dt.clone().view(ts).to(td) if ctx.needs_input_grad[3] else None
         return (None, None, dR, dt) + (None,) * len(ctx.net._flat.params)
+
+
+class _InputBridge(torch.autograd.Function):
+    """_Bridge of LowerNet (differentiable_inputs) with upper_l, R, t as differentiable inputs: backward returns their gradients beside
+    the parameter gradients -- only those somebody needs."""
+
+    @staticmethod
+    def forward(ctx, net, args, upper_l, R, t, *params):
+        ctx.net = net
+        x, body, pin = args
+        need = ctx.needs_input_grad
+        want = (("upper_l",) if need[2] else ()) + (("pose",) if (need[3] or need[4]) else ())
+        outs = net._forward_impl(upper_l, x, body, R, t, pin, input_grad=want)
+        ctx.mark_non_differentiable(*outs[1:])
+        ctx.like = [(v.shape, v.dtype) for v in (upper_l, R, t)]
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if not ctx.net.training:
+            raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
+                                      "the reference detaches frozen nets (Train_Lower.py:195-196)")
+        ctx.net._backward_impl(grads[0])
+        ctx.net.flat().bind_grads()
+        # (copies: the arena's buffers are rewritten by the next step, and autograd may keep what it is handed as .grad)
+        out = [g.clone().view(shape).to(dtype) if (ctx.needs_input_grad[2 + i] and g is not None) else None
+               for i, (g, (shape, dtype)) in enumerate(zip(ctx.net.input_grads(), ctx.like))]
+        return (None, None) + tuple(out) + (None,) * len(ctx.net._flat.params)
 
 
 # =====================================================================================================
@@ -399,15 +428,31 @@ class UpperNet(_NetBase):
             self._saved = (B, T, N, R, body, c0, attn)
         return l, q, attn, hn, cn
 
-    def _backward_impl(self, dl):
+    def _backward_impl(self, dl, dl_extra=None):
+        """dl_extra (optional, [F,15,3]): a second gradient with respect to the predicted joints, added to dl's (the joint stage-3 step:
+        Lower_Net's d upper_l beside this net's own loss gradient; no head pose gradients then)."""
         ar = self.arena("train")
         B, T, N, R, body, c0, attn = self._saved
         F, rows = B * T, B * T * N
         G = self._flat.grad
-        dl = _f32c(dl)
         y, h1 = ar.get("y", (F, 87)), ar.get("h1", (F, 128))
         dy = ar.get("dy", (F, 87))
         pose = getattr(self, "_pose", None)
+        if dl_extra is not None:
+            if pose is not None:
+                raise ValueError("UpperNet: dl_extra cannot be combined with pose_grad")
+            if getattr(self, "_dy_ready", False):
+                # the fused loss launch has left the own loss's dy: the kinematics' backward is linear in its input gradient, so the
+                # second gradient's dy is added to it
+                dyx = ar.get("dy_extra", (F, 87))
+                hip.call("head_fk_backward", 0, y, body, B, F, _f32c(dl_extra), dyx, R)
+                ops.copy2d(dyx, dy, accumulate=True)
+            else:
+                dls = ar.get("dl_sum", (F, 45))
+                ops.copy2d(_f32c(dl).view(F, 45), dls)
+                ops.copy2d(_f32c(dl_extra).view(F, 45), dls, accumulate=True)
+                dl = dls
+        dl = _f32c(dl) if dl is not None else None
         if not getattr(self, "_dy_ready", False):
             if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
                 hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
@@ -517,7 +562,12 @@ class FusionModule(nn.Module):
 
 class LowerNet(_NetBase):
     """forward(upper_l[B,T,15,3], x[B,T,N,6], h0_p, c0_p, h0_k, c0_k, initial_body, R, t) -> (l[B,T,8,3], q[B,T,6,3,3]).
-    The four state arguments are ignored, as in the reference (Q7).  MUTATES x (Q1)."""
+    The four state arguments are ignored, as in the reference (Q7).  MUTATES x (Q1).
+    differentiable_inputs (default False: an upper_l, R or t that requires grad is refused): when True, such inputs receive their
+    gradients from backward -- both head-frame transforms (selected points, predicted joints), everything the joints feed (ST-GCN,
+    fc0) and, for R and t, the world transform behind the kinematics.  x and initial_body are not differentiable."""
+
+    differentiable_inputs = False
 
     def __init__(self, hidden_dim):
         super().__init__()
@@ -546,14 +596,30 @@ class LowerNet(_NetBase):
         cut its choice depends on the torch build; replaying the recorded choice lets the HIP path be compared with the
         reference's outputs (goldens G5 / G9) at the 1e-3 cm bar instead of through the oracle alone."""
         _require_gpu(x, "LowerNet")
-        _refuse_pose_grad("LowerNet", upper_l=upper_l, R=R, t=t)
+        if not self.differentiable_inputs:
+            _refuse_pose_grad("LowerNet", upper_l=upper_l, R=R, t=t)
+        elif _pose_wants_grad(upper_l, R, t):
+            self.flat()
+            return _InputBridge.apply(self, (x, initial_body, pin_select_idx), upper_l, R, t, *self._flat.params)
         args = (upper_l, x, initial_body, R, t, pin_select_idx)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self.flat()
             return _Bridge.apply(self, 1, args, *self._flat.params)
         return self._forward_impl(*args, stash=False)
 
-    def _forward_impl(self, upper_l, x, body, R, t, pin_select_idx=None, stash=True):
+    def input_grads(self):
+        """(d upper_l [F,15,3] | None, dR [F,3,3] | None, dt [F,3] | None) of the last backward behind an input_grad forward: arena
+        buffers, rewritten by the next one."""
+        ig = getattr(self, "_ingrad", None)
+        if ig is None:
+            raise RuntimeError("LowerNet.input_grads: the last forward did not ask for input gradients")
+        return ig["d_upper_l"], ig["dR"], ig["dt"]
+
+    def _forward_impl(self, upper_l, x, body, R, t, pin_select_idx=None, stash=True, input_grad=()):
+        """input_grad: a subset of {"upper_l", "pose"} -- _backward_impl also forms d loss / d upper_l, respectively d loss / d R and
+        d loss / d t (input_grads()).  "pose" keeps a copy of the points as they arrive (the second transform's UNTRANSFORMED input: x is
+        transformed in place), asks BasePointNet for its input gradient and takes the world transform's share from the kinematics
+        launch; "upper_l" alone costs none of these."""
         self.flat()
         training = self.training
         ar = self.arena("train" if stash else "eval")
@@ -565,8 +631,22 @@ class LowerNet(_NetBase):
         dev = x.device
         R, t, body = _f32c(R), _f32c(t), _f32c(body)
         up = ar.get("up", (F, V * 3))
+        upper_l = _f32c(upper_l)
+        self._ingrad = None
+        want = frozenset(input_grad)
+        if want:
+            if not stash or not want <= {"upper_l", "pose"}:
+                raise ValueError("LowerNet: input_grad is a subset of {'upper_l', 'pose'} and needs a forward that keeps its "
+                                 "activations (stash=True)")
+            pose = "pose" in want
+            raw = None
+            if pose:
+                raw = ar.get("pts_raw", (F * N, Cx))
+                ops.copy2d(x.view(F * N, Cx), raw)
+            self._ingrad = dict(upper_l=upper_l, raw=raw, t=t, d_upper_l=ar.get("d_upper_l", (F, V, 3)) if "upper_l" in want else None,
+                                dR=ar.get("dR", (F, 3, 3)) if pose else None, dt=ar.get("dt", (F, 3)) if pose else None)
         # Q1 (second transform after UpperNet) and the predicted joints' copy + transform: one launch
-        hip.call("transform2h_pair", x, F, N, Cx, R, t, up, V, _f32c(upper_l))
+        hip.call("transform2h_pair", x, F, N, Cx, R, t, up, V, upper_l)
         sel = ar.get("sel", (F * LOWER_POINTS, Cx))
         idx = ar.get("sel_idx", (F, LOWER_POINTS), dtype=torch.int64)
         prow = F * LOWER_POINTS
@@ -638,7 +718,9 @@ class LowerNet(_NetBase):
         jh = ar.get("jh", (F, 8, 3))
         l = torch.empty((B, T, 8, 3), dtype=torch.float32, device=dev)
         tick = self._flat.tick_args(self.seed_counter()) if training else (None, 0, None)   # BatchNorm counters + dropout seed
-        self._head_fk(ar, 1, y, body, B, F, q, jh, R, t, l, tick, stash)    # kinematics + head-to-world transform (+ loss), one launch
+        ig = self._ingrad
+        # kinematics + head-to-world transform (+ loss), one launch
+        self._head_fk(ar, 1, y, body, B, F, q, jh, R, t, l, tick, stash, pose=(ig["dR"], ig["dt"]) if (ig is not None and ig["dR"] is not None) else None)
         if stash:
             self._saved = (B, T, N, R, body)
         return l, q
@@ -897,8 +979,13 @@ class LowerNet(_NetBase):
         dl = _f32c(dl)
         y, f1, f0, cat = ar.get("y", (F, 42)), ar.get("f1", (F, 64)), ar.get("f0", (F, 128)), ar.get("cat", (F, 173))
         dy = ar.get("dy", (F, 42))
+        ig = getattr(self, "_ingrad", None)
+        pose = ig is not None and ig["dR"] is not None
         if not getattr(self, "_dy_ready", False):
-            hip.call("head_fk_backward", 1, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
+            if pose:                      # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
+                hip.call("head_fk_backward_pose", 1, y, body, B, F, dl, dy, R, ar.get("jh", (F, 8, 3)), ig["dR"], ig["dt"])
+            else:
+                hip.call("head_fk_backward", 1, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
         df1, df0, dcat = ar.get("df1", (F, 64)), ar.get("df0", (F, 128)), ar.get("dcat", (F, 173))
         leaves = []          # weight gradients of the fusion head and of the BiLSTM stack: leaves, issued together behind the stack
         blocks.linear_backward(dy, f1, fu.fc2, G, df1, relu_input=True, leaves=leaves)
@@ -939,14 +1026,26 @@ class LowerNet(_NetBase):
             blocks.linear_backward(dK, k_vec, fu.to_k, G, dk, accumulate_dx=True)
             blocks.linear_backward(dV, k_vec, fu.to_v, G, dk, accumulate_dx=True)
         sel = ar.get("sel", (prow, 6))
-        blocks.mlp3_backward(ar, "base", self.pointEncoder.module0, sel, p_vec[:, 3:64], dp[:, 3:64], G, False)
+        dsel = blocks.mlp3_backward(ar, "base", self.pointEncoder.module0, sel, p_vec[:, 3:64], dp[:, 3:64], G, pose)
         if slabs is not None:
-            self._gcn_backward_fused(ar, dk, B, T, G, slabs)
+            self._gcn_backward_fused(ar, dk, B, T, G, slabs, input_grad=ig is not None)
             slabs.run()
         else:
             self._gcn_backward(ar, dk, B, T, G)
+        if ig is not None:
+            # the head-frame transforms' shares.  The transformed joints feed fc0 (dcat's last 45 columns) and data_bn (gcn.dup); the
+            # selected points' transformed xyz feed BasePointNet's first layer (dsel) and the first columns of p_vec (dp)
+            dup = ar.get("gcn.dup", (F, V * 3))
+            dj = dcat[:, 128:173]
+            idx = ar.get("sel_idx", (F, LOWER_POINTS), dtype=torch.int64)
+            if pose:
+                hip.call("lower_inputs_backward", ig["raw"], ig["raw"].stride(0), F, N, idx, LOWER_POINTS, R, ig["t"], dsel, dsel.stride(0),
+                         dp, dp.stride(0), ig["upper_l"], V, dj, dj.stride(0), dup, dup.stride(0), 1, ig["dR"], ig["dt"], ig["d_upper_l"])
+            else:
+                hip.call("lower_inputs_backward", None, 0, F, N, None, LOWER_POINTS, R, ig["t"], None, 0, None, 0,
+                         ig["upper_l"], V, dj, dj.stride(0), dup, dup.stride(0), 0, None, None, ig["d_upper_l"])
 
-    def _gcn_backward_fused(self, ar, dk, B, T, G, slabs):
+    def _gcn_backward_fused(self, ar, dk, B, T, G, slabs, input_grad=False):
         """Backward of the fused ST-GCN step: per block reduce + apply of the closing BatchNorm pair, the temporal convolution's weight
         and input gradient (the latter with the next BatchNorm's sums in its epilogue), both einsum gradients with that BatchNorm's
         backward applied on load, the stacked 1x1 convs' weight gradient (slabs deferred) and input gradient: 7 launches (was 14)."""
@@ -1001,11 +1100,16 @@ class LowerNet(_NetBase):
             ops.grad_weight_deferred(dzr, inp, gWc, slabs, ar, "slab." + key + ".w", db=gbc)
             ops.grad_input(dzr, Wc, dinp)
             dcur = dinp
-        # data_bn: only its parameter gradients (its input, the predicted skeleton, is detached: Train_Lower.py:196)
+        # data_bn: only its parameter gradients (its input, the predicted skeleton, is detached: Train_Lower.py:196) ...
         dinp = dcur
         up = ar.get("up", (F, V * 3))
         st = ops.BnState(ar, "gcn.dbn", V * 3)
         hip.call("bn_param_grads", dinp.view(F, V * 3), V * 3, up, V * 3, st.all, F, V * 3, G(gcn.data_bn.weight), G(gcn.data_bn.bias))
+        if input_grad:
+            # ... unless somebody differentiates the skeleton: the two parameter gradients are the column sums its input gradient needs
+            dup = ar.get("gcn.dup", (F, V * 3))
+            hip.call("bn_input_grad", dinp.view(F, V * 3), V * 3, up, V * 3, st.all, F, V * 3, G(gcn.data_bn.weight), G(gcn.data_bn.bias),
+                     dup, dup.stride(0))
 
     def _gcn_backward(self, ar, dk, B, T, G):
         gcn = self.keyEncoder.gcn

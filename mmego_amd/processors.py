@@ -29,7 +29,9 @@ _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_
 class _Base:
     """Shared set-up: directories, frozen IMU_Net (or ground-truth head pose), datasets."""
     finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
+    finetune_upper = False        # (--finetune_upper: likewise)
     _imu_opt_shared = None
+    _upper_opt_shared = None
 
     def __init__(self, cfg, make_dirs=True):
         self.cfg = cfg
@@ -127,8 +129,11 @@ class _StageTrainer(_Base):
         self.finetune_imu = bool(getattr(cfg, "finetune_imu", False))
         if self.finetune_imu and (self.stage != "upper" or cfg.gt_head_pose or self.world > 1 or getattr(cfg, "resume_path", None)):
             raise SystemExit("--finetune_imu: Upper_Net stage with an IMU_Net checkpoint only; not data parallel, not with --resume")
+        self.finetune_upper = bool(getattr(cfg, "finetune_upper", False))
+        if self.finetune_upper and (self.stage != "lower" or self.world > 1 or getattr(cfg, "resume_path", None)):
+            raise SystemExit("--finetune_upper: Lower_Net stage only; not data parallel, not with --resume")
         self.model_IMU = self._load_imu()
-        self._imu_opt_shared = None
+        self._imu_opt_shared = self._upper_opt_shared = None
         self.train_data = PosePC(batch_length=self.frame_no)
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -153,11 +158,19 @@ class _StageTrainer(_Base):
             pg = self.pg
             # (--finetune_imu: the plain StageStep -- the IMU_Net is trained, there is no frozen forward to run ahead)
             pipelined = (self.model_IMU is not None and not self.finetune_imu and os.environ.get("MMEGO_PIPELINE_IMU", "1") != "0")
+            # (--finetune_upper: the plain StageStep too -- the engines around a frozen IMU_Net forward refuse a stage with two trained nets)
+            pipelined = pipelined and not self.finetune_upper
             imu_lr = getattr(self.cfg, "imu_lr", None)
             st = StageStep(self.stage, self.model, None if pipelined else self.model_IMU,
                            upper_frozen=getattr(self, "Upper_net", None), lr=self.learning_rate, process_group=pg,
                            use_graph=not pipelined, finetune_imu=self.finetune_imu,
-                           imu_lr=self.learning_rate if imu_lr is None else imu_lr)
+                           imu_lr=self.learning_rate if imu_lr is None else imu_lr,
+                           finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None))
+            if self.finetune_upper:                                     # one Upper_Net optimiser state for all batch sizes, too
+                if self._upper_opt_shared is not None:
+                    st.upper_opt = self._upper_opt_shared
+                else:
+                    self._upper_opt_shared = st.upper_opt
             if self.finetune_imu:                                       # one IMU_Net optimiser state for all batch sizes, too
                 if self._imu_opt_shared is not None:
                     st.imu_opt = self._imu_opt_shared
@@ -181,6 +194,8 @@ class _StageTrainer(_Base):
         self.model.train()
         if self.finetune_imu:
             self.model_IMU.train()                                      # (.eval() again for the epoch evaluation: eval_model)
+        if self.finetune_upper:
+            self.Upper_net.train()                                      # (likewise)
         nsel = self.model_out_joints
         if self._log is None:
             self._log = torch.zeros((64, 2), dtype=torch.float32, device=self.device)
@@ -261,6 +276,8 @@ class _StageTrainer(_Base):
                 self.save_models(epoch, self.model, self._optimizer(), early)
                 if self.finetune_imu:
                     self.save_imu(epoch)
+                if self.finetune_upper:
+                    self.save_upper(epoch)
             if stop:
                 print("Early stopping")
                 break
@@ -274,6 +291,17 @@ class _StageTrainer(_Base):
         os.makedirs(folder, exist_ok=True)
         path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
         torch.save(self.model_IMU.state_dict(), path)
+        return path
+
+
+    def save_upper(self, epoch):
+        """--finetune_upper: the trained Upper_Net beside the Lower_Net checkpoint, same file name, in an Upper_Net folder."""
+        if self.rank != 0:
+            return None
+        folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), "Upper_Net")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
+        torch.save(self.Upper_net.state_dict(), path)
         return path
 
 
@@ -347,6 +375,9 @@ class LowerTrainer(_StageTrainer):
 
     def eval_model(self):
         self.model.eval()
+        if self.finetune_upper:
+            self.Upper_net.eval()
+            self.Upper_net.weights_changed()          # (the fused Adam writes through raw pointers: no derived copy of old weights)
         return evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.test_data, self.batchsize, True, self._rng)[0]
 
 

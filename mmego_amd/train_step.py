@@ -142,6 +142,9 @@ def _refuse_finetune(who, stages):
     if any(getattr(st, "finetune_imu", False) for st in stages):
         raise ValueError("%s: a stage with finetune_imu=True trains its IMU_Net, which is then no frozen, shareable forward; run it as a "
                          "plain StageStep" % who)
+    if any(getattr(st, "finetune_upper", False) for st in stages):
+        raise ValueError("%s: a stage with finetune_upper=True trains its Upper_Net inside its own body (two nets, two optimisers); run it "
+                         "as a plain StageStep" % who)
 
 
 class StageStep:
@@ -153,20 +156,41 @@ class StageStep:
     ``finetune_imu`` (Upper stage): the IMU_Net is trained too, through the pose loss -- Train_Upper.py:162 without its .detach().
     Per minibatch: IMU_Net training forward -> R, t -> Upper_Net forward + loss + backward, which now leaves d loss / d R and
     d loss / d t (UpperNet.pose_grads) -> IMU_Net backward -> two Adam steps (Upper_Net at ``lr``, IMU_Net at ``imu_lr`` with stage
-    1's weight decay).  The body is still one HIP graph."""
+    1's weight decay).  The body is still one HIP graph.
+
+    ``finetune_upper`` (Lower stage): joint stage-3 training -- Train_Lower.py:195-196 without its .detach().  ``upper_frozen`` is then
+    NOT frozen: per minibatch it runs a TRAIN-mode forward that keeps its activations, with its own L1(sum) loss on the 15 upper joints
+    (``upper_loss2``); Lower_Net's forward takes that prediction undetached, its backward leaves d loss_lower / d upper_l
+    (LowerNet.input_grads), and Upper_Net's backward runs on d(loss_lower + loss_upper); two Adam steps (Lower_Net at ``lr``, Upper_Net at
+    ``upper_lr``, default ``lr``).  The head pose is not trained (frozen IMU_Net, shared pose or the recording, as without the option).
+    The sum of the two stages' own losses, because the final skeleton takes 13 of its 21 joints from Upper_Net: the lower loss alone must
+    not be the only thing steering it.  One HIP graph."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
-                 use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001):
+                 use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None):
         assert stage in ("upper", "lower")
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
         self.finetune_imu = bool(finetune_imu)
-        self.imu_opt = None
+        self.finetune_upper = bool(finetune_upper)
+        self.imu_opt = self.upper_opt = None
+        if self.finetune_upper:
+            from .nets import LowerNet, UpperNet
+            if stage != "lower" or type(net) is not LowerNet:
+                raise ValueError("StageStep: finetune_upper trains Upper_Net through Lower_Net's input gradients: the Lower stage only")
+            if type(upper_frozen) is not UpperNet:
+                raise ValueError("StageStep: finetune_upper needs the Upper_Net to train as upper_frozen (a plain UpperNet; UpperNetwlocal "
+                                 "is not supported)")
+            if self.finetune_imu:
+                raise ValueError("StageStep: finetune_upper cannot be combined with finetune_imu (the head pose is not trained in stage 3)")
+            if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
+                raise ValueError("StageStep: finetune_upper is not data parallel yet (no all-reduce of the Upper_Net gradients)")
+            self.upper_opt = FusedAdam(upper_frozen.flat(), lr=lr if upper_lr is None else upper_lr, weight_decay=weight_decay)
         if self.finetune_imu:
             from .nets import UpperNet
             if stage != "upper" or type(net) is not UpperNet:
-                raise ValueError("StageStep: finetune_imu trains IMU_Net through Upper_Net's head-pose gradients; Lower_Net and "
-                                 "UpperNetwlocal produce none")
+                raise ValueError("StageStep: finetune_imu trains IMU_Net through Upper_Net's head-pose gradients; UpperNetwlocal produces "
+                                 "none, and Lower_Net's (LowerNet.input_grads) have no IMU_Net consumer yet")
             if imu_net is None or pose is not None:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
@@ -184,6 +208,9 @@ class StageStep:
         self.loss2 = torch.zeros(2, dtype=torch.float32, device=dev)   # [L1 sum, sum of per-joint Euclidean distances]
         self.loss = self.loss2[:1]
         self.last_pred = None
+        if self.finetune_upper:                                        # (loss2 stays the Lower stage's pair: the trainers log it)
+            self.upper_jmap = torch.tensor(UPPER_MAP, dtype=torch.int32, device=dev)
+            self.upper_loss2 = torch.zeros(2, dtype=torch.float32, device=dev)
 
     def _body(self):
         self._body_forward()
@@ -200,10 +227,14 @@ class StageStep:
         via_transform = (type(first_net) is UpperNet or (self.stage == "upper" and type(first_net) is UpperNetwlocal)) and s["x"].shape[-1] <= 8
         # the trained net's kinematics launch takes the loss, its gradient and the first backward step along (nets._head_fk)
         self.net.loss_hook = (s["target"], self.jmap, self.loss2, 1.0)
+        if self.finetune_upper:
+            self.upper_frozen.loss_hook = (s["target"], self.upper_jmap, self.upper_loss2, 1.0)
         try:
             self._body_forward_inner(s, B, T, first_net, via_transform)
         finally:
             self.net.loss_hook = None
+            if self.finetune_upper:
+                self.upper_frozen.loss_hook = None
 
     def _body_forward_inner(self, s, B, T, first_net, via_transform):
         from .nets import UpperNet
@@ -236,6 +267,17 @@ class StageStep:
                 else:
                     l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True)[0]
                 nsel = 15
+            elif self.finetune_upper:
+                upper = self.upper_frozen
+                if not upper.training:
+                    raise ValueError("StageStep: finetune_upper needs its Upper_Net in train mode (call .train() on it)")
+                # (not via_transform: x holds the fresh minibatch already)
+                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src)[0]
+                if not getattr(upper, "_dy_ready", False):
+                    hip.call("l1_loss", up, s["target"], self.upper_jmap, 15, 21, B * T, 1.0, self.upper_loss2, s["dl_up"])
+                l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True, input_grad=("upper_l",))[0]
+                self.last_upper_pred = up
+                nsel = 8
             else:
                 if via_transform and not self.upper_frozen.training:
                     up = self.upper_frozen._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=False, x_src=x_src)[0]
@@ -252,6 +294,9 @@ class StageStep:
     def _body_backward(self):
         with torch.no_grad():
             self.net._backward_impl(self.static["dl"])
+            if self.finetune_upper:
+                # d(loss_lower + loss_upper) / d(Upper_Net's joints): its own loss's share and Lower_Net's d upper_l
+                self.upper_frozen._backward_impl(self.static["dl_up"], dl_extra=self.net.input_grads()[0])
             if self.finetune_imu:
                 from . import imu_train
                 imu_train.backward(self.imu, *self.net.pose_grads())
@@ -267,12 +312,17 @@ class StageStep:
                            h0=torch.zeros(6, B, 64, device=dev), c0=torch.zeros(6, B, 64, device=dev),
                            dl=torch.empty(B, T, nsel, 3, device=dev), R_gt=R_gt,
                            t_gt=torch.empty(B, T, 3, device=dev))
+        if self.finetune_upper:
+            self.static["dl_up"] = torch.empty(B, T, 15, 3, device=dev)
         self.graph = None
 
     def _mutable_state(self):
         """What a body changes besides gradients/activations: BatchNorm running statistics + step counters and the dropout
-        counter of the trained net (the frozen nets run in eval mode)."""
-        return list(self.net.buffers()) + [self.net.seed_counter()] + ([self.imu.seed_counter()] if self.finetune_imu else [])
+        counter of the trained net(s) (the frozen nets run in eval mode)."""
+        extra = [self.imu.seed_counter()] if self.finetune_imu else []
+        if self.finetune_upper:                                        # (the second trained net's BatchNorm statistics and dropout counter)
+            extra += list(self.upper_frozen.buffers()) + [self.upper_frozen.seed_counter()]
+        return list(self.net.buffers()) + [self.net.seed_counter()] + extra
 
     def warm_up(self):
         """Run the body once WITHOUT side effects (sizes the arenas, sets kernel attributes before graph capture): the
@@ -301,6 +351,8 @@ class StageStep:
         self.opt.step()
         if self.finetune_imu:
             self.imu_opt.step()
+        if self.finetune_upper:
+            self.upper_opt.step()
         return self.loss
 
 
