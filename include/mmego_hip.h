@@ -545,6 +545,17 @@ int mmego_add(void* stream, const float* a, const float* b, float* out, long n);
  * layers; n may be 0) and, when seed_ctr is given, the next value of the dropout seed counter (mmego_lstm64_forward). */
 int mmego_inc_i64(void* stream, long long* x, long n, unsigned long long* seed_ctr);
 
+/* ---- inter-layer dropout of the LSTM stacks whose step kernels do not carry it (dropout.hip; IMU_Net training) -------
+ * taken[0] = seed_ctr[0], then seed_ctr[0] takes the value mmego_inc_i64 would give it: one training forward's seed word, which
+ * every mask of that forward and of its backward reads (the counter itself may move on in between). */
+int mmego_seed_take(void* stream, unsigned long long* seed_ctr, unsigned long long* taken);
+/* Y[r][c] = X[r][c] * m(r * cols + c), m = 0 or 1/(1-p): the mask mmego_lstm64_forward stores as drop_mask, from the same hash of
+ * (LOGICAL element index r * cols + c, seed_word[0], salt), whatever ldx and ldy are.  Y may be X itself (same base and ldx == ldy: in place); operands that overlap in any
+ * other way are refused.  No mask is stored: backward runs the same call on the gradient.  Needs 0 < p < 1, cols % 4 == 0, rows * cols < 2^32, ldx, ldy >= cols; 16-byte accesses when both
+ * bases and both leading dimensions are multiples of 4 floats, dword accesses otherwise. */
+int mmego_lstm_dropout(void* stream, const float* X, long ldx, float* Y, long ldy, long rows, long cols, float p,
+                       const unsigned long long* seed_word, int salt);
+
 /* ---- train-mode pointwise MLP layers, fused per layer (mlp_train.hip) -------------------------------------------------
  * k=1 conv -> BatchNorm (batch statistics) -> ReLU stages of Net/Upper_Net.py:242-301,147-177 and Net/Lower_Net.py:40-72 in
  * training.  Channel widths <= 64.  nblk = mmego_mlp_train_nblk(rows) workgroups per layer launch; statistics partials are

@@ -8,7 +8,8 @@
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
 --finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients), --finetune_upper [--upper_lr F]
-(stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+(stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses), --imu_dropout P (the
+IMU_Net that is TRAINED -- stage 1, or --finetune_imu -- gets nn.LSTM(dropout=P) between its BiLSTM layers).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -51,6 +52,9 @@ def build_parser():
                    help="--train --network Upper_Net only: train the IMU_Net as well, end to end through the pose loss (Train_Upper.py:162 "
                         "without its .detach()); the IMU_Net is saved beside the Upper_Net checkpoint, in an IMU_Net folder")
     p.add_argument("--imu_lr", type=float, help="learning rate of the IMU_Net under --finetune_imu (default: --lr / Config.lr)")
+    p.add_argument("--imu_dropout", type=float,
+                   help="--train --network IMU_Net, or --finetune_imu: inter-layer LSTM dropout rate in [0, 1) of the IMU_Net that is "
+                        "trained (default: none, as the reference's stage 1)")
     p.add_argument("--finetune_upper", action="store_true",
                    help="--train --network Lower_Net only: train the Upper_Net as well (Train_Lower.py:195-196 without its .detach()), on "
                         "the sum of the two stages' losses; the Upper_Net is saved beside the Lower_Net checkpoint, in an Upper_Net folder")
@@ -73,9 +77,21 @@ def check_finetune_upper(parser, args, world):
         parser.error("--finetune_upper cannot be combined with --resume yet: the Upper_Net's optimiser state is not part of a train state")
 
 
+def check_imu_dropout(parser, args):
+    """--imu_dropout belongs to a run that TRAINS an IMU_Net: stage 1, or stage 2 under --finetune_imu."""
+    if args.imu_dropout is None:
+        return
+    if not 0.0 <= args.imu_dropout < 1.0:
+        parser.error("--imu_dropout is a dropout rate: it has to lie in [0, 1), got %r" % (args.imu_dropout,))
+    if args.infer or not (args.train and (args.network == "IMU_Net" or (args.network == "Upper_Net" and args.finetune_imu))):
+        parser.error("--imu_dropout goes with --train --network IMU_Net or with --finetune_imu only (the runs that train an IMU_Net); "
+                     "a frozen IMU_Net runs in eval mode, where dropout does nothing")
+
+
 def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
     check_finetune_upper(parser, args, world)
+    check_imu_dropout(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -114,6 +130,7 @@ def apply_overrides(args):
     Config.resume_path = args.resume
     Config.finetune_imu = bool(args.finetune_imu)
     Config.imu_lr = args.imu_lr
+    Config.imu_dropout = args.imu_dropout
     Config.finetune_upper = bool(args.finetune_upper)
     Config.upper_lr = args.upper_lr
     if args.imu_precision is not None:

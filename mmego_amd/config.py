@@ -48,6 +48,7 @@ class _Common:
     data_parallel = False       # set by main.py when launched under torch.distributed.run
     finetune_upper = False      # --finetune_upper: stage 3 trains the Upper_Net too (train_step.StageStep)
     upper_lr = None             # --upper_lr: its learning rate (None: lr)
+    imu_dropout = None          # --imu_dropout: nn.LSTM(dropout=P) of the IMU_Net that is trained (None: 0, as the reference's stage 1)
 
 
 class Config(_Common):

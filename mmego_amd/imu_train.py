@@ -51,9 +51,27 @@ def _s3_pieces(ar, name, x):
     return blocks.split3_cvt(x, out=buf)
 
 
-def lstm_steps_forward_stash(ar, key, lstm, x, Bn, T, split3=False):
+def _drop_args(net, lstm, s, word):
+    """(p, seed word, first salt) of a stack's inter-layer dropout, None without: stack s (0: rnn_fast, 1: rnn_slow) masks the output of
+    its layer l with salt 8 * s + l.  nn.LSTM(dropout=p) drops the output of every layer but the last."""
+    p = net._drop_p(lstm)
+    return (p, word, 8 * s) if p > 0.0 and lstm.num_layers > 1 else None
+
+
+def _drop_rates(net):
+    """The two stacks' effective dropout rates in this mode; a rate outside [0, 1) is refused."""
+    rates = [net._drop_p(m) for m in (net.rnn_fast, net.rnn_slow)]
+    for p in rates:
+        if not 0.0 <= p < 1.0:
+            raise ValueError("IMUNet: the LSTM dropout rate must lie in [0, 1), got %r" % (p,))
+    return rates
+
+
+def lstm_steps_forward_stash(ar, key, lstm, x, Bn, T, split3=False, drop=None):
     """Like blocks.lstm_steps_forward but keeps gate activations / cell states of every step for backward.
-    split3: the input projections as fp32-accurate piece products on the bf16 matrix pipe (split3.hip) where _s3_worth says so."""
+    split3: the input projections as fp32-accurate piece products on the bf16 matrix pipe (split3.hip) where _s3_worth says so.
+    drop = (p, seed word, first salt): the next layer reads a dropped COPY "<key>.do<l>" of layer l's output (l < L - 1); the output
+    itself stays as the recurrence wrote it (its own h_{t-1}; backward's weight_hh gradients)."""
     H, L = lstm.hidden_size, lstm.num_layers
     cur = x
     out = None
@@ -78,18 +96,22 @@ def lstm_steps_forward_stash(ar, key, lstm, x, Bn, T, split3=False):
         cst = ar.get("%s.cst%d" % (key, l), (2, T, Bn, H))
         blocks.lstm_recurrence(ar, key, lstm, l, xp, out, Bn, T, gst=gst, cst=cst)
         cur = out
+        if drop is not None and l < L - 1:
+            cur = ops.lstm_dropout(out, ar.get("%s.do%d" % (key, l), (Bn * T, 2 * H)), drop[0], drop[1], drop[2] + l)
     return out
 
 
-def lstm_steps_backward(ar, key, lstm, x, Bn, T, dout, G, need_dx, split3=False):
+def lstm_steps_backward(ar, key, lstm, x, Bn, T, dout, G, need_dx, split3=False, drop=None):
     """dout [Bn*T, 2H] (rows b*T+t) -> gradients of every LSTM weight; returns d(x) if need_dx.
-    split3: the input-gradient products dX = dgates . W_ih as piece products on the bf16 matrix pipe where _s3_worth says so."""
+    split3: the input-gradient products dX = dgates . W_ih as piece products on the bf16 matrix pipe where _s3_worth says so.
+    drop: the forward's (p, seed word, first salt).  Layer l > 0 then read the dropped copy of layer l-1's output (its weight_ih
+    gradient does too), and its input gradient passes the same mask -- regenerated from the word, in place -- on its way down."""
     H, L = lstm.hidden_size, lstm.num_layers
     dev = x.device
     d_cur = dout
     zeros = ar.get("%s.zrow" % key, (Bn, H), zero=True)
     for l in range(L - 1, -1, -1):
-        inp = x if l == 0 else ar.get("%s.out%d" % (key, l - 1), (Bn * T, 2 * H))
+        inp = x if l == 0 else ar.get("%s.%s%d" % (key, "out" if drop is None else "do", l - 1), (Bn * T, 2 * H))
         out = ar.get("%s.out%d" % (key, l), (Bn * T, 2 * H))
         gst = ar.get("%s.gst%d" % (key, l), (2, T, Bn, 4 * H))
         cst = ar.get("%s.cst%d" % (key, l), (2, T, Bn, H))
@@ -190,6 +212,8 @@ def lstm_steps_backward(ar, key, lstm, x, Bn, T, dout, G, need_dx, split3=False)
             else:
                 ops.grad_input(dg[:, :4 * H], lstm.w("weight_ih", l, 0), dinp)
                 ops.grad_input(dg[:, 4 * H:], lstm.w("weight_ih", l, 1), dinp, accumulate=True)
+            if drop is not None and l > 0:
+                ops.lstm_dropout(dinp, dinp, drop[0], drop[1], drop[2] + l - 1)
             d_cur = dinp
     return d_cur if need_dx else None
 
@@ -203,6 +227,7 @@ def _train_split3(net):
 
 def forward_train(net, imu):
     """IMUNet forward keeping what backward needs.  Returns (R, t)."""
+    _drop_rates(net)                      # (a rate outside [0, 1) is refused before anything is launched)
     net.flat()
     ar = net.arena("train")
     B, T, S, Cin = imu.shape
@@ -212,11 +237,18 @@ def forward_train(net, imu):
     h = ar.get("fc1", (Bn * S, H))
     ops.linear(x, net.fc1.weight, net.fc1.bias, h, relu=True)
     s3 = _train_split3(net)
-    fast = lstm_steps_forward_stash(ar, "fast", net.rnn_fast, h, Bn, S, split3=s3)
+    net._drop = (None, None)
+    if any(_drop_args(net, m, s, None) is not None for s, m in enumerate((net.rnn_fast, net.rnn_slow))):
+        # one seed word per training forward: every mask of this forward and of its backward reads the arena's copy, so the counter
+        # is free to move on (a second forward before the backward changes the first one's masks no more than its stashes)
+        word = ops.seed_take(net.seed_counter(), ar.get("drop.word", (1,), dtype=torch.int64))
+        net._drop = (_drop_args(net, net.rnn_fast, 0, word), _drop_args(net, net.rnn_slow, 1, word))
+    dfa, dsl = net._drop
+    fast = lstm_steps_forward_stash(ar, "fast", net.rnn_fast, h, Bn, S, split3=s3, drop=dfa)
     pooled = ar.get("pooled", (Bn, 2 * H))
     attn = ar.get("attn", (Bn, S))
     blocks.attn_pool_forward(fast, net.attn, Bn, S, 2 * H, pooled, attn)
-    slow = lstm_steps_forward_stash(ar, "slow", net.rnn_slow, pooled, B, T, split3=s3)
+    slow = lstm_steps_forward_stash(ar, "slow", net.rnn_slow, pooled, B, T, split3=s3, drop=dsl)
     y = ar.get("y", (Bn, 9))
     ops.linear(slow, net.fc2.weight, net.fc2.bias, y)
     R = torch.empty((B, T, 3, 3), dtype=torch.float32, device=dev)
@@ -239,13 +271,14 @@ def backward(net, dR, dt):
     blocks.linear_backward(dy, slow, net.fc2, G, dslow)
     pooled = ar.get("pooled", (Bn, 2 * H))
     s3 = _train_split3(net)
-    dpooled = lstm_steps_backward(ar, "slow", net.rnn_slow, pooled, B, T, dslow, G, True, split3=s3)
+    dfa, dsl = net._drop                  # (the forward's rates and seed word)
+    dpooled = lstm_steps_backward(ar, "slow", net.rnn_slow, pooled, B, T, dslow, G, True, split3=s3, drop=dsl)
     fast = ar.get("fast.out%d" % (net.rnn_fast.num_layers - 1), (Bn * S, 2 * H))
     attn = ar.get("attn", (Bn, S))
     dfast = ar.get("dfast", (Bn * S, 2 * H))
     blocks.attn_pool_backward(ar, "pool", fast, net.attn, attn, dpooled, Bn, S, 2 * H, dfast, G)
     h = ar.get("fc1", (Bn * S, H))
-    dh = lstm_steps_backward(ar, "fast", net.rnn_fast, h, Bn, S, dfast, G, True, split3=s3)
+    dh = lstm_steps_backward(ar, "fast", net.rnn_fast, h, Bn, S, dfast, G, True, split3=s3, drop=dfa)
     ops.relu_mask_(dh, h)
     x = ar.get("x", (Bn * S, Cin))
     blocks.linear_backward(dh, x, net.fc1, G)

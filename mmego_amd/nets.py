@@ -1200,6 +1200,11 @@ class IMUNet(_NetBase):
         # stage-1 TRAINING (imu_train.py): "split3" runs rnn_fast's input-projection, input-gradient AND weight-gradient products as
         # fp32-accurate piece products on the bf16 matrix pipe (opt-in; the recurrent steps stay on the fp32 kernels)
         self.train_precision = os.environ.get("MMEGO_IMU_TRAIN_PRECISION", "fp32")
+        # what the last training forward (imu_train.forward_train) leaves for its backward: the minibatch shape, and per stack the
+        # inter-layer dropout it APPLIED -- (rate, seed word, first salt) or None for rnn_fast and rnn_slow.  Backward regenerates the
+        # forward's masks from this, whatever lstm_dropout or the mode have become in between.
+        self._saved = None
+        self._drop = (None, None)
 
     def _pulled_pairs(self):
         """The two directions' input weights of every BiLSTM layer back to back: stage-1 training's input gradient of a layer is
@@ -1253,9 +1258,6 @@ class IMUNet(_NetBase):
         if h0_i is not None:
             raise NotImplementedError("IMUNet: the reference never passes h0_i; only None is supported")
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.rnn_fast.dropout > 0.0 or self.rnn_slow.dropout > 0.0:
-                raise NotImplementedError("IMUNet training with LSTM dropout > 0 is not supported (the reference trains "
-                                          "stage 1 with dropout=0, Train_IMU.py:50); construct it with dropout=0 or call .eval()")
             from .imu_train import ImuBridge
             self.flat()
             return ImuBridge.apply(self, _f32c(imu), *self._flat.params)

@@ -401,6 +401,27 @@ def copy2d(X, Y, accumulate=False):
     return Y
 
 
+def seed_take(seed_ctr, taken):
+    """taken[0] = seed_ctr[0]; seed_ctr[0] advances as mmego_inc_i64 advances it (int64 device words)."""
+    for t in (seed_ctr, taken):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.numel() >= 1):
+            raise TypeError("seed_take needs int64 device words")
+    hip.call("seed_take", seed_ctr, taken)
+    return taken
+
+
+def lstm_dropout(x, y, p, seed_word, salt):
+    """y = x * mask: nn.LSTM(dropout=p)'s inverted dropout from the counter-based hash of (logical element index, seed_word[0], salt)
+    (mmego_lstm_dropout; the kernel refuses p outside (0, 1) and a column count that is no multiple of 4).  y may be x."""
+    x, y = _rows(x), _rows(y)
+    if x.shape != y.shape:
+        raise ValueError("lstm_dropout shape mismatch")
+    if not (isinstance(seed_word, torch.Tensor) and seed_word.is_cuda and seed_word.dtype == torch.int64):
+        raise TypeError("lstm_dropout needs an int64 device seed word")
+    hip.call("lstm_dropout", x, x.stride(0), y, y.stride(0), x.shape[0], x.shape[1], float(p), seed_word, int(salt))
+    return y
+
+
 def gather_rows(X, idx, Y):
     """Y[i, :] = X[idx[i], :] for contiguous fp32 X [n, W], int64 idx [m], Y [m, W]."""
     _chk(X, 2), _chk(Y, 2)

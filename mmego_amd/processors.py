@@ -61,8 +61,9 @@ class _Base:
         return "a" if getattr(self.cfg, "resume_path", None) else "w"     # --resume continues the logs instead of truncating them
 
     def _load_imu(self):
-        # (--finetune_imu: built without dropout -- same state_dict keys -- because its training forward has none, as in stage 1)
-        imu = IMUNet(15, 6 + 3, 512, 2, True, 0 if getattr(self.cfg, "finetune_imu", False) else 0.1).to(self.device).eval()
+        # (--finetune_imu: built without dropout -- same state_dict keys -- as in stage 1, unless --imu_dropout asks for a rate)
+        drop = (getattr(self.cfg, "imu_dropout", None) or 0) if getattr(self.cfg, "finetune_imu", False) else 0.1
+        imu = IMUNet(15, 6 + 3, 512, 2, True, drop).to(self.device).eval()
         if self.cfg.gt_head_pose:
             print("[mmego_amd] head pose from the recording (R_R0R, ground-truth head joint); IMU_Net not used")
             return None
@@ -471,7 +472,7 @@ class ImuTrainer(_Base):
         super().__init__(Config)
         cfg = self.cfg
         self.num_epochs, self.save_slot, self.learning_rate = cfg.epochs, 50, cfg.lr
-        self.model_IMU = IMUNet(15, 6 + 3, 512, 2, True, 0).to(self.device)
+        self.model_IMU = IMUNet(15, 6 + 3, 512, 2, True, getattr(cfg, "imu_dropout", None) or 0).to(self.device)      # (--imu_dropout)
         if cfg.IMU_pretrained:
             self.model_IMU.load(cfg.model_IMU_path)
         from .params import FusedAdam

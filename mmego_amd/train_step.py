@@ -195,8 +195,6 @@ class StageStep:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_imu is not data parallel yet (no all-reduce of the IMU_Net gradients)")
-            if imu_net.rnn_fast.dropout > 0.0 or imu_net.rnn_slow.dropout > 0.0:
-                raise ValueError("StageStep: finetune_imu needs an IMU_Net built with dropout=0 (its training forward has no dropout)")
             self.imu_opt = FusedAdam(imu_net.flat(), lr=lr if imu_lr is None else imu_lr, weight_decay=imu_weight_decay)
         self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay)
         self.pg = process_group
