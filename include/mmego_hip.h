@@ -765,6 +765,21 @@ int mmego_bn_input_grad(void* stream, const float* dY, long lddy, const float* X
  * launch: the workgroup that finishes last stores it). */
 int mmego_adam_step(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
                     double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket);
+/* Global-norm gradient clipping (clip_grad_norm_ ahead of the optimiser step), as two launches without a host read.
+ * mmego_grad_norm_nblk: how many partial records mmego_grad_sqnorm writes for n floats (a function of n alone, <= 2048; pure host
+ * helper).  mmego_grad_sqnorm: part[b] = the fp64 sum of workgroup b's g[i]^2 (each product formed in fp64), the skip ranges -- same
+ * HOST array and checks as mmego_adam_step -- left out; the order of summation depends on n alone.  npart must equal
+ * mmego_grad_norm_nblk(n).
+ * mmego_adam_step_clipped: mmego_adam_step with every gradient element multiplied (fp32, rounded once) by
+ * cf = (float)min(1, max_norm / (norm + 1e-6)), norm = sqrt(sum of part[0..npart)) in double; weight decay is added to the clipped
+ * gradient.  A non-finite norm skips the step: p, m, v and state stay bit for bit, the step count does not advance.  max_norm > 0;
+ * +inf never clips.  stats: 8 device doubles kept by the call {this step's norm, sum of finite norms, their maximum, steps seen,
+ * steps with cf < 1, steps skipped as non-finite, reserved, reserved}. */
+int mmego_grad_norm_nblk(long n);
+int mmego_grad_sqnorm(void* stream, const float* g, long n, const long* skip, int nskip, double* part, int npart);
+int mmego_adam_step_clipped(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
+                            const double* part, int npart, double max_norm, double* stats);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,9 @@ Added flags (not in the reference): --gt_head_pose (use the recorded head pose w
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
 --finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients), --finetune_upper [--upper_lr F]
 (stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses), --imu_dropout P (the
-IMU_Net that is TRAINED -- stage 1, or --finetune_imu -- gets nn.LSTM(dropout=P) between its BiLSTM layers).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+IMU_Net that is TRAINED -- stage 1, or --finetune_imu -- gets nn.LSTM(dropout=P) between its BiLSTM layers), --clip_grad_norm X (every
+trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
+"Grad norm" line per net and epoch; `inf` only measures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -59,7 +61,21 @@ def build_parser():
                    help="--train --network Lower_Net only: train the Upper_Net as well (Train_Lower.py:195-196 without its .detach()), on "
                         "the sum of the two stages' losses; the Upper_Net is saved beside the Lower_Net checkpoint, in an Upper_Net folder")
     p.add_argument("--upper_lr", type=float, help="learning rate of the Upper_Net under --finetune_upper (default: --lr / Config.lr)")
+    p.add_argument("--clip_grad_norm", type=float,
+                   help="--train: clip every trained net's gradient to this global norm ahead of its Adam step (one clip_grad_norm_ per "
+                        "optimiser, on the SUM-loss gradient of the global minibatch), skip a step whose gradient is not finite, and print "
+                        "the norms once per epoch; `inf` measures without clipping (default: no clipping)")
     return p
+
+
+def check_clip_grad_norm(parser, args):
+    """--clip_grad_norm belongs to a training run and is a positive threshold (inf allowed: measure only)."""
+    if args.clip_grad_norm is None:
+        return
+    if not args.clip_grad_norm > 0.0:                  # (false for NaN as well)
+        parser.error("--clip_grad_norm is a gradient-norm threshold: it has to be > 0 (inf: measure only), got %r" % (args.clip_grad_norm,))
+    if args.infer or not args.train:
+        parser.error("--clip_grad_norm goes with --train only (it bounds the optimiser's step)")
 
 
 def check_finetune_upper(parser, args, world):
@@ -92,6 +108,7 @@ def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
+    check_clip_grad_norm(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -133,6 +150,7 @@ def apply_overrides(args):
     Config.imu_dropout = args.imu_dropout
     Config.finetune_upper = bool(args.finetune_upper)
     Config.upper_lr = args.upper_lr
+    Config.clip_grad_norm = args.clip_grad_norm
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

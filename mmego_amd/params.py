@@ -101,13 +101,24 @@ class FlatParams:
 
 
 class FusedAdam:
-    """torch.optim.Adam semantics (betas 0.9/0.999, eps 1e-8, coupled weight decay) in one launch."""
+    """torch.optim.Adam semantics (betas 0.9/0.999, eps 1e-8, coupled weight decay) in one launch.
 
-    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    max_grad_norm (None: off): torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) ahead of every step, over THIS net's
+    gradients, as two launches and no host read (mmego_grad_sqnorm, mmego_adam_step_clipped).  A step whose gradient norm is not
+    finite is skipped on the device -- weights, moments and step count stay as they are -- and counted; `grad_stats()` reads the
+    norms and counts seen since the last `reset_grad_stats()`.  float("inf") measures without ever clipping."""
+
+    STAT_KEYS = ("last", "sum", "max", "steps", "clipped", "skipped")
+
+    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("max_grad_norm has to be > 0 (or None: no clipping), got %r" % (max_grad_norm,))
         self.flat = flat
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.m = self.v = self.state = self._ticket = None
         self._skip = None
+        self._part = self._stats = None
 
     def _skip_ranges(self, f):
         """Element ranges of parameters that never receive a gradient (`module.never_trained()`, e.g. IMU_Net.fc3):
@@ -134,14 +145,25 @@ class FusedAdam:
             self.v = torch.zeros_like(f.flat_p)
             self.state = torch.zeros(3, dtype=torch.float64, device=f.device)
             self._ticket = torch.zeros(1, dtype=torch.int32, device=f.device)
+            self._part = self._stats = None
+        if self.max_grad_norm is not None and self._part is None:
+            # (only a clipping optimiser owns these; built before the first step, so before anything captures their addresses)
+            self._part = torch.zeros(hip.lib().mmego_grad_norm_nblk(f.flat_p.numel()), dtype=torch.float64, device=f.device)
+            self._stats = torch.zeros(8, dtype=torch.float64, device=f.device)
         return f
 
     def step(self):
         f = self._ensure()
         skip = self._skip_ranges(f)
-        hip.call("adam_step", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
-                 float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                 skip if skip is not False else None, skip.numel() // 2 if skip is not False else 0, self._ticket)
+        ranges = (skip if skip is not False else None, skip.numel() // 2 if skip is not False else 0)
+        if self.max_grad_norm is None:
+            hip.call("adam_step", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
+                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket)
+        else:
+            hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
+            hip.call("adam_step_clipped", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
+                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket,
+                     self._part, self._part.numel(), self.max_grad_norm, self._stats)
         # the update went through raw pointers (no tensor._version bump): tell the net to drop derived copies of its weights
         changed = getattr(f.module, "weights_changed", None)
         if changed is not None:
@@ -149,6 +171,25 @@ class FusedAdam:
 
     def zero_grad(self):
         pass  # every backward overwrites the flat gradient buffer
+
+    def grad_stats(self):
+        """The gradient norms of the steps since the last reset, from ONE device read: {"last", "sum", "max", "steps", "clipped",
+        "skipped", "mean"} (mean and max over the steps with a finite norm).  None without max_grad_norm."""
+        if self.max_grad_norm is None:
+            return None
+        self._ensure()
+        vals = self._stats.tolist()
+        out = dict(zip(self.STAT_KEYS, vals))
+        for k in ("steps", "clipped", "skipped"):
+            out[k] = int(out[k])
+        finite = out["steps"] - out["skipped"]
+        out["mean"] = out["sum"] / finite if finite else float("nan")
+        return out
+
+    def reset_grad_stats(self):
+        if self.max_grad_norm is not None:
+            self._ensure()
+            self._stats.zero_()
 
     def layout(self):
         """The fingerprint of the flat layout: (parameter name, offset, numel) in buffer order.  The order inside the flat buffers
@@ -162,7 +203,7 @@ class FusedAdam:
         bit-exact resume needs, also after the flat layout of the net has changed."""
         self._ensure()
         return {"m": self.m.cpu(), "v": self.v.cpu(), "state": self.state.cpu(), "lr": self.lr, "betas": tuple(self.betas),
-                "eps": self.eps, "weight_decay": self.weight_decay, "layout": self.layout()}
+                "eps": self.eps, "weight_decay": self.weight_decay, "layout": self.layout(), "max_grad_norm": self.max_grad_norm}
 
     def load_state_dict(self, sd):
         """Moments are matched to parameters BY NAME through the saved layout; a state saved under another flat order lands on
@@ -200,3 +241,6 @@ class FusedAdam:
             self.m.copy_(m_new); self.v.copy_(v_new)
         self.state.copy_(sd["state"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+        if "max_grad_norm" in sd:          # (as lr: the saved value wins, a resumed run clips as the run it continues; a state from
+            self.max_grad_norm = None if sd["max_grad_norm"] is None else float(sd["max_grad_norm"])    # before the key: ours stays)
+            self._ensure()                 # (the record buffer, should the state switch clipping on)

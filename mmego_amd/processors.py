@@ -30,6 +30,7 @@ class _Base:
     """Shared set-up: directories, frozen IMU_Net (or ground-truth head pose), datasets."""
     finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
     finetune_upper = False        # (--finetune_upper: likewise)
+    _opt_shared = None
     _imu_opt_shared = None
     _upper_opt_shared = None
 
@@ -120,6 +121,19 @@ class _Base:
         return float(m[:21].mean()), float(m[41]), float(m[42]), m[:21], m[21:41]
 
 
+def report_grad_norms(rank, named_opts):
+    """--clip_grad_norm: after an epoch's training pass, one line per trained net from ONE device read per optimiser (rank 0), then the
+    counters start again.  An optimiser that does not clip (no flag) is neither read nor reported."""
+    for name, opt in named_opts:
+        if opt is None or opt.max_grad_norm is None:
+            continue
+        if rank == 0:
+            s = opt.grad_stats()
+            print("Grad norm ({}): mean {:.6g} max {:.6g} clipped {}/{} skipped {}".format(
+                name, s["mean"], s["max"], s["clipped"], s["steps"], s["skipped"]))
+        opt.reset_grad_stats()
+
+
 class _StageTrainer(_Base):
     stage = None
 
@@ -166,7 +180,8 @@ class _StageTrainer(_Base):
                            upper_frozen=getattr(self, "Upper_net", None), lr=self.learning_rate, process_group=pg,
                            use_graph=not pipelined, finetune_imu=self.finetune_imu,
                            imu_lr=self.learning_rate if imu_lr is None else imu_lr,
-                           finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None))
+                           finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
+                           clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
             if self.finetune_upper:                                     # one Upper_Net optimiser state for all batch sizes, too
                 if self._upper_opt_shared is not None:
                     st.upper_opt = self._upper_opt_shared
@@ -211,7 +226,8 @@ class _StageTrainer(_Base):
             if B == 0:              # short last global minibatch, nothing for this rank: zero gradient, same collective + update
                 if self._opt_shared is None:
                     from .params import FusedAdam
-                    self._opt_shared = FusedAdam(self.model.flat(), lr=self.learning_rate)
+                    self._opt_shared = FusedAdam(self.model.flat(), lr=self.learning_rate,
+                                                 max_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
                     if self._resume is not None:
                         self._opt_shared.load_state_dict(self._resume["optimizer"])
                 empty_step(self.model, self._opt_shared, self.pg)
@@ -257,6 +273,8 @@ class _StageTrainer(_Base):
         for epoch in range(self.start_epoch, self.num_epochs):
             print("epoch: {}".format(epoch + 1))
             self.train_once()
+            report_grad_norms(self.rank, (("Upper_Net" if self.stage == "upper" else "Lower_Net", self._opt_shared),
+                                          ("IMU_Net", self._imu_opt_shared), ("Upper_Net", self._upper_opt_shared)))
             # a persistent rnn_slow launch of the frozen IMU_Net whose workgroups were not co-resident reports it only through a
             # sticky word: read once per epoch (train_once has just synchronised for its log) -- never train on silently
             blocks.seq_xcd_raise()
@@ -477,7 +495,8 @@ class ImuTrainer(_Base):
             self.model_IMU.load(cfg.model_IMU_path)
         from .params import FusedAdam
         self._dp_start(self.model_IMU)
-        self.optimizer_IMU = FusedAdam(self.model_IMU.flat(), lr=self.learning_rate, weight_decay=0.001)
+        self.optimizer_IMU = FusedAdam(self.model_IMU.flat(), lr=self.learning_rate, weight_decay=0.001,
+                                       max_grad_norm=getattr(cfg, "clip_grad_norm", None))
         self.train_data = PosePC(batch_length=self.frame_no)
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -504,7 +523,8 @@ class ImuTrainer(_Base):
             B, T = b["imu"].shape[0], b["imu"].shape[1]
             st = self._steps.get(B)
             if st is None:                                              # one graph per minibatch size, one optimiser
-                st = ImuStep(self.model_IMU, lr=self.learning_rate, weight_decay=0.001, process_group=pg, use_graph=True)
+                st = ImuStep(self.model_IMU, lr=self.learning_rate, weight_decay=0.001, process_group=pg, use_graph=True,
+                             clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
                 st.opt = self.optimizer_IMU
                 self._steps[B] = st
             if st.static is None or st.static["imu"].data_ptr() != b["imu"].data_ptr():
@@ -551,6 +571,7 @@ class ImuTrainer(_Base):
         for epoch in range(self.start_epoch, self.num_epochs):
             print("epoch: {}".format(epoch + 1))
             train_loss = self.train_imu_once()
+            report_grad_norms(self.rank, (("IMU_Net", self.optimizer_IMU),))
             eval_loss, eval_loss_l = self.eval_imu()
             if self.rank == 0:
                 self.lossfile.write("%d %f\n" % (epoch + 1, eval_loss))

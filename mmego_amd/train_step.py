@@ -164,10 +164,16 @@ class StageStep:
     (LowerNet.input_grads), and Upper_Net's backward runs on d(loss_lower + loss_upper); two Adam steps (Lower_Net at ``lr``, Upper_Net at
     ``upper_lr``, default ``lr``).  The head pose is not trained (frozen IMU_Net, shared pose or the recording, as without the option).
     The sum of the two stages' own losses, because the final skeleton takes 13 of its 21 joints from Upper_Net: the lower loss alone must
-    not be the only thing steering it.  One HIP graph."""
+    not be the only thing steering it.  One HIP graph.
+
+    ``clip_grad_norm`` (None: off): every optimiser this step builds -- ``opt``, ``imu_opt``, ``upper_opt`` -- clips ITS net's gradient
+    to that global norm ahead of its update (FusedAdam(max_grad_norm=...)): one clip_grad_norm_ per optimiser, as the nets have separate
+    optimisers and learning rates.  Data parallel, the all-reduce precedes ``opt.step()``: every rank clips the summed gradient by the
+    same norm."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
-                 use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None):
+                 use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
+                 clip_grad_norm=None):
         assert stage in ("upper", "lower")
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
@@ -185,7 +191,8 @@ class StageStep:
                 raise ValueError("StageStep: finetune_upper cannot be combined with finetune_imu (the head pose is not trained in stage 3)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_upper is not data parallel yet (no all-reduce of the Upper_Net gradients)")
-            self.upper_opt = FusedAdam(upper_frozen.flat(), lr=lr if upper_lr is None else upper_lr, weight_decay=weight_decay)
+            self.upper_opt = FusedAdam(upper_frozen.flat(), lr=lr if upper_lr is None else upper_lr, weight_decay=weight_decay,
+                                       max_grad_norm=clip_grad_norm)
         if self.finetune_imu:
             from .nets import UpperNet
             if stage != "upper" or type(net) is not UpperNet:
@@ -195,8 +202,9 @@ class StageStep:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_imu is not data parallel yet (no all-reduce of the IMU_Net gradients)")
-            self.imu_opt = FusedAdam(imu_net.flat(), lr=lr if imu_lr is None else imu_lr, weight_decay=imu_weight_decay)
-        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay)
+            self.imu_opt = FusedAdam(imu_net.flat(), lr=lr if imu_lr is None else imu_lr, weight_decay=imu_weight_decay,
+                                     max_grad_norm=clip_grad_norm)
+        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
@@ -359,9 +367,9 @@ class ImuStep:
     position loss (sum), backward through the two BiLSTM(512) stacks, Adam with coupled weight decay -- with static
     buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound)."""
 
-    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True):
+    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None):
         self.net = net
-        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay)
+        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
