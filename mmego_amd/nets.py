@@ -170,6 +170,23 @@ class _NetBase(nn.Module):
         self.load_state_dict(torch.load(pathname, map_location=dev))
 
 
+def _bridge_backward(ctx, dl):
+    """What every bridge's backward starts with: the net's backward pipeline on d loss / d (first output), gradients bound to .grad."""
+    if not ctx.net.training:
+        raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
+                                  "the reference detaches frozen nets (Train_Lower.py:195-196)")
+    ctx.net._backward_impl(dl)
+    ctx.net.flat().bind_grads()
+
+
+def _grads_for_caller(ctx, first, grads, like):
+    """Input gradients as autograd takes them: ``grads`` belong to the forward arguments from position ``first`` on, ``like`` holds their
+    (shape, dtype); only those somebody needs, as copies (the arena's buffers are rewritten by the next step, and autograd may keep
+    what it is handed as .grad)."""
+    return tuple(g.clone().view(shape).to(dtype) if (ctx.needs_input_grad[first + i] and g is not None) else None
+                 for i, (g, (shape, dtype)) in enumerate(zip(grads, like)))
+
+
 class _Bridge(torch.autograd.Function):
     """One autograd node per net: forward/backward are the hand-written kernel pipelines."""
 
@@ -182,11 +199,7 @@ class _Bridge(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        if not ctx.net.training:
-            raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
-                                      "the reference detaches frozen nets (Train_Lower.py:195-196)")
-        ctx.net._backward_impl(grads[0])
-        ctx.net.flat().bind_grads()
+        _bridge_backward(ctx, grads[0])
         return (None, None, None) + (None,) * len(ctx.net._flat.params)
 
 
@@ -212,22 +225,13 @@ class _PoseBridge(torch.autograd.Function):
         x, h0, c0, body = args
         outs = net._forward_impl(x, h0, c0, body, R, t, pose_grad=True)
         ctx.mark_non_differentiable(*outs[1:])
-        ctx.pose_like = (R.shape, R.dtype, t.shape, t.dtype)
+        ctx.like = [(v.shape, v.dtype) for v in (R, t)]
         return outs
 
     @staticmethod
     def backward(ctx, *grads):
-        if not ctx.net.training:
-            raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
-                                      "the reference detaches frozen nets (Train_Lower.py:195-196)")
-        ctx.net._backward_impl(grads[0])
-        ctx.net.flat().bind_grads()
-        dR, dt = ctx.net.pose_grads()
-        rs, rd, ts, td = ctx.pose_like
-        # (copies: the arena's buffers are rewritten by the next step, and autograd may keep what it is handed as .grad)
-        dR = dR.clone().view(rs).to(rd) if ctx.needs_input_grad[2] else None
-        dt = dt.clone().view(ts).to(td) if ctx.needs_input_grad[3] else None
-        return (None, None, dR, dt) + (None,) * len(ctx.net._flat.params)
+        _bridge_backward(ctx, grads[0])
+        return (None, None) + _grads_for_caller(ctx, 2, ctx.net.pose_grads(), ctx.like) + (None,) * len(ctx.net._flat.params)
 
 
 class _InputBridge(torch.autograd.Function):
@@ -247,15 +251,8 @@ class _InputBridge(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        if not ctx.net.training:
-            raise NotImplementedError("backward through an eval-mode net (running-stat BatchNorm) is not supported; "
-                                      "the reference detaches frozen nets (Train_Lower.py:195-196)")
-        ctx.net._backward_impl(grads[0])
-        ctx.net.flat().bind_grads()
-        # (copies: the arena's buffers are rewritten by the next step, and autograd may keep what it is handed as .grad)
-        out = [g.clone().view(shape).to(dtype) if (ctx.needs_input_grad[2 + i] and g is not None) else None
-               for i, (g, (shape, dtype)) in enumerate(zip(ctx.net.input_grads(), ctx.like))]
-        return (None, None) + tuple(out) + (None,) * len(ctx.net._flat.params)
+        _bridge_backward(ctx, grads[0])
+        return (None, None) + _grads_for_caller(ctx, 2, ctx.net.input_grads(), ctx.like) + (None,) * len(ctx.net._flat.params)
 
 
 # =====================================================================================================

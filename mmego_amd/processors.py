@@ -10,6 +10,7 @@ Data parallel (not in the reference): when launched under torch.distributed.run 
 own shard of every epoch's shuffled order; gradients are summed with one RCCL all-reduce per step.
 """
 import os
+import types
 
 import numpy as np
 import torch
@@ -18,7 +19,8 @@ from . import blocks, hip, ops
 from .config import Config, ConfigDemo
 from .data import DeviceArrays, PosePC, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
-from .train_step import PipelinedStages, StageStep, broadcast_flag, empty_step, shard_of, sync_replicas
+from .params import FusedAdam
+from .train_step import TRAINED, ImuStep, PipelinedStages, StageStep, broadcast_flag, empty_step, shard_of, sync_replicas
 from .utils import EarlyStopping
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,9 +32,11 @@ class _Base:
     """Shared set-up: directories, frozen IMU_Net (or ground-truth head pose), datasets."""
     finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
     finetune_upper = False        # (--finetune_upper: likewise)
-    _opt_shared = None
-    _imu_opt_shared = None
-    _upper_opt_shared = None
+    # The trainer's optimisers, keyed like train_step.TRAINED ("opt": the stage's own net, "imu_opt", "upper_opt"): ONE set, handed to
+    # the step of every minibatch size, read by the grad-norm report and the checkpoint (a trainer's __init__ makes it a dict)
+    _opts = types.MappingProxyType({})
+    weight_decay = 0.0            # of "opt" (stage 1: coupled 1e-3)
+    net_name = None               # what "opt" trains, as the grad-norm report calls it
 
     def __init__(self, cfg, make_dirs=True):
         self.cfg = cfg
@@ -110,6 +114,68 @@ class _Base:
         print("[mmego_amd] resumed from %s at epoch %d" % (path, self.start_epoch))
         return ts
 
+    def _main_opt(self, model):
+        """The optimiser of the trainer's own net: built ONCE -- by the first step or the first empty-shard step, whichever comes -- and
+        that is where a --resume state is loaded."""
+        if "opt" not in self._opts:
+            self._opts["opt"] = FusedAdam(model.flat(), lr=self.learning_rate, weight_decay=self.weight_decay,
+                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
+            if self._resume is not None:
+                self._opts["opt"].load_state_dict(self._resume["optimizer"])
+        return self._opts["opt"]
+
+    def save_beside(self, epoch, folder, net):
+        """A second trained net beside the stage's checkpoint, same file name, in a folder of its own (--finetune_imu: IMU_Net,
+        --finetune_upper: Upper_Net)."""
+        if self.rank != 0:
+            return None
+        folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), folder)
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
+        torch.save(net.state_dict(), path)
+        return path
+
+    def _epochs(self, model, train, evaluate, report, also_saved=()):
+        """The epoch loop of every trainer (reference Train_Upper.py:90-132, Train_Lower.py:110-153, Train_IMU.py:90-112).  ``train()``: one
+        training pass; ``evaluate()`` -> a tuple that starts (eval_loss, eval_loss_l, ...); ``report(epoch, what train() returned, what
+        evaluate() returned)``: the trainer's lines beyond log-loss.txt, called on every rank; ``also_saved``: (folder, net) pairs
+        saved beside the checkpoint."""
+        early = EarlyStopping(patience=30)
+        if getattr(self.cfg, "resume_path", None):
+            ts = self.load_train_state(self.cfg.resume_path, model)
+            if ts["early"] is not None:
+                early.counter, early.best_score = ts["early"]
+        out = None
+        names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
+        for epoch in range(self.start_epoch, self.num_epochs):
+            print("epoch: {}".format(epoch + 1))
+            trained = train()
+            report_grad_norms(self.rank, [(names[o], self._opts[o]) for o, _ in TRAINED if o in self._opts])
+            # a persistent rnn_slow launch of the frozen IMU_Net whose workgroups were not co-resident reports it only through a
+            # sticky word: read once per epoch (the training pass has just synchronised for its log) -- never train on silently
+            blocks.seq_xcd_raise()
+            sync_replicas(model, self.pg, params=False)            # BatchNorm running statistics: rank 0's, on every rank
+            out = evaluate()
+            eval_loss, eval_loss_l = out[0], out[1]
+            if self.rank == 0:
+                self.lossfile.write("%d %f\n" % (epoch + 1, eval_loss))
+                self.lossfile.write(str(eval_loss_l) + "\n")
+                self.lossfile.flush()
+            report(epoch, trained, out)
+            # every rank evaluates its own copy of the test split (the reference's unseeded padding makes them differ), so
+            # the ranks could disagree on when to stop and leave each other hanging in the next all-reduce: rank 0 decides
+            stop = broadcast_flag(early(eval_loss), self.device, self.pg)
+            # (the reference saves before the evaluation pass; saving after it keeps the RNG / early-stopping state in the
+            #  checkpoint consistent with "epoch finished", which is what --resume continues from)
+            if (epoch + 1) % self.save_slot == 0 or epoch + 1 == self.num_epochs or stop:
+                self.save_models(epoch, model, self._main_opt(model), early)
+                for folder, net in also_saved:
+                    self.save_beside(epoch, folder, net)
+            if stop:
+                print("Early stopping")
+                break
+        return out
+
     def pose_metrics(self, upper_l, lower_l, target):
         """Demo_test per-batch figures on the device -> (all, upper, lower, per_joint[21], angle[20])."""
         F = upper_l.shape[0] * upper_l.shape[1]
@@ -148,7 +214,7 @@ class _StageTrainer(_Base):
         if self.finetune_upper and (self.stage != "lower" or self.world > 1 or getattr(cfg, "resume_path", None)):
             raise SystemExit("--finetune_upper: Lower_Net stage only; not data parallel, not with --resume")
         self.model_IMU = self._load_imu()
-        self._imu_opt_shared = self._upper_opt_shared = None
+        self._opts = {}
         self.train_data = PosePC(batch_length=self.frame_no)
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -159,10 +225,6 @@ class _StageTrainer(_Base):
         self.start_epoch, self._resume = 0, None
         self._train_dev = None
         self._log = None
-        self._opt_shared = None
-
-    def _optimizer(self):
-        return self._opt_shared
 
     def _step_for(self, B):
         """One StageStep (static buffers, optional HIP graph) per minibatch size.  With a frozen IMU_Net in the loop its forward
@@ -176,28 +238,14 @@ class _StageTrainer(_Base):
             # (--finetune_upper: the plain StageStep too -- the engines around a frozen IMU_Net forward refuse a stage with two trained nets)
             pipelined = pipelined and not self.finetune_upper
             imu_lr = getattr(self.cfg, "imu_lr", None)
+            self._main_opt(self.model)
+            # (one optimiser state per trained net for all batch sizes: the step takes what the dict holds and adds what it builds)
             st = StageStep(self.stage, self.model, None if pipelined else self.model_IMU,
                            upper_frozen=getattr(self, "Upper_net", None), lr=self.learning_rate, process_group=pg,
                            use_graph=not pipelined, finetune_imu=self.finetune_imu,
                            imu_lr=self.learning_rate if imu_lr is None else imu_lr,
                            finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
-                           clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
-            if self.finetune_upper:                                     # one Upper_Net optimiser state for all batch sizes, too
-                if self._upper_opt_shared is not None:
-                    st.upper_opt = self._upper_opt_shared
-                else:
-                    self._upper_opt_shared = st.upper_opt
-            if self.finetune_imu:                                       # one IMU_Net optimiser state for all batch sizes, too
-                if self._imu_opt_shared is not None:
-                    st.imu_opt = self._imu_opt_shared
-                else:
-                    self._imu_opt_shared = st.imu_opt
-            if self._opt_shared is not None:
-                st.opt = self._opt_shared                               # one optimiser state for all batch sizes
-            else:
-                self._opt_shared = st.opt
-                if self._resume is not None:
-                    st.opt.load_state_dict(self._resume["optimizer"])
+                           clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts)
             st.engine = None
             if pipelined:
                 st.imu_next = torch.empty((B, self.frame_no) + tuple(self._train_dev.shape["imu"][1:]), dtype=torch.float32,
@@ -224,13 +272,7 @@ class _StageTrainer(_Base):
         for i, idx in enumerate(todo):
             B = len(idx)
             if B == 0:              # short last global minibatch, nothing for this rank: zero gradient, same collective + update
-                if self._opt_shared is None:
-                    from .params import FusedAdam
-                    self._opt_shared = FusedAdam(self.model.flat(), lr=self.learning_rate,
-                                                 max_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
-                    if self._resume is not None:
-                        self._opt_shared.load_state_dict(self._resume["optimizer"])
-                empty_step(self.model, self._opt_shared, self.pg)
+                empty_step(self.model, self._main_opt(self.model), self.pg)
                 primed = None
                 continue
             st = self._step_for(B)
@@ -264,69 +306,16 @@ class _StageTrainer(_Base):
         return accs, losses
 
     def _train_loop(self, extra_print):
-        early = EarlyStopping(patience=30)
-        if getattr(self.cfg, "resume_path", None):
-            ts = self.load_train_state(self.cfg.resume_path, self.model)
-            if ts["early"] is not None:
-                early.counter, early.best_score = ts["early"]
-        out = None
-        for epoch in range(self.start_epoch, self.num_epochs):
-            print("epoch: {}".format(epoch + 1))
-            self.train_once()
-            report_grad_norms(self.rank, (("Upper_Net" if self.stage == "upper" else "Lower_Net", self._opt_shared),
-                                          ("IMU_Net", self._imu_opt_shared), ("Upper_Net", self._upper_opt_shared)))
-            # a persistent rnn_slow launch of the frozen IMU_Net whose workgroups were not co-resident reports it only through a
-            # sticky word: read once per epoch (train_once has just synchronised for its log) -- never train on silently
-            blocks.seq_xcd_raise()
-            sync_replicas(self.model, self.pg, params=False)       # BatchNorm running statistics: rank 0's, on every rank
-            out = self.eval_model()
-            eval_loss, eval_loss_l, eval_accu, second, accu_ll, angle_ll = out
-            if self.rank == 0:
-                self.lossfile.write("%d %f\n" % (epoch + 1, eval_loss))
-                self.lossfile.write(str(eval_loss_l) + "\n")
-                self.lossfile.flush()
-                extra_print(epoch, out)
-            # every rank evaluates its own copy of the test split (the reference's unseeded padding makes them differ), so
-            # the ranks could disagree on when to stop and leave each other hanging in the next all-reduce: rank 0 decides
-            stop = broadcast_flag(early(eval_loss), self.device, self.pg)
-            # (the reference saves before the evaluation pass; saving after it keeps the RNG / early-stopping state in the
-            #  checkpoint consistent with "epoch finished", which is what --resume continues from)
-            if (epoch + 1) % self.save_slot == 0 or epoch + 1 == self.num_epochs or stop:
-                self.save_models(epoch, self.model, self._optimizer(), early)
-                if self.finetune_imu:
-                    self.save_imu(epoch)
-                if self.finetune_upper:
-                    self.save_upper(epoch)
-            if stop:
-                print("Early stopping")
-                break
-        return out
-
-    def save_imu(self, epoch):
-        """--finetune_imu: the trained IMU_Net beside the Upper_Net checkpoint, same file name, in an IMU_Net folder."""
-        if self.rank != 0:
-            return None
-        folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), "IMU_Net")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
-        torch.save(self.model_IMU.state_dict(), path)
-        return path
-
-
-    def save_upper(self, epoch):
-        """--finetune_upper: the trained Upper_Net beside the Lower_Net checkpoint, same file name, in an Upper_Net folder."""
-        if self.rank != 0:
-            return None
-        folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), "Upper_Net")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
-        torch.save(self.Upper_net.state_dict(), path)
-        return path
+        """``extra_print(epoch, out)``: rank 0's lines to log-eval.txt and stdout."""
+        return self._epochs(self.model, self.train_once, self.eval_model,
+                            lambda epoch, _, out: extra_print(epoch, out) if self.rank == 0 else None,
+                            ([("IMU_Net", self.model_IMU)] if self.finetune_imu else []) +
+                            ([("Upper_Net", self.Upper_net)] if self.finetune_upper else []))
 
 
 class UpperTrainer(_StageTrainer):
     """`python main.py --train --network Upper_Net` (reference Train_Upper.MMEgo)."""
-    stage = "upper"
+    stage, net_name = "upper", "Upper_Net"
     model_out_joints = 15
 
     def __init__(self):
@@ -366,7 +355,7 @@ class UpperTrainer(_StageTrainer):
 
 class LowerTrainer(_StageTrainer):
     """`python main.py --train --network Lower_Net` (reference Train_Lower.MMEgo)."""
-    stage = "lower"
+    stage, net_name = "lower", "Lower_Net"
     model_out_joints = 8
 
     def __init__(self):
@@ -485,6 +474,7 @@ class Evaluator(_Base):
 class ImuTrainer(_Base):
     """`python main.py --train --network IMU_Net` (reference Train_IMU.MMEgo): stage 1, geodesic + 100 x position loss,
     Adam with coupled weight decay 1e-3."""
+    weight_decay, net_name = 0.001, "IMU_Net"
 
     def __init__(self):
         super().__init__(Config)
@@ -493,10 +483,8 @@ class ImuTrainer(_Base):
         self.model_IMU = IMUNet(15, 6 + 3, 512, 2, True, getattr(cfg, "imu_dropout", None) or 0).to(self.device)      # (--imu_dropout)
         if cfg.IMU_pretrained:
             self.model_IMU.load(cfg.model_IMU_path)
-        from .params import FusedAdam
         self._dp_start(self.model_IMU)
-        self.optimizer_IMU = FusedAdam(self.model_IMU.flat(), lr=self.learning_rate, weight_decay=0.001,
-                                       max_grad_norm=getattr(cfg, "clip_grad_norm", None))
+        self._opts = {}
         self.train_data = PosePC(batch_length=self.frame_no)
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -508,7 +496,6 @@ class ImuTrainer(_Base):
         self._steps = {}
 
     def train_imu_once(self):
-        from .train_step import ImuStep
         self.model_IMU.train()
         losses = []
         pg = self.pg
@@ -517,16 +504,13 @@ class ImuTrainer(_Base):
         for idx in batch_indices(len(self.train_data), self.batchsize * self.world, True, self._rng):
             idx = idx[shard_of(self.rank, self.world)]
             if len(idx) == 0:       # nothing for this rank in a short last global minibatch: zero gradient, same update
-                empty_step(self.model_IMU, self.optimizer_IMU, pg)
+                empty_step(self.model_IMU, self._main_opt(self.model_IMU), pg)
                 continue
             b = self._train_dev.gather(idx)
             B, T = b["imu"].shape[0], b["imu"].shape[1]
             st = self._steps.get(B)
             if st is None:                                              # one graph per minibatch size, one optimiser
-                st = ImuStep(self.model_IMU, lr=self.learning_rate, weight_decay=0.001, process_group=pg, use_graph=True,
-                             clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
-                st.opt = self.optimizer_IMU
-                self._steps[B] = st
+                st = self._steps[B] = ImuStep(self.model_IMU, process_group=pg, use_graph=True, opt=self._main_opt(self.model_IMU))
             if st.static is None or st.static["imu"].data_ptr() != b["imu"].data_ptr():
                 st.bind(b["imu"], b["R_R0R"], b["target"])
             st.step()
@@ -562,26 +546,7 @@ class ImuTrainer(_Base):
         return float(np.mean(tot)), np.mean(np.stack((tot - 100.0 * pos, pos), axis=1), axis=0)
 
     def train_imu(self):
-        early = EarlyStopping(patience=30)
-        if getattr(self.cfg, "resume_path", None):
-            ts = self.load_train_state(self.cfg.resume_path, self.model_IMU)
-            self.optimizer_IMU.load_state_dict(ts["optimizer"])
-            if ts["early"] is not None:
-                early.counter, early.best_score = ts["early"]
-        for epoch in range(self.start_epoch, self.num_epochs):
-            print("epoch: {}".format(epoch + 1))
-            train_loss = self.train_imu_once()
-            report_grad_norms(self.rank, (("IMU_Net", self.optimizer_IMU),))
-            eval_loss, eval_loss_l = self.eval_imu()
-            if self.rank == 0:
-                self.lossfile.write("%d %f\n" % (epoch + 1, eval_loss))
-                self.lossfile.write(str(eval_loss_l) + "\n")
-                self.lossfile.flush()
+        def report(epoch, train_loss, out):
             print("Train_loss: {}".format(train_loss))
-            print("Eval_loss: {}  Eval_loss_l (angle, H_pos): {}".format(eval_loss, eval_loss_l))
-            stop = broadcast_flag(early(eval_loss), self.device, self.pg)       # rank 0 decides for everybody
-            if (epoch + 1) % self.save_slot == 0 or epoch + 1 == self.num_epochs or stop:
-                self.save_models(epoch, self.model_IMU, self.optimizer_IMU, early)
-            if stop:
-                print("Early stopping")
-                break
+            print("Eval_loss: {}  Eval_loss_l (angle, H_pos): {}".format(out[0], out[1]))
+        self._epochs(self.model_IMU, self.train_imu_once, self.eval_imu, report)

@@ -137,17 +137,85 @@ def needs_exclusive(nets):
     return any(getattr(m, a, "fp32") != "fp32" for m in nets if m is not None for a in ("precision", "train_precision"))
 
 
+# Everything a StageStep may train, as (optimiser attribute, net attribute), in update order.  Read LIVE wherever it is used: callers
+# replace st.opt / st.imu_opt by wrappers (tests/test_clip_grad_norm_gpu.py) and step() has to call the wrapper.
+TRAINED = (("opt", "net"), ("imu_opt", "imu"), ("upper_opt", "upper_frozen"))
+_REFUSED = {"imu_opt": "%s: a stage with finetune_imu=True trains its IMU_Net, which is then no frozen, shareable forward; run it as a "
+                       "plain StageStep",
+            "upper_opt": "%s: a stage with finetune_upper=True trains its Upper_Net inside its own body (two nets, two optimisers); run it "
+                         "as a plain StageStep"}
+
+
 def _refuse_finetune(who, stages):
-    """The multi-stage engines run FROZEN IMU_Nets (shared, prefetched or beside another stage); a stage that trains its own does not fit."""
-    if any(getattr(st, "finetune_imu", False) for st in stages):
-        raise ValueError("%s: a stage with finetune_imu=True trains its IMU_Net, which is then no frozen, shareable forward; run it as a "
-                         "plain StageStep" % who)
-    if any(getattr(st, "finetune_upper", False) for st in stages):
-        raise ValueError("%s: a stage with finetune_upper=True trains its Upper_Net inside its own body (two nets, two optimisers); run it "
-                         "as a plain StageStep" % who)
+    """The multi-stage engines run FROZEN IMU_Nets (shared, prefetched or beside another stage) and one optimiser per stage: a stage that
+    trains more than its own net does not fit."""
+    for o, _ in TRAINED[1:]:
+        if any(getattr(st, o, None) is not None for st in stages):
+            raise ValueError(_REFUSED[o] % who)
 
 
-class StageStep:
+class _Engine:
+    """What every step engine is: the capture protocol and step().  An engine supplies its ``_body``, the tensors the body changes besides
+    gradients and activations (``_mutable_state``), the number of warm-up runs ahead of a capture (``warm_ups``) and its ``_update``."""
+    warm_ups = 1
+    graph = None
+
+    def warm_up(self):
+        """Run the body WITHOUT side effects (sizes the arenas, sets kernel attributes before graph capture): the mutable state is put
+        back afterwards, so graph and eager runs -- and a resumed run -- see identical states."""
+        keep = [t.clone() for t in self._mutable_state()]
+        for _ in range(self.warm_ups):
+            self._body()
+            torch.cuda.synchronize()
+        for t, k in zip(self._mutable_state(), keep):
+            t.copy_(k)
+        torch.cuda.synchronize()
+
+    def prepare(self):
+        """Size the arenas and capture the HIP graph without changing any state (so that the first step() costs what every step costs)."""
+        if self.use_graph and self.graph is None:
+            self.warm_up()
+            self.graph = _capture_body(self._body)
+
+    def step(self):
+        if self.use_graph:
+            self.prepare()
+            self.graph.replay()
+        else:
+            self._body()
+        self._update()
+        return self._losses()
+
+    # -- an engine around ONE trained net and its flat gradient buffer (StageStep, ImuStep) ---------------------------------------
+    def optimisers(self):
+        return [opt for opt in (getattr(self, o, None) for o, _ in TRAINED) if opt is not None]
+
+    def _update(self):
+        allreduce_grads(self.net._flat, self.pg)
+        for opt in self.optimisers():
+            opt.step()
+
+    def _losses(self):
+        return self.loss
+
+
+class _StagesEngine(_Engine):
+    """An engine around several StageSteps (``stages``) whose gradients ``pair`` all-reduces: each stage trains its one net."""
+
+    def _mutable_state(self):
+        return [t for st in self.stages for t in st._mutable_state()]
+
+    def _update(self):
+        self.pair.allreduce()
+        for st in self.stages:
+            for opt in st.optimisers():
+                opt.step()
+
+    def _losses(self):
+        return [st.loss for st in self.stages]
+
+
+class StageStep(_Engine):
     """One training stage's per-minibatch body with static buffers (graph friendly).
 
     ``imu_net=None`` takes the head pose from the recording (R_gt, ground-truth head joint) instead of the
@@ -169,16 +237,25 @@ class StageStep:
     ``clip_grad_norm`` (None: off): every optimiser this step builds -- ``opt``, ``imu_opt``, ``upper_opt`` -- clips ITS net's gradient
     to that global norm ahead of its update (FusedAdam(max_grad_norm=...)): one clip_grad_norm_ per optimiser, as the nets have separate
     optimisers and learning rates.  Data parallel, the all-reduce precedes ``opt.step()``: every rank clips the summed gradient by the
-    same norm."""
+    same norm.
+
+    ``optimisers`` (a dict keyed "opt" / "imu_opt" / "upper_opt"): the ones in it are used as they are, the missing ones are built and
+    put into it -- a trainer hands ONE dict to the steps of all its minibatch sizes, so every optimiser is built once."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
-                 clip_grad_norm=None):
+                 clip_grad_norm=None, optimisers=None):
         assert stage in ("upper", "lower")
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
         self.finetune_imu = bool(finetune_imu)
         self.finetune_upper = bool(finetune_upper)
+        opts = {} if optimisers is None else optimisers
+
+        def opt_for(key, trained, lr, weight_decay):
+            if opts.get(key) is None:
+                opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+            return opts[key]
         self.imu_opt = self.upper_opt = None
         if self.finetune_upper:
             from .nets import LowerNet, UpperNet
@@ -191,8 +268,7 @@ class StageStep:
                 raise ValueError("StageStep: finetune_upper cannot be combined with finetune_imu (the head pose is not trained in stage 3)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_upper is not data parallel yet (no all-reduce of the Upper_Net gradients)")
-            self.upper_opt = FusedAdam(upper_frozen.flat(), lr=lr if upper_lr is None else upper_lr, weight_decay=weight_decay,
-                                       max_grad_norm=clip_grad_norm)
+            self.upper_opt = opt_for("upper_opt", upper_frozen, lr if upper_lr is None else upper_lr, weight_decay)
         if self.finetune_imu:
             from .nets import UpperNet
             if stage != "upper" or type(net) is not UpperNet:
@@ -202,9 +278,8 @@ class StageStep:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_imu is not data parallel yet (no all-reduce of the IMU_Net gradients)")
-            self.imu_opt = FusedAdam(imu_net.flat(), lr=lr if imu_lr is None else imu_lr, weight_decay=imu_weight_decay,
-                                     max_grad_norm=clip_grad_norm)
-        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+            self.imu_opt = opt_for("imu_opt", imu_net, lr if imu_lr is None else imu_lr, imu_weight_decay)
+        self.opt = opt_for("opt", net, lr, weight_decay)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
@@ -236,65 +311,60 @@ class StageStep:
         if self.finetune_upper:
             self.upper_frozen.loss_hook = (s["target"], self.upper_jmap, self.upper_loss2, 1.0)
         try:
-            self._body_forward_inner(s, B, T, first_net, via_transform)
+            with torch.no_grad():
+                self._body_forward_inner(s, B, T, via_transform)
         finally:
             self.net.loss_hook = None
             if self.finetune_upper:
                 self.upper_frozen.loss_hook = None
 
-    def _body_forward_inner(self, s, B, T, first_net, via_transform):
-        from .nets import UpperNet
+    def _head_pose(self, s, B, T):
+        """(R, t) of the minibatch: the trained IMU_Net's, the shared pose, the frozen IMU_Net's, or the recording's."""
+        if self.finetune_imu:
+            from . import imu_train
+            return imu_train.forward_train(self.imu, s["imu"])
+        if self.pose is not None:
+            return self.pose
+        if self.imu is not None:
+            return self.imu(s["imu"])
+        ops.copy2d(s["target"].view(B * T, 63)[:, 60:63], s["t_gt"].view(B * T, 3))
+        return s["R_gt"], s["t_gt"]
+
+    def _l1_fallback(self, net, pred, jmap, nsel, loss2, dl):
+        """The loss as a launch of its own, where ``net``'s kinematics launch did not take it along (nets._head_fk: no fused form)."""
+        if not getattr(net, "_dy_ready", False):
+            s = self.static
+            hip.call("l1_loss", pred, s["target"], jmap, nsel, 21, s["x"].shape[0] * s["x"].shape[1], 1.0, loss2, dl)
+
+    def _body_forward_inner(self, s, B, T, via_transform):
         if not via_transform:
             ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
-        x_src = s["x_src"] if via_transform else None
-        with torch.no_grad():
-            if self.finetune_imu:
-                from . import imu_train
-                R, t = imu_train.forward_train(self.imu, s["imu"])
-                # (without x_src the net keeps its own copy of the untransformed points)
-                l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src, pose_grad=True)[0]
-                if not getattr(self.net, "_dy_ready", False):
-                    hip.call("l1_loss", l, s["target"], self.jmap, 15, 21, B * T, 1.0, self.loss2, s["dl"])
-                self.last_pred = l
-                return
-            if self.pose is not None:
-                R, t = self.pose
-            elif self.imu is not None:
-                R, t = self.imu(s["imu"])
+        x_src = s["x_src"] if via_transform else None       # (without x_src the net keeps its own copy of the untransformed points)
+        R, t = self._head_pose(s, B, T)
+        if self.stage == "upper":
+            from .nets_local import UpperNetwlocal
+            # (Net/Upper_Net.py:406-432: UpperNetwlocal takes a second state pair for the anchor branch)
+            states = (s["h0"], s["c0"]) * (2 if isinstance(self.net, UpperNetwlocal) else 1)
+            pose_grad = {"pose_grad": True} if self.finetune_imu else {}      # (only a trained IMU_Net consumes d loss / d R, d loss / d t)
+            l = self.net._forward_impl(s["x"], *states, s["body"], R, t, stash=True, x_src=x_src, **pose_grad)[0]
+            nsel = 15
+        else:
+            upper = self.upper_frozen
+            if self.finetune_upper and not upper.training:
+                raise ValueError("StageStep: finetune_upper needs its Upper_Net in train mode (call .train() on it)")
+            if self.finetune_upper or (via_transform and not upper.training):
+                # (trained: a train-mode forward that keeps its activations; frozen: the eval forward)
+                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=self.finetune_upper, x_src=x_src)[0]
             else:
-                R, t = s["R_gt"], s["t_gt"]
-                ops.copy2d(s["target"].view(B * T, 63)[:, 60:63], t.view(B * T, 3))
-            if self.stage == "upper":
-                from .nets_local import UpperNetwlocal
-                if isinstance(self.net, UpperNetwlocal):     # (Net/Upper_Net.py:406-432: a second state pair for the anchor branch)
-                    l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src)[0]
-                elif via_transform:
-                    l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src)[0]
-                else:
-                    l = self.net._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True)[0]
-                nsel = 15
-            elif self.finetune_upper:
-                upper = self.upper_frozen
-                if not upper.training:
-                    raise ValueError("StageStep: finetune_upper needs its Upper_Net in train mode (call .train() on it)")
-                # (not via_transform: x holds the fresh minibatch already)
-                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src)[0]
-                if not getattr(upper, "_dy_ready", False):
-                    hip.call("l1_loss", up, s["target"], self.upper_jmap, 15, 21, B * T, 1.0, self.upper_loss2, s["dl_up"])
-                l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True, input_grad=("upper_l",))[0]
+                if via_transform:
+                    ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
+                up = upper(s["x"], s["h0"], s["c0"], s["body"], R, t)[0]
+            if self.finetune_upper:
+                self._l1_fallback(upper, up, self.upper_jmap, 15, self.upper_loss2, s["dl_up"])
                 self.last_upper_pred = up
-                nsel = 8
-            else:
-                if via_transform and not self.upper_frozen.training:
-                    up = self.upper_frozen._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=False, x_src=x_src)[0]
-                else:
-                    if via_transform:
-                        ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
-                    up = self.upper_frozen(s["x"], s["h0"], s["c0"], s["body"], R, t)[0]
-                l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True)[0]
-                nsel = 8
-            if not getattr(self.net, "_dy_ready", False):
-                hip.call("l1_loss", l, s["target"], self.jmap, nsel, 21, B * T, 1.0, self.loss2, s["dl"])
+            l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True, input_grad=("upper_l",) if self.finetune_upper else ())[0]
+            nsel = 8
+        self._l1_fallback(self.net, l, self.jmap, nsel, self.loss2, s["dl"])
         self.last_pred = l
 
     def _body_backward(self):
@@ -325,51 +395,18 @@ class StageStep:
     def _mutable_state(self):
         """What a body changes besides gradients/activations: BatchNorm running statistics + step counters and the dropout
         counter of the trained net(s) (the frozen nets run in eval mode)."""
-        extra = [self.imu.seed_counter()] if self.finetune_imu else []
-        if self.finetune_upper:                                        # (the second trained net's BatchNorm statistics and dropout counter)
-            extra += list(self.upper_frozen.buffers()) + [self.upper_frozen.seed_counter()]
-        return list(self.net.buffers()) + [self.net.seed_counter()] + extra
-
-    def warm_up(self):
-        """Run the body once WITHOUT side effects (sizes the arenas, sets kernel attributes before graph capture): the
-        mutable state is put back afterwards, so graph and eager runs -- and a resumed run -- see identical states."""
-        keep = [t.clone() for t in self._mutable_state()]
-        self._body()
-        torch.cuda.synchronize()
-        for t, k in zip(self._mutable_state(), keep):
-            t.copy_(k)
-        torch.cuda.synchronize()
-
-    def prepare(self):
-        """Size the arenas and capture the HIP graph without changing any state (so that the first step() costs what
-        every step costs)."""
-        if self.use_graph and self.graph is None:
-            self.warm_up()
-            self.graph = _capture_body(self._body)
-
-    def step(self):
-        if self.use_graph:
-            self.prepare()
-            self.graph.replay()
-        else:
-            self._body()
-        allreduce_grads(self.net._flat, self.pg)
-        self.opt.step()
-        if self.finetune_imu:
-            self.imu_opt.step()
-        if self.finetune_upper:
-            self.upper_opt.step()
-        return self.loss
+        nets = [getattr(self, n) for o, n in TRAINED if getattr(self, o) is not None]
+        return [t for net in nets for t in list(net.buffers()) + [net.seed_counter()]]
 
 
-class ImuStep:
+class ImuStep(_Engine):
     """Stage-1 per-minibatch body (reference Processor/Train/Train_IMU.py:114-149): IMU_Net forward, geodesic + 100 x
     position loss (sum), backward through the two BiLSTM(512) stacks, Adam with coupled weight decay -- with static
     buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound)."""
 
-    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None):
+    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None):
         self.net = net
-        self.opt = FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        self.opt = opt if opt is not None else FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
@@ -394,26 +431,15 @@ class ImuStep:
             hip.call("imu_loss", R, t, s["R_gt"], s["head"], B * T, 1.0, self.loss, s["dR"], s["dt"])
             imu_train.backward(self.net, s["dR"], s["dt"])
 
-    def step(self):
-        if self.use_graph:
-            if self.graph is None:
-                keep = self.net.seed_counter().clone()
-                self._body()                                   # warm-up (side-effect free: IMU_Net has no BatchNorm)
-                torch.cuda.synchronize()
-                self.net.seed_counter().copy_(keep)
-                self.graph = _capture_body(self._body)
-            self.graph.replay()
-        else:
-            self._body()
-        allreduce_grads(self.net._flat, self.pg)
-        self.opt.step()
-        return self.loss
+    def _mutable_state(self):
+        return [self.net.seed_counter()]                       # (IMU_Net has no BatchNorm: the dropout counter is all a body changes)
 
 
-class SharedImuStages:
+class SharedImuStages(_StagesEngine):
     """The "IMU-shared" arrangement of SURVEY 8-d: ONE frozen IMU_Net forward per minibatch feeds both stage bodies (they
     run as two concurrent branches after it).  Not what the reference does (each stage program runs its own IMU_Net
     forward); reported beside the literal U+L step."""
+    warm_ups = 2          # the bodies fork: the second run sizes the side streams' scratch (ops.scratch is keyed by capture stream)
 
     def __init__(self, imu_net, stages, imu_in, use_graph=True):
         self.imu, self.stages, self.imu_in = imu_net, list(stages), imu_in
@@ -434,27 +460,8 @@ class SharedImuStages:
             ops.copy2d(t.view(-1, 3), self.t.view(-1, 3))
         self.pair._bodies()
 
-    def step(self):
-        if self.use_graph:
-            if self.graph is None:
-                keep = [[t.clone() for t in st._mutable_state()] for st in self.stages]
-                for _ in range(2):
-                    self._body()
-                    torch.cuda.synchronize()
-                for st, ks in zip(self.stages, keep):
-                    for t, k in zip(st._mutable_state(), ks):
-                        t.copy_(k)
-                torch.cuda.synchronize()
-                self.graph = _capture_body(self._body)
-            self.graph.replay()
-        else:
-            self._body()
-        self.pair.allreduce()
-        for st in self.stages:
-            st.opt.step()
 
-
-class ConcurrentStages:
+class ConcurrentStages(_StagesEngine):
     """Several INDEPENDENT stage bodies per minibatch as concurrent branches of one HIP graph.
 
     In the reference the Upper and Lower stages are separate programs (Train_Lower.py:129-137 loads a frozen, already
@@ -485,6 +492,13 @@ class ConcurrentStages:
         pg = self.stages[0].pg
         if len(pgs) == 1 and pg is not None and torch.distributed.get_world_size(pg) > 1 and len(self.stages) > 1:
             self.bucket = GradBucket.of([st.net for st in self.stages])
+
+    @property
+    def pair(self):
+        """The engines built around a ConcurrentStages call theirs `pair`; this one is its own.  (A property, not an attribute: a
+        reference to itself would leave a dropped engine -- and its HIP graph -- to the cyclic collector, which may run inside somebody
+        else's capture, where destroying a graph is an error.)"""
+        return self
 
     def allreduce(self):
         if self.bucket is not None:
@@ -566,33 +580,16 @@ class ConcurrentStages:
         for side in self.side:
             main.wait_stream(side)
 
-    def prepare(self):
-        """Warm-up (side-effect free) and graph capture, so that the first step() costs what every step costs."""
-        if self.use_graph and self.graph is None:
-            for st in self.stages:                          # warm-up one by one: sizes arenas, sets kernel attributes
-                st.warm_up()
-            keep = [[t.clone() for t in st._mutable_state()] for st in self.stages]
-            self._bodies()                                  # per-stream scratch buffers of the side streams
-            torch.cuda.synchronize()
-            for st, ks in zip(self.stages, keep):
-                for t, k in zip(st._mutable_state(), ks):
-                    t.copy_(k)
-            torch.cuda.synchronize()
-            self.graph = _capture_body(self._bodies)
+    def _body(self):
+        self._bodies()
 
-    def step(self):
-        if self.use_graph:
-            self.prepare()
-            self.graph.replay()
-        else:
-            self._bodies()
-        self.allreduce()
-        for st in self.stages:
-            st.opt.step()
-        return [st.loss for st in self.stages]
+    def warm_up(self):
+        for st in self.stages:                              # each stage alone first: sizes its arenas, sets its kernel attributes
+            st.warm_up()
+        super().warm_up()                                   # then all of them: the per-stream scratch buffers of the side streams
 
 
-class PipelinedStages:
+class PipelinedStages(_StagesEngine):
     """ConcurrentStages with the frozen IMU_Net forwards moved one minibatch ahead (a prefetch pipeline).
 
     The IMU_Net forwards of a stage body depend on nothing the step changes (frozen weights, the minibatch's IMU samples), so
@@ -606,6 +603,7 @@ class PipelinedStages:
     Every step still runs both IMU_Net forwards in full; results are bit-identical to ConcurrentStages on the same sequence of
     minibatches (tests/test_hip_local.py).  `imu_next` is the static buffer the caller fills with minibatch i+1's IMU samples
     before step i; `prime()` runs the forwards for the first minibatch."""
+    warm_ups = 2          # side streams: the second run sizes their scratch (ops.scratch is keyed by capture stream)
 
     def __init__(self, stages, imu_nets, imu_next, use_graph=True, unguarded=False):
         self.stages, self.imus, self.imu_next = list(stages), list(imu_nets), imu_next
@@ -675,28 +673,6 @@ class PipelinedStages:
         self.pair._bodies()
         main.wait_stream(self.side)
 
-    def prepare(self):
-        if self.use_graph and self.graph is None:
-            keep = [[t.clone() for t in st._mutable_state()] for st in self.stages]
-            keep_pose = [[t.clone() for pr in (self.cur, self.nxt) for pose in pr for t in pose]]
-            for _ in range(2):
-                self._body()
-                torch.cuda.synchronize()
-            for st, ks in zip(self.stages, keep):
-                for t, k in zip(st._mutable_state(), ks):
-                    t.copy_(k)
-            for t, k in zip([t for pr in (self.cur, self.nxt) for pose in pr for t in pose], keep_pose[0]):
-                t.copy_(k)
-            torch.cuda.synchronize()
-            self.graph = _capture_body(self._body)
-
-    def step(self):
-        if self.use_graph:
-            self.prepare()
-            self.graph.replay()
-        else:
-            self._body()
-        self.pair.allreduce()
-        for st in self.stages:
-            st.opt.step()
-        return [st.loss for st in self.stages]
+    def _mutable_state(self):
+        # (a warm-up run also moves the prefetched head poses on: the `cur` / `nxt` buffers are put back with the stages' state)
+        return super()._mutable_state() + [t for pr in (self.cur, self.nxt) for pose in pr for t in pose]

@@ -21,6 +21,7 @@ import torch
 
 from conftest import ROOT
 from oracle import geometry as geo
+from step_helpers import entry_points as _entry_points
 
 pytestmark = pytest.mark.gpu
 
@@ -326,11 +327,6 @@ def test_refusals_launch_nothing(dev):
 
 
 # ---- 8. FusedAdam -------------------------------------------------------------------------------------------------------------------------
-def _entry_points(body):
-    from mmego_amd.plan import StepPlan
-    return [n for sg in StepPlan().record(body).segments for n, _ in sg.calls]
-
-
 def test_fused_adam_launches_and_never_trained_ranges(dev):
     from mmego_amd import nets
     from mmego_amd.params import FusedAdam

@@ -16,6 +16,7 @@ from oracle import geometry as geo
 from oracle import nets as on
 from oracle import skeleton as sk
 from oracle import train as ot
+from step_helpers import entry_points as _entry_points
 
 pytestmark = pytest.mark.gpu
 
@@ -122,12 +123,6 @@ def test_upper_head_pose_gradients_against_oracle(dev):
             err, scale = _rel_err(dth, dto)
             print("   dt max err %.3e at scale %.3e (%.2e of it)" % (err, scale, err / scale))
             assert err < GRAD_BAR * scale, (tag, "dt", err, scale)
-
-
-def _entry_points(body):
-    from mmego_amd.plan import StepPlan
-    plan = StepPlan().record(body)
-    return [n for sg in plan.segments for n, _ in sg.calls]
 
 
 def test_head_pose_gradients_are_reproducible_and_free_when_unused(dev):

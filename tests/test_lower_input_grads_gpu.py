@@ -15,6 +15,7 @@ from conftest import GOLDEN, set_lstm_dropout
 from oracle import geometry as geo
 from oracle import nets as on
 from oracle import train as ot
+from step_helpers import entry_points as _entry_points
 
 pytestmark = pytest.mark.gpu
 
@@ -244,12 +245,6 @@ def test_lower_input_gradients_are_reproducible_and_leave_parameter_gradients_al
         want = v if v is not None else torch.zeros_like(dict(o.named_parameters())[k])
         err = float((p0[k].double().cpu() - want).abs().max())
         assert err < GRAD_BAR * scale, (k, err, scale)
-
-
-def _entry_points(body):
-    from mmego_amd.plan import StepPlan
-    plan = StepPlan().record(body)
-    return [n for sg in plan.segments for n, _ in sg.calls]
 
 
 def test_default_lower_step_is_unchanged(dev):
