@@ -190,8 +190,8 @@ typedef struct MmegoLstm64Bwd {
   float* dgates[2]; long dgs;
   int B, T;
 } MmegoLstm64Bwd;
-int mmego_lstm64_forward_multi(void* stream, int n, const void* descs);
-int mmego_lstm64_backward_multi(void* stream, int n, const void* descs);
+int mmego_lstm64_forward_multi(void* stream, int n, const MmegoLstm64Fwd* descs);
+int mmego_lstm64_backward_multi(void* stream, int n, const MmegoLstm64Bwd* descs);
 
 /* ---- bf16-operand / fp32-accumulate forward of the frozen IMU_Net (bf16.hip; BASELINE config 5) -------------------
  * Opt-in precision mode, never the parity path.  bf16 values cross the ABI as raw bits in unsigned short.
@@ -600,7 +600,7 @@ int mmego_mlp_dw_reduce(void* stream, long rows, int nlayers, const float* part0
  * nblk records `stride` floats apart, element (m, n) of a record at m * 64 + n (e.g. the pooling kernels' attention-parameter partials:
  * Cout = 1, Cin = 64, stride 128). */
 typedef struct MmegoDwRed { const float* part; float* dW; int Cout, Cin; long rows; int nblk; long stride; } MmegoDwRed;
-int mmego_mlp_dw_reduce_multi(void* stream, int n, const void* descs);
+int mmego_mlp_dw_reduce_multi(void* stream, int n, const MmegoDwRed* descs);
 
 /* ---- LocalVoxelNet training step (vox.hip): Net/Upper_Net.py:180-205 -------------------------------------------------------------
  * Conv3d(64, 96, k=3) over the whole 3x3x3 anchor grid (= a 1728 -> 96 map per frame), two 1x1x1 convs 96 -> 128 -> 64, a train-mode
@@ -618,12 +618,13 @@ int mmego_mlp_dw_reduce_multi(void* stream, int n, const void* descs);
  *   vox_l1_bwd    dZ as above for the first layer (C = 96), dX[rows][K] = dZ W[C][K]
  *   vox_dw        dW1[C1][K] = dZ1^T X, dW2[C2][C1] = dZ2^T Y1, dW3[C3][C2] = dZ3^T Y2 (assigned)
  * The conv biases get no gradient (exactly zero in front of a batch-statistics BatchNorm). */
+struct MmegoBnRef;                 /* (defined with the fused ST-GCN step below) */
 int mmego_vox_ok(long rows, int K, int C1, int C2, int C3);
 int mmego_vox_l1_fwd(void* stream, const float* X, long ldx, long rows, int K, const float* W, const float* bias, int C, float* Z,
                      float* rec);
-int mmego_vox_mid_fwd(void* stream, const float* Zin, const float* rec_in, const void* bn, long rows, int Cin, float* Yin,
+int mmego_vox_mid_fwd(void* stream, const float* Zin, const float* rec_in, const struct MmegoBnRef* bn, long rows, int Cin, float* Yin,
                       const float* W, const float* bias, int Cout, float* Zout, float* rec_out);
-int mmego_vox_out_fwd(void* stream, const float* Z, const float* rec, const void* bn, long rows, int C, float* Y, long ldy);
+int mmego_vox_out_fwd(void* stream, const float* Z, const float* rec, const struct MmegoBnRef* bn, long rows, int C, float* Y, long ldy);
 int mmego_vox_bwd_sums(void* stream, const float* dY, long lddy, const float* Y, long ldy, const float* Z, const float* state,
                        long rows, int C, float* G, float* prt);
 int mmego_vox_mid_bwd(void* stream, const float* G, const float* Z, const float* state, const float* prt, long rows, int Cout,
@@ -662,7 +663,7 @@ typedef struct MmegoGcnFront {
   long F; int V;
 } MmegoGcnFront;
 int mmego_gcn_front_nrec(long F);
-int mmego_gcn_front(void* stream, const void* desc);
+int mmego_gcn_front(void* stream, const MmegoGcnFront* desc);
 /* mmego_tconv in the fused training step: in_bn = MmegoBnRef of the BatchNorm (+ReLU) in front, out_rec [ceil(rows/64)][Cout] =
  * records of the output for the BatchNorm behind; mmego_tconv_bwd_stats = the input-gradient call (X = dY, gradient pack) whose
  * epilogue leaves bw_rec [ceil(rows/64)][Cout] = (sum g, sum g xhat), g = dAct . [bn(ymix) > 0], for the BatchNorm + ReLU in front of
@@ -670,7 +671,7 @@ int mmego_gcn_front(void* stream, const void* desc);
  * mmego_tconv_pack mode 2 of W[Co][Ci][taps]; kind 1: a k=1 conv weight W[Co][Ci] (both multiples of 32) in the FRAGMENT-MAJOR order
  * mmego_gcn_front reads with one coalesced 1-KB fetch per MFMA operand group (gcn.hip, pack_multi_kernel) -- MmegoGcnFront.W then
  * points at that copy when cin >= 32. */
-int mmego_tconv_train(void* stream, const float* X, long ldx, const void* in_bn, const float* Wp, const float* bias, float* Y,
+int mmego_tconv_train(void* stream, const float* X, long ldx, const MmegoBnRef* in_bn, const float* Wp, const float* bias, float* Y,
                       long ldy, float* act, float* out_rec, int B, int T, int V, int Cin, int Cout, int taps);
 int mmego_tconv_bwd_stats(void* stream, const float* dY, long lddy, const float* Wp, float* dAct, long ldda, const float* ymix,
                           long ldym, const float* state, float* bw_rec, int B, int T, int V, int Cin, int Cout, int taps);
@@ -679,7 +680,7 @@ int mmego_tconv_bwd_stats(void* stream, const float* dY, long lddy, const float*
  * (mmego_pack_multi kind 2: 2 * taps * Co * Ci floats, the forward image then the input-gradient image); out_rec / bw_rec are per
  * SEQUENCE: [B][Cout], T*V rows per record. */
 int mmego_tconv_seq_ok(int T, int V, int Cin, int Cout);
-int mmego_tconv_seq_train(void* stream, const float* X, long ldx, const void* in_bn, const float* Wf, const float* bias, float* Y,
+int mmego_tconv_seq_train(void* stream, const float* X, long ldx, const MmegoBnRef* in_bn, const float* Wf, const float* bias, float* Y,
                           long ldy, float* act, float* out_rec, int B, int T, int V, int Cin, int Cout, int taps);
 int mmego_tconv_seq_bwd(void* stream, const float* dY, long lddy, const float* Wf, float* dAct, long ldda, const float* ymix,
                         long ldym, const float* state, float* bw_rec, int B, int T, int V, int Cin, int Cout, int taps);
@@ -705,7 +706,7 @@ int mmego_tconv_eval_bf16(void* stream, const unsigned short* X, const unsigned 
                           const float* res, long ldr, float* Y, long ldy, int relu, int B, int T, int V, int Cin, int Cout, int taps);
 int mmego_tconv_pack_bf16(void* stream, const float* W, int Cout, int Cin, int taps, unsigned short* Wp);
 typedef struct MmegoPack { const float* W; float* Wp; int Co, Ci, taps, kind; } MmegoPack;
-int mmego_pack_multi(void* stream, int n, const void* descs);
+int mmego_pack_multi(void* stream, int n, const MmegoPack* descs);
 /* Backward of a block's closing pair out = relu(BN(X1) + BN(X2)) (same dY, mask = out): reduce -> rec [ceil(rows/64)][2C] (sum g, sum
  * g xhat), virtual channels [0, C) = first BatchNorm, [C, 2C) = second; apply: finalize in the prologue, dX = a (g - mean(g) - xhat
  * mean(g xhat)) for both, d(gamma) / d(beta) by workgroup 0.  st1 / st2: state [4][C].  C % 4 == 0, C <= 128. */
@@ -744,7 +745,7 @@ int mmego_copy2d_pair(void* stream, const float* X1, long ldx1, float* Y1, long 
                       float* Y2, long ldy2, long rows2, int C2);
 int mmego_topk_rows2(void* stream, const float* pts, long F, int N, int C, int keep, float* out, long long* idx, float* out2, long ld2,
                      int n2);
-int mmego_slab_reduce(void* stream, int n, const void* descs);
+int mmego_slab_reduce(void* stream, int n, const MmegoSlab* descs);
 /* d(gamma)[c] = sum_r dY[r][c] xhat[r][c], d(beta)[c] = sum_r dY[r][c] of a BatchNorm whose input gradient is not needed (data_bn,
  * GCN.py:310: the skeleton input is detached, Train_Lower.py:196); state [4][C]. */
 int mmego_bn_param_grads(void* stream, const float* dY, long lddy, const float* X, long ldx, const float* state, long rows, int C,

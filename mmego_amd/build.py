@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmmego_hip.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "mmego_hip.h")     # the C ABI: csrc/common.h includes it
 ARCH = "gfx950"
 # No packed-fp32 instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 / v_pk_mov_b32) in any kernel: the target feature is switched
 # off for the device compilation.  r06 finding: such an instruction whose op_sel takes the HIGH register of its
@@ -41,12 +42,18 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def shared_deps():
+    """What every object file depends on besides its own source: the device headers, the ABI header and this recipe."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [HEADER, os.path.abspath(__file__)]
+
+
+def fresh(product, deps):
+    """True when `product` exists and is newer than every file of `deps`."""
+    return os.path.exists(product) and os.path.getmtime(product) > max(os.path.getmtime(d) for d in deps)
+
+
 def stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return not fresh(LIB, sources() + shared_deps())
 
 
 def build_library(force=False, verbose=True, variant=None, extra_flags=()):
@@ -60,12 +67,9 @@ def build_library(force=False, verbose=True, variant=None, extra_flags=()):
     objdir = os.path.join(HERE, "build" if variant is None else "build_" + variant)
     os.makedirs(objdir, exist_ok=True)
 
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    newest_h = max([os.path.getmtime(h) for h in headers] + [os.path.getmtime(os.path.abspath(__file__))])
-
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), newest_h):
+        if not force and fresh(obj, [src] + shared_deps()):
             return obj                  # (object newer than its source, every header and this recipe: keep it)
         cmd = [hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(extra_flags) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch_setup.h"
+#include "../../include/mmego_hip.h"   // the C ABI: every definition is checked against its declaration
 
 #define MMEGO_OK 0
 #define MMEGO_EBADARG (-1)

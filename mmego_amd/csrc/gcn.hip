@@ -559,9 +559,8 @@ extern "C" int mmego_tconv(void* stream, const float* X, long ldx, const float* 
 // Training forward of the fused step: the BatchNorm (+ ReLU) in front is given by its partial records (finalized in the prologue by
 // every workgroup; workgroup 0 writes its state and updates the running statistics), the activated rows are kept in `act`, and the
 // (mean, M2) records of the OUTPUT's columns per 64-row tile go to out_rec[ceil(rows / 64)][Cout] for the BatchNorm behind.
-extern "C" int mmego_tconv_train(void* stream, const float* X, long ldx, const void* in_bn, const float* Wp, const float* bias, float* Y,
+extern "C" int mmego_tconv_train(void* stream, const float* X, long ldx, const MmegoBnRef* h, const float* Wp, const float* bias, float* Y,
                                  long ldy, float* act, float* out_rec, int B, int T, int V, int Cin, int Cout, int taps) {
-  const MmegoBnRefH* h = static_cast<const MmegoBnRefH*>(in_bn);
   MMEGO_REQUIRE((long)B * T * V * ldx < (1L << 30) && (long)Cout * Cin < (1L << 30));
   MMEGO_REQUIRE(X && h && Wp && Y && out_rec && B > 0 && T > 0 && V > 0 && Cin >= 4 && Cin <= 256 && Cout >= 1 && taps >= 1 && (taps & 1) &&
                 ldx >= Cin && ldy >= Cout);
@@ -809,9 +808,8 @@ extern "C" int mmego_tconv_seq_ok(int T, int V, int Cin, int Cout) {
 
 // mmego_tconv_train / mmego_tconv_bwd_stats on the sequence-tiled kernel: Wf = the fragment-major pack (mmego_pack_multi kind 2; its
 // second half for the input gradient); records per SEQUENCE: out_rec / bw_rec [B][Cout], T V rows per record.
-extern "C" int mmego_tconv_seq_train(void* stream, const float* X, long ldx, const void* in_bn, const float* Wf, const float* bias, float* Y,
+extern "C" int mmego_tconv_seq_train(void* stream, const float* X, long ldx, const MmegoBnRef* h, const float* Wf, const float* bias, float* Y,
                                      long ldy, float* act, float* out_rec, int B, int T, int V, int Cin, int Cout, int taps) {
-  const MmegoBnRefH* h = static_cast<const MmegoBnRefH*>(in_bn);
   MMEGO_REQUIRE(X && h && Wf && Y && out_rec && B > 0 && taps == 9 && mmego_tconv_seq_ok(T, V, Cin, Cout) && ldx >= Cin && ldy >= Cout);
   MMEGO_REQUIRE((ldx % 4) == 0 && (ldy % 4) == 0 && (((uintptr_t)X | (uintptr_t)Wf | (uintptr_t)Y | (uintptr_t)act) & 15) == 0);
   MMEGO_REQUIRE(h->rec && h->nrec >= 1 && h->rows_per_rec >= 1 && h->gamma && h->beta && (h->running_mean == nullptr) == (h->running_var == nullptr));
@@ -874,10 +872,7 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(PackTab t) {
   }
 }
 
-struct MmegoPackH { const float* W; float* Wp; int Co, Ci, taps, kind; };
-
-extern "C" int mmego_pack_multi(void* stream, int n, const void* descs) {
-  const MmegoPackH* h = static_cast<const MmegoPackH*>(descs);
+extern "C" int mmego_pack_multi(void* stream, int n, const MmegoPack* h) {
   MMEGO_REQUIRE(h && n >= 1 && n <= 8);
   PackTab t;
   int blk = 0;

@@ -856,21 +856,9 @@ __global__ __launch_bounds__(256) void bn_input_grad_kernel(const float* __restr
 // =============================================================================================================================
 // C ABI
 // =============================================================================================================================
-struct MmegoGcnFrontH {          // host-side mirror of include/mmego_hip.h's MmegoGcnFront (same field order)
-  const float* X1; long ld1; const float* X2; long ld2; int in_mode;
-  MmegoBnRefH bn1, bn2;
-  float* xact;
-  const float* W; const float* bias; int cin, nout;
-  int mix, K, cout; const float* A; const float* importance;
-  float* Z; long ldz; float* Y; float* recY; float* recR;
-  float* outT; int T;
-  long F; int V;
-};
-
 extern "C" int mmego_gcn_front_nrec(long F) { return cdiv(F, GF_FPB); }
 
-extern "C" int mmego_gcn_front(void* stream, const void* desc) {
-  const MmegoGcnFrontH* h = static_cast<const MmegoGcnFrontH*>(desc);
+extern "C" int mmego_gcn_front(void* stream, const MmegoGcnFront* h) {
   MMEGO_REQUIRE(h && h->X1 && h->W && h->F > 0 && h->V >= 1 && h->V <= 15 && h->cin >= 1 && h->nout >= 32 && (h->nout % 32) == 0);
   MMEGO_REQUIRE(h->in_mode == 0 || h->in_mode == 1);
   GcnFrontD p;
@@ -982,10 +970,7 @@ extern "C" int mmego_graph_dA_fused(void* stream, const float* Z, long ldz, cons
   return MMEGO_OK;
 }
 
-struct MmegoSlabH { const float* ws; float* out; const float* scale; float* asum; int kind, nsplit, M, N, taps; long scm; };
-
-extern "C" int mmego_slab_reduce(void* stream, int n, const void* descs) {
-  const MmegoSlabH* h = static_cast<const MmegoSlabH*>(descs);
+extern "C" int mmego_slab_reduce(void* stream, int n, const MmegoSlab* h) {
   MMEGO_REQUIRE(h && n >= 1 && n <= SLAB_MAX);
   SlabTable t;
   t.n = n;

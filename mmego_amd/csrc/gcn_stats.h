@@ -142,13 +142,7 @@ __device__ __forceinline__ float2 rec_from_shifted(float shift, float s1, float 
   return float2{shift + md, fmaxf(s2 - s1 * md, 0.f)};
 }
 
-// host-side mirror of include/mmego_hip.h's MmegoBnRef (same field order)
-struct MmegoBnRefH {
-  const float* rec; int nrec; int rows_per_rec;
-  const float* gamma; const float* beta; float* running_mean; float* running_var; float momentum; float eps;
-  float* state;
-};
-static inline BnRefD bnref_device(const MmegoBnRefH* h) {
+static inline BnRefD bnref_device(const MmegoBnRef* h) {
   BnRefD d;
   d.rec = reinterpret_cast<const float2*>(h->rec); d.nrec = h->nrec; d.rpr = h->rows_per_rec;
   d.gamma = h->gamma; d.beta = h->beta; d.rmean = h->running_mean; d.rvar = h->running_var; d.momentum = h->momentum; d.eps = h->eps;

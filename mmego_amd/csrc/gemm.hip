@@ -13,7 +13,6 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "../../include/mmego_hip.h"       // MmegoGemmDesc (mmego_gemm_group)
 
 #include "gemm_tile.h"
 #include "lstm_cell.h"

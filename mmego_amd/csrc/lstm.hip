@@ -14,7 +14,7 @@
 #include "common.h"
 #include "lstm_cell.h"
 #include <stddef.h>
-#include "../../include/mmego_hip.h"       // MmegoLstm64Fwd / MmegoLstm64Bwd (the _multi entry points)
+#include <string.h>
 
 // ---------------------------------------------------------------------------------------------
 // H = 64 persistent sequence kernels
@@ -32,6 +32,17 @@ struct Lstm64P {
   // have out's layout; the mask of element i is a hash of (i, seed_ctr[0], salt)
   float* drop_y; float* drop_mask; float drop_p; const unsigned long long* seed_ctr; unsigned salt;
 };
+// The kernels' by-value parameter types are the ABI's descriptors (MmegoLstm64Fwd / MmegoLstm64Bwd of include/mmego_hip.h) under the names
+// the kernels were compiled with: same size, and every field at the same offset with the same size.  l64_param copies one across.
+#define L64_SAME_FIELD(P, D, f) && offsetof(P, f) == offsetof(D, f) && sizeof(P::f) == sizeof(D::f)
+#define L64_SAME_LAYOUT(P, D, FIELDS) static_assert(sizeof(P) == sizeof(D) FIELDS(L64_SAME_FIELD, P, D), #D " is " #P)
+#define L64_FWD_FIELDS(X, P, D)                                                                                                        \
+  X(P, D, xproj) X(P, D, xs) X(P, D, whh) X(P, D, bhh) X(P, D, h0) X(P, D, c0) X(P, D, out) X(P, D, os) X(P, D, hn) X(P, D, cn)       \
+  X(P, D, gates) X(P, D, cst) X(P, D, hprev) X(P, D, B) X(P, D, T) X(P, D, drop_y) X(P, D, drop_mask) X(P, D, drop_p) X(P, D, seed_ctr) \
+  X(P, D, salt)
+L64_SAME_LAYOUT(Lstm64P, MmegoLstm64Fwd, L64_FWD_FIELDS);
+template <class P, class D>
+static inline P l64_param(const D& d) { P p; memcpy(&p, &d, sizeof p); return p; }
 
 // (the cell update runs on the fast activations of lstm_cell.h: the step loop of this kernel issued ~490 VALU instructions per 64
 // MFMAs, most of them libm expf and 64-bit address arithmetic)
@@ -203,8 +214,6 @@ __global__ __launch_bounds__(256) void lstm64_fwd_kernel(Lstm64P p) { lstm64_fwd
 // shape and no data in common (Net/Upper_Net.py:333-339 and :208-216) -- one after the other each layer was 8 workgroups on a 256-CU
 // chip, twice.
 #define L64_MAX_MULTI 4
-static_assert(sizeof(Lstm64P) == sizeof(MmegoLstm64Fwd) && offsetof(Lstm64P, seed_ctr) == offsetof(MmegoLstm64Fwd, seed_ctr) &&
-              offsetof(Lstm64P, B) == offsetof(MmegoLstm64Fwd, B), "MmegoLstm64Fwd is Lstm64P");
 struct Lstm64Multi { Lstm64P p[L64_MAX_MULTI]; };
 template <bool FULL, bool STASH, bool DROP>
 __global__ __launch_bounds__(256) void lstm64_fwd_multi_kernel(Lstm64Multi m) { lstm64_fwd_body<FULL, STASH, DROP>(m.p[blockIdx.z]); }
@@ -263,7 +272,9 @@ struct Lstm64BwdP {
   float* dgates[2]; long dgs;
   int B, T;
 };
-
+#define L64_BWD_FIELDS(X, P, D) \
+  X(P, D, dout) X(P, D, dos) X(P, D, gates) X(P, D, cst) X(P, D, c0) X(P, D, whh) X(P, D, dgates) X(P, D, dgs) X(P, D, B) X(P, D, T)
+L64_SAME_LAYOUT(Lstm64BwdP, MmegoLstm64Bwd, L64_BWD_FIELDS);
 
 // FULL as in lstm64_fwd_kernel: straight-line step loop (no row predicates, the prefetch unconditional, loads from explicit
 // global pointers), so the compiler counts its waits instead of draining the memory pipe every step.
@@ -381,7 +392,6 @@ __device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
 
 template <bool FULL>
 __global__ __launch_bounds__(256) void lstm64_bwd_kernel(Lstm64BwdP p) { lstm64_bwd_body<FULL>(p); }
-static_assert(sizeof(Lstm64BwdP) == sizeof(MmegoLstm64Bwd) && offsetof(Lstm64BwdP, dgs) == offsetof(MmegoLstm64Bwd, dgs), "MmegoLstm64Bwd is Lstm64BwdP");
 struct Lstm64BwdMulti { Lstm64BwdP p[L64_MAX_MULTI]; };
 template <bool FULL>
 __global__ __launch_bounds__(256) void lstm64_bwd_multi_kernel(Lstm64BwdMulti m) { lstm64_bwd_body<FULL>(m.p[blockIdx.z]); }
@@ -409,23 +419,22 @@ extern "C" int mmego_lstm64_backward(void* stream, int B, int T, const float* do
 // n <= 4 independent stacks' layers per launch.  descs: n host structs MmegoLstm64Fwd / MmegoLstm64Bwd (include/mmego_hip.h: the argument
 // lists of mmego_lstm64_forward / _backward as structs); every stack must have the same B and T and the same options (stashes for all or
 // none, dropout for all or none).
-extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const void* descs) {
-  MMEGO_REQUIRE(descs && n >= 1 && n <= L64_MAX_MULTI);
-  const Lstm64P* h = static_cast<const Lstm64P*>(descs);
+extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const MmegoLstm64Fwd* h) {
+  MMEGO_REQUIRE(h && n >= 1 && n <= L64_MAX_MULTI);
   Lstm64Multi m;
   const int B = h[0].B, T = h[0].T;
   const bool st_ = h[0].gates[0] != nullptr, dr = h[0].drop_mask != nullptr;
   for (int i = 0; i < n; ++i) {
-    const Lstm64P& p = h[i];
+    const MmegoLstm64Fwd& p = h[i];
     MMEGO_REQUIRE(p.B == B && p.T == T && B > 0 && T > 0 && p.xproj[0] && p.xproj[1] && p.whh[0] && p.whh[1] && p.out);
     MMEGO_REQUIRE((((uintptr_t)p.whh[0] | (uintptr_t)p.whh[1]) & 15) == 0);
     MMEGO_REQUIRE((p.drop_mask == nullptr) == (p.drop_y == nullptr) && (p.drop_mask != nullptr) == dr);
     MMEGO_REQUIRE(!p.drop_mask || (p.seed_ctr && p.drop_p > 0.f && p.drop_p < 1.f && (long)B * T * p.os < (1L << 32)));
     MMEGO_REQUIRE((p.gates[0] != nullptr) == st_ && (p.gates[1] != nullptr) == st_ && (p.cst[0] != nullptr) == st_ && (p.cst[1] != nullptr) == st_ &&
                   (p.hprev[0] != nullptr) == st_ && (p.hprev[1] != nullptr) == st_);
-    m.p[i] = p;
+    m.p[i] = l64_param<Lstm64P>(p);
   }
-  for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = h[0];
+  for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = m.p[0];
   const size_t lds = (size_t)(64 * 16) * sizeof(float);
   const bool full = B % 16 == 0;
 #define L64_FWDM_LAUNCH(F_, S_, D_) hipLaunchKernelGGL((lstm64_fwd_multi_kernel<F_, S_, D_>), dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m)
@@ -445,19 +454,18 @@ extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const void* descs
   return MMEGO_OK;
 }
 
-extern "C" int mmego_lstm64_backward_multi(void* stream, int n, const void* descs) {
-  MMEGO_REQUIRE(descs && n >= 1 && n <= L64_MAX_MULTI);
-  const Lstm64BwdP* h = static_cast<const Lstm64BwdP*>(descs);
+extern "C" int mmego_lstm64_backward_multi(void* stream, int n, const MmegoLstm64Bwd* h) {
+  MMEGO_REQUIRE(h && n >= 1 && n <= L64_MAX_MULTI);
   Lstm64BwdMulti m;
   const int B = h[0].B, T = h[0].T;
   for (int i = 0; i < n; ++i) {
-    const Lstm64BwdP& p = h[i];
+    const MmegoLstm64Bwd& p = h[i];
     MMEGO_REQUIRE(p.B == B && p.T == T && B > 0 && T > 0 && p.dout && p.gates[0] && p.gates[1] && p.cst[0] && p.cst[1] && p.whh[0] && p.whh[1] &&
                   p.dgates[0] && p.dgates[1]);
     MMEGO_REQUIRE((((uintptr_t)p.whh[0] | (uintptr_t)p.whh[1]) & 15) == 0);
-    m.p[i] = p;
+    m.p[i] = l64_param<Lstm64BwdP>(p);
   }
-  for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = h[0];
+  for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = m.p[0];
   const size_t lds = (size_t)(256 * 16) * sizeof(float);
   if (B % 16 == 0) hipLaunchKernelGGL(lstm64_bwd_multi_kernel<true>, dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m);
   else hipLaunchKernelGGL(lstm64_bwd_multi_kernel<false>, dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m);

@@ -751,10 +751,8 @@ extern "C" int mmego_mlp_dw_reduce(void* stream, long rows, int nlayers, const f
 
 // The same sum for up to 9 layers of SEVERAL chains in one launch (a net with two or three pointwise-MLP chains had one reduce launch
 // per chain at the end of each: the partials stay where they are until the pass ends, one node instead of two or three).
-struct MmegoDwRedH { const float* part; float* dW; int Cout, Cin; long rows; int nblk; long stride; };   // host mirror of include/mmego_hip.h's MmegoDwRed
-extern "C" int mmego_mlp_dw_reduce_multi(void* stream, int n, const void* descs) {
-  MMEGO_REQUIRE(n >= 1 && n <= MT_DW_MAX && descs);
-  const MmegoDwRedH* d = static_cast<const MmegoDwRedH*>(descs);
+extern "C" int mmego_mlp_dw_reduce_multi(void* stream, int n, const MmegoDwRed* d) {
+  MMEGO_REQUIRE(n >= 1 && n <= MT_DW_MAX && d);
   MlpDwP p = {};
   for (int l = 0; l < n; ++l) {
     MMEGO_REQUIRE(d[l].part && d[l].dW && (d[l].rows > 0 || d[l].nblk > 0) && d[l].Cout >= 1 && d[l].Cout <= 64 && d[l].Cin >= 1 && d[l].Cin <= 64);

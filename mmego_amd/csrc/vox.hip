@@ -409,15 +409,15 @@ extern "C" int mmego_vox_l1_fwd(void* stream, const float* X, long ldx, long row
   return MMEGO_OK;
 }
 
-static inline BnRefD vox_bn(const void* bn, const float* rec, long rows) {
-  BnRefD d = bnref_device(static_cast<const MmegoBnRefH*>(bn));
+static inline BnRefD vox_bn(const MmegoBnRef* bn, const float* rec, long rows) {
+  BnRefD d = bnref_device(bn);
   d.rec = reinterpret_cast<const float2*>(rec);
   d.nrec = (int)cdiv(rows, 16);
   d.rpr = 16;
   return d;
 }
 
-extern "C" int mmego_vox_mid_fwd(void* stream, const float* Zin, const float* rec_in, const void* bn, long rows, int Cin, float* Yin,
+extern "C" int mmego_vox_mid_fwd(void* stream, const float* Zin, const float* rec_in, const MmegoBnRef* bn, long rows, int Cin, float* Yin,
                                  const float* W, const float* bias, int Cout, float* Zout, float* rec_out) {
   MMEGO_REQUIRE(Zin && rec_in && bn && Yin && W && bias && Zout && rec_out && rows > 1 && rows <= 65535L * 16 && ((uintptr_t)W & 15) == 0);
   const BnRefD d = vox_bn(bn, rec_in, rows);
@@ -435,7 +435,7 @@ extern "C" int mmego_vox_mid_fwd(void* stream, const float* Zin, const float* re
   return MMEGO_OK;
 }
 
-extern "C" int mmego_vox_out_fwd(void* stream, const float* Z, const float* rec, const void* bn, long rows, int C, float* Y, long ldy) {
+extern "C" int mmego_vox_out_fwd(void* stream, const float* Z, const float* rec, const MmegoBnRef* bn, long rows, int C, float* Y, long ldy) {
   MMEGO_REQUIRE(Z && rec && bn && Y && rows > 1 && rows <= 65535L * 16 && C > 0 && C <= 128 && ldy >= C);
   const BnRefD d = vox_bn(bn, rec, rows);
   MMEGO_REQUIRE(d.gamma && d.beta && d.state);

@@ -1,6 +1,7 @@
 """ctypes binding of libmmego_hip.so (the C ABI declared in include/mmego_hip.h).
 
-The prototypes are parsed from the header itself, so binding and header cannot drift.  There is NO
+The prototypes and the descriptor structs (ctypes.Structure classes) are read from the header itself, so binding and
+header cannot drift; the kernel files include the same header, so neither can the definitions.  There is NO
 fallback: if the library is missing or a kernel launch fails, a RuntimeError is raised.
 """
 import ctypes
@@ -13,13 +14,26 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "mmego_hip.h")
 LIBPATH = os.environ.get("MMEGO_HIP_LIB") or os.path.join(_HERE, "lib", "libmmego_hip.so")    # (MMEGO_HIP_LIB: A/B builds of scripts/)
 
-_CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+_CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "unsigned": ctypes.c_uint}
 
 
-def parse_header(path=HEADER):
+def header_text(path=HEADER):
+    """The header without its comments."""
+    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+
+
+def _ctype(typ, structs):
+    """ctypes type of a C type as the header spells it: any pointer is an address, a descriptor struct by value is its class."""
+    typ = typ.replace("const ", "").strip()
+    if "*" in typ:
+        return ctypes.c_void_p
+    if typ not in _CT and typ not in structs:
+        raise RuntimeError("mmego_hip.h: type %r is not one this binding reads" % typ)
+    return _CT.get(typ) or structs[typ]
+
+
+def parse_protos(text):
     """-> {name: [(ctype, argname), ...]} for every `int mmego_*(...)` declaration."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     protos = {}
     for m in re.finditer(r"\bint\s+(mmego_\w+)\s*\(([^)]*)\)\s*;", text):
         args = []
@@ -28,24 +42,60 @@ def parse_header(path=HEADER):
             if not a or a == "void":
                 continue
             name = re.search(r"(\w+)$", a).group(1)
-            typ = a[: -len(name)].strip()
-            args.append((ctypes.c_void_p if "*" in typ else _CT[typ.replace("const ", "")], name))
+            args.append((_ctype(a[: -len(name)], ()), name))
         protos[m.group(1)] = args
     return protos
 
 
+def parse_structs(text):
+    """-> {C name: ctypes.Structure class} for every `typedef struct MmegoX { ... } MmegoX;`, the class named X.  A member declaration is
+    `type a, b;` with type a scalar, a pointer or a struct defined above, and a declarator a name or `name[N]`; anything else raises."""
+    structs = {}
+    for m in re.finditer(r"typedef struct (\w+) \{(.*?)\} (\w+);", text, flags=re.S):
+        cname, fields = m.group(1), []
+        if m.group(3) != cname or not cname.startswith("Mmego"):
+            raise RuntimeError("mmego_hip.h: struct %s is not typedef'd as Mmego<Name> under its own name" % cname)
+        for decl in m.group(2).split(";"):
+            decl = " ".join(decl.split())
+            if not decl:
+                continue
+            d = re.fullmatch(r"([\w ]+?\** ?)(\w+(?:\[\d+\])?(?:, ?\w+(?:\[\d+\])?)*)", decl)
+            if not d:
+                raise RuntimeError("mmego_hip.h: %s has a member declaration this binding does not read: %r" % (cname, decl))
+            typ = _ctype(d.group(1), structs)
+            for name in d.group(2).split(","):
+                name, _, dim = name.strip().partition("[")
+                fields.append((name, typ * int(dim[:-1]) if dim else typ))
+        structs[cname] = type(cname[5:], (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s of include/mmego_hip.h." % cname})
+    return structs
+
+
+def parse_header(path=HEADER):
+    return parse_protos(header_text(path))
+
+
+def check_gemm_desc(protos, desc):
+    """mmego_gemm's parameters behind the stream are MmegoGemmDesc's fields, in order: gemm_group fills one from the other."""
+    params, fields = [n for _, n in protos["mmego_gemm"][1:]], [n for n, _ in desc._fields_]
+    if params != fields:
+        raise RuntimeError("mmego_hip.h: mmego_gemm's parameters %s are not MmegoGemmDesc's fields %s" % (params, fields))
+
+
+_protos = parse_header()
+_structs = parse_structs(header_text())
+globals().update((c.__name__, c) for c in _structs.values())    # GemmDesc, BnRef, GcnFront, Pack, DwRed, Lstm64Fwd, Lstm64Bwd, Slab
+_GEMM_PARAMS = [n for _, n in _protos["mmego_gemm"][1:]]
 _lib = None
-_protos = None
 
 
 def lib():
-    global _lib, _protos
+    global _lib
     if _lib is None:
+        check_gemm_desc(_protos, GemmDesc)
         if not os.path.exists(LIBPATH):
             raise RuntimeError("libmmego_hip.so is not built (%s). Run `python -m mmego_amd.build` "
                                "(or __graft_entry__.build()); there is no CPU fallback." % LIBPATH)
         _lib = ctypes.CDLL(LIBPATH)
-        _protos = parse_header()
         for name, args in _protos.items():
             fn = getattr(_lib, name)
             fn.restype = ctypes.c_int
@@ -79,80 +129,19 @@ def stream_handle():
     return torch.cuda.current_stream().cuda_stream
 
 
-class GemmDesc(ctypes.Structure):
-    """MmegoGemmDesc of include/mmego_hip.h: one mmego_gemm argument set (the stream aside)."""
-    _fields_ = [("A", ctypes.c_void_p), ("sam", ctypes.c_long), ("sak", ctypes.c_long),
-                ("B", ctypes.c_void_p), ("sbk", ctypes.c_long), ("sbn", ctypes.c_long),
-                ("C", ctypes.c_void_p), ("scm", ctypes.c_long), ("scn", ctypes.c_long),
-                ("bias", ctypes.c_void_p),
-                ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("nbatch", ctypes.c_int),
-                ("sAb", ctypes.c_long), ("sBb", ctypes.c_long), ("sCb", ctypes.c_long),
-                ("relu", ctypes.c_int), ("accumulate", ctypes.c_int),
-                ("splitk_ws", ctypes.c_void_p), ("nsplit", ctypes.c_int),
-                ("sBiasb", ctypes.c_long),
-                ("cmul", ctypes.c_void_p), ("asum", ctypes.c_void_p)]
+def _bnref_of(bn, state, rec=None, nrec=0, rows_per_rec=0):
+    """A BatchNorm module whose batch statistics arrive as partial records."""
+    return BnRef(rec=ptr(rec), nrec=int(nrec), rows_per_rec=int(rows_per_rec), gamma=ptr(bn.weight), beta=ptr(bn.bias),
+                 running_mean=ptr(bn.running_mean), running_var=ptr(bn.running_var), momentum=float(bn.momentum), eps=float(bn.eps),
+                 state=ptr(state))
 
 
-class BnRef(ctypes.Structure):
-    """MmegoBnRef of include/mmego_hip.h: a BatchNorm whose batch statistics arrive as partial records."""
-    _fields_ = [("rec", ctypes.c_void_p), ("nrec", ctypes.c_int), ("rows_per_rec", ctypes.c_int),
-                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
-                ("momentum", ctypes.c_float), ("eps", ctypes.c_float), ("state", ctypes.c_void_p)]
-
-    @staticmethod
-    def of(bn, state, rec=None, nrec=0, rows_per_rec=0):
-        return BnRef(ptr(rec), int(nrec), int(rows_per_rec), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                     float(bn.momentum), float(bn.eps), ptr(state))
-
-
-class GcnFront(ctypes.Structure):
-    """MmegoGcnFront of include/mmego_hip.h."""
-    _fields_ = [("X1", ctypes.c_void_p), ("ld1", ctypes.c_long), ("X2", ctypes.c_void_p), ("ld2", ctypes.c_long), ("in_mode", ctypes.c_int),
-                ("bn1", BnRef), ("bn2", BnRef), ("xact", ctypes.c_void_p),
-                ("W", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("cin", ctypes.c_int), ("nout", ctypes.c_int),
-                ("mix", ctypes.c_int), ("K", ctypes.c_int), ("cout", ctypes.c_int), ("A", ctypes.c_void_p), ("importance", ctypes.c_void_p),
-                ("Z", ctypes.c_void_p), ("ldz", ctypes.c_long), ("Y", ctypes.c_void_p), ("recY", ctypes.c_void_p), ("recR", ctypes.c_void_p),
-                ("outT", ctypes.c_void_p), ("T", ctypes.c_int), ("F", ctypes.c_long), ("V", ctypes.c_int)]
-
-
-class Pack(ctypes.Structure):
-    """MmegoPack of include/mmego_hip.h: one weight re-layout of mmego_pack_multi."""
-    _fields_ = [("W", ctypes.c_void_p), ("Wp", ctypes.c_void_p), ("Co", ctypes.c_int), ("Ci", ctypes.c_int), ("taps", ctypes.c_int),
-                ("kind", ctypes.c_int)]
-
-
-class DwRed(ctypes.Structure):
-    """MmegoDwRed of include/mmego_hip.h: one layer's weight-gradient partials to be summed by mmego_mlp_dw_reduce_multi."""
-    _fields_ = [("part", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int), ("rows", ctypes.c_long),
-                ("nblk", ctypes.c_int), ("stride", ctypes.c_long)]
-
-
-class Lstm64Fwd(ctypes.Structure):
-    """MmegoLstm64Fwd of include/mmego_hip.h: one stack's layer for mmego_lstm64_forward_multi."""
-    _P2 = ctypes.c_void_p * 2
-    _fields_ = [("xproj", _P2), ("xs", ctypes.c_long), ("whh", _P2), ("bhh", _P2), ("h0", _P2), ("c0", _P2),
-                ("out", ctypes.c_void_p), ("os", ctypes.c_long), ("hn", _P2), ("cn", _P2), ("gates", _P2), ("cst", _P2), ("hprev", _P2),
-                ("B", ctypes.c_int), ("T", ctypes.c_int), ("drop_y", ctypes.c_void_p), ("drop_mask", ctypes.c_void_p),
-                ("drop_p", ctypes.c_float), ("seed_ctr", ctypes.c_void_p), ("salt", ctypes.c_uint)]
-
-
-class Lstm64Bwd(ctypes.Structure):
-    """MmegoLstm64Bwd of include/mmego_hip.h."""
-    _P2 = ctypes.c_void_p * 2
-    _fields_ = [("dout", ctypes.c_void_p), ("dos", ctypes.c_long), ("gates", _P2), ("cst", _P2), ("c0", _P2), ("whh", _P2),
-                ("dgates", _P2), ("dgs", ctypes.c_long), ("B", ctypes.c_int), ("T", ctypes.c_int)]
+BnRef.of = staticmethod(_bnref_of)
 
 
 def pair2(a, b):
     """Two device addresses as a descriptor's pointer pair."""
     return (ctypes.c_void_p * 2)(ptr(a), ptr(b))
-
-
-class Slab(ctypes.Structure):
-    """MmegoSlab of include/mmego_hip.h: one deferred partial-product sum."""
-    _fields_ = [("ws", ctypes.c_void_p), ("out", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("asum", ctypes.c_void_p),
-                ("kind", ctypes.c_int), ("nsplit", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int), ("taps", ctypes.c_int),
-                ("scm", ctypes.c_long)]
 
 
 _gemm_rec = None
@@ -189,13 +178,10 @@ class gemm_group:
                 part = rec[i:i + 10]
                 arr = (GemmDesc * len(part))()
                 for dsc, a in zip(arr, part):
-                    for (fname, _), v in zip(GemmDesc._fields_, a):
+                    for fname, v in zip(_GEMM_PARAMS, a):
                         setattr(dsc, fname, _conv(v))
                 call("gemm_group", len(part), arr)          # (the array object, not its address: a recorded call keeps it alive)
         return False
-
-
-# (mmego_gemm's argument list behind the stream: C at 6 with strides at 7 / 8, M N K nbatch at 10..13, sCb at 16, asum at 23)
 
 
 def _launch(name, *args):
@@ -217,15 +203,15 @@ def _ptr_of(a):
 
 def _gemm_out_extents(args):
     """Byte ranges [lo, hi) a recorded mmego_gemm writes: C (M x N x nbatch through its strides) and asum (M floats per batch)."""
-    out = []
-    M, N, nb = int(args[10]), int(args[11]), max(1, int(args[13]))
-    c = _ptr_of(args[6])
+    out, a = [], dict(zip(_GEMM_PARAMS, args))
+    M, N, nb = int(a["M"]), int(a["N"]), max(1, int(a["nbatch"]))
+    c = _ptr_of(a["C"])
     if c is not None:
-        span = (M - 1) * abs(int(args[7])) + (N - 1) * abs(int(args[8])) + 1
+        span = (M - 1) * abs(int(a["scm"])) + (N - 1) * abs(int(a["scn"])) + 1
         for b in range(nb):              # (per batch: the batches of a pair product may lie apart, with other leaves' slots between)
-            lo = c + 4 * b * int(args[16])
+            lo = c + 4 * b * int(a["sCb"])
             out.append((lo, lo + 4 * span))
-    s = _ptr_of(args[23])
+    s = _ptr_of(a["asum"])
     if s is not None:
         out.append((s, s + 4 * M * nb))
     return out

@@ -38,6 +38,39 @@ def test_step_structure_is_the_recorded_one(dev):
     assert not bad, bad
 
 
+def test_every_launch_of_a_step_matches_its_declaration(dev):
+    """One whole step() of every configuration, recorded with plan.StepPlan: every (entry point, arguments) has as many arguments, with the
+    stream, as include/mmego_hip.h declares parameters, and every argument sits on a parameter of its kind -- a tensor, None, ctypes
+    array or Structure on a pointer; a Python float on a float or double; a bool or int (a raw address is an int) on an int, a long or
+    a pointer.  ctypes itself accepts surplus trailing arguments, and a tensor becomes an integer that a long parameter would swallow."""
+    import ctypes
+    from mmego_amd import hip
+    from mmego_amd.plan import StepPlan
+    protos = hip.parse_header()
+    kinds = (((torch.Tensor, type(None), ctypes.Array, ctypes.Structure), (ctypes.c_void_p,)),
+             ((float,), (ctypes.c_float, ctypes.c_double)),
+             ((bool, int), (ctypes.c_int, ctypes.c_long, ctypes.c_void_p)))
+    bad, nlaunch = [], 0
+    for name in sh.CONFIGS:
+        eng, _ = sh.build(name, dev, use_graph=False)
+        eng.step()
+        torch.cuda.synchronize()
+        for sg in StepPlan().record(eng.step).segments:
+            for entry, args in sg.calls:
+                nlaunch += 1
+                (stream_t, stream_name), params = protos["mmego_" + entry][0], protos["mmego_" + entry][1:]
+                assert stream_t is ctypes.c_void_p and stream_name == "stream", entry
+                if len(args) != len(params):
+                    bad.append("%s: %s takes %d arguments behind the stream, %d given" % (name, entry, len(params), len(args)))
+                    continue
+                for v, (ct, pname) in zip(args, params):
+                    allowed = [cts for pys, cts in kinds if isinstance(v, pys)]
+                    if not allowed or ct not in allowed[0]:
+                        bad.append("%s: %s(%s): a %s on a %s parameter" % (name, entry, pname, type(v).__name__, ct.__name__))
+    print("%d launches checked" % nlaunch)
+    assert nlaunch > 14 * 20 and not bad, sorted(set(bad))
+
+
 @pytest.mark.parametrize("name", ["imu_step_dropout", "upper_finetune_imu", "lower_finetune_upper", "shared_fp32"])
 def test_graph_form_equals_eager_form(dev, name):
     """Two steps as a replayed HIP graph and two steps of the eager body, same start (tests/step_helpers.py's shapes): losses, every
