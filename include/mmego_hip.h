@@ -328,6 +328,14 @@ int mmego_head_fk_backward(void* stream, int which, const float* y, const float*
  * (slots added in index order).  dy as from mmego_head_fk_backward, bit for bit. */
 int mmego_head_fk_backward_pose(void* stream, int which, const float* y, const float* body, int B, long F, const float* dj,
                                 float* dy, const float* Rw, const float* joints_h, float* dRw, float* dtw);
+/* mmego_head_fk_backward_pose of a SECOND gradient dj wrt the world-frame joints, accumulated onto what an earlier launch left:
+ * dy[f] += that call's dy;  dRw[f] = (dRw[f] + that call's dRw[f]) + dR_add[f],  dtw likewise (fp32 adds in this order).  dRw and dtw
+ * both NULL: dy only (joints_h is then not read);  dR_add / dt_add NULL: that term is skipped.  One thread per frame reads and writes
+ * its own rows: fixed order, two runs give the same bits.  No two of the buffers may overlap (dy / dRw / dtw are read and written, every
+ * pointer is __restrict__ in the kernel): in particular dR_add / dt_add are not dRw / dtw, and dj is not a view of dy. */
+int mmego_head_fk_backward_extra(void* stream, int which, const float* y, const float* body, int B, long F, const float* dj,
+                                 float* dy, const float* Rw, const float* joints_h, float* dRw, float* dtw, const float* dR_add,
+                                 const float* dt_add);
 /* mmego_head_fk_forward -> mmego_l1_loss (scale, loss[2], gradient = sign) -> mmego_head_fk_backward as ONE launch.  The loss is a
  * fixed-order sum: per-workgroup partial pairs in scratch (2 * ceil(F/64) + 1 doubles; the last double's storage is a ticket that must
  * be 0 before the first call and is left 0), added in index order by the workgroup that finishes last.  map [nslots]: target joint of

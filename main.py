@@ -8,8 +8,9 @@
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
 --finetune_imu [--imu_lr F] (stage 2 trains the IMU_Net too, through Upper_Net's head-pose gradients), --finetune_upper [--upper_lr F]
-(stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses), --imu_dropout P (the
-IMU_Net that is TRAINED -- stage 1, or --finetune_imu -- gets nn.LSTM(dropout=P) between its BiLSTM layers), --clip_grad_norm X (every
+(stage 3 trains the Upper_Net too, through Lower_Net's input gradients, on the sum of the two stages' losses), --finetune_all [--upper_lr F
+--imu_lr F] (stage 3 trains all three nets end to end on that sum: IMU_Net through Upper_Net's and Lower_Net's head-pose gradients),
+--imu_dropout P (the IMU_Net that is TRAINED -- stage 1, --finetune_imu or --finetune_all -- gets nn.LSTM(dropout=P) between its BiLSTM layers), --clip_grad_norm X (every
 trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
 "Grad norm" line per net and epoch; `inf` only measures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
@@ -61,6 +62,11 @@ def build_parser():
                    help="--train --network Lower_Net only: train the Upper_Net as well (Train_Lower.py:195-196 without its .detach()), on "
                         "the sum of the two stages' losses; the Upper_Net is saved beside the Lower_Net checkpoint, in an Upper_Net folder")
     p.add_argument("--upper_lr", type=float, help="learning rate of the Upper_Net under --finetune_upper (default: --lr / Config.lr)")
+    p.add_argument("--finetune_all", action="store_true",
+                   help="--train --network Lower_Net only: train IMU_Net, Upper_Net and Lower_Net together on loss_lower + loss_upper "
+                        "(IMU_Net through both nets' head-pose gradients; it means --finetune_imu and --finetune_upper for stage 3 and is "
+                        "given without them); the two nets are saved beside the Lower_Net checkpoint, in IMU_Net and Upper_Net folders; "
+                        "--upper_lr, --imu_lr and --imu_dropout apply")
     p.add_argument("--clip_grad_norm", type=float,
                    help="--train: clip every trained net's gradient to this global norm ahead of its Adam step (one clip_grad_norm_ per "
                         "optimiser, on the SUM-loss gradient of the global minibatch), skip a step whose gradient is not finite, and print "
@@ -82,7 +88,7 @@ def check_finetune_upper(parser, args, world):
     """--finetune_upper fits one arrangement only; everything else is refused before any work starts.  (--gt_head_pose is fine: the
     head pose is not what is trained.)"""
     if not args.finetune_upper:
-        if args.upper_lr is not None:
+        if args.upper_lr is not None and not args.finetune_all:
             parser.error("--upper_lr is the Upper_Net's learning rate under --finetune_upper; without that flag the Upper_Net is frozen")
         return
     if not (args.train and args.network == "Lower_Net") or args.infer:
@@ -99,22 +105,41 @@ def check_imu_dropout(parser, args):
         return
     if not 0.0 <= args.imu_dropout < 1.0:
         parser.error("--imu_dropout is a dropout rate: it has to lie in [0, 1), got %r" % (args.imu_dropout,))
+    if args.finetune_all:
+        return                      # (check_finetune_all has made sure that this run trains an IMU_Net)
     if args.infer or not (args.train and (args.network == "IMU_Net" or (args.network == "Upper_Net" and args.finetune_imu))):
         parser.error("--imu_dropout goes with --train --network IMU_Net or with --finetune_imu only (the runs that train an IMU_Net); "
                      "a frozen IMU_Net runs in eval mode, where dropout does nothing")
 
 
+def check_finetune_all(parser, args, world):
+    """--finetune_all fits one arrangement only; everything else is refused before any work starts."""
+    if not args.finetune_all:
+        return
+    if args.finetune_imu or args.finetune_upper:
+        parser.error("--finetune_all already means --finetune_imu and --finetune_upper for stage 3: give it alone")
+    if not (args.train and args.network == "Lower_Net") or args.infer:
+        parser.error("--finetune_all goes with --train --network Lower_Net only (stage 3 training IMU_Net, Upper_Net and Lower_Net together)")
+    if args.gt_head_pose:
+        parser.error("--finetune_all trains the IMU_Net, so it needs one; --gt_head_pose takes the head pose from the recording instead")
+    if world > 1:
+        parser.error("--finetune_all is not data parallel yet (WORLD_SIZE=%d): the IMU_Net and Upper_Net gradients have no all-reduce" % world)
+    if args.resume:
+        parser.error("--finetune_all cannot be combined with --resume yet: three optimiser states are not part of a train state")
+
+
 def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
+    check_finetune_all(parser, args, world)
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
     check_clip_grad_norm(parser, args)
     if not args.finetune_imu:
-        if args.imu_lr is not None:
+        if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
         return
     if not (args.train and args.network == "Upper_Net"):
-        parser.error("--finetune_imu goes with --train --network Upper_Net only (training the IMU_Net through Lower_Net's head-pose gradients is not offered on the command line)")
+        parser.error("--finetune_imu goes with --train --network Upper_Net only (stage 3 trains the IMU_Net under --finetune_all, together with the Upper_Net)")
     if args.gt_head_pose:
         parser.error("--finetune_imu needs an IMU_Net to train; --gt_head_pose takes the head pose from the recording instead")
     if world > 1:
@@ -150,6 +175,7 @@ def apply_overrides(args):
     Config.imu_dropout = args.imu_dropout
     Config.finetune_upper = bool(args.finetune_upper)
     Config.upper_lr = args.upper_lr
+    Config.finetune_all = bool(args.finetune_all)
     Config.clip_grad_norm = args.clip_grad_norm
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__

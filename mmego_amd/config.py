@@ -47,6 +47,7 @@ class _Common:
     gt_head_pose = False
     data_parallel = False       # set by main.py when launched under torch.distributed.run
     finetune_upper = False      # --finetune_upper: stage 3 trains the Upper_Net too (train_step.StageStep)
+    finetune_all = False        # --finetune_all: stage 3 trains IMU_Net, Upper_Net and Lower_Net together (train_step.StageStep)
     upper_lr = None             # --upper_lr: its learning rate (None: lr)
     imu_dropout = None          # --imu_dropout: nn.LSTM(dropout=P) of the IMU_Net that is trained (None: 0, as the reference's stage 1)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)

@@ -477,6 +477,96 @@ __global__ __launch_bounds__(64) void head_fk_bwd_kernel(const float* __restrict
     for (int i = 0; i < 3; ++i) dyf[P::seed_off[s] + i] = g[P::seed_slot[s]][i];
 }
 
+// head_fk_bwd_kernel<WHICH, true> for a SECOND gradient wrt the world-frame joints, accumulated onto what an earlier launch (the fused
+// loss launch, for the net's own loss) has left: dy += its dy; dRw = (dRw + its dRw) + dR_add, dtw likewise (dRw / dtw NULL: dy only;
+// dR_add / dt_add NULL: that term is skipped).  The three-net step's turning point: Lower_Net's d upper_l enters Upper_Net's backward
+// here, and Lower_Net's own pose gradients (dR_add, dt_add) join Upper_Net's on the same launch.  A kernel of its own, not a third
+// form of the template above: the two existing instantiations stay instruction for instruction.  Same arithmetic as that kernel,
+// statement by statement, up to the stores; one thread per frame owns every address it reads and writes: no atomics, fixed order.
+template <int WHICH>
+__global__ __launch_bounds__(64) void head_fk_bwd_extra_kernel(const float* __restrict__ y, const float* __restrict__ body, int B, long F,
+                                                               const float* __restrict__ dj, float* __restrict__ dy,
+                                                               const float* __restrict__ Rw, const float* __restrict__ joints,
+                                                               float* __restrict__ dRw, float* __restrict__ dtw,
+                                                               const float* __restrict__ dR_add, const float* __restrict__ dt_add) {
+  using P = FkC<WHICH>;
+  long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F) return;
+  float yv[P::ny];                       // (preloaded: see the forward kernel)
+#pragma unroll
+  for (int i = 0; i < P::ny; ++i) yv[i] = y[f * P::ny + i];
+  const float* yf = yv;
+  const float* bf = body + (f % B) * 60;
+  float g[P::nslots][3];
+#pragma unroll
+  for (int s = 0; s < P::nslots; ++s)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) g[s][i] = dj[(f * P::nslots + s) * 3 + i];
+  if (dRw) {
+    float pr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < P::nslots; ++s) {
+      const float* jp = joints + (f * P::nslots + s) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        pt[i] += g[s][i];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pr[k * 3 + i] += jp[k] * g[s][i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const float v = dRw[f * 9 + i] + pr[i];
+      dRw[f * 9 + i] = dR_add ? v + dR_add[f * 9 + i] : v;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float v = dtw[f * 3 + i] + pt[i];
+      dtw[f * 3 + i] = dt_add ? v + dt_add[f * 3 + i] : v;
+    }
+  }
+  {
+    const float* Rf = Rw + f * 9;
+#pragma unroll
+    for (int s = 0; s < P::nslots; ++s) {
+      const float v0 = g[s][0], v1 = g[s][1], v2 = g[s][2];
+      g[s][0] = dot3_nofma(Rf[0], Rf[1], Rf[2], v0, v1, v2);
+      g[s][1] = dot3_nofma(Rf[3], Rf[4], Rf[5], v0, v1, v2);
+      g[s][2] = dot3_nofma(Rf[6], Rf[7], Rf[8], v0, v1, v2);
+    }
+  }
+  float gq[P::nrot][9];
+#pragma unroll
+  for (int k = 0; k < P::nrot; ++k)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) gq[k][i] = 0.f;
+#pragma unroll
+  for (int k = P::nbones - 1; k >= 0; --k) {
+    const float* bv = bf + P::row[k] * 3;
+    const float b0 = bv[0], b1 = bv[1], b2 = bv[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      g[P::parent[k]][i] += g[P::child[k]][i];
+      gq[P::rot[k]][i * 3 + 0] += g[P::child[k]][i] * b0;
+      gq[P::rot[k]][i * 3 + 1] += g[P::child[k]][i] * b1;
+      gq[P::rot[k]][i * 3 + 2] += g[P::child[k]][i] * b2;
+    }
+  }
+  float* dyf = dy + f * P::ny;
+#pragma unroll
+  for (int k = 0; k < P::nrot; ++k) {
+    float d6[6];
+    rot6d_bwd(yf + 6 * k, 1e-12f, gq[k], d6);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) dyf[6 * k + i] = dyf[6 * k + i] + d6[i];
+  }
+  // (columns behind the rotations that are no seed get a zero from the plain kernel: nothing to add)
+#pragma unroll
+  for (int s = 0; s < P::nseed; ++s)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dyf[P::seed_off[s] + i] = dyf[P::seed_off[s] + i] + g[P::seed_slot[s]][i];
+}
+
 // Forward kinematics + head-to-world transform + L1(sum) loss against the selected target joints + the loss gradient (its sign)
 // + the backward of the transform and of the kinematics, in ONE launch: one thread per frame in 64-thread workgroups (one wave per
 // workgroup: the frame's ~400 live values fit the unified register file).  The loss is a fixed-order sum: every workgroup publishes its
@@ -1023,6 +1113,18 @@ extern "C" int mmego_head_fk_backward_pose(void* stream, int which, const float*
   MMEGO_REQUIRE(F > 0 && B > 0 && (which == 0 || which == 1) && Rw && joints_h && dRw && dtw);
   if (which == 0) hipLaunchKernelGGL((head_fk_bwd_kernel<0, true>), dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw);
   else hipLaunchKernelGGL((head_fk_bwd_kernel<1, true>), dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw);
+  MMEGO_LAUNCH_CHECK();
+  return MMEGO_OK;
+}
+
+// mmego_head_fk_backward_pose of a second joint gradient, accumulated: dy += ..., dRw = (dRw + ...) + dR_add, dtw likewise.
+extern "C" int mmego_head_fk_backward_extra(void* stream, int which, const float* y, const float* body, int B, long F,
+                                            const float* dj, float* dy, const float* Rw, const float* joints_h,
+                                            float* dRw, float* dtw, const float* dR_add, const float* dt_add) {
+  MMEGO_REQUIRE((which == 0 || which == 1) && y && body && dj && dy && Rw && B > 0 && F > 0);
+  MMEGO_REQUIRE((dRw != nullptr) == (dtw != nullptr) && (!dRw || joints_h) && (dRw || (!dR_add && !dt_add)));
+  if (which == 0) hipLaunchKernelGGL(head_fk_bwd_extra_kernel<0>, dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw, dR_add, dt_add);
+  else hipLaunchKernelGGL(head_fk_bwd_extra_kernel<1>, dim3(cdiv(F, 64)), dim3(64), 0, (hipStream_t)stream, y, body, B, F, dj, dy, Rw, joints_h, dRw, dtw, dR_add, dt_add);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }

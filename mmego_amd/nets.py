@@ -425,9 +425,11 @@ class UpperNet(_NetBase):
             self._saved = (B, T, N, R, body, c0, attn)
         return l, q, attn, hn, cn
 
-    def _backward_impl(self, dl, dl_extra=None):
+    def _backward_impl(self, dl, dl_extra=None, pose_add=None):
         """dl_extra (optional, [F,15,3]): a second gradient with respect to the predicted joints, added to dl's (the joint stage-3 step:
-        Lower_Net's d upper_l beside this net's own loss gradient; no head pose gradients then)."""
+        Lower_Net's d upper_l beside this net's own loss gradient).  Behind a pose_grad forward the head pose's gradients cover both.
+        pose_add (optional, (dR [F,3,3], dt [F,3]); needs dl_extra and a pose_grad forward): somebody else's gradients with respect to the
+        same head pose (the three-net step: Lower_Net's), added to pose_grads()."""
         ar = self.arena("train")
         B, T, N, R, body, c0, attn = self._saved
         F, rows = B * T, B * T * N
@@ -435,15 +437,20 @@ class UpperNet(_NetBase):
         y, h1 = ar.get("y", (F, 87)), ar.get("h1", (F, 128))
         dy = ar.get("dy", (F, 87))
         pose = getattr(self, "_pose", None)
+        if pose_add is not None and (dl_extra is None or pose is None):
+            raise ValueError("UpperNet: pose_add goes with dl_extra behind a pose_grad forward")
         if dl_extra is not None:
-            if pose is not None:
-                raise ValueError("UpperNet: dl_extra cannot be combined with pose_grad")
             if getattr(self, "_dy_ready", False):
-                # the fused loss launch has left the own loss's dy: the kinematics' backward is linear in its input gradient, so the
-                # second gradient's dy is added to it
-                dyx = ar.get("dy_extra", (F, 87))
-                hip.call("head_fk_backward", 0, y, body, B, F, _f32c(dl_extra), dyx, R)
-                ops.copy2d(dyx, dy, accumulate=True)
+                # the fused loss launch has left the own loss's dy (and its dR, dt): the kinematics' backward is linear in its input
+                # gradient, so the second gradient's dy is added to it
+                if pose is not None:
+                    # ... and its world-transform share of dR, dt, and pose_add, by the same launch
+                    hip.call("head_fk_backward_extra", 0, y, body, B, F, _f32c(dl_extra), dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3],
+                             *(pose_add if pose_add is not None else (None, None)))
+                else:
+                    dyx = ar.get("dy_extra", (F, 87))
+                    hip.call("head_fk_backward", 0, y, body, B, F, _f32c(dl_extra), dyx, R)
+                    ops.copy2d(dyx, dy, accumulate=True)
             else:
                 dls = ar.get("dl_sum", (F, 45))
                 ops.copy2d(_f32c(dl).view(F, 45), dls)
@@ -453,6 +460,9 @@ class UpperNet(_NetBase):
         if not getattr(self, "_dy_ready", False):
             if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
                 hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
+                if pose_add is not None:
+                    ops.copy2d(_f32c(pose_add[0]).view(F, 9), pose[2].view(F, 9), accumulate=True)
+                    ops.copy2d(_f32c(pose_add[1]).view(F, 3), pose[3].view(F, 3), accumulate=True)
             else:
                 hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
         dh1 = ar.get("dh1", (F, 128))

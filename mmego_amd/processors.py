@@ -66,8 +66,9 @@ class _Base:
         return "a" if getattr(self.cfg, "resume_path", None) else "w"     # --resume continues the logs instead of truncating them
 
     def _load_imu(self):
-        # (--finetune_imu: built without dropout -- same state_dict keys -- as in stage 1, unless --imu_dropout asks for a rate)
-        drop = (getattr(self.cfg, "imu_dropout", None) or 0) if getattr(self.cfg, "finetune_imu", False) else 0.1
+        # (--finetune_imu, --finetune_all: built without dropout -- same state_dict keys -- as in stage 1, unless --imu_dropout asks for a rate)
+        trained = getattr(self.cfg, "finetune_imu", False) or getattr(self.cfg, "finetune_all", False)
+        drop = (getattr(self.cfg, "imu_dropout", None) or 0) if trained else 0.1
         imu = IMUNet(15, 6 + 3, 512, 2, True, drop).to(self.device).eval()
         if self.cfg.gt_head_pose:
             print("[mmego_amd] head pose from the recording (R_R0R, ground-truth head joint); IMU_Net not used")
@@ -126,7 +127,7 @@ class _Base:
 
     def save_beside(self, epoch, folder, net):
         """A second trained net beside the stage's checkpoint, same file name, in a folder of its own (--finetune_imu: IMU_Net,
-        --finetune_upper: Upper_Net)."""
+        --finetune_upper: Upper_Net, --finetune_all: both)."""
         if self.rank != 0:
             return None
         folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), folder)
@@ -207,10 +208,16 @@ class _StageTrainer(_Base):
         super().__init__(Config)
         cfg = self.cfg
         self.num_epochs, self.save_slot, self.learning_rate = cfg.epochs, 50, cfg.lr
-        self.finetune_imu = bool(getattr(cfg, "finetune_imu", False))
-        if self.finetune_imu and (self.stage != "upper" or cfg.gt_head_pose or self.world > 1 or getattr(cfg, "resume_path", None)):
+        self.finetune_all = bool(getattr(cfg, "finetune_all", False))
+        if self.finetune_all and (self.stage != "lower" or cfg.gt_head_pose or self.world > 1 or getattr(cfg, "resume_path", None)
+                                  or getattr(cfg, "finetune_imu", False) or getattr(cfg, "finetune_upper", False)):
+            raise SystemExit("--finetune_all: Lower_Net stage with an IMU_Net checkpoint only, without --finetune_imu / --finetune_upper; not "
+                             "data parallel, not with --resume")
+        # (--finetune_all: the Lower stage with both options -- train_step.StageStep's three-net step)
+        self.finetune_imu = bool(getattr(cfg, "finetune_imu", False)) or self.finetune_all
+        if self.finetune_imu and not self.finetune_all and (self.stage != "upper" or cfg.gt_head_pose or self.world > 1 or getattr(cfg, "resume_path", None)):
             raise SystemExit("--finetune_imu: Upper_Net stage with an IMU_Net checkpoint only; not data parallel, not with --resume")
-        self.finetune_upper = bool(getattr(cfg, "finetune_upper", False))
+        self.finetune_upper = bool(getattr(cfg, "finetune_upper", False)) or self.finetune_all
         if self.finetune_upper and (self.stage != "lower" or self.world > 1 or getattr(cfg, "resume_path", None)):
             raise SystemExit("--finetune_upper: Lower_Net stage only; not data parallel, not with --resume")
         self.model_IMU = self._load_imu()
@@ -386,6 +393,9 @@ class LowerTrainer(_StageTrainer):
         if self.finetune_upper:
             self.Upper_net.eval()
             self.Upper_net.weights_changed()          # (the fused Adam writes through raw pointers: no derived copy of old weights)
+        if self.finetune_imu:                         # (--finetune_all)
+            self.model_IMU.eval()
+            self.model_IMU.weights_changed()
         return evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.test_data, self.batchsize, True, self._rng)[0]
 
 

@@ -234,6 +234,15 @@ class StageStep(_Engine):
     The sum of the two stages' own losses, because the final skeleton takes 13 of its 21 joints from Upper_Net: the lower loss alone must
     not be the only thing steering it.  One HIP graph.
 
+    ``finetune_upper`` AND ``finetune_imu`` (Lower stage): the three-net step.  IMU_Net training forward -> R, t -> Upper_Net train-mode
+    forward (own loss, pose_grad) -> Lower_Net train-mode forward on that prediction and the same R, t (input_grad upper_l + pose) ->
+    loss_lower + loss_upper; backward: Lower_Net leaves d upper_l, dR_L, dt_L; Upper_Net runs on its own loss gradient plus d upper_l and
+    leaves dR, dt = world transform of its own loss + world transform of d upper_l + Lower_Net's dR_L, dt_L (those three from ONE launch,
+    mmego_head_fk_backward_extra) + its head-frame transform; IMU_Net backward on that sum; three Adam steps (Lower_Net at ``lr``,
+    Upper_Net at ``upper_lr``, IMU_Net at ``imu_lr`` with stage 1's weight decay).  IMU_Net has no loss term of its own.  Lower_Net's
+    POINT input stays data: the points it gets were transformed once by Upper_Net in place (Q1), and that transform's dependence on R, t
+    is not differentiated (LowerNet.differentiable_inputs: "x gets none").  One HIP graph; not data parallel.
+
     ``clip_grad_norm`` (None: off): every optimiser this step builds -- ``opt``, ``imu_opt``, ``upper_opt`` -- clips ITS net's gradient
     to that global norm ahead of its update (FusedAdam(max_grad_norm=...)): one clip_grad_norm_ per optimiser, as the nets have separate
     optimisers and learning rates.  Data parallel, the all-reduce precedes ``opt.step()``: every rank clips the summed gradient by the
@@ -264,16 +273,18 @@ class StageStep(_Engine):
             if type(upper_frozen) is not UpperNet:
                 raise ValueError("StageStep: finetune_upper needs the Upper_Net to train as upper_frozen (a plain UpperNet; UpperNetwlocal "
                                  "is not supported)")
-            if self.finetune_imu:
-                raise ValueError("StageStep: finetune_upper cannot be combined with finetune_imu (the head pose is not trained in stage 3)")
+            if self.finetune_imu and (imu_net is None or pose is not None):
+                raise ValueError("StageStep: finetune_upper with finetune_imu (the three-net step) needs an IMU_Net of its own to train "
+                                 "(no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
                 raise ValueError("StageStep: finetune_upper is not data parallel yet (no all-reduce of the Upper_Net gradients)")
             self.upper_opt = opt_for("upper_opt", upper_frozen, lr if upper_lr is None else upper_lr, weight_decay)
         if self.finetune_imu:
             from .nets import UpperNet
-            if stage != "upper" or type(net) is not UpperNet:
+            if not self.finetune_upper and (stage != "upper" or type(net) is not UpperNet):
                 raise ValueError("StageStep: finetune_imu trains IMU_Net through Upper_Net's head-pose gradients; UpperNetwlocal produces "
-                                 "none, and Lower_Net's (LowerNet.input_grads) have no IMU_Net consumer yet")
+                                 "none, and Lower_Net's (LowerNet.input_grads) reach it through a trained Upper_Net only (finetune_upper "
+                                 "as well: the three-net step)")
             if imu_net is None or pose is not None:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
@@ -354,7 +365,8 @@ class StageStep(_Engine):
                 raise ValueError("StageStep: finetune_upper needs its Upper_Net in train mode (call .train() on it)")
             if self.finetune_upper or (via_transform and not upper.training):
                 # (trained: a train-mode forward that keeps its activations; frozen: the eval forward)
-                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=self.finetune_upper, x_src=x_src)[0]
+                pose_grad = {"pose_grad": True} if self.finetune_imu else {}      # (the three-net step: Upper_Net hands dR, dt to IMU_Net)
+                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=self.finetune_upper, x_src=x_src, **pose_grad)[0]
             else:
                 if via_transform:
                     ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
@@ -362,7 +374,10 @@ class StageStep(_Engine):
             if self.finetune_upper:
                 self._l1_fallback(upper, up, self.upper_jmap, 15, self.upper_loss2, s["dl_up"])
                 self.last_upper_pred = up
-            l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True, input_grad=("upper_l",) if self.finetune_upper else ())[0]
+            # (the three-net step: Lower_Net's own pose gradients as well -- its two head-frame transforms and its world transform; the
+            #  points it receives, transformed once by Upper_Net, stay data)
+            want = (("upper_l", "pose") if self.finetune_imu else ("upper_l",)) if self.finetune_upper else ()
+            l = self.net._forward_impl(up, s["x"], s["body"], R, t, stash=True, input_grad=want)[0]
             nsel = 8
         self._l1_fallback(self.net, l, self.jmap, nsel, self.loss2, s["dl"])
         self.last_pred = l
@@ -372,10 +387,12 @@ class StageStep(_Engine):
             self.net._backward_impl(self.static["dl"])
             if self.finetune_upper:
                 # d(loss_lower + loss_upper) / d(Upper_Net's joints): its own loss's share and Lower_Net's d upper_l
-                self.upper_frozen._backward_impl(self.static["dl_up"], dl_extra=self.net.input_grads()[0])
+                d_up, dR_l, dt_l = self.net.input_grads()
+                # (the three-net step: Lower_Net's dR, dt join Upper_Net's three shares there)
+                self.upper_frozen._backward_impl(self.static["dl_up"], dl_extra=d_up, pose_add=(dR_l, dt_l) if self.finetune_imu else None)
             if self.finetune_imu:
                 from . import imu_train
-                imu_train.backward(self.imu, *self.net.pose_grads())
+                imu_train.backward(self.imu, *(self.upper_frozen if self.finetune_upper else self.net).pose_grads())
 
     def bind(self, x, imu, body, target, R_gt=None):
         """Register the (device-resident) minibatch buffers; contents may be overwritten between steps."""
