@@ -12,7 +12,9 @@ available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam
 --imu_lr F] (stage 3 trains all three nets end to end on that sum: IMU_Net through Upper_Net's and Lower_Net's head-pose gradients),
 --imu_dropout P (the IMU_Net that is TRAINED -- stage 1, --finetune_imu or --finetune_all -- gets nn.LSTM(dropout=P) between its BiLSTM layers), --clip_grad_norm X (every
 trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
-"Grad norm" line per net and epoch; `inf` only measures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+"Grad norm" line per net and epoch; `inf` only measures), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
+UpperNetwlocal with the anchor branch -- the net trained by --train --network Upper_Net, the class the Upper checkpoint is loaded into by
+--train --network Lower_Net and --infer).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -71,7 +73,25 @@ def build_parser():
                    help="--train: clip every trained net's gradient to this global norm ahead of its Adam step (one clip_grad_norm_ per "
                         "optimiser, on the SUM-loss gradient of the global minibatch), skip a step whose gradient is not finite, and print "
                         "the norms once per epoch; `inf` measures without clipping (default: no clipping)")
+    p.add_argument("--upper_variant", type=str, choices=["global", "wlocal"], default=None,
+                   help="which net Upper_Net is: global (default: UpperNet) or wlocal (UpperNetwlocal, with the anchor branch).  --train "
+                        "--network Upper_Net trains it (with --finetune_imu, --imu_lr, --imu_dropout, --clip_grad_norm, --resume and "
+                        "--gt_head_pose as for global); --train --network Lower_Net and --infer load the Upper checkpoint into it.  wlocal "
+                        "stays frozen in stage 3: not with --finetune_upper / --finetune_all")
     return p
+
+
+def check_upper_variant(parser, args):
+    """--upper_variant names the Upper net of a run that has one; the options that train it in stage 3 know the plain UpperNet only."""
+    if args.upper_variant is None:
+        return
+    if args.train and args.network == "IMU_Net":
+        parser.error("--upper_variant does not go with --network IMU_Net: stage 1 runs no Upper_Net")
+    if args.upper_variant == "wlocal":
+        for flag in ("finetune_upper", "finetune_all"):
+            if getattr(args, flag):
+                parser.error("--upper_variant wlocal cannot be combined with --%s: stage 3 trains a plain UpperNet only (UpperNetwlocal "
+                             "stays frozen there)" % flag)
 
 
 def check_clip_grad_norm(parser, args):
@@ -130,6 +150,7 @@ def check_finetune_all(parser, args, world):
 
 def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
+    check_upper_variant(parser, args)
     check_finetune_all(parser, args, world)
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
@@ -177,6 +198,8 @@ def apply_overrides(args):
     Config.upper_lr = args.upper_lr
     Config.finetune_all = bool(args.finetune_all)
     Config.clip_grad_norm = args.clip_grad_norm
+    for c in both:
+        c.upper_variant = args.upper_variant or "global"
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

@@ -50,6 +50,7 @@ class _Common:
     finetune_all = False        # --finetune_all: stage 3 trains IMU_Net, Upper_Net and Lower_Net together (train_step.StageStep)
     upper_lr = None             # --upper_lr: its learning rate (None: lr)
     imu_dropout = None          # --imu_dropout: nn.LSTM(dropout=P) of the IMU_Net that is trained (None: 0, as the reference's stage 1)
+    upper_variant = "global"    # --upper_variant: the class behind "Upper_Net" -- "global" (UpperNet) or "wlocal" (UpperNetwlocal, anchor branch)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
 
 

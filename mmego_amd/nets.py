@@ -153,6 +153,41 @@ class _NetBase(nn.Module):
         else:
             hip.call("head_fk_forward", which, y, body, B, F, q, jh, R, t, l, *tick)
 
+    # -- head-pose gradients of the Upper nets (UpperNet, nets_local.UpperNetwlocal): the head-frame transform in front ----------------
+    _pose = None          # (raw, t, dR, dt) behind a pose_grad forward: the untransformed points, the translation, the gradients' arena buffers
+
+    def pose_grads(self):
+        """(dR [F,3,3], dt [F,3]) of the last backward behind a pose_grad forward: arena buffers, rewritten by the next one."""
+        if getattr(self, "_pose", None) is None:
+            raise RuntimeError("%s.pose_grads: the last forward did not ask for the head pose's gradients" % type(self).__name__)
+        return self._pose[2], self._pose[3]
+
+    def _pose_begin(self, ar, x, x_src, t, pose_grad, stash):
+        """Start of a forward that transforms x [B,T,N,Cx] into the head frame in place: without pose_grad nothing is kept and nothing
+        launched.  With it: the UNTRANSFORMED points (x_src when given -- the caller leaves it alone until backward has run -- else a copy
+        taken here, ahead of the transform) and the arena buffers dR, dt that _backward_impl fills."""
+        self._pose = None
+        if not pose_grad:
+            return
+        if not stash:
+            raise ValueError("%s: pose_grad needs a forward that keeps its activations (stash=True)" % type(self).__name__)
+        B, T, N, Cx = x.shape
+        F, rows = B * T, B * T * N
+        if x_src is not None:
+            raw = x_src.view(rows, Cx)
+        else:
+            raw = ar.get("pts_raw", (rows, Cx))
+            ops.copy2d(x.view(rows, Cx), raw)
+        self._pose = (raw, t, ar.get("dR", (F, 3, 3)), ar.get("dt", (F, 3)))
+
+    def _pose_head_share(self, F, N, R, dfeats, dpts):
+        """End of such a net's backward: the head-frame transform's share of dR, dt, ADDED to the world transform's (which the kinematics
+        launch has left in the buffers).  The transformed xyz feed PointNet's first layer (dpts) and the first columns of the per-point
+        feature rows (dfeats: GlobalPointNet's input and, in UpperNetwlocal, the grouped rows' offsets xyz - anchor, whose gradient the
+        anchor scatter has added there); range, velocity and intensity do not depend on the pose."""
+        raw, t, dR, dt = self._pose
+        hip.call("transform2h_backward", raw, raw.stride(0), F, N, R, t, dfeats, dfeats.stride(0), dpts, dpts.stride(0), 1, dR, dt)
+
     def _drop_p(self, lstm):
         if not self.training:
             return 0.0
@@ -212,18 +247,19 @@ def _refuse_pose_grad(who, **named):
     bad = [k for k, v in named.items() if isinstance(v, torch.Tensor) and v.requires_grad]
     if bad and torch.is_grad_enabled():
         raise NotImplementedError("%s: %s require%s grad, but this net's backward produces no input gradients (UpperNet differentiates "
-                                  "its head pose R, t; LowerNet its upper_l, R, t once differentiable_inputs = True); detach them"
+                                  "its head pose R, t; LowerNet its upper_l, R, t and UpperNetwlocal its R, t once "
+                                  "differentiable_inputs = True); detach them"
                                   % (who, ", ".join(bad), "s" if len(bad) == 1 else ""))
 
 
 class _PoseBridge(torch.autograd.Function):
-    """_Bridge of UpperNet with the head pose as differentiable inputs: backward returns dR, dt beside the parameter gradients."""
+    """_Bridge of UpperNet (and of UpperNetwlocal with differentiable_inputs) with the head pose as differentiable inputs: backward returns
+    dR, dt beside the parameter gradients.  ``args``: the forward's arguments in front of R, t."""
 
     @staticmethod
     def forward(ctx, net, args, R, t, *params):
         ctx.net = net
-        x, h0, c0, body = args
-        outs = net._forward_impl(x, h0, c0, body, R, t, pose_grad=True)
+        outs = net._forward_impl(*args, R, t, pose_grad=True)
         ctx.mark_non_differentiable(*outs[1:])
         ctx.like = [(v.shape, v.dtype) for v in (R, t)]
         return outs
@@ -317,12 +353,6 @@ class UpperNet(_NetBase):
             return _Bridge.apply(self, 1, args, *self._flat.params)
         return self._forward_impl(*args, stash=False)
 
-    def pose_grads(self):
-        """(dR [F,3,3], dt [F,3]) of the last backward behind a pose_grad forward: arena buffers, rewritten by the next one."""
-        if getattr(self, "_pose", None) is None:
-            raise RuntimeError("UpperNet.pose_grads: the last forward did not ask for the head pose's gradients")
-        return self._pose[2], self._pose[3]
-
     # -- pipelines ---------------------------------------------------------------------------------
     def _forward_impl(self, x, h0, c0, body, R, t, stash=True, x_src=None, pose_grad=False):
         """x_src (optional, x's shape): the minibatch is read from there and x receives the transformed copy (one launch for a
@@ -343,16 +373,7 @@ class UpperNet(_NetBase):
         c0 = _f32c(c0) if c0 is not None else None
         vec = ar.get("vec", (F, 64))
         attn = torch.empty((F, N, 1), dtype=torch.float32, device=x.device)
-        self._pose = None
-        if pose_grad:
-            if not stash:
-                raise ValueError("UpperNet: pose_grad needs a forward that keeps its activations (stash=True)")
-            if x_src is not None:
-                raw = x_src.view(rows, Cx)
-            else:
-                raw = ar.get("pts_raw", (rows, Cx))
-                ops.copy2d(x.view(rows, Cx), raw)
-            self._pose = (raw, t, ar.get("dR", (F, 3, 3)), ar.get("dt", (F, 3)))
+        self._pose_begin(ar, x, x_src, t, pose_grad, stash)
         if not training and not stash and self._front_fusable(Cx, N):
             # eval mode: transform, PointNet, concat, GlobalPointNet and the attention pooling as ONE launch (front.hip); the
             # per-point 28- / 64-channel tensors never exist in memory
@@ -489,10 +510,7 @@ class UpperNet(_NetBase):
             pts = ar.get("pts", (rows, 6))
             dpts = blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, pose is not None)
         if pose is not None:
-            # the head-frame transform's share, added to the world transform's: the transformed xyz feed PointNet's first layer (dpts)
-            # and the first columns of GlobalPointNet's input (dfeats); range, velocity and intensity do not depend on the pose
-            raw, t, dR, dt = pose
-            hip.call("transform2h_backward", raw, raw.stride(0), F, N, R, t, dfeats, dfeats.stride(0), dpts, dpts.stride(0), 1, dR, dt)
+            self._pose_head_share(F, N, R, dfeats, dpts)
 
 
 # =====================================================================================================

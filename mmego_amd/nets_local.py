@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import blocks, hip, ops
 from .blocks import LstmParams
-from .nets import GlobalModule, PointNet, _Bridge, _Mlp3, _NetBase, _f32c, _refuse_pose_grad, _require_gpu
+from .nets import GlobalModule, PointNet, _Bridge, _Mlp3, _NetBase, _PoseBridge, _f32c, _pose_wants_grad, _refuse_pose_grad, _require_gpu
 
 N_ANCHOR, N_GROUP = 27, 8
 _LOCAL_FUSED = True      # the anchor branch on the fused kernels of local.hip
@@ -68,7 +68,13 @@ class CombineModule(nn.Module):
 
 class UpperNetwlocal(_NetBase):
     """forward(x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t) ->
-    (l, q, global_weights, anchor_weights, hn_g, cn_g, hn_a, cn_a).  MUTATES x (Q1)."""
+    (l, q, global_weights, anchor_weights, hn_g, cn_g, hn_a, cn_a).  MUTATES x (Q1).
+    differentiable_inputs (default False: an R or t that requires grad is refused): when True, such a head pose receives its gradients
+    from backward, as UpperNet's does -- the world transform behind the kinematics and the head-frame transform in front, whose xyz feed
+    PointNet, GlobalPointNet's input and the grouped rows' offsets xyz - anchor.  The group indices are a selection and carry none; x,
+    initial_body and the four states are not differentiable."""
+
+    differentiable_inputs = False
 
     def __init__(self):
         super().__init__()
@@ -115,24 +121,32 @@ class UpperNetwlocal(_NetBase):
 
     def forward(self, x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t):
         _require_gpu(x, "UpperNetwlocal")
-        _refuse_pose_grad("UpperNetwlocal", R=R, t=t)
         args = (x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t)
+        if not self.differentiable_inputs:
+            _refuse_pose_grad("UpperNetwlocal", R=R, t=t)
+        elif _pose_wants_grad(R, t):
+            self.flat()
+            return _PoseBridge.apply(self, args[:6], R, t, *self._flat.params)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self.flat()
             return _Bridge.apply(self, 1, args, *self._flat.params)
         return self._forward_impl(*args, stash=False)
 
-    def _forward_impl(self, x, h0g, c0g, h0a, c0a, body, R, t, stash=True, x_src=None):
+    def _forward_impl(self, x, h0g, c0g, h0a, c0a, body, R, t, stash=True, x_src=None, pose_grad=False):
+        """x_src, pose_grad: as in nets.UpperNet._forward_impl (pose_grads() behind the backward of a pose_grad forward)."""
         self.flat()
         training = self.training
         ar = self.arena("train" if stash else "eval")
         if not (x.dtype == torch.float32 and x.is_contiguous()):
             raise ValueError("UpperNetwlocal: x must be a contiguous fp32 tensor (it is transformed in place)")
+        if x_src is not None and not (x_src.dtype == torch.float32 and x_src.is_contiguous() and x_src.shape == x.shape):
+            raise ValueError("UpperNetwlocal: x_src must be a contiguous fp32 tensor of x's shape")
         B, T, N, Cx = x.shape
         F, rows = B * T, B * T * N
         dev = x.device
         R, t, body = _f32c(R), _f32c(t), _f32c(body)
         h0g, c0g, h0a, c0a = [_f32c(v) if v is not None else None for v in (h0g, c0g, h0a, c0a)]
+        self._pose_begin(ar, x, x_src, t, pose_grad, stash)
         feats = ar.get("feats", (rows, 28))
         keep = ar.get("pts", (rows, Cx)) if stash else None
         if Cx <= 8:
@@ -229,7 +243,9 @@ class UpperNetwlocal(_NetBase):
         jh = ar.get("jh", (F, 15, 3))
         l = torch.empty((B, T, 15, 3), dtype=torch.float32, device=dev)
         tick = self._flat.tick_args(self.seed_counter()) if training else (None, 0, None)   # BatchNorm counters + dropout seed
-        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash)    # kinematics + head-to-world transform (+ loss), one launch
+        pose = self._pose
+        # kinematics + head-to-world transform (+ loss, + the world transform's share of dR, dt), one launch
+        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash, pose=pose[2:] if pose is not None else None)
         if stash:
             self._saved = (B, T, N, R, body, c0g, c0a, gw, aw)
         return l, q, gw, aw, hn_g, cn_g, hn_a, cn_a
@@ -243,8 +259,12 @@ class UpperNetwlocal(_NetBase):
         dl = _f32c(dl)
         y, h1, cat = ar.get("y", (F, 87)), ar.get("h1", (F, 128)), ar.get("cat", (F, 256))
         dy = ar.get("dy", (F, 87))
+        pose = self._pose
         if not getattr(self, "_dy_ready", False):
-            hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
+            if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
+                hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
+            else:
+                hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
         dh1 = ar.get("dh1", (F, 128))
         blocks.linear_backward(dy, h1, self.module3.fc2, G, dh1, relu_input=True)
         dcat = ar.get("dcat", (F, 256))
@@ -302,4 +322,7 @@ class UpperNetwlocal(_NetBase):
                 dgrouped = blocks.mlp3_backward(ar, "lp", lp, grouped, l3, dl3, G, True)
                 hip.call("anchor_group_backward", dgrouped, gidx, F, N, 25, dfeats, 28)
             pts = ar.get("pts", (rows, 6))
-            blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, False)
+            dpts = blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, pose is not None)
+        if pose is not None:
+            # (dfeats[:, 0:3] holds GlobalPointNet's share and, added by the anchor scatter, the grouped rows' offset columns')
+            self._pose_head_share(F, N, R, dfeats, dpts)

@@ -20,12 +20,37 @@ from .config import Config, ConfigDemo
 from .data import DeviceArrays, PosePC, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam
-from .train_step import TRAINED, ImuStep, PipelinedStages, StageStep, broadcast_flag, empty_step, shard_of, sync_replicas
+from .nets_local import UpperNetwlocal
+from .train_step import TRAINED, ImuStep, PipelinedStages, StageStep, broadcast_flag, call_upper, empty_step, shard_of, sync_replicas
 from .utils import EarlyStopping
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # where report/, model/, lossAndacc/ go: the reference's Processor/Train (Train_Upper.py:22-50) unless MMEGO_TRAIN_DIR says otherwise
 _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_HERE), "Processor", "Train")
+
+
+UPPER_VARIANTS = {"global": UpperNet, "wlocal": UpperNetwlocal}          # --upper_variant -> the class behind "Upper_Net"
+
+
+def upper_variant_of(state_dict):
+    """Which Upper net a state_dict belongs to, by its keys (the anchor branch and its combine head against the plain head); None: neither."""
+    keys = list(state_dict)
+    if any(k.startswith(("module2.", "module3.")) for k in keys):
+        return "wlocal"
+    if any(k.startswith("mlpHead.") for k in keys):
+        return "global"
+    return None
+
+
+def load_upper_state(net, state_dict, variant, source):
+    """load_state_dict for an Upper net built for --upper_variant ``variant``: a checkpoint of the other variant ends the run with a message
+    that names the flag instead of a list of mismatched keys."""
+    found = upper_variant_of(state_dict)
+    if found is not None and found != variant:
+        raise SystemExit("%s is an Upper_Net checkpoint of the %r variant (%s), but this run builds the %r variant (%s): pass "
+                         "--upper_variant %s, or a checkpoint of the %r variant"
+                         % (source, found, UPPER_VARIANTS[found].__name__, variant, UPPER_VARIANTS[variant].__name__, found, variant))
+    net.load_state_dict(state_dict)
 
 
 class _Base:
@@ -64,6 +89,20 @@ class _Base:
 
     def _log_mode(self):
         return "a" if getattr(self.cfg, "resume_path", None) else "w"     # --resume continues the logs instead of truncating them
+
+    def _upper_variant(self):
+        v = getattr(self.cfg, "upper_variant", None) or "global"
+        if v not in UPPER_VARIANTS:
+            raise SystemExit("--upper_variant: %r is not one of %s" % (v, ", ".join(sorted(UPPER_VARIANTS))))
+        return v
+
+    def _new_upper(self, path=None):
+        """The Upper net of --upper_variant on the device; ``path``: a checkpoint to load into it."""
+        v = self._upper_variant()
+        net = UPPER_VARIANTS[v]().to(self.device)
+        if path is not None:
+            load_upper_state(net, torch.load(path, map_location=self.device), v, path)
+        return net
 
     def _load_imu(self):
         # (--finetune_imu, --finetune_all: built without dropout -- same state_dict keys -- as in stage 1, unless --imu_dropout asks for a rate)
@@ -107,7 +146,10 @@ class _Base:
         if not path.endswith(".train_state.pth"):
             path = path[:-4] + ".train_state.pth"
         ts = torch.load(path, map_location="cpu", weights_only=False)
-        model.load_state_dict(ts["model"])
+        if isinstance(model, tuple(UPPER_VARIANTS.values())):
+            load_upper_state(model, ts["model"], self._upper_variant(), path)
+        else:
+            model.load_state_dict(ts["model"])
         model.seed_counter().copy_(ts["dropout_counter"])
         self._rng.set_state(ts["rng"])
         self.start_epoch = int(ts["epoch"])
@@ -220,6 +262,9 @@ class _StageTrainer(_Base):
         self.finetune_upper = bool(getattr(cfg, "finetune_upper", False)) or self.finetune_all
         if self.finetune_upper and (self.stage != "lower" or self.world > 1 or getattr(cfg, "resume_path", None)):
             raise SystemExit("--finetune_upper: Lower_Net stage only; not data parallel, not with --resume")
+        if self.finetune_upper and self._upper_variant() != "global":
+            raise SystemExit("--upper_variant wlocal: --finetune_upper / --finetune_all train a plain UpperNet only (UpperNetwlocal stays "
+                             "frozen in stage 3)")
         self.model_IMU = self._load_imu()
         self._opts = {}
         self.train_data = PosePC(batch_length=self.frame_no)
@@ -327,9 +372,7 @@ class UpperTrainer(_StageTrainer):
 
     def __init__(self):
         super().__init__()
-        self.model = UpperNet().to(self.device)
-        if self.cfg.Upper_pretrained:
-            self.model.load(self.cfg.model_upper_path)
+        self.model = self._new_upper(self.cfg.model_upper_path if self.cfg.Upper_pretrained else None)      # (--upper_variant)
         self._dp_start(self.model)
 
     def train_upper(self):
@@ -370,8 +413,7 @@ class LowerTrainer(_StageTrainer):
         self.model = LowerNet(hidden_dim=64).to(self.device)
         if self.cfg.Lower_pretrained:
             self.model.load(self.cfg.model_lower_path)
-        self.Upper_net = UpperNet().to(self.device).eval()
-        self.Upper_net.load(self.cfg.model_upper_path)
+        self.Upper_net = self._new_upper(self.cfg.model_upper_path).eval()      # (--upper_variant: the class the checkpoint is loaded into)
         self._dp_start(self.model)
 
     def train_lower(self):
@@ -427,7 +469,7 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
             h0, c0, E = scratch[key]
             tgt, body = b["target"], b["skl"]
             R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
-            up = upper_net(b["data"], h0, c0, body, R, t)[0]
+            up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]      # (an UpperNet or an UpperNetwlocal)
             if lower_net is None:
                 hip.call("pose_errors_upper", up.contiguous(), tgt, F, E)
                 ops.colsum(E, log[i])
@@ -462,8 +504,7 @@ class Evaluator(_Base):
         cfg = self.cfg
         self.model = LowerNet(hidden_dim=64).to(self.device).eval()
         self.model_IMU = self._load_imu()
-        self.Upper_net = UpperNet().to(self.device).eval()
-        self.Upper_net.load(cfg.model_upper_path)
+        self.Upper_net = self._new_upper(cfg.model_upper_path).eval()           # (--upper_variant)
         self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no)
 
     def eval_model(self):

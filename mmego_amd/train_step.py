@@ -128,6 +128,17 @@ def broadcast_flag(value, device, process_group, src=0):
     return bool(t.item() != 0.0)
 
 
+def call_upper(net, x, h0, c0, body, R, t, **impl):
+    """An Upper net of either kind on one zero-state pair: UpperNet takes it once, UpperNetwlocal a second time for its anchor branch
+    (Net/Upper_Net.py:406-432).  Without keywords the public call ``net(...)``; with them (stash, x_src, pose_grad) ``net._forward_impl``.
+    -> the net's output tuple; [0] is the 15 upper joints for both."""
+    from .nets_local import UpperNetwlocal
+    states = (h0, c0) * (2 if isinstance(net, UpperNetwlocal) else 1)
+    if impl:
+        return net._forward_impl(x, *states, body, R, t, **impl)
+    return net(x, *states, body, R, t)
+
+
 def needs_exclusive(nets):
     """True when one of the nets runs bf16-MFMA kernels (IMUNet.precision / train_precision, UpperNet / LowerNet.precision other than
     "fp32").  r06: a kernel that shares a CU with a bf16-MFMA workgroup of another kernel can compute wrong
@@ -224,7 +235,9 @@ class StageStep(_Engine):
     ``finetune_imu`` (Upper stage): the IMU_Net is trained too, through the pose loss -- Train_Upper.py:162 without its .detach().
     Per minibatch: IMU_Net training forward -> R, t -> Upper_Net forward + loss + backward, which now leaves d loss / d R and
     d loss / d t (UpperNet.pose_grads) -> IMU_Net backward -> two Adam steps (Upper_Net at ``lr``, IMU_Net at ``imu_lr`` with stage
-    1's weight decay).  The body is still one HIP graph.
+    1's weight decay).  The body is still one HIP graph.  The trained net is an UpperNet or an UpperNetwlocal.
+
+    ``upper_frozen`` (Lower stage): a frozen UpperNet or UpperNetwlocal (``call_upper``); the options that TRAIN it take an UpperNet only.
 
     ``finetune_upper`` (Lower stage): joint stage-3 training -- Train_Lower.py:195-196 without its .detach().  ``upper_frozen`` is then
     NOT frozen: per minibatch it runs a TRAIN-mode forward that keeps its activations, with its own L1(sum) loss on the 15 upper joints
@@ -281,10 +294,11 @@ class StageStep(_Engine):
             self.upper_opt = opt_for("upper_opt", upper_frozen, lr if upper_lr is None else upper_lr, weight_decay)
         if self.finetune_imu:
             from .nets import UpperNet
-            if not self.finetune_upper and (stage != "upper" or type(net) is not UpperNet):
-                raise ValueError("StageStep: finetune_imu trains IMU_Net through Upper_Net's head-pose gradients; UpperNetwlocal produces "
-                                 "none, and Lower_Net's (LowerNet.input_grads) reach it through a trained Upper_Net only (finetune_upper "
-                                 "as well: the three-net step)")
+            from .nets_local import UpperNetwlocal
+            if not self.finetune_upper and (stage != "upper" or type(net) not in (UpperNet, UpperNetwlocal)):
+                raise ValueError("StageStep: finetune_imu trains IMU_Net through the head-pose gradients of the Upper stage's net (UpperNet "
+                                 "or UpperNetwlocal); Lower_Net's (LowerNet.input_grads) reach it through a trained Upper_Net only "
+                                 "(finetune_upper as well: the three-net step)")
             if imu_net is None or pose is not None:
                 raise ValueError("StageStep: finetune_imu needs an IMU_Net of its own (no recorded or shared head pose)")
             if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
@@ -314,9 +328,9 @@ class StageStep(_Engine):
         B, T = s["x"].shape[0], s["x"].shape[1]
         from .nets import UpperNet
         first_net = self.net if self.stage == "upper" else self.upper_frozen
-        # fresh batch (x is transformed in place): Upper_Net's transform launch reads it from x_src; other nets get a copy first
+        # fresh batch (x is transformed in place): an Upper net's transform launch reads it from x_src; other nets get a copy first
         from .nets_local import UpperNetwlocal
-        via_transform = (type(first_net) is UpperNet or (self.stage == "upper" and type(first_net) is UpperNetwlocal)) and s["x"].shape[-1] <= 8
+        via_transform = type(first_net) in (UpperNet, UpperNetwlocal) and s["x"].shape[-1] <= 8
         # the trained net's kinematics launch takes the loss, its gradient and the first backward step along (nets._head_fk)
         self.net.loss_hook = (s["target"], self.jmap, self.loss2, 1.0)
         if self.finetune_upper:
@@ -353,11 +367,8 @@ class StageStep(_Engine):
         x_src = s["x_src"] if via_transform else None       # (without x_src the net keeps its own copy of the untransformed points)
         R, t = self._head_pose(s, B, T)
         if self.stage == "upper":
-            from .nets_local import UpperNetwlocal
-            # (Net/Upper_Net.py:406-432: UpperNetwlocal takes a second state pair for the anchor branch)
-            states = (s["h0"], s["c0"]) * (2 if isinstance(self.net, UpperNetwlocal) else 1)
             pose_grad = {"pose_grad": True} if self.finetune_imu else {}      # (only a trained IMU_Net consumes d loss / d R, d loss / d t)
-            l = self.net._forward_impl(s["x"], *states, s["body"], R, t, stash=True, x_src=x_src, **pose_grad)[0]
+            l = call_upper(self.net, s["x"], s["h0"], s["c0"], s["body"], R, t, stash=True, x_src=x_src, **pose_grad)[0]
             nsel = 15
         else:
             upper = self.upper_frozen
@@ -366,11 +377,11 @@ class StageStep(_Engine):
             if self.finetune_upper or (via_transform and not upper.training):
                 # (trained: a train-mode forward that keeps its activations; frozen: the eval forward)
                 pose_grad = {"pose_grad": True} if self.finetune_imu else {}      # (the three-net step: Upper_Net hands dR, dt to IMU_Net)
-                up = upper._forward_impl(s["x"], s["h0"], s["c0"], s["body"], R, t, stash=self.finetune_upper, x_src=x_src, **pose_grad)[0]
+                up = call_upper(upper, s["x"], s["h0"], s["c0"], s["body"], R, t, stash=self.finetune_upper, x_src=x_src, **pose_grad)[0]
             else:
                 if via_transform:
                     ops.copy2d(s["x_src"].view(B * T, -1), s["x"].view(B * T, -1))
-                up = upper(s["x"], s["h0"], s["c0"], s["body"], R, t)[0]
+                up = call_upper(upper, s["x"], s["h0"], s["c0"], s["body"], R, t)[0]
             if self.finetune_upper:
                 self._l1_fallback(upper, up, self.upper_jmap, 15, self.upper_loss2, s["dl_up"])
                 self.last_upper_pred = up
