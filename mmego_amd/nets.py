@@ -126,6 +126,23 @@ class _NetBase(nn.Module):
             self._seed = torch.tensor([0x9E3779B97F4A7C15 & 0x7FFFFFFFFFFFFFFF], dtype=torch.int64, device=dev)
         return self._seed
 
+    def _ptr_table(self, slot, tensors):
+        """Host-side int64 table of ``tensors``' device pointers (one kernel argument for all of them), kept under ``slot`` and rebuilt
+        when a tensor moved."""
+        ptrs = tuple(v.data_ptr() for v in tensors)
+        ent = self.__dict__.get(slot)
+        if ent is None or ent[0] != ptrs:
+            ent = self.__dict__[slot] = (ptrs, torch.tensor(ptrs, dtype=torch.int64))
+        return ent[1]
+
+    def _bridged(self, args):
+        """End of a public forward whose inputs want no gradient: through the autograd node when a parameter may want one, else the plain
+        pipeline that keeps nothing."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            self.flat()
+            return _Bridge.apply(self, 1, args, *self._flat.params)
+        return self._forward_impl(*args, stash=False)
+
     # -- kinematics head, optionally with the trainer's loss and the start of backward in the same launch ----------------
     loss_hook = None      # (target [B,T,21,3], joint map int32, loss buffer [2], scale): set by train_step.StageStep around a step
 
@@ -152,6 +169,17 @@ class _NetBase(nn.Module):
             self._dy_ready = True
         else:
             hip.call("head_fk_forward", which, y, body, B, F, q, jh, R, t, l, *tick)
+
+    def _head_fk_backward(self, ar, which, y, body, B, F, dl, dy, R, jh_shape, pose, second=False):
+        """Start of every backward, _head_fk's companion: the kinematics' backward dl -> dy (world -> head frame inside the kernel) -- unless
+        the fused loss launch has left dy already.  pose = (dR, dt): ... and the world transform's share of the head pose's gradients
+        (which that launch has left as well).  second: a gradient of its own BEHIND the fused launch's, so launched all the same."""
+        if getattr(self, "_dy_ready", False) and not second:
+            return
+        if pose is not None:
+            hip.call("head_fk_backward_pose", which, y, body, B, F, dl, dy, R, ar.get("jh", jh_shape), *pose)
+        else:
+            hip.call("head_fk_backward", which, y, body, B, F, dl, dy, R)
 
     # -- head-pose gradients of the Upper nets (UpperNet, nets_local.UpperNetwlocal): the head-frame transform in front ----------------
     _pose = None          # (raw, t, dR, dt) behind a pose_grad forward: the untransformed points, the translation, the gradients' arena buffers
@@ -181,10 +209,12 @@ class _NetBase(nn.Module):
         self._pose = (raw, t, ar.get("dR", (F, 3, 3)), ar.get("dt", (F, 3)))
 
     def _pose_head_share(self, F, N, R, dfeats, dpts):
-        """End of such a net's backward: the head-frame transform's share of dR, dt, ADDED to the world transform's (which the kinematics
-        launch has left in the buffers).  The transformed xyz feed PointNet's first layer (dpts) and the first columns of the per-point
+        """End of such a net's backward behind a pose_grad forward (nothing otherwise): the head-frame transform's share of dR, dt, ADDED
+        to the world transform's (which the kinematics launch has left in the buffers).  The transformed xyz feed PointNet's first layer (dpts) and the first columns of the per-point
         feature rows (dfeats: GlobalPointNet's input and, in UpperNetwlocal, the grouped rows' offsets xyz - anchor, whose gradient the
         anchor scatter has added there); range, velocity and intensity do not depend on the pose."""
+        if self._pose is None:
+            return
         raw, t, dR, dt = self._pose
         hip.call("transform2h_backward", raw, raw.stride(0), F, N, R, t, dfeats, dfeats.stride(0), dpts, dpts.stride(0), 1, dR, dt)
 
@@ -330,56 +360,42 @@ class MLPHead(nn.Module):
         self.fc2 = nn.Linear(128, 14 * 6 + 3)
 
 
-class UpperNet(_NetBase):
-    """forward(x[B,T,N,6], h0_g[6,B,64], c0_g[6,B,64], initial_body[B,20,3], R[B,T,3,3], t[B,T,3])
-    -> (l[B,T,15,3], q[B,T,14,3,3], global_weights[B*T,N,1], hn_g, cn_g).  MUTATES x (Q1).
-    R, t that require grad receive their gradients from backward (both transforms: head frame in front, world frame behind);
-    x, initial_body, h0_g, c0_g are not differentiable."""
+class _UpperBase(_NetBase):
+    """The spine of both Upper nets (UpperNet below, nets_local.UpperNetwlocal): PointNet and the global branch in front -- checked,
+    transformed into the head frame, stashed --, the two-layer head with the kinematics behind whatever sequence model(s) the net has,
+    and the same three pieces backward.  The nets keep their sequence models, their `_saved`, the anchor branch and the ORDER of their
+    backward's launches: the pieces below defer nothing and open no dw_reduce_group themselves."""
+
+    state_pairs = 1       # (h0, c0) pairs in the forward's signature: train_step.call_upper hands one zero pair to each
 
     def __init__(self):
         super().__init__()
-        self.module0 = PointNet()
+        self.module0 = PointNet()                 # (these two first: the subclasses' modules register behind them -- state_dict keys, flat layout)
         self.module1 = GlobalModule()
-        self.mlpHead = MLPHead()
 
-    def forward(self, x, h0_g, c0_g, initial_body, R, t):
-        _require_gpu(x, "UpperNet")
-        args = (x, h0_g, c0_g, initial_body, R, t)
-        if _pose_wants_grad(R, t):
-            self.flat()
-            return _PoseBridge.apply(self, args[:4], R, t, *self._flat.params)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self.flat()
-            return _Bridge.apply(self, 1, args, *self._flat.params)
-        return self._forward_impl(*args, stash=False)
+    def _front_one_launch(self, x, x_src, R, t, vec, attn):
+        """A net's own form of the whole front as one launch, when it has one for this call: True when it ran."""
+        return False
 
-    # -- pipelines ---------------------------------------------------------------------------------
-    def _forward_impl(self, x, h0, c0, body, R, t, stash=True, x_src=None, pose_grad=False):
-        """x_src (optional, x's shape): the minibatch is read from there and x receives the transformed copy (one launch for a
-        trainer's 'fresh batch' copy and the transform).
-        pose_grad: _backward_impl also forms d loss / d R and d loss / d t (pose_grads()).  The head-frame transform's share needs
-        the UNTRANSFORMED points: x_src when given (the caller leaves it alone until backward has run), else a copy taken here."""
-        self.flat()
-        training = self.training
-        ar = self.arena("train" if stash else "eval")
+    def _front(self, ar, x, x_src, R, t, stash, pose_grad):
+        """x [B,T,N,Cx] into the head frame in place (Q1), PointNet, GlobalPointNet, attention pooling over the points.
+        x_src (optional, x's shape): the minibatch is read from there and x receives the transformed copy (one launch for a trainer's
+        'fresh batch' copy and the transform).  pose_grad: see _pose_begin.
+        -> (feats [rows,28] -- None behind _front_one_launch --, vec [F,64], attention weights [F,N,1], R, t as contiguous fp32)."""
+        who = type(self).__name__
         if not (x.dtype == torch.float32 and x.is_contiguous()):
-            raise ValueError("UpperNet: x must be a contiguous fp32 tensor (it is transformed in place)")
+            raise ValueError("%s: x must be a contiguous fp32 tensor (it is transformed in place)" % who)
         if x_src is not None and not (x_src.dtype == torch.float32 and x_src.is_contiguous() and x_src.shape == x.shape):
-            raise ValueError("UpperNet: x_src must be a contiguous fp32 tensor of x's shape")
+            raise ValueError("%s: x_src must be a contiguous fp32 tensor of x's shape" % who)
+        training = self.training
         B, T, N, Cx = x.shape
         F, rows = B * T, B * T * N
-        R, t, body = _f32c(R), _f32c(t), _f32c(body)
-        h0 = _f32c(h0) if h0 is not None else None
-        c0 = _f32c(c0) if c0 is not None else None
+        R, t = _f32c(R), _f32c(t)
         vec = ar.get("vec", (F, 64))
         attn = torch.empty((F, N, 1), dtype=torch.float32, device=x.device)
         self._pose_begin(ar, x, x_src, t, pose_grad, stash)
-        if not training and not stash and self._front_fusable(Cx, N):
-            # eval mode: transform, PointNet, concat, GlobalPointNet and the attention pooling as ONE launch (front.hip); the
-            # per-point 28- / 64-channel tensors never exist in memory
-            hip.call("upper_front_eval_bf16" if self._bf16_eval(training) else "upper_front_eval", x, x_src, R, t, F, N, self._front_table(),
-                     float(self.module0.cb1.eps), vec, attn)
-            return self._forward_tail(ar, vec, attn, B, T, N, h0, c0, body, R, t, stash, training)
+        if not stash and self._front_one_launch(x, x_src, R, t, vec, attn):
+            return None, vec, attn, R, t          # (feats, pts, g3 are not taken from the arena)
         feats = ar.get("feats", (rows, 28))
         keep = ar.get("pts", (rows, Cx)) if stash else None
         if Cx <= 8:
@@ -405,7 +421,89 @@ class UpperNet(_NetBase):
         else:
             blocks.mlp3_forward(ar, "gp", gpn, feats, g3, training)
             blocks.attn_pool_forward(g3, gpn.attn, F, N, 64, vec, attn)
-        return self._forward_tail(ar, vec, attn, B, T, N, h0, c0, body, R, t, stash, training)
+        return feats, vec, attn, R, t
+
+    def _head(self, ar, fc1, fc2, inp, body, B, T, R, t, stash):
+        """fc1 + ReLU, fc2, then kinematics + head-to-world transform (+ loss, + the world transform's share of dR, dt) as one launch
+        (Net/Upper_Net.py:393-404) -> (l [B,T,15,3], q [B,T,14,3,3])."""
+        F = B * T
+        h1 = ar.get("h1", (F, 128))
+        ops.linear(inp, fc1.weight, fc1.bias, h1, relu=True)
+        y = ar.get("y", (F, 87))
+        ops.linear(h1, fc2.weight, fc2.bias, y)
+        q = torch.empty((B, T, 14, 3, 3), dtype=torch.float32, device=inp.device)
+        jh = ar.get("jh", (F, 15, 3))
+        l = torch.empty((B, T, 15, 3), dtype=torch.float32, device=inp.device)
+        tick = self._flat.tick_args(self.seed_counter()) if self.training else (None, 0, None)   # BatchNorm counters + dropout seed
+        pose = self._pose
+        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash, pose=pose[2:] if pose is not None else None)
+        return l, q
+
+    def _head_backward(self, ar, fc1, fc2, inp, dinp, F, G, leaves=None):
+        """dy -> d ``inp`` through fc2, the ReLU and fc1; the weight gradients at once or, with ``leaves``, when the caller runs those."""
+        dh1 = ar.get("dh1", (F, 128))
+        blocks.linear_backward(ar.get("dy", (F, 87)), ar.get("h1", (F, 128)), fc2, G, dh1, relu_input=True, leaves=leaves)
+        blocks.linear_backward(dh1, inp, fc1, G, dinp, leaves=leaves)
+
+    def _global_backward(self, ar, F, N, attn, dvec, G):
+        """The global branch behind d vec: attention pooling and GlobalPointNet, inside the pooled chain's launches or as the launch
+        chain, whichever the forward ran -> d feats [rows,28]."""
+        rows = F * N
+        g3, dg3 = ar.get("g3", (rows, 64)), ar.get("dg3", (rows, 64))
+        feats = ar.get("feats", (rows, 28))
+        gpn = self.module1.gpointnet
+        if getattr(self, "_gpool_fused", False):
+            blocks.pool128_backward_fused(ar, "gp", gpn, gpn.attn, attn, ar.get("vec", (F, 64)), dvec, rows, dg3, G)
+            return blocks._mlp3_backward_fused(ar, "gp", gpn, feats, dg3, G, True, have_sums=True)
+        blocks.attn_pool_backward(ar, "gpool", g3, gpn.attn, attn, dvec, F, N, 64, dg3, G)
+        return blocks.mlp3_backward(ar, "gp", gpn, feats, g3, dg3, G, True)
+
+    def _pointnet_backward(self, ar, F, N, dfeats, G):
+        """PointNet behind its columns of d feats -> d pts, formed only for a differentiable head pose (_pose_head_share takes it, behind
+        the caller's dw_reduce_group)."""
+        rows = F * N
+        feats = ar.get("feats", (rows, 28))
+        return blocks.mlp3_backward(ar, "m0", self.module0, ar.get("pts", (rows, 6)), feats[:, 4:28], dfeats[:, 4:28], G, self._pose is not None)
+
+
+class UpperNet(_UpperBase):
+    """forward(x[B,T,N,6], h0_g[6,B,64], c0_g[6,B,64], initial_body[B,20,3], R[B,T,3,3], t[B,T,3])
+    -> (l[B,T,15,3], q[B,T,14,3,3], global_weights[B*T,N,1], hn_g, cn_g).  MUTATES x (Q1).
+    R, t that require grad receive their gradients from backward (both transforms: head frame in front, world frame behind);
+    x, initial_body, h0_g, c0_g are not differentiable."""
+
+    def __init__(self):
+        super().__init__()
+        self.mlpHead = MLPHead()
+
+    def forward(self, x, h0_g, c0_g, initial_body, R, t):
+        _require_gpu(x, "UpperNet")
+        args = (x, h0_g, c0_g, initial_body, R, t)
+        if _pose_wants_grad(R, t):
+            self.flat()
+            return _PoseBridge.apply(self, args[:4], R, t, *self._flat.params)
+        return self._bridged(args)
+
+    # -- pipelines ---------------------------------------------------------------------------------
+    def _forward_impl(self, x, h0, c0, body, R, t, stash=True, x_src=None, pose_grad=False):
+        """x_src, pose_grad: _UpperBase._front.  pose_grad: _backward_impl also forms d loss / d R and d loss / d t (pose_grads()); the
+        head-frame transform's share needs the UNTRANSFORMED points: x_src when given (the caller leaves it alone until backward has
+        run), else a copy taken here."""
+        self.flat()
+        ar = self.arena("train" if stash else "eval")
+        feats, vec, attn, R, t = self._front(ar, x, x_src, R, t, stash, pose_grad)
+        B, T, N, _ = x.shape
+        body = _f32c(body)
+        h0 = _f32c(h0) if h0 is not None else None
+        c0 = _f32c(c0) if c0 is not None else None
+        # sequence model, head and kinematics behind the per-frame feature vector (Net/Upper_Net.py:333-364,393-404)
+        lstm = self.module1.grnn
+        seq, hn, cn = blocks.lstm64_forward(ar, "grnn", lstm, vec, B, T, h0, c0, stash, self._drop_p(lstm) if stash else 0.0,
+                                            self.seed_counter())
+        l, q = self._head(ar, self.mlpHead.fc1, self.mlpHead.fc2, seq, body, B, T, R, t, stash)
+        if stash:
+            self._saved = (B, T, N, R, body, c0, attn)
+        return l, q, attn, hn, cn
 
     def _front_fusable(self, Cx, N):
         layers = blocks._mlp3_layers(self.module0) + blocks._mlp3_layers(self.module1.gpointnet)
@@ -415,36 +513,20 @@ class UpperNet(_NetBase):
                 and all(conv.bias is not None for conv, _ in layers) and self.module1.gpointnet.attn.bias is not None)
 
     def _front_table(self):
-        """Host-side pointer table of mmego_upper_front_eval (38 device pointers), rebuilt when a tensor moved."""
+        """Host-side pointer table of mmego_upper_front_eval (38 device pointers)."""
         layers = blocks._mlp3_layers(self.module0) + blocks._mlp3_layers(self.module1.gpointnet)
         ts = [v for conv, bn in layers for v in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        ts += [self.module1.gpointnet.attn.weight, self.module1.gpointnet.attn.bias]
-        ptrs = tuple(v.data_ptr() for v in ts)
-        ent = self.__dict__.get("_front_tab")
-        if ent is None or ent[0] != ptrs:
-            ent = self.__dict__["_front_tab"] = (ptrs, torch.tensor(ptrs, dtype=torch.int64))
-        return ent[1]
+        return self._ptr_table("_front_tab", ts + [self.module1.gpointnet.attn.weight, self.module1.gpointnet.attn.bias])
 
-    def _forward_tail(self, ar, vec, attn, B, T, N, h0, c0, body, R, t, stash, training):
-        """Sequence model, head and kinematics behind the per-frame feature vector (Net/Upper_Net.py:333-364,393-404)."""
-        F = B * T
-        lstm = self.module1.grnn
-        seq, hn, cn = blocks.lstm64_forward(ar, "grnn", lstm, vec, B, T, h0, c0, stash, self._drop_p(lstm) if stash else 0.0,
-                                            self.seed_counter())
-        h1 = ar.get("h1", (F, 128))
-        ops.linear(seq, self.mlpHead.fc1.weight, self.mlpHead.fc1.bias, h1, relu=True)
-        y = ar.get("y", (F, 87))
-        ops.linear(h1, self.mlpHead.fc2.weight, self.mlpHead.fc2.bias, y)
-        q = torch.empty((B, T, 14, 3, 3), dtype=torch.float32, device=vec.device)
-        jh = ar.get("jh", (F, 15, 3))
-        l = torch.empty((B, T, 15, 3), dtype=torch.float32, device=vec.device)
-        tick = self._flat.tick_args(self.seed_counter()) if training else (None, 0, None)   # BatchNorm counters + dropout seed
-        pose = getattr(self, "_pose", None)
-        # kinematics + head-to-world transform (+ loss), one launch
-        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash, pose=pose[2:] if (stash and pose is not None) else None)
-        if stash:
-            self._saved = (B, T, N, R, body, c0, attn)
-        return l, q, attn, hn, cn
+    def _front_one_launch(self, x, x_src, R, t, vec, attn):
+        """eval mode: transform, PointNet, concat, GlobalPointNet and the attention pooling as ONE launch (front.hip); the per-point
+        28- / 64-channel tensors never exist in memory."""
+        B, T, N, Cx = x.shape
+        if self.training or not self._front_fusable(Cx, N):
+            return False
+        hip.call("upper_front_eval_bf16" if self._bf16_eval(False) else "upper_front_eval", x, x_src, R, t, B * T, N, self._front_table(),
+                 float(self.module0.cb1.eps), vec, attn)
+        return True
 
     def _backward_impl(self, dl, dl_extra=None, pose_add=None):
         """dl_extra (optional, [F,15,3]): a second gradient with respect to the predicted joints, added to dl's (the joint stage-3 step:
@@ -453,15 +535,15 @@ class UpperNet(_NetBase):
         same head pose (the three-net step: Lower_Net's), added to pose_grads()."""
         ar = self.arena("train")
         B, T, N, R, body, c0, attn = self._saved
-        F, rows = B * T, B * T * N
+        F = B * T
         G = self._flat.grad
-        y, h1 = ar.get("y", (F, 87)), ar.get("h1", (F, 128))
-        dy = ar.get("dy", (F, 87))
-        pose = getattr(self, "_pose", None)
+        y, dy = ar.get("y", (F, 87)), ar.get("dy", (F, 87))
+        pose = self._pose
+        ready = getattr(self, "_dy_ready", False)
         if pose_add is not None and (dl_extra is None or pose is None):
             raise ValueError("UpperNet: pose_add goes with dl_extra behind a pose_grad forward")
         if dl_extra is not None:
-            if getattr(self, "_dy_ready", False):
+            if ready:
                 # the fused loss launch has left the own loss's dy (and its dR, dt): the kinematics' backward is linear in its input
                 # gradient, so the second gradient's dy is added to it
                 if pose is not None:
@@ -470,7 +552,7 @@ class UpperNet(_NetBase):
                              *(pose_add if pose_add is not None else (None, None)))
                 else:
                     dyx = ar.get("dy_extra", (F, 87))
-                    hip.call("head_fk_backward", 0, y, body, B, F, _f32c(dl_extra), dyx, R)
+                    self._head_fk_backward(ar, 0, y, body, B, F, _f32c(dl_extra), dyx, R, (F, 15, 3), None, second=True)
                     ops.copy2d(dyx, dy, accumulate=True)
             else:
                 dls = ar.get("dl_sum", (F, 45))
@@ -478,39 +560,20 @@ class UpperNet(_NetBase):
                 ops.copy2d(_f32c(dl_extra).view(F, 45), dls, accumulate=True)
                 dl = dls
         dl = _f32c(dl) if dl is not None else None
-        if not getattr(self, "_dy_ready", False):
-            if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
-                hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
-                if pose_add is not None:
-                    ops.copy2d(_f32c(pose_add[0]).view(F, 9), pose[2].view(F, 9), accumulate=True)
-                    ops.copy2d(_f32c(pose_add[1]).view(F, 3), pose[3].view(F, 3), accumulate=True)
-            else:
-                hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
-        dh1 = ar.get("dh1", (F, 128))
+        self._head_fk_backward(ar, 0, y, body, B, F, dl, dy, R, (F, 15, 3), pose[2:] if pose is not None else None)
+        if pose_add is not None and not ready:
+            ops.copy2d(_f32c(pose_add[0]).view(F, 9), pose[2].view(F, 9), accumulate=True)
+            ops.copy2d(_f32c(pose_add[1]).view(F, 3), pose[3].view(F, 3), accumulate=True)
         leaves = []          # weight gradients of the head and of the BiLSTM stack: leaves, issued together behind the stack
-        blocks.linear_backward(dy, h1, self.mlpHead.fc2, G, dh1, relu_input=True, leaves=leaves)
-        seq = ar.get("grnn.out2", (F, 128))
         dseq = ar.get("dseq", (F, 128))
-        blocks.linear_backward(dh1, seq, self.mlpHead.fc1, G, dseq, leaves=leaves)
+        self._head_backward(ar, self.mlpHead.fc1, self.mlpHead.fc2, ar.get("grnn.out2", (F, 128)), dseq, F, G, leaves)
         lstm = self.module1.grnn
-        vec = ar.get("vec", (F, 64))
-        dvec = blocks.lstm64_backward(ar, "grnn", lstm, vec, B, T, c0, dseq, G, self._drop_p(lstm), True, leaves=leaves)
+        dvec = blocks.lstm64_backward(ar, "grnn", lstm, ar.get("vec", (F, 64)), B, T, c0, dseq, G, self._drop_p(lstm), True, leaves=leaves)
         blocks.run_leaves(leaves)
-        g3 = ar.get("g3", (rows, 64))
-        dg3 = ar.get("dg3", (rows, 64))
-        feats = ar.get("feats", (rows, 28))
-        gpn = self.module1.gpointnet
         with blocks.dw_reduce_group():                         # the two chains' weight-gradient partials: one reduce launch
-            if getattr(self, "_gpool_fused", False):
-                blocks.pool128_backward_fused(ar, "gp", gpn, gpn.attn, attn, vec, dvec, rows, dg3, G)
-                dfeats = blocks._mlp3_backward_fused(ar, "gp", gpn, feats, dg3, G, True, have_sums=True)
-            else:
-                blocks.attn_pool_backward(ar, "gpool", g3, gpn.attn, attn, dvec, F, N, 64, dg3, G)
-                dfeats = blocks.mlp3_backward(ar, "gp", gpn, feats, g3, dg3, G, True)
-            pts = ar.get("pts", (rows, 6))
-            dpts = blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, pose is not None)
-        if pose is not None:
-            self._pose_head_share(F, N, R, dfeats, dpts)
+            dfeats = self._global_backward(ar, F, N, attn, dvec, G)
+            dpts = self._pointnet_backward(ar, F, N, dfeats, G)
+        self._pose_head_share(F, N, R, dfeats, dpts)
 
 
 # =====================================================================================================
@@ -626,11 +689,7 @@ class LowerNet(_NetBase):
         elif _pose_wants_grad(upper_l, R, t):
             self.flat()
             return _InputBridge.apply(self, (x, initial_body, pin_select_idx), upper_l, R, t, *self._flat.params)
-        args = (upper_l, x, initial_body, R, t, pin_select_idx)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self.flat()
-            return _Bridge.apply(self, 1, args, *self._flat.params)
-        return self._forward_impl(*args, stash=False)
+        return self._bridged((upper_l, x, initial_body, R, t, pin_select_idx))
 
     def input_grads(self):
         """(d upper_l [F,15,3] | None, dR [F,3,3] | None, dt [F,3] | None) of the last backward behind an input_grad forward: arena
@@ -1006,11 +1065,7 @@ class LowerNet(_NetBase):
         dy = ar.get("dy", (F, 42))
         ig = getattr(self, "_ingrad", None)
         pose = ig is not None and ig["dR"] is not None
-        if not getattr(self, "_dy_ready", False):
-            if pose:                      # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
-                hip.call("head_fk_backward_pose", 1, y, body, B, F, dl, dy, R, ar.get("jh", (F, 8, 3)), ig["dR"], ig["dt"])
-            else:
-                hip.call("head_fk_backward", 1, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
+        self._head_fk_backward(ar, 1, y, body, B, F, dl, dy, R, (F, 8, 3), (ig["dR"], ig["dt"]) if pose else None)
         df1, df0, dcat = ar.get("df1", (F, 64)), ar.get("df0", (F, 128)), ar.get("dcat", (F, 173))
         leaves = []          # weight gradients of the fusion head and of the BiLSTM stack: leaves, issued together behind the stack
         blocks.linear_backward(dy, f1, fu.fc2, G, df1, relu_input=True, leaves=leaves)

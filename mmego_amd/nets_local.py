@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import blocks, hip, ops
 from .blocks import LstmParams
-from .nets import GlobalModule, PointNet, _Bridge, _Mlp3, _NetBase, _PoseBridge, _f32c, _pose_wants_grad, _refuse_pose_grad, _require_gpu
+from .nets import _Mlp3, _PoseBridge, _UpperBase, _f32c, _pose_wants_grad, _refuse_pose_grad, _require_gpu
 
 N_ANCHOR, N_GROUP = 27, 8
 _LOCAL_FUSED = True      # the anchor branch on the fused kernels of local.hip
@@ -66,7 +66,7 @@ class CombineModule(nn.Module):
         self.fc2 = nn.Linear(128, 14 * 6 + 3)
 
 
-class UpperNetwlocal(_NetBase):
+class UpperNetwlocal(_UpperBase):
     """forward(x, h0_g, c0_g, h0_a, c0_a, initial_body, R, t) ->
     (l, q, global_weights, anchor_weights, hn_g, cn_g, hn_a, cn_a).  MUTATES x (Q1).
     differentiable_inputs (default False: an R or t that requires grad is refused): when True, such a head pose receives its gradients
@@ -75,11 +75,10 @@ class UpperNetwlocal(_NetBase):
     initial_body and the four states are not differentiable."""
 
     differentiable_inputs = False
+    state_pairs = 2       # (the global and the anchor BiLSTM stack)
 
     def __init__(self):
         super().__init__()
-        self.module0 = PointNet()
-        self.module1 = GlobalModule()
         self.module2 = LocalModule()
         self.module3 = CombineModule()
         self._anchors = None
@@ -95,15 +94,11 @@ class UpperNetwlocal(_NetBase):
         return bool(_LOCAL_FUSED and N in (64, 128, 256) and dims == [(32, 31), (48, 32), (64, 48)] and lp.attn.weight.shape == (1, 64))
 
     def _local_table(self):
-        """Host-side pointer table of mmego_local_front_eval (20 device pointers), rebuilt when a tensor moved."""
+        """Host-side pointer table of mmego_local_front_eval (20 device pointers)."""
         lp = self.module2.apointnet
         ts = [v for conv, bn in ((lp.conv1, lp.cb1), (lp.conv2, lp.cb2), (lp.conv3, lp.cb3))
-              for v in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)] + [lp.attn.weight, lp.attn.bias]
-        ptrs = tuple(v.data_ptr() for v in ts)
-        ent = self.__dict__.get("_local_tab")
-        if ent is None or ent[0] != ptrs:
-            ent = self.__dict__["_local_tab"] = (ptrs, torch.tensor(ptrs, dtype=torch.int64))
-        return ent[1]
+              for v in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        return self._ptr_table("_local_tab", ts + [lp.attn.weight, lp.attn.bias])
 
     def local_branch_bytes(self, F, N):
         """HBM bytes per frame the anchor branch's activations move between launches in one training step (written once + read
@@ -127,54 +122,19 @@ class UpperNetwlocal(_NetBase):
         elif _pose_wants_grad(R, t):
             self.flat()
             return _PoseBridge.apply(self, args[:6], R, t, *self._flat.params)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self.flat()
-            return _Bridge.apply(self, 1, args, *self._flat.params)
-        return self._forward_impl(*args, stash=False)
+        return self._bridged(args)
 
     def _forward_impl(self, x, h0g, c0g, h0a, c0a, body, R, t, stash=True, x_src=None, pose_grad=False):
         """x_src, pose_grad: as in nets.UpperNet._forward_impl (pose_grads() behind the backward of a pose_grad forward)."""
         self.flat()
         training = self.training
         ar = self.arena("train" if stash else "eval")
-        if not (x.dtype == torch.float32 and x.is_contiguous()):
-            raise ValueError("UpperNetwlocal: x must be a contiguous fp32 tensor (it is transformed in place)")
-        if x_src is not None and not (x_src.dtype == torch.float32 and x_src.is_contiguous() and x_src.shape == x.shape):
-            raise ValueError("UpperNetwlocal: x_src must be a contiguous fp32 tensor of x's shape")
-        B, T, N, Cx = x.shape
-        F, rows = B * T, B * T * N
+        feats, vec, gw, R, t = self._front(ar, x, x_src, R, t, stash, pose_grad)          # PointNet and the global branch
+        B, T, N, _ = x.shape
+        F = B * T
         dev = x.device
-        R, t, body = _f32c(R), _f32c(t), _f32c(body)
+        body = _f32c(body)
         h0g, c0g, h0a, c0a = [_f32c(v) if v is not None else None for v in (h0g, c0g, h0a, c0a)]
-        self._pose_begin(ar, x, x_src, t, pose_grad, stash)
-        feats = ar.get("feats", (rows, 28))
-        keep = ar.get("pts", (rows, Cx)) if stash else None
-        if Cx <= 8:
-            # Q1: in place on the caller's tensor; the copy kept for backward and the xyz + intensity columns of the feature buffer leave
-            # from the same launch, and a trainer's fresh minibatch (x_src) enters through it (as in nets.UpperNet)
-            ops.transform2h_(x, R, t, src=x_src, keep=keep, feats=feats, nfeat=4)
-            pts = keep if stash else x.view(rows, Cx)
-        else:
-            if x_src is not None:
-                ops.copy2d(x_src.view(rows, Cx), x.view(rows, Cx))
-            ops.transform2h_(x, R, t)
-            pts = x.view(rows, Cx)
-            if stash:
-                ops.copy2d(pts, keep)
-                pts = keep
-            ops.copy2d(pts[:, :4], feats[:, :4])
-        blocks.mlp3_forward(ar, "m0", self.module0, pts, feats[:, 4:28], training)
-        # global branch
-        g3 = ar.get("g3", (rows, 64))
-        vec = ar.get("vec", (F, 64))
-        gw = torch.empty((F, N, 1), dtype=torch.float32, device=dev)
-        gpn = self.module1.gpointnet
-        self._gpool_fused = bool(stash and blocks.pool128_fusable(gpn, feats, N, training))
-        if self._gpool_fused:       # the pooling inside the chain's last launch: g3 (the activated rows) is never stored
-            blocks.mlp3_forward(ar, "gp", gpn, feats, g3, training, pool=(gpn.attn, vec, gw))
-        else:
-            blocks.mlp3_forward(ar, "gp", gpn, feats, g3, training)
-            blocks.attn_pool_forward(g3, gpn.attn, F, N, 64, vec, gw)
         p_g = self._drop_p(self.module1.grnn) if stash else 0.0
         cat = ar.get("cat", (F, 256))
         # local branch: grouping -> LocalPointNet (+attention pool over the 8 members) -> voxel net -> BiLSTM
@@ -234,18 +194,7 @@ class UpperNetwlocal(_NetBase):
             ar, [("grnn", self.module1.grnn, vec, h0g, c0g, p_g, self.seed_counter(), 0),
                  ("arnn", self.module2.arnn.rnn, vvec, h0a, c0a, p_a, self.seed_counter(), 1)], B, T, stash,
             last_out=(cat[:, :128], cat[:, 128:]))          # (the last layers write the two halves of the concatenation themselves)
-        # combine head
-        h1 = ar.get("h1", (F, 128))
-        ops.linear(cat, self.module3.fc1.weight, self.module3.fc1.bias, h1, relu=True)
-        y = ar.get("y", (F, 87))
-        ops.linear(h1, self.module3.fc2.weight, self.module3.fc2.bias, y)
-        q = torch.empty((B, T, 14, 3, 3), dtype=torch.float32, device=dev)
-        jh = ar.get("jh", (F, 15, 3))
-        l = torch.empty((B, T, 15, 3), dtype=torch.float32, device=dev)
-        tick = self._flat.tick_args(self.seed_counter()) if training else (None, 0, None)   # BatchNorm counters + dropout seed
-        pose = self._pose
-        # kinematics + head-to-world transform (+ loss, + the world transform's share of dR, dt), one launch
-        self._head_fk(ar, 0, y, body, B, F, q, jh, R, t, l, tick, stash, pose=pose[2:] if pose is not None else None)
+        l, q = self._head(ar, self.module3.fc1, self.module3.fc2, cat, body, B, T, R, t, stash)         # combine head
         if stash:
             self._saved = (B, T, N, R, body, c0g, c0a, gw, aw)
         return l, q, gw, aw, hn_g, cn_g, hn_a, cn_a
@@ -256,19 +205,11 @@ class UpperNetwlocal(_NetBase):
         F, rows = B * T, B * T * N
         grows = F * N_ANCHOR * N_GROUP
         G = self._flat.grad
-        dl = _f32c(dl)
-        y, h1, cat = ar.get("y", (F, 87)), ar.get("h1", (F, 128)), ar.get("cat", (F, 256))
-        dy = ar.get("dy", (F, 87))
         pose = self._pose
-        if not getattr(self, "_dy_ready", False):
-            if pose is not None:          # ... and the world transform's share of dR, dt (the fused loss launch has left it otherwise)
-                hip.call("head_fk_backward_pose", 0, y, body, B, F, dl, dy, R, ar.get("jh", (F, 15, 3)), pose[2], pose[3])
-            else:
-                hip.call("head_fk_backward", 0, y, body, B, F, dl, dy, R)           # (world -> head frame inside the kernel)
-        dh1 = ar.get("dh1", (F, 128))
-        blocks.linear_backward(dy, h1, self.module3.fc2, G, dh1, relu_input=True)
+        self._head_fk_backward(ar, 0, ar.get("y", (F, 87)), body, B, F, _f32c(dl), ar.get("dy", (F, 87)), R, (F, 15, 3),
+                               pose[2:] if pose is not None else None)
         dcat = ar.get("dcat", (F, 256))
-        blocks.linear_backward(dh1, cat, self.module3.fc1, G, dcat)
+        self._head_backward(ar, self.module3.fc1, self.module3.fc2, ar.get("cat", (F, 256)), dcat, F, G)       # (weight gradients at once)
         with blocks.dw_reduce_group():                         # the three chains' weight-gradient partials: one reduce launch
             # global branch
             vec = ar.get("vec", (F, 64))
@@ -276,15 +217,8 @@ class UpperNetwlocal(_NetBase):
             dvec, dvvec = blocks.lstm64_backward_multi(
                 ar, [("grnn", self.module1.grnn, vec, c0g, dcat[:, :128], self._drop_p(self.module1.grnn)),
                      ("arnn", self.module2.arnn.rnn, vvec, c0a, dcat[:, 128:], self._drop_p(self.module2.arnn.rnn))], B, T, G, True)
-            g3, dg3 = ar.get("g3", (rows, 64)), ar.get("dg3", (rows, 64))
             feats = ar.get("feats", (rows, 28))
-            gpn = self.module1.gpointnet
-            if getattr(self, "_gpool_fused", False):
-                blocks.pool128_backward_fused(ar, "gp", gpn, gpn.attn, gw, vec, dvec, rows, dg3, G)
-                dfeats = blocks._mlp3_backward_fused(ar, "gp", gpn, feats, dg3, G, True, have_sums=True)
-            else:
-                blocks.attn_pool_backward(ar, "gpool", g3, gpn.attn, gw, dvec, F, N, 64, dg3, G)
-                dfeats = blocks.mlp3_backward(ar, "gp", gpn, feats, g3, dg3, G, True)
+            dfeats = self._global_backward(ar, F, N, gw, dvec, G)
             # local branch
             voxT = ar.get("voxT", (F, 64 * N_ANCHOR))
             if getattr(self, "_vox_fused", False):
@@ -321,8 +255,6 @@ class UpperNetwlocal(_NetBase):
                 blocks.attn_pool_backward(ar, "lpool", l3, lp.attn, aw, dvox, F * N_ANCHOR, N_GROUP, 64, dl3, G)
                 dgrouped = blocks.mlp3_backward(ar, "lp", lp, grouped, l3, dl3, G, True)
                 hip.call("anchor_group_backward", dgrouped, gidx, F, N, 25, dfeats, 28)
-            pts = ar.get("pts", (rows, 6))
-            dpts = blocks.mlp3_backward(ar, "m0", self.module0, pts, feats[:, 4:28], dfeats[:, 4:28], G, pose is not None)
-        if pose is not None:
-            # (dfeats[:, 0:3] holds GlobalPointNet's share and, added by the anchor scatter, the grouped rows' offset columns')
-            self._pose_head_share(F, N, R, dfeats, dpts)
+            dpts = self._pointnet_backward(ar, F, N, dfeats, G)
+        # (dfeats[:, 0:3] holds GlobalPointNet's share and, added by the anchor scatter, the grouped rows' offset columns')
+        self._pose_head_share(F, N, R, dfeats, dpts)

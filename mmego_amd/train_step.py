@@ -12,6 +12,7 @@ import os
 import torch
 
 from . import hip, ops
+from .nets import LowerNet, UpperNet, _UpperBase
 from .params import FusedAdam
 from .plan import StepPlan
 
@@ -132,8 +133,7 @@ def call_upper(net, x, h0, c0, body, R, t, **impl):
     """An Upper net of either kind on one zero-state pair: UpperNet takes it once, UpperNetwlocal a second time for its anchor branch
     (Net/Upper_Net.py:406-432).  Without keywords the public call ``net(...)``; with them (stash, x_src, pose_grad) ``net._forward_impl``.
     -> the net's output tuple; [0] is the 15 upper joints for both."""
-    from .nets_local import UpperNetwlocal
-    states = (h0, c0) * (2 if isinstance(net, UpperNetwlocal) else 1)
+    states = (h0, c0) * net.state_pairs
     if impl:
         return net._forward_impl(x, *states, body, R, t, **impl)
     return net(x, *states, body, R, t)
@@ -280,7 +280,6 @@ class StageStep(_Engine):
             return opts[key]
         self.imu_opt = self.upper_opt = None
         if self.finetune_upper:
-            from .nets import LowerNet, UpperNet
             if stage != "lower" or type(net) is not LowerNet:
                 raise ValueError("StageStep: finetune_upper trains Upper_Net through Lower_Net's input gradients: the Lower stage only")
             if type(upper_frozen) is not UpperNet:
@@ -293,9 +292,7 @@ class StageStep(_Engine):
                 raise ValueError("StageStep: finetune_upper is not data parallel yet (no all-reduce of the Upper_Net gradients)")
             self.upper_opt = opt_for("upper_opt", upper_frozen, lr if upper_lr is None else upper_lr, weight_decay)
         if self.finetune_imu:
-            from .nets import UpperNet
-            from .nets_local import UpperNetwlocal
-            if not self.finetune_upper and (stage != "upper" or type(net) not in (UpperNet, UpperNetwlocal)):
+            if not self.finetune_upper and (stage != "upper" or not isinstance(net, _UpperBase)):
                 raise ValueError("StageStep: finetune_imu trains IMU_Net through the head-pose gradients of the Upper stage's net (UpperNet "
                                  "or UpperNetwlocal); Lower_Net's (LowerNet.input_grads) reach it through a trained Upper_Net only "
                                  "(finetune_upper as well: the three-net step)")
@@ -326,11 +323,9 @@ class StageStep(_Engine):
         """Fresh batch, head pose, forward of the trained net (and of the frozen Upper_Net in the Lower stage), loss."""
         s = self.static
         B, T = s["x"].shape[0], s["x"].shape[1]
-        from .nets import UpperNet
         first_net = self.net if self.stage == "upper" else self.upper_frozen
         # fresh batch (x is transformed in place): an Upper net's transform launch reads it from x_src; other nets get a copy first
-        from .nets_local import UpperNetwlocal
-        via_transform = type(first_net) in (UpperNet, UpperNetwlocal) and s["x"].shape[-1] <= 8
+        via_transform = isinstance(first_net, _UpperBase) and s["x"].shape[-1] <= 8
         # the trained net's kinematics launch takes the loss, its gradient and the first backward step along (nets._head_fk)
         self.net.loss_hook = (s["target"], self.jmap, self.loss2, 1.0)
         if self.finetune_upper:

@@ -1,5 +1,5 @@
 """Writes tests/golden/step_structure.json: the launch structure of one whole step() of every step engine of mmego_amd/train_step.py
-(StageStep in its seven forms, ImuStep with and without dropout, ConcurrentStages as branches and as one chain, SharedImuStages,
+(StageStep in its ten forms, ImuStep with and without dropout, ConcurrentStages as branches and as one chain, SharedImuStages,
 PipelinedStages in fp32 and split3), which tests/test_step_engines_gpu.py::test_step_structure_is_the_recorded_one holds every later
 commit to.  The configurations and what is dumped: tests/step_helpers.py.
 

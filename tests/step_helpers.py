@@ -80,15 +80,17 @@ def _upper(dev, use_graph, imu=None, wlocal=False, **kw):
     return st, [net, imu]
 
 
-def _lower(dev, use_graph, finetune_upper=False):
-    from mmego_amd import nets
+def _lower(dev, use_graph, finetune_upper=False, wlocal=False, finetune_imu=False):
+    from mmego_amd import nets, nets_local
     from mmego_amd.train_step import StageStep
     x, imu_in, body, target, R = batch(dev)
-    upper = nets.UpperNet().to(dev).train(finetune_upper)
+    upper = (nets_local.UpperNetwlocal() if wlocal else nets.UpperNet()).to(dev).train(finetune_upper)
     net = nets.LowerNet(64).to(dev).train()
-    st = StageStep("lower", net, None, upper_frozen=upper, lr=3e-5, use_graph=use_graph, finetune_upper=finetune_upper, upper_lr=1e-5)
-    st.bind(x, imu_in, body, target, R_gt=R)
-    return st, [net, upper]
+    imu = nets.IMUNet(15, 9, 64, 2, True, 0).to(dev).train() if finetune_imu else None
+    st = StageStep("lower", net, imu, upper_frozen=upper, lr=3e-5, use_graph=use_graph, finetune_upper=finetune_upper, upper_lr=1e-5,
+                   finetune_imu=finetune_imu, imu_lr=1e-5)
+    st.bind(x, imu_in, body, target, R_gt=None if imu is not None else R)
+    return st, [net, upper, imu]
 
 
 def _imu(dev, use_graph, drop):
@@ -130,9 +132,12 @@ CONFIGS = {
     "upper_frozen_imu": lambda dev, g: _upper(dev, g, imu="frozen"),
     "upper_wlocal": lambda dev, g: _upper(dev, g, wlocal=True),
     "upper_finetune_imu": lambda dev, g: _upper(dev, g, imu="trained", finetune_imu=True),
+    "upper_wlocal_finetune_imu": lambda dev, g: _upper(dev, g, wlocal=True, imu="trained", finetune_imu=True),
     "upper_recorded_pose_clip": lambda dev, g: _upper(dev, g, clip_grad_norm=1.0),
     "lower_frozen_upper": lambda dev, g: _lower(dev, g),
+    "lower_frozen_wlocal": lambda dev, g: _lower(dev, g, wlocal=True),
     "lower_finetune_upper": lambda dev, g: _lower(dev, g, finetune_upper=True),
+    "lower_finetune_all": lambda dev, g: _lower(dev, g, finetune_upper=True, finetune_imu=True),
     "imu_step": lambda dev, g: _imu(dev, g, 0),
     "imu_step_dropout": lambda dev, g: _imu(dev, g, 0.1),
     "concurrent_fp32": lambda dev, g: _two_stage(dev, g, "concurrent"),

@@ -94,3 +94,22 @@ def test_checkpoint_of_the_other_variant_is_refused_by_name():
     processors.load_upper_state(other, wloc.state_dict(), "wlocal", "some/upper.pth")
     for k, v in wloc.state_dict().items():
         assert torch.equal(other.state_dict()[k], v), k
+
+
+def test_parameter_names_and_flat_order_of_both_upper_nets_are_the_recorded_ones():
+    """named_parameters, named_buffers and flat_param_order (as names) of a fresh UpperNet and a fresh UpperNetwlocal equal
+    tests/golden/upper_param_order.json, recorded on the commit before the two nets got one base class: checkpoints, upper_variant_of and
+    the flat buffer's layout depend on names and registration order."""
+    import json
+    import os
+
+    from conftest import GOLDEN
+    from mmego_amd import nets, nets_local
+    want = json.load(open(os.path.join(GOLDEN, "upper_param_order.json")))
+    assert sorted(want) == ["UpperNet", "UpperNetwlocal"]
+    for cls in (nets.UpperNet, nets_local.UpperNetwlocal):
+        net = cls()
+        names = {id(p): n for n, p in net.named_parameters()}
+        got = {"named_parameters": [n for n, _ in net.named_parameters()], "named_buffers": [n for n, _ in net.named_buffers()],
+               "flat_param_order": [names[id(p)] for p in net.flat_param_order()]}
+        assert got == want[cls.__name__], cls.__name__
