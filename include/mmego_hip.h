@@ -373,6 +373,33 @@ int mmego_pose_errors(void* stream, const float* upper, const float* lower, cons
  * U[f,29] sum |upper - target[upper_joint_map]| of the frame (its share of L1Loss(sum)).  upper [F,15,3], target [F,21,3], U [F,30]. */
 int mmego_pose_errors_upper(void* stream, const float* upper, const float* target, long F, float* U);
 
+/* ---- aligned evaluation metrics (metrics.hip; not in the reference) ------------------------------------
+ * What mmego_pose_errors' absolute joint error mixes, taken apart per frame: the articulated pose against the placement of the whole
+ * body by the head pose.  upper [F,15,3], lower [F,8,3] or NULL, target [F,21,3].  With `lower` the J = 21 joints are the skeleton as
+ * mmego_pose_errors assembles it (lower overwrites the shared hips); with lower = NULL the J = 15 upper joints in upper_joint_map order
+ * against target[:, upper_joint_map].  Root = joint 0 (spine base, position 0 of the upper map too).  The prediction p is fitted onto
+ * the target g: minimise sum_j |s R (p_j - pbar) + gbar - g_j|^2 over PROPER rotations R (det = +1, never a reflection), s = 1 (rigid
+ * fit) or the optimal s (similarity fit, Procrustes); pbar, gbar: centroids over the J joints.  Row A[f, :], lda >= width =
+ * mmego_pose_errors_aligned_width(J, nthr) = 3 J + 3 + nthr:
+ *   A[f, 0:J]     root-relative error per joint (m), |(p_j - p_0) - (g_j - g_0)|
+ *   A[f, J:2J]    error per joint after the rigid fit
+ *   A[f, 2J:3J]   error per joint after the similarity fit (PA-MPJPE per joint)
+ *   A[f, 3J]      rotation angle of the fit (deg, in [0, 180]);  A[f, 3J+1] = |pbar - gbar| (m);  A[f, 3J+2] = the similarity scale s
+ *   A[f, 3J+3+k]  fraction of the J joints whose ABSOLUTE error |p_j - g_j| is <= thr[k] (PCK); thr: nthr floats (m), 0 <= nthr <= 8
+ * Horn's quaternion form, the eigenpair by a fixed number of cyclic Jacobi sweeps, s = lambda_max / sum_j |p_j - pbar|^2, the angle as
+ * 2 atan2(|q_xyz|, |q_w|); all in double from the fp32 inputs, float stores; sums over the joints in index order (two launches give the
+ * same bits).  A prediction without spread: s = 0, R = I, angle 0; a zero covariance: R = I; where the best rotation is not unique
+ * (collinear joints) one maximiser is taken -- the sum of squared residuals is the same for all.  Means over frames via mmego_colsum. */
+int mmego_pose_errors_aligned_width(int J, int nthr);
+int mmego_pose_errors_aligned(void* stream, const float* upper, const float* lower, const float* target, long F, const float* thr,
+                              int nthr, float* A, long lda);
+/* Temporal quality of the same J joints: upper [B,T,15,3], lower [B,T,8,3] or NULL, target [B,T,21,3], T >= 3.  Acc[b, j] (row stride
+ * lda >= J) = mean over t = 1 .. T-2 of |(p[t-1] - 2 p[t] + p[t+1]) - (g[t-1] - 2 g[t] + g[t+1])| of joint j, in m per frame^2: the
+ * error of the second differences (acceleration error; jitter shows here and in no per-frame figure).  Double inside, summed in t
+ * order, float stores. */
+int mmego_pose_accel_errors(void* stream, const float* upper, const float* lower, const float* target, long B, int T, float* Acc,
+                            long lda);
+
 /* ---- eval-mode front end of Upper_Net in one launch (front.hip) ---------------------------------------
  * Per frame of N points (x [F,N,6], N a multiple of 16, <= 1024): Transform2H (Utils.py:284-292; bit-identical to mmego_transform2h,
  * written back into x -- quirk Q1 -- from x_src when given), PointNet 6-8-16-24 (Net/Upper_Net.py:242-266), concat with the first

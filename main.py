@@ -14,7 +14,10 @@ available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam
 trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
 "Grad norm" line per net and epoch; `inf` only measures), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
 UpperNetwlocal with the anchor branch -- the net trained by --train --network Upper_Net, the class the Upper checkpoint is loaded into by
---train --network Lower_Net and --infer).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+--train --network Lower_Net and --infer), --metrics {reference,full} (full: beside the reference's figures, the evaluation pass of --infer
+and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
+rotation, shift and scale, PCK and the acceleration error on the device -- pose error apart from placement error; printed only, the log
+files keep their format).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -78,7 +81,23 @@ def build_parser():
                         "--network Upper_Net trains it (with --finetune_imu, --imu_lr, --imu_dropout, --clip_grad_norm, --resume and "
                         "--gt_head_pose as for global); --train --network Lower_Net and --infer load the Upper checkpoint into it.  wlocal "
                         "stays frozen in stage 3: not with --finetune_upper / --finetune_all")
+    p.add_argument("--metrics", type=str, choices=["reference", "full"], default="reference",
+                   help="figures of the evaluation pass: reference (default: what the reference reports) or full (also root-relative, "
+                        "rigid-aligned and Procrustes-aligned joint errors, the alignment's rotation / shift / scale, PCK at 5, 10 and 15 cm "
+                        "and the acceleration error, computed on the device in the same pass).  --infer prints them behind the "
+                        "reference's lines; --train --network Upper_Net / Lower_Net prints one more line per epoch (stdout only; model "
+                        "selection and early stopping do not look at them)")
     return p
+
+
+def check_metrics(parser, args):
+    """--metrics full belongs to a run whose evaluation pass compares skeletons: --infer, or stage 2 / stage 3 training."""
+    if args.metrics != "full":
+        return
+    if not (args.train or args.infer):
+        parser.error("--metrics full goes with --train or --infer (it adds figures to their evaluation pass)")
+    if args.network == "IMU_Net":
+        parser.error("--metrics full does not go with --network IMU_Net: stage 1 evaluates a head pose, there is no skeleton to align")
 
 
 def check_upper_variant(parser, args):
@@ -151,6 +170,7 @@ def check_finetune_all(parser, args, world):
 def check_finetune(parser, args, world):
     """--finetune_imu fits one arrangement only; everything else is refused before any work starts."""
     check_upper_variant(parser, args)
+    check_metrics(parser, args)
     check_finetune_all(parser, args, world)
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
@@ -200,6 +220,7 @@ def apply_overrides(args):
     Config.clip_grad_norm = args.clip_grad_norm
     for c in both:
         c.upper_variant = args.upper_variant or "global"
+        c.metrics = args.metrics
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

@@ -386,6 +386,48 @@ def colsum(X, out, accumulate=False, out2=None, scale=None):
     return out
 
 
+def _pose_inputs(upper, lower, target):
+    """The three joint tensors of the aligned metrics, [..., 15 | 8 | 21, 3] contiguous with the same leading shape; -> J."""
+    lead = tuple(upper.shape[:-2])
+    for t, n in ((upper, 15), (lower, 8), (target, 21)):
+        if t is None:
+            continue
+        _chk(t)
+        if tuple(t.shape) != lead + (n, 3) or not t.is_contiguous():
+            raise ValueError("expected a contiguous %s tensor, got %s" % (lead + (n, 3), tuple(t.shape)))
+    return 15 if lower is None else 21
+
+
+def pose_errors_aligned_width(J, nthr):
+    return hip.lib().mmego_pose_errors_aligned_width(int(J), int(nthr))
+
+
+def pose_errors_aligned(upper, lower, target, thr, A):
+    """Per-frame rows of mmego_pose_errors_aligned into A [F, >= 3 J + 3 + nthr] (root-relative, rigid-fit and similarity-fit joint
+    errors; fit angle, shift and scale; PCK at the thresholds thr, a device tensor of metres, or None).  lower None: the 15 upper joints."""
+    J = _pose_inputs(upper, lower, target)
+    F = upper.numel() // 45
+    nthr = 0 if thr is None else _chk(thr, 1).numel()
+    A = _rows(A)
+    if A.shape[0] != F or A.shape[1] < pose_errors_aligned_width(J, nthr) or (thr is not None and not thr.is_contiguous()):
+        raise ValueError("pose_errors_aligned: A is %s for %d frames, %d joints and %d thresholds" % (tuple(A.shape), F, J, nthr))
+    hip.call("pose_errors_aligned", upper, lower, target, F, thr, nthr, A, A.stride(0))
+    return A
+
+
+def pose_accel_errors(upper, lower, target, Acc):
+    """Acc [B, >= J] <- the acceleration error per sequence and joint (mmego_pose_accel_errors); inputs [B, T, ., 3], T >= 3."""
+    J = _pose_inputs(upper, lower, target)
+    if upper.dim() != 4:
+        raise ValueError("pose_accel_errors: inputs are [B, T, joints, 3]")
+    B, T = upper.shape[0], upper.shape[1]
+    Acc = _rows(Acc)
+    if Acc.shape[0] != B or Acc.shape[1] < J:
+        raise ValueError("pose_accel_errors: Acc is %s for %d sequences and %d joints" % (tuple(Acc.shape), B, J))
+    hip.call("pose_accel_errors", upper, lower, target, B, T, Acc, Acc.stride(0))
+    return Acc
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

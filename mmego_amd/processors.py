@@ -30,6 +30,8 @@ _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_
 
 
 UPPER_VARIANTS = {"global": UpperNet, "wlocal": UpperNetwlocal}          # --upper_variant -> the class behind "Upper_Net"
+METRICS = ("reference", "full")                                          # --metrics
+PCK_THRESHOLDS_CM = (5.0, 10.0, 15.0)                                    # --metrics full: PCK of the absolute joint errors
 
 
 def upper_variant_of(state_dict):
@@ -61,6 +63,7 @@ class _Base:
     # the step of every minibatch size, read by the grad-norm report and the checkpoint (a trainer's __init__ makes it a dict)
     _opts = types.MappingProxyType({})
     weight_decay = 0.0            # of "opt" (stage 1: coupled 1e-3)
+    last_metrics = None           # (--metrics full: aligned_summary of the last evaluation pass; eval_model's return value stays the reference's)
     net_name = None               # what "opt" trains, as the grad-norm report calls it
 
     def __init__(self, cfg, make_dirs=True):
@@ -95,6 +98,9 @@ class _Base:
         if v not in UPPER_VARIANTS:
             raise SystemExit("--upper_variant: %r is not one of %s" % (v, ", ".join(sorted(UPPER_VARIANTS))))
         return v
+
+    def _metrics(self):
+        return getattr(self.cfg, "metrics", None) or "reference"
 
     def _new_upper(self, path=None):
         """The Upper net of --upper_variant on the device; ``path``: a checkpoint to load into it."""
@@ -386,6 +392,8 @@ class UpperTrainer(_StageTrainer):
             print("Average Joint Rotation Error: {}".format(sum(angle_ll) / len(angle_ll)))
             print(accu_ll)
             print("Eval_loss: {} Eval_loss_l (l, g): {} \n Angle_loss: {} \n".format(eval_loss, eval_loss_l, angle_ll))
+            if self.last_metrics is not None:                        # (--metrics full: stdout only, the log files keep their format)
+                print(metrics_line(self.last_metrics))
         return self._train_loop(report)
 
     def eval_model(self):
@@ -397,7 +405,8 @@ class UpperTrainer(_StageTrainer):
         if self.finetune_imu:
             self.model_IMU.eval()
             self.model_IMU.weights_changed()          # (the fused Adam writes through raw pointers: no derived copy of old weights)
-        m = _epoch_eval(self, self.test_data, self.batchsize, True, self._rng, self.model_IMU, self.model, None)
+        m = _epoch_eval(self, self.test_data, self.batchsize, True, self._rng, self.model_IMU, self.model, None, self._metrics())
+        self.last_metrics = aligned_summary(m[:, 30:], 15) if self._metrics() == "full" else None      # (--metrics full: the 15 upper joints)
         eval_loss = float(np.mean(m[:, 29]))                                 # L1(sum) / B / T per minibatch
         return (eval_loss, np.asarray([eval_loss / self.cfg.joint_num_upper]), float(np.mean(m[:, :15].mean(axis=1))),
                 float(np.mean(m[:, 29] / 45.0)), m[:, :15].mean(axis=0), m[:, 15:29].mean(axis=0))
@@ -428,6 +437,8 @@ class LowerTrainer(_StageTrainer):
             print("Average Joint Rotation Error: {}".format(sum(angle_ll) / len(angle_ll)))
             print(accu_ll)
             print("Eval_loss: {} Eval_loss_l (l, g): {} \n Angle_loss: {}".format(eval_loss, eval_loss_l, angle_ll))
+            if self.last_metrics is not None:                        # (--metrics full: stdout only, the log files keep their format)
+                print(metrics_line(self.last_metrics))
         return self._train_loop(report)
 
     def eval_model(self):
@@ -438,24 +449,39 @@ class LowerTrainer(_StageTrainer):
         if self.finetune_imu:                         # (--finetune_all)
             self.model_IMU.eval()
             self.model_IMU.weights_changed()
-        return evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.test_data, self.batchsize, True, self._rng)[0]
+        out, summary = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.test_data, self.batchsize, True, self._rng,
+                                     self._metrics())
+        self.last_metrics = summary if self._metrics() == "full" else None
+        return out
 
 
-def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net):
+def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference"):
     """One evaluation pass with ONE host synchronisation: -> float64 array [n_minibatches, W] of per-frame MEANS per minibatch.
     lower_net None: W = 30, the columns of mmego_pose_errors_upper; else W = 45: the 43 columns of mmego_pose_errors, then the
     Lower stage's L1(sum) loss per frame and its mean joint distance.  The split is uploaded once per dataset object
-    (DeviceArrays) and minibatches are gathered on the device in the order `data.batches` would produce (same RNG use)."""
+    (DeviceArrays) and minibatches are gathered on the device in the order `data.batches` would produce (same RNG use).
+    metrics="full": the same launches, and per minibatch one mmego_pose_errors_aligned launch (the 21 joints with a Lower_Net, the 15
+    upper joints without) with its colsum, and -- for T >= 3 -- one mmego_pose_accel_errors launch with its colsum over the sequences,
+    into further columns of the same device log: W is followed by the 3 J + 3 + len(PCK_THRESHOLDS_CM) columns of
+    mmego_pose_errors_aligned (per-frame means) and J columns of acceleration error (per-sequence means; NaN when T < 3)."""
+    if metrics not in METRICS:
+        raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
     dev = base.device
     arrays = DeviceArrays.of(dataset, dev)                  # (one copy per split, shared with eval_imu; ADVICE r03)
     todo = list(batch_indices(len(dataset), batch_size, shuffle, rng))
     W = 30 if lower_net is None else 45
-    log = torch.zeros((len(todo), W), dtype=torch.float32, device=dev)
+    full = metrics == "full"
+    J = 15 if lower_net is None else 21
+    WA = ops.pose_errors_aligned_width(J, len(PCK_THRESHOLDS_CM)) if full else 0
+    log = torch.zeros((len(todo), W + WA + (J if full else 0)), dtype=torch.float32, device=dev)
     frames = np.empty(len(todo), dtype=np.float64)
+    seqs = np.full(len(todo), np.nan)                       # (sequences per minibatch whose acceleration error was taken)
     scratch = base.__dict__.setdefault("_eval_scratch", {})
     lmap = scratch.get("lmap")
     if lmap is None:
         lmap = scratch["lmap"] = torch.tensor(list(base.cfg.lower_joint_map), dtype=torch.int32, device=dev)
+    if full and "pck_thr" not in scratch:
+        scratch["pck_thr"] = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
     with torch.no_grad():
         for i, idx in enumerate(todo):
             b = arrays.gather(idx)                          # fresh copies: the nets transform `data` in place (Q1)
@@ -470,6 +496,7 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
             tgt, body = b["target"], b["skl"]
             R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
             up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]      # (an UpperNet or an UpperNetwlocal)
+            lo = None
             if lower_net is None:
                 hip.call("pose_errors_upper", up.contiguous(), tgt, F, E)
                 ops.colsum(E, log[i])
@@ -478,21 +505,70 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
                 hip.call("pose_errors", up.contiguous(), lo.contiguous(), tgt, F, E)
                 ops.colsum(E, log[i, :43])
                 hip.call("l1_loss", lo.contiguous(), tgt, lmap, 8, 21, F, 1.0, log[i, 43:45], None)
-    out = log.cpu().numpy().astype(np.float64) / frames[:, None]             # the epoch's one device -> host read
+            if full:
+                up, lo = up.contiguous().view(B, T, 15, 3), None if lo is None else lo.contiguous().view(B, T, 8, 3)
+                akey = ("aligned", B, T, J)
+                if akey not in scratch:
+                    scratch[akey] = (torch.empty((F, WA), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.float32, device=dev))
+                A, Acc = scratch[akey]
+                ops.pose_errors_aligned(up, lo, tgt, scratch["pck_thr"], A)
+                ops.colsum(A, log[i, W:W + WA])
+                if T >= 3:
+                    ops.pose_accel_errors(up, lo, tgt, Acc)
+                    ops.colsum(Acc, log[i, W + WA:])
+                    seqs[i] = B
+    out = log.cpu().numpy().astype(np.float64)                               # the epoch's one device -> host read
+    out[:, :W + WA] /= frames[:, None]
+    out[:, W + WA:] /= seqs[:, None]
     blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
     return out
 
 
-def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None):
+def aligned_summary(m, J):
+    """The --metrics full figures from _epoch_eval's columns behind the reference's (m [n_minibatches, 3 J + 3 + nthr + J]): means over
+    minibatches of per-minibatch means, lengths in cm.  J = 21: the three joint errors also as means over the upper and the lower joint
+    map of the one 21-joint fit."""
+    nthr = len(PCK_THRESHOLDS_CM)
+    errs = {"root_rel_cm": m[:, :J], "rigid_cm": m[:, J:2 * J], "pa_cm": m[:, 2 * J:3 * J]}
+    s = {}
+    for name, blk in errs.items():
+        s[name] = float(np.mean(blk.mean(axis=1))) * 100
+        if J == 21:
+            s[name[:-3] + "_upper_cm"] = float(np.mean(blk[:, list(Config.upper_joint_map)].mean(axis=1))) * 100
+            s[name[:-3] + "_lower_cm"] = float(np.mean(blk[:, list(Config.lower_joint_map)].mean(axis=1))) * 100
+    s["align_rot_deg"] = float(np.mean(m[:, 3 * J]))
+    s["align_shift_cm"] = float(np.mean(m[:, 3 * J + 1])) * 100
+    s["pa_scale"] = float(np.mean(m[:, 3 * J + 2]))
+    s["pck"] = {c: float(np.mean(m[:, 3 * J + 3 + k])) for k, c in enumerate(PCK_THRESHOLDS_CM)}
+    acc = m[:, 3 * J + 3 + nthr:]
+    s["accel_cm"] = None if np.isnan(acc).any() else float(np.mean(acc.mean(axis=1))) * 100
+    s["per_joint_root_rel_cm"] = errs["root_rel_cm"].mean(axis=0) * 100
+    s["per_joint_pa_cm"] = errs["pa_cm"].mean(axis=0) * 100
+    return s
+
+
+def metrics_line(s):
+    """One line of the --metrics full figures (the trainers' extra line per epoch)."""
+    acc = "n/a" if s["accel_cm"] is None else "%.4f" % s["accel_cm"]
+    return ("Aligned metrics: root-relative {:.4f} cm, rigid-aligned {:.4f} cm, PA-MPJPE {:.4f} cm, fit rotation {:.4f} deg, shift {:.4f} cm, "
+            "scale {:.5f}, PCK {}, acceleration error {} cm/frame^2").format(
+                s["root_rel_cm"], s["rigid_cm"], s["pa_cm"], s["align_rot_deg"], s["align_shift_cm"], s["pa_scale"],
+                " ".join("@%gcm %.4f" % (c, v) for c, v in s["pck"].items()), acc)
+
+
+def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference"):
     """IMU -> Upper -> Lower over a data split (reference Processor/Test/Demo_test.py:71-184, Train_Lower.py:232-332); returns
-    (reference-style tuple, summary dict).  Device-resident split, one host read per pass (_epoch_eval)."""
+    (reference-style tuple, summary dict).  Device-resident split, one host read per pass (_epoch_eval).  metrics="full": the same
+    tuple and summary keys from the same launches, and the summary also holds aligned_summary's keys for the 21 joints."""
     cfg = base.cfg
-    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net)
+    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics)
     eval_loss = float(np.mean(m[:, 43]))
     accu_l, accu_up, accu_lo = m[:, :21].mean(axis=1), m[:, 41], m[:, 42]
     accu_ll, angle_ll = m[:, :21].mean(axis=0), m[:, 21:41].mean(axis=0)
     summary = dict(all_cm=float(np.mean(accu_l)) * 100, upper_cm=float(np.mean(accu_up)) * 100, lower_cm=float(np.mean(accu_lo)) * 100,
                    rot_deg=float(sum(angle_ll) / len(angle_ll)), per_joint_cm=accu_ll * 100)
+    if metrics == "full":
+        summary.update(aligned_summary(m[:, 45:], 21))
     return (eval_loss, np.asarray([eval_loss / cfg.joint_num_lower]), float(np.mean(accu_l)), float(np.mean(accu_lo)), accu_ll, angle_ll), summary
 
 
@@ -510,12 +586,24 @@ class Evaluator(_Base):
     def eval_model(self):
         self.model.load(self.cfg.model_lower_path)
         self.model.eval()
-        out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False)
+        out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics())
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
         print("Average Joint Rotation Error(°): {}".format(s["rot_deg"]))
         print("Per Joint Localization Error(cm): {}".format(s["per_joint_cm"]))
+        if self._metrics() == "full":
+            self.last_metrics = s
+            for name, parts in (("Root-relative", "root_rel"), ("Rigid-aligned", "rigid"), ("Procrustes-aligned (PA-MPJPE)", "pa")):
+                print("{} Joint Error(cm): {} (upper {}, lower {})".format(name, s[parts + "_cm"], s[parts + "_upper_cm"], s[parts + "_lower_cm"]))
+            print("Alignment Rotation(°): {}".format(s["align_rot_deg"]))
+            print("Alignment Shift(cm): {}".format(s["align_shift_cm"]))
+            print("Procrustes Scale: {}".format(s["pa_scale"]))
+            for c, v in s["pck"].items():
+                print("PCK@{:g}cm: {}".format(c, v))
+            print("Acceleration Error(cm/frame^2): {}".format(s["accel_cm"]))
+            print("Per Joint Root-relative Error(cm): {}".format(s["per_joint_root_rel_cm"]))
+            print("Per Joint Procrustes-aligned Error(cm): {}".format(s["per_joint_pa_cm"]))
         return out
 
     def eval_all_skeleton(self):
