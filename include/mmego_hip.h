@@ -112,6 +112,24 @@ int mmego_copy2d(void* stream, const float* X, long ldx, float* Y, long ldy, lon
 /* Y[i,:] = X[idx[i],:] (rows of W floats, idx int64; indices outside [0,nsrc) give zero rows): minibatch assembly from
  * the HBM-resident dataset -- replaces the DataLoader collate + per-batch host->device copies of Train_Upper.py:140-150. */
 int mmego_gather_rows(void* stream, const float* X, long nsrc, long W, const long long* idx, long nout, float* Y);
+/* Point clouds packed on the device, a fresh random packing per output frame (frame_pack.hip; data.FrameStore under --point_keep).
+ * pts [P][5] holds every frame's raw returns (x, y, z, intensity, velocity), frame f owning rows frame_off[f] .. frame_off[f+1]
+ * (int64 CSR offsets); output frame q = 0 .. nout-1 packs frame f = frame_idx[q] into out[q] [pc_no][6] as data.pack_points does:
+ *   convert  (x, y, z, intensity, velocity) -> (x, y, z, r, velocity, intensity), r = sqrtf(x*x + y*y + z*z) in fp32;
+ *   keep     n = min(frame_off[f+1] - frame_off[f], max_n) points (n <= 0: an all-zero frame); point j < n survives when
+ *            (key(KK, q, j) >> 8) * 2^-24 < keep_p (fp32; keep_p = 1 keeps all); if none survives, the point with the smallest
+ *            (key(KO, q, j), j) does.  The survivors in increasing j are Q[0 .. n');
+ *   place    n' <  pc_no: slot s receives Q[rank(s)], rank over the slots by (key(KO, q, s), s), if rank(s) < n', else six zeros;
+ *            n' >= pc_no: slot r receives the survivor of rank r, rank over the survivors by (key(KO, q, j), j), j the point's number.
+ * The integer recipe (32-bit unsigned arithmetic; hash32 and dropout_key as in csrc/common.h):
+ *   KK = dropout_key(seed, 0x4b454550), KO = dropout_key(seed, 0x4f524452)        -- the keep and the ordering stream of a launch
+ *   key(K, q, i) = hash32(hash32(K ^ hash32((unsigned)q)) ^ (unsigned)i)
+ * q, not f, is the counter: a frame listed twice in one launch (overlapping windows) gets two independent packings.  The same seed
+ * gives the same output, bit for bit.  Refused: null pointers, nout < 1 or >= 2^31, pc_no outside [1, 1024], max_n < 1 or beyond what
+ * 64 KB of LDS hold (4 waves x (max(max_n, pc_no) + max_n) words), keep_p outside (0, 1], out not 8-byte aligned.  The caller answers for
+ * frame_idx lying inside the offset array. */
+int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
+                      int pc_no, int max_n, float keep_p, unsigned long long seed, float* out);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

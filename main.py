@@ -17,7 +17,9 @@ UpperNetwlocal with the anchor branch -- the net trained by --train --network Up
 --train --network Lower_Net and --infer), --metrics {reference,full} (full: beside the reference's figures, the evaluation pass of --infer
 and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
 rotation, shift and scale, PCK and the acceleration error on the device -- pose error apart from placement error; printed only, the log
-files keep their format).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+files keep their format), --window_jitter (every epoch each training window moves to a valid start within +-(frame_no-1) frames of its
+own) and --point_keep P (every minibatch's clouds are packed afresh on the device, each radar return kept with probability P): what a
+run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched.  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -87,7 +89,29 @@ def build_parser():
                         "and the acceleration error, computed on the device in the same pass).  --infer prints them behind the "
                         "reference's lines; --train --network Upper_Net / Lower_Net prints one more line per epoch (stdout only; model "
                         "selection and early stopping do not look at them)")
+    p.add_argument("--window_jitter", action="store_true",
+                   help="--train: every epoch moves each training window to a start drawn uniformly from the valid starts within "
+                        "+-(frame_no - 1) frames of its own (one recording, no frame of a test window; frames outside the reference's "
+                        "window grid are used).  Draws are functions of (--seed, epoch); evaluation stays on the reference's test windows")
+    p.add_argument("--point_keep", type=float,
+                   help="--train --network Upper_Net / Lower_Net: every minibatch's point clouds are packed afresh on the device from the "
+                        "raw radar returns, each return kept with probability P in (0, 1] (1: only the packing is re-drawn); draws are "
+                        "functions of (--seed, epoch, minibatch).  Evaluation stays on the loader's packing")
     return p
+
+
+def check_frame_store(parser, args):
+    """--window_jitter and --point_keep change what a training run is trained on: they go with --train, and --point_keep with a net
+    that reads points."""
+    if not args.window_jitter and args.point_keep is None:
+        return
+    if args.point_keep is not None and not 0.0 < args.point_keep <= 1.0:          # (false for NaN as well)
+        parser.error("--point_keep is the probability that a radar return is kept: it has to lie in (0, 1], got %r" % (args.point_keep,))
+    if args.infer or not args.train:
+        parser.error("--window_jitter and --point_keep go with --train only: evaluation runs on the reference's test windows with the "
+                     "loader's packing")
+    if args.point_keep is not None and args.network == "IMU_Net":
+        parser.error("--point_keep does not go with --network IMU_Net: stage 1 reads no points (--window_jitter does)")
 
 
 def check_metrics(parser, args):
@@ -175,6 +199,7 @@ def check_finetune(parser, args, world):
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
     check_clip_grad_norm(parser, args)
+    check_frame_store(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -218,6 +243,9 @@ def apply_overrides(args):
     Config.upper_lr = args.upper_lr
     Config.finetune_all = bool(args.finetune_all)
     Config.clip_grad_norm = args.clip_grad_norm
+    Config.window_jitter = bool(args.window_jitter)
+    Config.point_keep = args.point_keep
+    Config.seed = args.seed
     for c in both:
         c.upper_variant = args.upper_variant or "global"
         c.metrics = args.metrics

@@ -51,6 +51,9 @@ class _Common:
     upper_lr = None             # --upper_lr: its learning rate (None: lr)
     imu_dropout = None          # --imu_dropout: nn.LSTM(dropout=P) of the IMU_Net that is trained (None: 0, as the reference's stage 1)
     upper_variant = "global"    # --upper_variant: the class behind "Upper_Net" -- "global" (UpperNet) or "wlocal" (UpperNetwlocal, anchor branch)
+    window_jitter = False       # --window_jitter: every epoch moves each training window to a valid start within +-(frame_no-1) frames (data.FrameStore)
+    point_keep = None           # --point_keep: clouds re-packed on the device per minibatch, each return kept with this probability (None: the loader's packing)
+    seed = None                 # --seed, as main.py got it (None: 0 for what FrameStore draws)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
 
 

@@ -76,8 +76,12 @@ def imu_to_radar_frame(imu, orientation_ref):
 class PosePC:
     """Dataset of non-overlapping ``frame_no``-frame windows (taken from the tail of each recording)."""
 
-    def __init__(self, train=True, vis=False, batch_length=None, root=None):
+    def __init__(self, train=True, vis=False, batch_length=None, root=None, keep_frames=False):
+        """keep_frames (for FrameStore): the per-frame packed clouds, which are packed anyway, stay in ``frame_packed_`` instead of being
+        dropped after the windows are cut.  The other per-frame views (``frame_pts_`` ... ``win_start_``) are the decoded arrays
+        themselves and are always there; nothing else about the object depends on the keyword."""
         self.vis, self.train = vis, train
+        self._keep_frames = bool(keep_frames)
         self.pc_no = Config.pc_no
         self.frame_no = batch_length if batch_length is not None else Config.frame_no
         self.joint_selection = Config.kinect_joint_selection
@@ -89,9 +93,10 @@ class PosePC:
         if not vis:
             order = np.arange(n)
             np.random.RandomState(Config.dataset_random_seed).shuffle(order)    # same permutation as shuffling each array
-            for name in ("data_ti_", "data_key_", "skl_", "ground_", "foot_contact_", "imu_", "R_R0R_", "t_R0R_"):
+            for name in ("data_ti_", "data_key_", "skl_", "ground_", "foot_contact_", "imu_", "R_R0R_", "t_R0R_", "win_start_"):
                 setattr(self, name, getattr(self, name)[order])
         cut = int(n * 0.8)
+        self.split_cut = n if vis else cut              # windows [0, split_cut) of the arrays train, the rest test
         sl = slice(0, n) if vis else (slice(0, cut) if train else slice(cut, n))
         self._items = [getattr(self, k)[sl] for k in ("data_ti_", "data_key_", "skl_", "imu_", "ground_",
                                                       "foot_contact_", "R_R0R_", "t_R0R_")]
@@ -168,6 +173,7 @@ class PosePC:
         dec = self._decode()
         win = {k: [] for k in ("ti", "key", "imu", "skl", "ground", "foot", "R", "t", "RtW")}
         bones = [b for b in dec["bones"]]
+        packed, starts = [], []                          # every frame's packed cloud; every window's first frame (global number)
         f0 = 0                                           # first frame of the snippet in the packed arrays
         p0 = 0                                           # first point of that frame in dec["pts"]
         for count in dec["snip_len"]:
@@ -175,16 +181,28 @@ class PosePC:
             for f in range(f0, f0 + int(count)):
                 n = int(dec["npts"][f])
                 rec["ti"].append(pack_points(dec["pts"][p0:p0 + n], self.pc_no))     # consumes numpy's RNG like the reference
+                if self._keep_frames:
+                    packed.append(rec["ti"][-1])
                 p0 += n
                 for k in ("key", "imu", "ground", "foot", "R", "t", "RtW"):
                     rec[k].append(dec[k][f])
             f0 += int(count)
             L = self.frame_no
             while len(rec["ti"]) >= L:
+                starts.append(f0 - int(count) + len(rec["ti"]) - L)
                 for k in rec:
                     win[k].append(rec[k][-L:])
                     rec[k] = rec[k][:-L]
                 win["skl"].append(bones)
+        # the per-frame views (FrameStore): the decoded arrays as they are, the recording number of every frame, the packed clouds of
+        # ALL frames (the head of a recording that fills no window included), and every window's first frame in data_ti_'s order
+        nf = len(dec["npts"])
+        self.frame_pts_, self.frame_npts_ = dec["pts"], np.asarray(dec["npts"], dtype=np.int64)
+        self.frame_key_, self.frame_imu_, self.frame_R_ = dec["key"], dec["imu"], dec["R"]
+        self.frame_rec_ = np.repeat(np.arange(len(dec["snip_len"]), dtype=np.int64), np.asarray(dec["snip_len"], dtype=np.int64))
+        self.frame_bones_ = np.asarray(dec["bones"])
+        self.frame_packed_ = (np.asarray(packed, dtype=np.float32).reshape(nf, self.pc_no, 6) if self._keep_frames else None)
+        self.win_start_ = np.asarray(starts, dtype=np.int64)
         print("data load end")
         return tuple(np.asarray(win[k]) for k in ("ti", "key", "imu", "skl", "ground", "foot", "R", "t", "RtW"))
 
@@ -263,6 +281,160 @@ def _gather_field_into(self, name, index, out):
 
 
 DeviceArrays.gather_field_into = _gather_field_into
+
+
+def _mix64(*words):
+    """One 64-bit word from a tuple of integers (splitmix64 steps): the seeds FrameStore derives from (seed, epoch, ...)."""
+    M = 0xFFFFFFFFFFFFFFFF
+    s = 0x6A09E667F3BCC908
+    for w in words:
+        s = (s + (int(w) & M) + 0x9E3779B97F4A7C15) & M
+        s = ((s ^ (s >> 30)) * 0xBF58476D1CE4E5B9) & M
+        s = ((s ^ (s >> 27)) * 0x94D049BB133111EB) & M
+        s ^= s >> 31
+    return s
+
+
+class FrameStore:
+    """The training split of a PosePC resident in HBM FRAME-major (about 110 MB for Sample_data: per frame the IMU samples, the
+    skeleton, the head rotation and the host-packed cloud, plus the raw radar returns with CSR offsets), with minibatches of windows
+    assembled ON the device from any window start -- the device-side counterpart of DeviceArrays for the two options that DeviceArrays'
+    finished windows cannot serve:
+
+      jitter       begin_epoch(epoch) moves every training window to a start drawn uniformly from the VALID starts within
+                   +-(frame_no - 1) frames of its own: starts whose frame_no frames lie in one recording and touch no frame of a
+                   test window (frames that belong to no window are fair game).  A window without such freedom keeps its start.
+      point_keep   every gather packs the raw returns of its frames afresh on the device (mmego_pack_frames): each return kept with
+                   probability point_keep, the survivors at random slots (or a random ordered subsample of them), as pack_points does
+                   once per load on the host.  1.0 only re-draws the packing.
+
+    Both off: the reference's windows and the loader's packing -- gather() returns what DeviceArrays(dataset).gather() returns.
+    The start draws come from a RandomState of their own seeded by (seed, epoch), the packing seeds from (seed, epoch, minibatch
+    number): neither touches the RNG of the minibatch order, every data-parallel rank draws the same starts, and a run resumed
+    at an epoch continues the same sequence.  ``index`` of gather / gather_field_into holds training-window numbers, as for
+    DeviceArrays; the buffers are static per minibatch size and `data` is a fresh copy every call (the nets transform it in place)."""
+
+    UNUSED, TRAIN, TEST = 0, 1, 2
+    FIELDS = DeviceArrays.FIELDS
+
+    def __init__(self, dataset, device, jitter=False, point_keep=None, seed=0):
+        import torch
+        from . import ops
+        if getattr(dataset, "frame_packed_", None) is None:
+            raise ValueError("FrameStore needs the per-frame clouds: build the PosePC with keep_frames=True")
+        if dataset.vis or not dataset.train:
+            raise ValueError("FrameStore serves the training split of a PosePC(train=True)")
+        if point_keep is not None and not 0.0 < float(point_keep) <= 1.0:
+            raise ValueError("point_keep is a probability in (0, 1], got %r" % (point_keep,))
+        self.device, self.n = device, len(dataset)
+        self.jitter, self.point_keep, self.seed = bool(jitter), None if point_keep is None else float(point_keep), int(seed)
+        self.L, self.pc_no = L, pc_no = int(dataset.frame_no), int(dataset.pc_no)
+        self.F = F = len(dataset.frame_npts_)
+        # who owns a frame: the one PosePC knows both sides of the split
+        cut = dataset.split_cut
+        self.ref_starts = np.asarray(dataset.win_start_[:cut], dtype=np.int64)
+        self.owner = np.zeros(F, dtype=np.int8)
+        span = np.arange(L)
+        self.owner[(self.ref_starts[:, None] + span).ravel()] = self.TRAIN
+        self.owner[(np.asarray(dataset.win_start_[cut:], dtype=np.int64)[:, None] + span).ravel()] = self.TEST
+        # valid starts: frame_no frames of one recording, none of them a test frame
+        rec = np.asarray(dataset.frame_rec_)
+        ntest = np.concatenate([[0], np.cumsum(self.owner == self.TEST)])
+        s = np.arange(max(F - L + 1, 0))
+        self._valid = (rec[s] == rec[s + L - 1]) & (ntest[s + L] == ntest[s]) if len(s) else np.zeros(0, dtype=bool)
+        # per training window: the valid starts within +-(L-1) of its own, as one CSR list
+        cand = []
+        for s0 in self.ref_starts:
+            lo, hi = max(int(s0) - (L - 1), 0), min(int(s0) + (L - 1), F - L)
+            cand.append(lo + np.nonzero(self._valid[lo:hi + 1])[0])
+        self._cand_len = np.asarray([len(c) for c in cand], dtype=np.int64)
+        if (self._cand_len < 1).any():
+            raise ValueError("a training window's own start is not valid: the dataset's windows and split do not belong together")
+        self._cand_off = np.concatenate([[0], np.cumsum(self._cand_len)])[:-1]
+        self._cand = np.concatenate(cand) if cand else np.zeros(0, dtype=np.int64)
+        self.n_movable = int((self._cand_len > 1).sum())
+        # the split in HBM, frame-major
+        f32 = lambda a, rows: torch.as_tensor(np.ascontiguousarray(a).reshape(rows, -1), dtype=torch.float32).to(device)
+        self.shape = {name: tuple(np.shape(dataset._items[i])[1:]) for name, i in self.FIELDS}
+        self.src = {"imu": f32(dataset.frame_imu_, F), "target": f32(dataset.frame_key_, F), "R_R0R": f32(dataset.frame_R_, F),
+                    "data": f32(dataset.frame_packed_, F), "skl": f32(dataset.frame_bones_, 1)}
+        self.width = {name: self.src[name].shape[1] for name in self.src}
+        npts = np.asarray(dataset.frame_npts_, dtype=np.int64)
+        self.max_n = int(npts.max()) if F else 1
+        self.pts = self.off = None
+        if self.point_keep is not None:
+            if pc_no > ops.PACK_FRAMES_MAX_PC_NO or self.max_n > ops.pack_frames_max_n(pc_no):
+                raise ValueError("a frame of %d points at pc_no = %d is beyond what mmego_pack_frames' 64 KB of LDS hold (at most %d points)"
+                                 % (self.max_n, pc_no, ops.pack_frames_max_n(pc_no)))
+            pts = np.asarray(dataset.frame_pts_, dtype=np.float32).reshape(-1, 5)
+            self.pts = torch.as_tensor(pts if len(pts) else np.zeros((1, 5), np.float32)).to(device)
+            self.off = torch.as_tensor(np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)).to(device)
+        self._out, self._zero_idx = {}, {}
+        self.begin_epoch(0)
+
+    def valid_starts(self):
+        """Every s for which frames s .. s+frame_no-1 lie in one recording and none is a test frame."""
+        return np.nonzero(self._valid)[0]
+
+    def begin_epoch(self, epoch):
+        """The epoch's window starts (jitter: one draw per training window from RandomState(seed, epoch)) and minibatch counter."""
+        self.epoch, self._minibatch = int(epoch), 0
+        if not self.jitter:
+            self.starts = self.ref_starts
+            return self.starts
+        s = _mix64(self.seed, self.epoch, 0x4A495454)
+        rs = np.random.RandomState([s & 0xFFFFFFFF, s >> 32])
+        k = np.minimum((rs.random_sample(self.n) * self._cand_len).astype(np.int64), self._cand_len - 1)
+        self.starts = self._cand[self._cand_off + k]
+        return self.starts
+
+    def frame_index(self, index):
+        """Host: the frame numbers [len(index) * frame_no] of the windows ``index`` at this epoch's starts."""
+        fi = (self.starts[np.asarray(index, dtype=np.int64)][:, None] + np.arange(self.L)).ravel()
+        if len(fi) and (fi.min() < 0 or fi.max() >= self.F):
+            raise IndexError("window start outside the frame arrays")
+        return np.ascontiguousarray(fi)
+
+    def _upload(self, index):
+        import torch
+        return torch.as_tensor(self.frame_index(index)).to(self.device), len(index)
+
+    def _field(self, name, fidx, B, dst, pack_seed):
+        import torch
+        from . import ops
+        if name == "skl":                                   # one bone set for the whole recording campaign: row 0, B times
+            z = self._zero_idx.get(B)
+            if z is None:
+                z = self._zero_idx[B] = torch.zeros(B, dtype=torch.int64, device=self.device)
+            return ops.gather_rows(self.src["skl"], z, dst.view(B, -1))
+        if name == "data" and self.point_keep is not None:
+            return ops.pack_frames(self.pts, self.off, fidx, dst.view(B * self.L, self.pc_no, 6), self.max_n, self.point_keep, pack_seed)
+        return ops.gather_rows(self.src[name], fidx, dst.view(B * self.L, self.width[name]))
+
+    def gather(self, index):
+        """index: int array of training-window numbers -> dict of device tensors [len(index), ...] (buffers reused per batch size)."""
+        import torch
+        fidx, B = self._upload(index)
+        pack_seed = _mix64(self.seed, self.epoch, self._minibatch, 0x5041434B)
+        self._minibatch += 1
+        out = {}
+        for name, _ in self.FIELDS:
+            key = (name, B)
+            dst = self._out.get(key)
+            if dst is None:
+                dst = torch.empty((B,) + self.shape[name], dtype=torch.float32, device=self.device)
+                self._out[key] = dst
+            self._field(name, fidx, B, dst, pack_seed)
+            out[name] = dst
+        return out
+
+    def gather_field_into(self, name, index, out):
+        """One field of the windows `index`, at this epoch's starts, into a caller-owned buffer (DeviceArrays.gather_field_into)."""
+        if name == "data" and self.point_keep is not None:
+            raise ValueError("the re-drawn clouds belong to gather(): their seed is its minibatch counter")
+        fidx, B = self._upload(index)
+        self._field(name, fidx, B, out, 0)
+        return out
 
 
 class ArraySplit:

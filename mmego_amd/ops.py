@@ -475,6 +475,34 @@ def gather_rows(X, idx, Y):
     return Y
 
 
+PACK_FRAMES_MAX_PC_NO = 1024
+
+
+def pack_frames_max_n(pc_no):
+    """The largest per-frame point count mmego_pack_frames takes at ``pc_no`` slots: 64 KB of LDS, four waves, per wave
+    max(max_n, pc_no) keys and max_n survivor numbers."""
+    words = 64 * 1024 // 4 // 4
+    return max(0, min(words // 2, words - int(pc_no)))
+
+
+def pack_frames(pts, frame_off, frame_idx, out, max_n, keep_p, seed):
+    """out[q] [pc_no, 6] = a fresh random packing of the raw points [P, 5] of frame frame_idx[q] (int64 CSR offsets frame_off; every
+    index has to lie in [0, len(frame_off) - 1): the caller's to check, the index lives on the device), each point kept with probability
+    keep_p (mmego_pack_frames: the recipe is in the header).  The same ``seed`` (an integer below 2^64) gives the same output."""
+    _chk(pts, 2)
+    if not (pts.is_contiguous() and pts.shape[1] == 5 and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+            and out.dim() == 3 and out.shape[2] == 6):
+        raise ValueError("pack_frames needs contiguous fp32 points [P, 5] and a contiguous fp32 out [nout, pc_no, 6]")
+    for t in (frame_off, frame_idx):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1):
+            raise ValueError("pack_frames needs contiguous int64 device offsets and frame numbers")
+    if frame_idx.numel() != out.shape[0] or frame_off.numel() < 2:
+        raise ValueError("pack_frames shape mismatch")
+    hip.call("pack_frames", pts, frame_off, frame_idx, frame_idx.numel(), out.shape[1], int(max_n), float(keep_p),
+             int(seed) & 0xFFFFFFFFFFFFFFFF, out)
+    return out
+
+
 def relu_mask_(G, H):
     G, H = _rows(G), _rows(H)
     hip.call("relu_mask", G, G.stride(0), H, H.stride(0), G.shape[0], G.shape[1])

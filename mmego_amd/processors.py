@@ -17,7 +17,7 @@ import torch
 
 from . import blocks, hip, ops
 from .config import Config, ConfigDemo
-from .data import DeviceArrays, PosePC, batch_indices
+from .data import DeviceArrays, FrameStore, PosePC, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam
 from .nets_local import UpperNetwlocal
@@ -89,6 +89,36 @@ class _Base:
         if self.world > 1:
             sync_replicas(model, self.pg)
             model.seed_counter().bitwise_xor_((self.rank * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF)
+
+    def _frame_store_options(self):
+        """(--window_jitter, --point_keep): either one makes the training split a data.FrameStore instead of DeviceArrays."""
+        keep = getattr(self.cfg, "point_keep", None)
+        return bool(getattr(self.cfg, "window_jitter", False)), None if keep is None else float(keep)
+
+    def _load_splits(self):
+        """The two PosePC splits; the training one keeps its per-frame clouds when a FrameStore is going to serve it."""
+        jitter, keep = self._frame_store_options()
+        self.train_data = PosePC(batch_length=self.frame_no, keep_frames=jitter or keep is not None)
+        self.test_data = PosePC(train=False, batch_length=self.frame_no)
+        self._epoch = 0               # (the epoch _epochs is in: what a FrameStore draws its window starts and packing seeds from)
+
+    def _train_arrays(self):
+        """The training split in HBM, uploaded at the first training pass: finished windows (DeviceArrays: the reference's windows, the
+        loader's packing), or -- --window_jitter / --point_keep -- frames (FrameStore), told which epoch begins."""
+        if self._train_dev is None:
+            jitter, keep = self._frame_store_options()
+            if not jitter and keep is None:
+                self._train_dev = DeviceArrays(self.train_data, self.device)
+            else:
+                fs = self._train_dev = FrameStore(self.train_data, self.device, jitter=jitter, point_keep=keep,
+                                                  seed=getattr(self.cfg, "seed", None) or 0)
+                if self.rank == 0:
+                    print("[mmego_amd] frame store: %d frames, %d valid window starts (%d training windows, %d of them movable)%s%s"
+                          % (fs.F, len(fs.valid_starts()), fs.n, fs.n_movable, "; window jitter on" if jitter else "",
+                             "" if keep is None else "; clouds re-drawn per minibatch, point_keep %g" % keep))
+        if isinstance(self._train_dev, FrameStore):
+            self._train_dev.begin_epoch(self._epoch)
+        return self._train_dev
 
     def _log_mode(self):
         return "a" if getattr(self.cfg, "resume_path", None) else "w"     # --resume continues the logs instead of truncating them
@@ -198,6 +228,7 @@ class _Base:
         names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
         for epoch in range(self.start_epoch, self.num_epochs):
             print("epoch: {}".format(epoch + 1))
+            self._epoch = epoch
             trained = train()
             report_grad_norms(self.rank, [(names[o], self._opts[o]) for o, _ in TRAINED if o in self._opts])
             # a persistent rnn_slow launch of the frozen IMU_Net whose workgroups were not co-resident reports it only through a
@@ -273,8 +304,7 @@ class _StageTrainer(_Base):
                              "frozen in stage 3)")
         self.model_IMU = self._load_imu()
         self._opts = {}
-        self.train_data = PosePC(batch_length=self.frame_no)
-        self.test_data = PosePC(train=False, batch_length=self.frame_no)
+        self._load_splits()
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
         self.lossfile = open(os.path.join(rep, "log-loss.txt"), self._log_mode()) if self.rank == 0 else None
         self.evalfile = open(os.path.join(rep, "log-eval.txt"), self._log_mode()) if self.rank == 0 else None
@@ -322,8 +352,7 @@ class _StageTrainer(_Base):
         if self._log is None:
             self._log = torch.zeros((64, 2), dtype=torch.float32, device=self.device)
         nlog, scales = 0, []
-        if self._train_dev is None:                                     # the training set lives in HBM (51 MB for Sample_data)
-            self._train_dev = DeviceArrays(self.train_data, self.device)
+        self._train_arrays()                                            # the training set lives in HBM (51 MB for Sample_data)
         todo = [idx[shard_of(self.rank, self.world)]                    # this rank's shard of every global minibatch
                 for idx in batch_indices(len(self.train_data), self.batchsize * self.world, True, self._rng)]
         primed = None                                                   # number of the minibatch whose head poses are ready
@@ -624,8 +653,7 @@ class ImuTrainer(_Base):
             self.model_IMU.load(cfg.model_IMU_path)
         self._dp_start(self.model_IMU)
         self._opts = {}
-        self.train_data = PosePC(batch_length=self.frame_no)
-        self.test_data = PosePC(train=False, batch_length=self.frame_no)
+        self._load_splits()
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
         self.lossfile = open(os.path.join(rep, "log-loss.txt"), self._log_mode()) if self.rank == 0 else None
         self._rng = np.random.RandomState(1234)
@@ -638,8 +666,7 @@ class ImuTrainer(_Base):
         self.model_IMU.train()
         losses = []
         pg = self.pg
-        if self._train_dev is None:
-            self._train_dev = DeviceArrays(self.train_data, self.device)
+        self._train_arrays()
         for idx in batch_indices(len(self.train_data), self.batchsize * self.world, True, self._rng):
             idx = idx[shard_of(self.rank, self.world)]
             if len(idx) == 0:       # nothing for this rank in a short last global minibatch: zero gradient, same update
