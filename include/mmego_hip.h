@@ -130,6 +130,25 @@ int mmego_gather_rows(void* stream, const float* X, long nsrc, long W, const lon
  * frame_idx lying inside the offset array. */
 int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
                       int pc_no, int max_n, float keep_p, unsigned long long seed, float* out);
+/* Dense inference (blend.hip; processors.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
+ * src [nrows][C] contiguous; the cover of frame f = 0 .. F-1 is the CSR list k in [cov_off[f], cov_off[f+1]) (int64 offsets) of source
+ * rows cov_row[k] (int32) with weights cov_w[k]:
+ *   dst[f, c] = (sum_k w_k src[row_k, c]) / (sum_k w_k), c < C; the columns of dst[f] (row stride ldd) beyond C are not touched;
+ *   spread[f] (spread may be NULL; needs C % 3 == 0, J = C / 3) = sqrt(sum_k w_k sum_j |x_kj - m_j|^2 / (J sum_k w_k)), x_kj the j-th
+ *               3-vector of row_k and m the blend as a double, before its rounding: the weighted RMS distance of the windows' joints
+ *               from the blended joint -- how much the windows disagree about the frame.
+ * Products and sums in double in CSR order, the J joints' sum in a fixed tree, one float store: a frame covered once receives its row
+ * bit for bit ((w x) / w is exact in double for fp32 w, x), and two launches give the same bits.  An empty list, or weights that sum to
+ * zero, give a zero row and spread 0; no NaN is made here.  One wave per frame, one lane per column: C <= 64.  Refused: a null src,
+ * cov_off, cov_row, cov_w or dst, F < 1 or >= 2^31, C outside [1, 64], ldd < C, spread with C % 3 != 0.  The caller answers for cov_off
+ * ascending from 0 and for cov_row lying in [0, nrows) (ops.blend_windows checks both on the host); an entry outside is skipped. */
+int mmego_blend_windows(void* stream, const float* src, long nrows, int C, const long long* cov_off, const int* cov_row,
+                        const float* cov_w, long F, float* dst, long ldd, float* spread);
+/* out[p, c] = sum over the rows r = p (mod period) of X[r, c], p < period, c < C <= 64: a per-row table of windows of `period` frames
+ * folded by position in the window ([W*T][43] joint errors -> [T][43]).  rows % period == 0, 1 <= period <= 64, ldx >= C, ldo >= C.
+ * One workgroup per phase: its rows are dealt round-robin to 16 waves, each sums its share in ascending order in double, the 16
+ * partial sums are added in wave order, one float store (two launches give the same bits; no workspace, no atomics). */
+int mmego_colsum_phase(void* stream, const float* X, long ldx, long rows, int C, int period, float* out, long ldo);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

@@ -3,7 +3,7 @@
 
   python main.py --train --network {IMU_Net,Upper_Net,Lower_Net} [--epochs N --lr F --batch_size N --device cuda:0
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
-  python main.py --infer [--vis]
+  python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --save_pred PATH]]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -19,7 +19,10 @@ and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-a
 rotation, shift and scale, PCK and the acceleration error on the device -- pose error apart from placement error; printed only, the log
 files keep their format), --window_jitter (every epoch each training window moves to a valid start within +-(frame_no-1) frames of its
 own) and --point_keep P (every minibatch's clouds are packed afresh on the device, each radar return kept with probability P): what a
-run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched.  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched; --infer --dense [--stride S --blend
+{mean,triangle} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
+apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
+by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -97,7 +100,40 @@ def build_parser():
                    help="--train --network Upper_Net / Lower_Net: every minibatch's point clouds are packed afresh on the device from the "
                         "raw radar returns, each return kept with probability P in (0, 1] (1: only the packing is re-drawn); draws are "
                         "functions of (--seed, epoch, minibatch).  Evaluation stays on the loader's packing")
+    p.add_argument("--dense", action="store_true",
+                   help="--infer only: sliding-window inference over whole recordings -- overlapping frame_no-frame windows --stride frames "
+                        "apart (tail-anchored, plus one window at every recording's head), every frame's pose blended on the device from "
+                        "the windows that cover it.  Prints the reference's five lines for the blend, the single-window figures, the error "
+                        "by position in the window, the windows' mean disagreement and the plan's counts (--metrics full: the aligned lines, "
+                        "the acceleration error per recording, across window seams); --batch_size is the window minibatch (default 64)")
+    p.add_argument("--stride", type=int, help="--dense: frames between window starts, in [1, frame_no] (default: frame_no // 2)")
+    p.add_argument("--blend", type=str, choices=["mean", "triangle"], default=None,
+                   help="--dense: weight of a window's prediction for a frame -- mean (default: 1) or triangle (min(p + 1, frame_no - p) at "
+                        "position p: the window's middle counts most)")
+    p.add_argument("--save_pred", type=str,
+                   help="--dense: write the per-frame arrays to this .npz -- pred [F, 21, 3] (NaN where no window covers the frame: "
+                        "recordings shorter than frame_no), covered, spread, recording, frame_in_recording, target, stride, blend, frame_no")
     return p
+
+
+def check_dense(parser, args):
+    """--dense is a mode of --infer; --stride, --blend and --save_pred belong to it."""
+    if not args.dense:
+        for flag in ("stride", "blend", "save_pred"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % flag)
+        return
+    if args.train:
+        parser.error("--dense does not go with --train: it is an inference pass (training on the dense plan is not provided)")
+    if not args.infer:
+        parser.error("--dense goes with --infer only")
+    if args.vis:
+        parser.error("--dense does not go with --vis: it writes its skeletons with --save_pred instead")
+    if args.stride is not None and not 1 <= args.stride <= Config.frame_no:
+        parser.error("--stride has to lie in [1, %d] (frame_no): a larger one leaves frames between windows uncovered, got %d"
+                     % (Config.frame_no, args.stride))
+    if args.batch_size is not None and args.batch_size < 1:
+        parser.error("--batch_size is the window minibatch of the dense pass: at least 1, got %d" % args.batch_size)
 
 
 def check_frame_store(parser, args):
@@ -200,6 +236,7 @@ def check_finetune(parser, args, world):
     check_imu_dropout(parser, args)
     check_clip_grad_norm(parser, args)
     check_frame_store(parser, args)
+    check_dense(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -249,6 +286,8 @@ def apply_overrides(args):
     for c in both:
         c.upper_variant = args.upper_variant or "global"
         c.metrics = args.metrics
+    ConfigDemo.dense, ConfigDemo.stride, ConfigDemo.blend = bool(args.dense), args.stride, args.blend or "mean"
+    ConfigDemo.save_pred, ConfigDemo.dense_batch_size = args.save_pred, args.batch_size
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:
@@ -286,6 +325,8 @@ def main(argv=None):
         processor = MMEgo()
         if args.vis:
             processor.eval_all_skeleton()
+        elif args.dense:
+            processor.eval_dense()
         else:
             processor.eval_model()
     if torch.distributed.is_initialized():

@@ -67,3 +67,8 @@ class Config(_Common):
 class ConfigDemo(_Common):
     Idx = 1
     batch_per_action = 3
+    dense = False               # --dense: sliding-window inference over whole recordings (processors.dense_infer)
+    stride = None               # --stride: frames between window starts (None: frame_no // 2)
+    blend = "mean"              # --blend: mean or triangle
+    save_pred = None            # --save_pred: .npz of the per-frame skeletons
+    dense_batch_size = None     # --batch_size under --dense: windows per minibatch (None: 64)

@@ -437,6 +437,115 @@ class FrameStore:
         return out
 
 
+BLENDS = ("mean", "triangle")
+
+
+class DensePlan:
+    """Sliding-window inference, host side: overlapping ``T``-frame windows at a stride ``S`` in [1, T] over recordings of the given
+    lengths (frame-major: recording i owns the global frames [a_i, b_i)), and for every frame the list of window rows that cover it.
+
+      windows   a recording shorter than T has none (its frames stay uncovered); otherwise the starts are b - T - k S, k = 0, 1, ...
+                while >= a, united with a: tail-anchored like PosePC's grid, so at S = T they are PosePC's windows plus one head window
+                per recording whose length is no multiple of T.  Windows are numbered recording by recording, ascending start.
+      starts    [W] first global frame of every window;  recording [W] its recording
+      row_frame [W T] int64: the global frame of window row w T + p
+      cover     of frame f, as CSR: cov_off [F + 1] int64, cov_row [nnz] int32 (rows w T + p, ascending w within a frame), cov_w [nnz]
+                fp32 (blend "mean": 1; "triangle": min(p + 1, T - p), the window's middle counts most); covered [F] the counts.
+    Every frame of a recording of at least T frames is covered, at most ceil(T / S) + 1 times."""
+
+    def __init__(self, lengths, T, stride, blend="mean"):
+        T, S = int(T), int(stride)
+        if T < 1 or not 1 <= S <= T:
+            raise ValueError("dense windows: the stride has to lie in [1, %d] (a larger one leaves frames between windows uncovered), got %r"
+                             % (T, stride))
+        if blend not in BLENDS:
+            raise ValueError("blend: %r is not one of %s" % (blend, ", ".join(BLENDS)))
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        self.T, self.stride, self.blend = T, S, blend
+        self.F = F = int(lengths.sum())
+        self.rec_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        starts, recs = [], []
+        for i, (a, b) in enumerate(zip(self.rec_off[:-1], self.rec_off[1:])):
+            if b - a < T:
+                continue
+            s = np.arange(b - T, a - 1, -S, dtype=np.int64)[::-1]
+            if s[0] != a:
+                s = np.concatenate([[a], s])
+            starts.append(s)
+            recs.append(np.full(len(s), i, dtype=np.int64))
+        self.starts = np.concatenate(starts).astype(np.int64) if starts else np.zeros(0, np.int64)
+        self.recording = np.concatenate(recs) if recs else np.zeros(0, np.int64)
+        self.W = W = len(self.starts)
+        self.row_frame = np.ascontiguousarray((self.starts[:, None] + np.arange(T, dtype=np.int64)).ravel())
+        if W * T >= 2 ** 31:
+            raise ValueError("dense windows: %d window rows do not fit the cover's int32 row numbers" % (W * T))
+        order = np.argsort(self.row_frame, kind="stable")           # rows by frame; within a frame in row order = ascending window
+        self.cov_row = np.ascontiguousarray(order.astype(np.int32))
+        self.covered = np.bincount(self.row_frame, minlength=F).astype(np.int64)
+        self.cov_off = np.concatenate([[0], np.cumsum(self.covered)]).astype(np.int64)
+        p = self.cov_row % T
+        self.cov_w = (np.ones(len(p), np.float32) if blend == "mean" else np.minimum(p + 1, T - p).astype(np.float32))
+        self.max_cover = int(self.covered.max()) if F else 0
+        self.frame_rec = np.repeat(np.arange(len(lengths), dtype=np.int64), lengths)
+        self.frame_in_recording = np.arange(F, dtype=np.int64) - self.rec_off[:-1][self.frame_rec]
+
+
+class DenseWindows(DensePlan):
+    """The DensePlan of a PosePC(train=False, vis=True, keep_frames=True, batch_length=T) with the recordings resident in HBM frame-major
+    (the five fields of FrameStore.src, uploaded once) and windows assembled on the device from the plan's starts.  Every frame keeps the
+    one packed cloud the loader drew for it, whichever window it is served in: a run is a function of its inputs alone."""
+
+    FIELDS = DeviceArrays.FIELDS
+
+    def __init__(self, dataset, device, stride, blend="mean"):
+        import torch
+        if getattr(dataset, "frame_packed_", None) is None:
+            raise ValueError("DenseWindows needs the per-frame clouds: build the PosePC with keep_frames=True")
+        if not dataset.vis:
+            raise ValueError("DenseWindows serves whole recordings: build the PosePC with train=False, vis=True")
+        F = len(dataset.frame_npts_)
+        nrec = int(dataset.frame_rec_.max()) + 1 if F else 0
+        super().__init__(np.bincount(np.asarray(dataset.frame_rec_, dtype=np.int64), minlength=nrec), dataset.frame_no, stride, blend)
+        self.device, self.pc_no = device, int(dataset.pc_no)
+        f32 = lambda a, rows: torch.as_tensor(np.ascontiguousarray(a).reshape(rows, -1), dtype=torch.float32).to(device)
+        T = self.T
+        self.shape = {"data": (T, self.pc_no, 6), "target": (T,) + tuple(np.shape(dataset.frame_key_)[1:]),
+                      "skl": tuple(np.shape(dataset.frame_bones_)), "imu": (T,) + tuple(np.shape(dataset.frame_imu_)[1:]),
+                      "R_R0R": (T,) + tuple(np.shape(dataset.frame_R_)[1:])}
+        self.src = {"imu": f32(dataset.frame_imu_, F), "target": f32(dataset.frame_key_, F), "R_R0R": f32(dataset.frame_R_, F),
+                    "data": f32(dataset.frame_packed_, F), "skl": f32(dataset.frame_bones_, 1)}
+        self.width = {name: self.src[name].shape[1] for name in self.src}
+        self._out, self._zero_idx = {}, {}
+
+    def frame_index(self, index):
+        """Host: the frame numbers [len(index) * T] of the windows ``index``."""
+        index = np.asarray(index, dtype=np.int64)
+        if len(index) and (index.min() < 0 or index.max() >= self.W):
+            raise IndexError("window number outside the plan's %d windows" % self.W)
+        return np.ascontiguousarray((self.starts[index][:, None] + np.arange(self.T)).ravel())
+
+    def gather(self, index):
+        """index: int array of window numbers -> dict of device tensors [len(index), T, ...] like DeviceArrays.gather (buffers reused per
+        batch size; `data` is a fresh copy every call: the nets transform it in place)."""
+        import torch
+        from . import ops
+        fidx, B = torch.as_tensor(self.frame_index(index)).to(self.device), len(index)
+        out = {}
+        for name, _ in self.FIELDS:
+            dst = self._out.get((name, B))
+            if dst is None:
+                dst = self._out[(name, B)] = torch.empty((B,) + self.shape[name], dtype=torch.float32, device=self.device)
+            if name == "skl":                                   # one bone set for the whole recording campaign: row 0, B times
+                z = self._zero_idx.get(B)
+                if z is None:
+                    z = self._zero_idx[B] = torch.zeros(B, dtype=torch.int64, device=self.device)
+                ops.gather_rows(self.src["skl"], z, dst.view(B, -1))
+            else:
+                ops.gather_rows(self.src[name], fidx, dst.view(B * self.T, self.width[name]))
+            out[name] = dst
+        return out
+
+
 class ArraySplit:
     """A data split given as arrays (what PosePC exposes to the trainers: `_items` in the reference loader's tuple order
     data, target, skl, imu, ground, foot_contact, R_R0R, t_R0R -- Dataset_sample.py:264-277).  For callers that hold windows

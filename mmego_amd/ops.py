@@ -428,6 +428,66 @@ def pose_accel_errors(upper, lower, target, Acc):
     return Acc
 
 
+BLEND_MAX_C = 64            # blend.hip BL_MAX_C: one lane per column
+
+
+def _cover_on(cover, nrows, device):
+    """The CSR cover (a data.DenseWindows / data.DensePlan, or its three host arrays cov_off, cov_row, cov_w) checked on the HOST against
+    a source of ``nrows`` rows -- offsets ascending from 0 to the list's length, every row in [0, nrows) -- and uploaded (a plan object
+    keeps its device copies).  -> (off, row, w, F)."""
+    import numpy as np
+    plan = cover if hasattr(cover, "cov_off") else None
+    off, row, w = (plan.cov_off, plan.cov_row, plan.cov_w) if plan is not None else cover
+    off, row, w = np.asarray(off), np.asarray(row), np.asarray(w)
+    if off.dtype != np.int64 or row.dtype != np.int32 or w.dtype != np.float32 or off.ndim != 1 or row.ndim != 1 or w.ndim != 1:
+        raise TypeError("blend_windows: the cover is int64 offsets, int32 rows and fp32 weights")
+    if len(off) < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != len(row) or len(row) != len(w):
+        raise ValueError("blend_windows: the cover's offsets do not ascend from 0 to the length of its row list")
+    if len(row) and (row.min() < 0 or row.max() >= nrows):
+        raise IndexError("blend_windows: the cover names rows outside the %d source rows" % nrows)
+    cache = plan.__dict__.setdefault("_cover_dev", {}) if plan is not None and hasattr(plan, "__dict__") else {}
+    dev = cache.get(str(device))
+    if dev is None:
+        one = lambda a: torch.as_tensor(np.ascontiguousarray(a) if len(a) else np.zeros(1, a.dtype)).to(device)     # (an empty list: still an address)
+        dev = cache[str(device)] = (one(off), one(row), one(w))
+    return dev + (len(off) - 1,)
+
+
+def blend_windows(src, cover, dst, spread=None):
+    """dst[f, :C] = the weighted mean of the rows of src [nrows, C] that cover frame f (mmego_blend_windows: double inside, CSR order; a
+    frame without cover gets zeros); spread [F] (optional, C % 3 == 0): the weighted RMS distance of those rows' joints from the blend.
+    ``cover``: the plan object (cov_off, cov_row, cov_w as host arrays) or the three arrays; it is checked on the host first.  dst may be
+    wider than C: its other columns stay."""
+    _chk(src, 2)
+    dst = _rows(dst)
+    nrows, C = src.shape
+    if not src.is_contiguous() or not 1 <= C <= BLEND_MAX_C:
+        raise ValueError("blend_windows needs a contiguous source of 1 to %d columns, got %s" % (BLEND_MAX_C, tuple(src.shape)))
+    off, row, w, F = _cover_on(cover, nrows, src.device)
+    if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
+        raise ValueError("blend_windows: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
+    if spread is not None:
+        _chk(spread, 1)
+        if spread.numel() != F or not spread.is_contiguous() or C % 3:
+            raise ValueError("blend_windows: spread is one contiguous float per frame, of rows of 3-vectors")
+    hip.call("blend_windows", src, nrows, C, off, row, w, F, dst, max(dst.stride(0), C), spread)
+    return dst
+
+
+def colsum_phase(X, period, out):
+    """out[p, c] = sum of X[r, c] over the rows r = p (mod period) (mmego_colsum_phase): X [rows, C <= 64], rows % period == 0,
+    out [period, >= C]."""
+    X, out = _rows(X), _rows(out)
+    rows, C = X.shape
+    period = int(period)
+    if not 1 <= period <= 64 or rows < 1 or rows % period or not 1 <= C <= BLEND_MAX_C:
+        raise ValueError("colsum_phase: %d rows of %d columns do not fold by a period of %d" % (rows, C, period))
+    if out.shape[0] != period or out.shape[1] < C:
+        raise ValueError("colsum_phase: out is %s for %d phases of %d columns" % (tuple(out.shape), period, C))
+    hip.call("colsum_phase", X, max(X.stride(0), C), rows, C, period, out, max(out.stride(0), C))
+    return out
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

@@ -601,6 +601,147 @@ def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuf
     return (eval_loss, np.asarray([eval_loss / cfg.joint_num_lower]), float(np.mean(accu_l)), float(np.mean(accu_lo)), accu_ll, angle_ll), summary
 
 
+def _error_summary(sums, n, prefix=""):
+    """The reference's five figures from the 43 column sums of mmego_pose_errors over n rows (float64), keys prefixed."""
+    m = sums / n
+    return {prefix + "all_cm": float(m[:21].mean()) * 100, prefix + "upper_cm": float(m[41]) * 100, prefix + "lower_cm": float(m[42]) * 100,
+            prefix + "rot_deg": float(m[21:41].mean()), prefix + "per_joint_cm": m[:21] * 100}
+
+
+def _accel_over_sequences(dev, up, lo, tgt, spans):
+    """Acceleration error over sequences of different lengths: one mmego_pose_accel_errors launch (B = 1, T = its length) per span
+    [r0, r1) of the row tensors up [., 45], lo [., 24], tgt [., 63]; spans shorter than 3 rows have no second difference and are left
+    out.  -> the mean over ALL interior frames (every sequence weighs by its length - 2) per joint, float64 [21] in metres, or None."""
+    spans = [(int(r0), int(r1)) for r0, r1 in spans if r1 - r0 >= 3]
+    if not spans:
+        return None
+    Acc = torch.empty((len(spans), 21), dtype=torch.float32, device=dev)
+    for i, (r0, r1) in enumerate(spans):
+        n = r1 - r0
+        ops.pose_accel_errors(up[r0:r1].view(1, n, 15, 3), lo[r0:r1].view(1, n, 8, 3), tgt[r0:r1].view(1, n, 21, 3), Acc[i:i + 1])
+    wt = np.asarray([r1 - r0 - 2 for r0, r1 in spans], dtype=np.float64)
+    return (Acc.cpu().numpy().astype(np.float64) * wt[:, None]).sum(axis=0) / wt.sum()
+
+
+def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference"):
+    """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
+    data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
+    grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
+    (mmego_blend_windows), and the reference's error kernels run on the blended frames and on the unblended window rows.
+    -> (summary, arrays).  summary: all_cm, upper_cm, lower_cm, rot_deg, per_joint_cm of the blend as means over the covered frames; the
+    same under single_ for the window rows; position_cm [T] the mean 21-joint error by position in the window (mmego_colsum_phase);
+    spread_cm the mean disagreement of the windows about a frame; windows, frames, covered_frames, max_cover.  metrics="full": also
+    aligned_summary's keys for the covered blended frames, with accel_cm taken PER RECORDING over its stitched blended frames (the first
+    figure that sees window seams), and single_accel_cm for the stitched reference windows when stride == frame_no (else None).
+    arrays (host): pred [F, 21, 3] (lower overwrites the shared hips; NaN where covered == 0), covered, spread, recording,
+    frame_in_recording, target; the two nets' blended joints before assembly, upper [F, 15, 3] and lower [F, 8, 3] (zeros where uncovered);
+    and, still on the device, win_up [W T, 45], win_lo [W T, 24] and the plan itself.
+    The figures come down in one read; the per-frame arrays in one each."""
+    from .data import DenseWindows
+    if metrics not in METRICS:
+        raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
+    dev = base.device
+    plan = DenseWindows(dataset, dev, stride, blend)
+    W, T, F = plan.W, plan.T, plan.F
+    if W == 0:
+        raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, T))
+    nets = [n for n in (imu_net, upper_net, lower_net) if n is not None]
+    was_training = [n.training for n in nets]
+    for n in nets:
+        n.eval()
+    try:
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics)
+    finally:
+        for n, tr in zip(nets, was_training):
+            n.train(tr)
+
+
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics):
+    """dense_infer behind its argument checks: the nets are in eval mode."""
+    dev = base.device
+    W, T, F = plan.W, plan.T, plan.F
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    win_up, win_lo = f32(W * T, 45), f32(W * T, 24)
+    with torch.no_grad():
+        state = {}
+        for s in range(0, W, batch_size):
+            idx = np.arange(s, min(s + batch_size, W))
+            b = plan.gather(idx)                                   # fresh copies: the nets transform `data` in place (Q1)
+            B = len(idx)
+            if B not in state:
+                state[B] = (torch.zeros((6, B, 64), device=dev), torch.zeros((6, B, 64), device=dev))
+            h0, c0 = state[B]
+            tgt, body = b["target"], b["skl"]
+            R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
+            up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]
+            lo, _ = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
+            win_up[s * T:(s + B) * T].copy_(up.reshape(B * T, 45))
+            win_lo[s * T:(s + B) * T].copy_(lo.reshape(B * T, 24))
+        # every frame from its windows
+        up_f, lo_f, spread = f32(F, 45), f32(F, 24), f32(F)
+        ops.blend_windows(win_up, plan, up_f, spread)
+        ops.blend_windows(win_lo, plan, lo_f)
+        tgt_f = plan.src["target"]                                 # [F, 63]
+        cov = np.flatnonzero(plan.covered)
+        Fc = len(cov)
+        up_c, lo_c, tgt_c, spread_c = up_f, lo_f, tgt_f, spread.view(F, 1)
+        if Fc < F:                                                 # zero rows never enter a mean
+            cidx = torch.as_tensor(cov).to(dev)
+            up_c, lo_c, tgt_c = (ops.gather_rows(x, cidx, f32(Fc, x.shape[1])) for x in (up_f, lo_f, tgt_f))
+            spread_c = ops.gather_rows(spread.view(F, 1), cidx, f32(Fc, 1))
+        full = metrics == "full"
+        WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
+        log = torch.zeros((3 + T, max(43, WA)), dtype=torch.float32, device=dev)
+        E = f32(Fc, 43)
+        hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
+        ops.colsum(E, log[0, :43])
+        ops.colsum(spread_c, log[1, :1])
+        # the unblended window rows: the same kernel, then by position in the window
+        tgt_w = ops.gather_rows(tgt_f, torch.as_tensor(plan.row_frame).to(dev), f32(W * T, 63))
+        Ew = f32(W * T, 43)
+        hip.call("pose_errors", win_up, win_lo, tgt_w, W * T, Ew)
+        ops.colsum(Ew, log[2, :43])
+        ops.colsum_phase(Ew, T, log[3:, :43])
+        if full:
+            thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
+            A = f32(Fc, WA)
+            ops.pose_errors_aligned(up_c.view(Fc, 15, 3), lo_c.view(Fc, 8, 3), tgt_c.view(Fc, 21, 3), thr, A)
+            alog = torch.zeros(WA, dtype=torch.float32, device=dev)
+            ops.colsum(A, alog)
+    out = log.cpu().numpy().astype(np.float64)                     # the figures' one device -> host read
+    summary = _error_summary(out[0, :43], Fc)
+    summary.update(_error_summary(out[2, :43], W * T, "single_"))
+    summary["position_cm"] = out[3:, :21].mean(axis=1) / W * 100
+    summary["spread_cm"] = float(out[1, 0]) / Fc * 100
+    summary.update(windows=W, frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=blend, frame_no=T)
+    if full:
+        spans = [(a, b) for a, b in zip(plan.rec_off[:-1], plan.rec_off[1:]) if b - a >= T]      # the covered recordings, whole
+        acc = _accel_over_sequences(dev, up_f, lo_f, tgt_f, spans)
+        m = np.concatenate([alog.cpu().numpy().astype(np.float64) / Fc, np.full(21, np.nan) if acc is None else acc])[None]
+        summary.update(aligned_summary(m, 21))
+        summary["single_accel_cm"] = None
+        if plan.stride == T:
+            # the reference's windows of a recording are its last len // T windows: consecutive rows of the window tensors
+            first = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="left")
+            last = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="right")
+            n_ref = (plan.rec_off[1:] - plan.rec_off[:-1]) // T
+            acc = _accel_over_sequences(dev, win_up, win_lo, tgt_w, [((l - n) * T, l * T) for f, l, n in zip(first, last, n_ref) if l > f])
+            summary["single_accel_cm"] = None if acc is None else float(acc.mean()) * 100
+    blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
+    up_h, lo_h = up_f.cpu().numpy().reshape(F, 15, 3), lo_f.cpu().numpy().reshape(F, 8, 3)
+    pred = np.zeros((F, 21, 3), dtype=np.float32)
+    pred[:, list(base.cfg.upper_joint_map)] = up_h
+    pred[:, list(base.cfg.lower_joint_map)] = lo_h                 # lower overwrites the shared hips (Demo_test.py:121-123)
+    pred[plan.covered == 0] = np.nan
+    arrays = dict(pred=pred, covered=plan.covered.astype(np.int32), spread=spread.cpu().numpy(), recording=plan.frame_rec,
+                  frame_in_recording=plan.frame_in_recording, target=tgt_f.cpu().numpy().reshape(F, 21, 3),
+                  upper=up_h, lower=lo_h, win_up=win_up, win_lo=win_lo, plan=plan)
+    return summary, arrays
+
+
+DENSE_SAVED = ("pred", "covered", "spread", "recording", "frame_in_recording", "target")      # --save_pred: the per-frame arrays of the file
+
+
 class Evaluator(_Base):
     """`python main.py --infer` (reference Processor/Test/Demo_test.MMEgo.eval_model)."""
 
@@ -610,7 +751,51 @@ class Evaluator(_Base):
         self.model = LowerNet(hidden_dim=64).to(self.device).eval()
         self.model_IMU = self._load_imu()
         self.Upper_net = self._new_upper(cfg.model_upper_path).eval()           # (--upper_variant)
-        self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no)
+        # (--dense: the per-frame clouds stay; nothing else about the object depends on the keyword)
+        self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no, keep_frames=bool(getattr(cfg, "dense", False)))
+
+    def eval_dense(self):
+        """`--infer --dense [--stride S --blend B --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
+        (the reference's five lines for the blend first), the per-frame skeletons written when asked for.  -> the summary."""
+        cfg = self.cfg
+        self.model.load(cfg.model_lower_path)
+        self.model.eval()
+        stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
+        s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
+                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics())
+        print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
+        print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
+        print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
+        print("Average Joint Rotation Error(°): {}".format(s["rot_deg"]))
+        print("Per Joint Localization Error(cm): {}".format(s["per_joint_cm"]))
+        print("Single-window (unblended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+            s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
+        print("Error by window position(cm): {}".format(s["position_cm"]))
+        print("Window Disagreement(cm): {}".format(s["spread_cm"]))
+        print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
+            s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
+        if self._metrics() == "full":
+            self._print_aligned(s)
+            print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
+        self.last_metrics = s
+        path = getattr(cfg, "save_pred", None)
+        if path:
+            np.savez(path, stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]),
+                     **{k: arrays[k] for k in DENSE_SAVED})
+            print("Per-frame skeletons saved in {}".format(path))
+        return s
+
+    def _print_aligned(self, s):
+        for name, parts in (("Root-relative", "root_rel"), ("Rigid-aligned", "rigid"), ("Procrustes-aligned (PA-MPJPE)", "pa")):
+            print("{} Joint Error(cm): {} (upper {}, lower {})".format(name, s[parts + "_cm"], s[parts + "_upper_cm"], s[parts + "_lower_cm"]))
+        print("Alignment Rotation(°): {}".format(s["align_rot_deg"]))
+        print("Alignment Shift(cm): {}".format(s["align_shift_cm"]))
+        print("Procrustes Scale: {}".format(s["pa_scale"]))
+        for c, v in s["pck"].items():
+            print("PCK@{:g}cm: {}".format(c, v))
+        print("Acceleration Error(cm/frame^2): {}".format(s["accel_cm"]))
+        print("Per Joint Root-relative Error(cm): {}".format(s["per_joint_root_rel_cm"]))
+        print("Per Joint Procrustes-aligned Error(cm): {}".format(s["per_joint_pa_cm"]))
 
     def eval_model(self):
         self.model.load(self.cfg.model_lower_path)
@@ -623,16 +808,7 @@ class Evaluator(_Base):
         print("Per Joint Localization Error(cm): {}".format(s["per_joint_cm"]))
         if self._metrics() == "full":
             self.last_metrics = s
-            for name, parts in (("Root-relative", "root_rel"), ("Rigid-aligned", "rigid"), ("Procrustes-aligned (PA-MPJPE)", "pa")):
-                print("{} Joint Error(cm): {} (upper {}, lower {})".format(name, s[parts + "_cm"], s[parts + "_upper_cm"], s[parts + "_lower_cm"]))
-            print("Alignment Rotation(°): {}".format(s["align_rot_deg"]))
-            print("Alignment Shift(cm): {}".format(s["align_shift_cm"]))
-            print("Procrustes Scale: {}".format(s["pa_scale"]))
-            for c, v in s["pck"].items():
-                print("PCK@{:g}cm: {}".format(c, v))
-            print("Acceleration Error(cm/frame^2): {}".format(s["accel_cm"]))
-            print("Per Joint Root-relative Error(cm): {}".format(s["per_joint_root_rel_cm"]))
-            print("Per Joint Procrustes-aligned Error(cm): {}".format(s["per_joint_pa_cm"]))
+            self._print_aligned(s)
         return out
 
     def eval_all_skeleton(self):
