@@ -149,6 +149,33 @@ int mmego_blend_windows(void* stream, const float* src, long nrows, int C, const
  * One workgroup per phase: its rows are dealt round-robin to 16 waves, each sums its share in ascending order in double, the 16
  * partial sums are added in wave order, one float store (two launches give the same bits; no workspace, no atomics). */
 int mmego_colsum_phase(void* stream, const float* X, long ldx, long rows, int C, int period, float* out, long ldo);
+/* The same blend with every bone's length kept (blend_bones.hip; processors.dense_infer under blend_space="bones").  src [nrows][3 J]
+ * holds rigid skeletons of J joints (3-vectors x_j) and the cover is mmego_blend_windows'; bones [NB][2] (int32, on the device) lists
+ * (child, parent) joint numbers in walk order -- every joint a child at most once, every parent a root (a joint that is no bone's child)
+ * or an earlier bone's child -- and bone_len [NB] (float, on the device) the lengths L_b.  Per frame, with its valid entries k (those
+ * whose row lies in [0, nrows)) in CSR order, their weights w_k and W = sum_k w_k:
+ *   no valid entry, or W == 0: a zero row, spread 0, fallback 0;   exactly one valid entry: its row, bit for bit;   otherwise
+ *   a root r:            pos_r = (sum_k w_k x_kr) / W, mmego_blend_windows' own arithmetic: those columns carry the same bits;
+ *   bone b = (c, p):     s = sum_k w_k (x_kc - x_kp), every difference formed in double;
+ *                        u = s / |s| where |s| > 1e-9 W L_b (and > 0), else -- the FALLBACK, counted in fallback[f] -- the normalised
+ *                        difference x_kc - x_kp of the entry with the largest weight (the first such on ties), or the zero vector where
+ *                        that difference is zero too;   pos_c = pos_p + L_b u, the bones taken in their listed order;
+ *   dst[f, 3 j + i] = (float) pos_j[i]: positions stay doubles until this one store; the columns of dst[f] beyond 3 J are not touched;
+ *   spread[f] (may be NULL) = mmego_blend_windows' spread against pos, the rigid positions before their rounding;
+ *   fallback[f] (int32, may be NULL) = the number of bones of the frame that took the fallback.
+ * Every blended bone has length L_b up to the rounding of its two endpoints.  No atomics, sums in a fixed order: two launches give the
+ * same bits.  One wave per frame, one lane per joint, the parent's position handed over by wave shuffles.  Refused: a null src, cov_off,
+ * cov_row, cov_w or dst, F < 1 or >= 2^31, J outside [1, 21], NB outside [0, J - 1], null bones or bone_len with NB > 0, ldd < 3 J.  The
+ * caller answers for the cover as for mmego_blend_windows and for the bone list (ops.blend_bones checks both on the host); a bone that
+ * names a joint outside [0, J) is left out, its child stays a root. */
+int mmego_blend_bones(void* stream, const float* src, long nrows, int J, const long long* cov_off, const int* cov_row,
+                      const float* cov_w, long F, const int* bones, const float* bone_len, int NB, float* dst, long ldd,
+                      float* spread, int* fallback);
+/* out[r, b] = | |x_rc - x_rp| - L_b | for the rows X [n][3 J] (row stride ldx) and the bones (c, p) = bones[b] with lengths bone_len[b]
+ * as above: in double, one float store, out [n][NB] (row stride ldo) -- a per-row table for mmego_colsum, as the error tables are.
+ * Refused: null pointers, n < 1 or >= 2^26, J outside [1, 21], NB outside [1, J - 1], ldx < 3 J, ldo < NB. */
+int mmego_bone_length_dev(void* stream, const float* X, long ldx, long n, int J, const int* bones, const float* bone_len, int NB,
+                          float* out, long ldo);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

@@ -3,7 +3,7 @@
 
   python main.py --train --network {IMU_Net,Upper_Net,Lower_Net} [--epochs N --lr F --batch_size N --device cuda:0
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
-  python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --save_pred PATH]]
+  python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones} --save_pred PATH]]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -20,9 +20,10 @@ rotation, shift and scale, PCK and the acceleration error on the device -- pose 
 files keep their format), --window_jitter (every epoch each training window moves to a valid start within +-(frame_no-1) frames of its
 own) and --point_keep P (every minibatch's clouds are packed afresh on the device, each radar return kept with probability P): what a
 run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched; --infer --dense [--stride S --blend
-{mean,triangle} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
+{mean,triangle} --blend_space {joints,bones} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
 apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
-by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons; --blend_space bones
+blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -110,6 +111,12 @@ def build_parser():
     p.add_argument("--blend", type=str, choices=["mean", "triangle"], default=None,
                    help="--dense: weight of a window's prediction for a frame -- mean (default: 1) or triangle (min(p + 1, frame_no - p) at "
                         "position p: the window's middle counts most)")
+    p.add_argument("--blend_space", type=str, choices=["joints", "bones"], default=None,
+                   help="--dense: what is blended over a frame's windows -- joints (default: every joint's 3-vector on its own; where the "
+                        "windows disagree about a bone's direction the blended bone comes out shorter) or bones (every bone's direction, set "
+                        "to the body's bone length and laid along the kinematic tree from the blended roots: the frames stay rigid "
+                        "skeletons).  Given, either value prints one more line, the blended and single-window deviation from the bone "
+                        "lengths, and adds blend_space and degenerate_bones to --save_pred's file")
     p.add_argument("--save_pred", type=str,
                    help="--dense: write the per-frame arrays to this .npz -- pred [F, 21, 3] (NaN where no window covers the frame: "
                         "recordings shorter than frame_no), covered, spread, recording, frame_in_recording, target, stride, blend, frame_no")
@@ -117,9 +124,9 @@ def build_parser():
 
 
 def check_dense(parser, args):
-    """--dense is a mode of --infer; --stride, --blend and --save_pred belong to it."""
+    """--dense is a mode of --infer; --stride, --blend, --blend_space and --save_pred belong to it."""
     if not args.dense:
-        for flag in ("stride", "blend", "save_pred"):
+        for flag in ("stride", "blend", "blend_space", "save_pred"):
             if getattr(args, flag) is not None:
                 parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % flag)
         return
@@ -287,7 +294,7 @@ def apply_overrides(args):
         c.upper_variant = args.upper_variant or "global"
         c.metrics = args.metrics
     ConfigDemo.dense, ConfigDemo.stride, ConfigDemo.blend = bool(args.dense), args.stride, args.blend or "mean"
-    ConfigDemo.save_pred, ConfigDemo.dense_batch_size = args.save_pred, args.batch_size
+    ConfigDemo.save_pred, ConfigDemo.dense_batch_size, ConfigDemo.blend_space = args.save_pred, args.batch_size, args.blend_space
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

@@ -70,5 +70,6 @@ class ConfigDemo(_Common):
     dense = False               # --dense: sliding-window inference over whole recordings (processors.dense_infer)
     stride = None               # --stride: frames between window starts (None: frame_no // 2)
     blend = "mean"              # --blend: mean or triangle
+    blend_space = None          # --blend_space: joints or bones (None: joints, without the bone-length figures)
     save_pred = None            # --save_pred: .npz of the per-frame skeletons
     dense_batch_size = None     # --batch_size under --dense: windows per minibatch (None: 64)

@@ -515,6 +515,7 @@ class DenseWindows(DensePlan):
         self.src = {"imu": f32(dataset.frame_imu_, F), "target": f32(dataset.frame_key_, F), "R_R0R": f32(dataset.frame_R_, F),
                     "data": f32(dataset.frame_packed_, F), "skl": f32(dataset.frame_bones_, 1)}
         self.width = {name: self.src[name].shape[1] for name in self.src}
+        self.bone_set = np.asarray(dataset.frame_bones_, dtype=np.float32).reshape(-1, 3).copy()     # host: src["skl"] row 0 as [20, 3]
         self._out, self._zero_idx = {}, {}
 
     def frame_index(self, index):

@@ -488,6 +488,90 @@ def colsum_phase(X, period, out):
     return out
 
 
+BONES_MAX_J = 21            # blend_bones.hip BB_MAX_J: one lane per joint
+
+_bones_dev = {}
+
+
+def _bones_on(bones, bone_len, J, device, who):
+    """The walk table ((child, parent) per bone, host integers) and the bone lengths checked on the HOST for rows of J joints -- every
+    joint a child at most once, every parent a root or an earlier bone's child (so there is no cycle), the lengths finite and positive
+    -- and uploaded once per table and device.  -> (bones int32 [NB, 2], bone_len fp32 [NB], NB)."""
+    import numpy as np
+    b = np.asarray(bones)
+    L = np.asarray(bone_len.detach().cpu() if isinstance(bone_len, torch.Tensor) else bone_len)
+    if b.size == 0:
+        b = np.zeros((0, 2), dtype=np.int32)
+    if b.ndim != 2 or b.shape[1] != 2 or not np.issubdtype(b.dtype, np.integer) or L.ndim != 1 or len(L) != len(b):
+        raise ValueError("%s: bones is [NB, 2] integers of (child, parent) and bone_len one length per bone" % who)
+    if not 1 <= J <= BONES_MAX_J or len(b) > J - 1:
+        raise ValueError("%s: rows of %d joints with %d bones (1 to %d joints, at most one bone less)" % (who, J, len(b), BONES_MAX_J))
+    if len(b) and (b.min() < 0 or b.max() >= J):
+        raise IndexError("%s: the bones name joints outside the %d of a row" % (who, J))
+    children = [int(c) for c in b[:, 0]]
+    if len(set(children)) != len(children):
+        raise ValueError("%s: a joint is the child of two bones" % who)
+    placed = set(range(J)) - set(children)              # the roots
+    for c, p in b.tolist():
+        if p not in placed:
+            raise ValueError("%s: bone (%d, %d) comes before its parent's own bone; the walk goes parents first" % (who, c, p))
+        placed.add(c)
+    L = L.astype(np.float32)
+    if len(L) and not (np.isfinite(L).all() and (L > 0).all()):
+        raise ValueError("%s: bone lengths have to be finite and positive" % who)
+    b = np.ascontiguousarray(b, dtype=np.int32)
+    key = (b.tobytes(), L.tobytes(), J, str(device))
+    dev = _bones_dev.get(key)
+    if dev is None:
+        if len(_bones_dev) >= 64:
+            _bones_dev.clear()
+        one = lambda a: torch.as_tensor(a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)).to(device)     # (no bone: still an address)
+        dev = _bones_dev[key] = (one(b), one(L))
+    return dev + (len(b),)
+
+
+def blend_bones(src, cover, bones, bone_len, dst, spread=None, fallback=None):
+    """dst[f, :3 J] = the bone-length-preserving blend of the rows of src [nrows, 3 J] (rigid skeletons of J <= 21 joints) that cover
+    frame f (mmego_blend_bones; the recipe is in the header): roots as blend_windows blends them, every bone's direction blended over
+    the cover, set to bone_len and laid along ``bones`` ([NB, 2] host integers (child, parent), parents first).  spread [F] (optional)
+    as blend_windows', against the rigid positions; fallback [F] int32 (optional): the bones per frame whose blended direction was
+    degenerate.  Cover, bones and lengths are checked on the host first; a refused call leaves every output untouched.  dst may be wider
+    than 3 J: its other columns stay."""
+    _chk(src, 2)
+    dst = _rows(dst)
+    nrows, C = src.shape
+    if not src.is_contiguous() or C % 3 or not 1 <= C // 3 <= BONES_MAX_J:
+        raise ValueError("blend_bones needs a contiguous source of 1 to %d 3-vectors a row, got %s" % (BONES_MAX_J, tuple(src.shape)))
+    bd, ld, NB = _bones_on(bones, bone_len, C // 3, src.device, "blend_bones")
+    off, row, w, F = _cover_on(cover, nrows, src.device)
+    if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
+        raise ValueError("blend_bones: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
+    if spread is not None:
+        _chk(spread, 1)
+        if spread.numel() != F or not spread.is_contiguous():
+            raise ValueError("blend_bones: spread is one contiguous float per frame")
+    if fallback is not None:
+        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
+                and fallback.numel() == F and fallback.is_contiguous()):
+            raise ValueError("blend_bones: fallback is one contiguous int32 device word per frame")
+    hip.call("blend_bones", src, nrows, C // 3, off, row, w, F, bd, ld, NB, dst, max(dst.stride(0), C), spread, fallback)
+    return dst
+
+
+def bone_length_dev(X, bones, bone_len, out):
+    """out[r, b] = | |X[r, c_b] - X[r, p_b]| - bone_len[b] | (mmego_bone_length_dev): X [n, 3 J] rows of 3-vectors (a strided row view is
+    fine), out [n, >= NB]; bones and lengths as blend_bones takes and checks them.  A per-row table for colsum."""
+    X, out = _rows(X), _rows(out)
+    n, C = X.shape
+    if n < 1 or C % 3 or not 1 <= C // 3 <= BONES_MAX_J:
+        raise ValueError("bone_length_dev needs rows of 1 to %d 3-vectors, got %s" % (BONES_MAX_J, tuple(X.shape)))
+    bd, ld, NB = _bones_on(bones, bone_len, C // 3, X.device, "bone_length_dev")
+    if NB < 1 or out.shape[0] != n or out.shape[1] < NB:
+        raise ValueError("bone_length_dev: out is %s for %d rows of %d bones" % (tuple(out.shape), n, NB))
+    hip.call("bone_length_dev", X, max(X.stride(0), C), n, C // 3, bd, ld, NB, out, max(out.stride(0), NB))
+    return out
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

@@ -15,7 +15,7 @@ import types
 import numpy as np
 import torch
 
-from . import blocks, hip, ops
+from . import blocks, hip, ops, skeleton
 from .config import Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
@@ -623,7 +623,17 @@ def _accel_over_sequences(dev, up, lo, tgt, spans):
     return (Acc.cpu().numpy().astype(np.float64) * wt[:, None]).sum(axis=0) / wt.sum()
 
 
-def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference"):
+BLEND_SPACES = ("joints", "bones")
+
+
+def bone_lengths(bone_set):
+    """L_b = float32(|body_b|), the norm taken in float64, of a bone set [20, 3] (row 0 of DenseWindows.src["skl"]): the lengths every
+    predicted skeleton has, both nets placing a child at parent + q . body_b with q orthonormal.  -> (upper [14], lower [6])."""
+    L = np.linalg.norm(np.asarray(bone_set, dtype=np.float64).reshape(-1, 3), axis=1).astype(np.float32)
+    return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
+
+
+def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -636,10 +646,19 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     arrays (host): pred [F, 21, 3] (lower overwrites the shared hips; NaN where covered == 0), covered, spread, recording,
     frame_in_recording, target; the two nets' blended joints before assembly, upper [F, 15, 3] and lower [F, 8, 3] (zeros where uncovered);
     and, still on the device, win_up [W T, 45], win_lo [W T, 24] and the plan itself.
+    blend_space: "joints" blends the 3-vectors of every joint independently (the launches above); "bones" blends every bone's DIRECTION
+    over the cover, sets it to the body's bone length and walks the kinematic tree from the vector-blended roots (mmego_blend_bones with
+    skeleton.WALK_UPPER / WALK_LOWER and bone_lengths of the campaign's bone set): the frames stay rigid skeletons, as every window's
+    prediction is, and everything downstream runs on them unchanged.  None (the default) is "joints".  Given explicitly, either value
+    adds to the summary bone_dev_cm, the mean over the covered frames and the 20 bones of | |bone| - L_b | on the blended rows (upper 14
+    from the upper rows, lower 6 from the lower rows; mmego_bone_length_dev), single_bone_dev_cm, the same over the window rows,
+    degenerate_bones, the bones that took mmego_blend_bones' fallback (0 for "joints"), and blend_space; and to the arrays fallback [F].
     The figures come down in one read; the per-frame arrays in one each."""
     from .data import DenseWindows
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
+    if blend_space is not None and blend_space not in BLEND_SPACES:
+        raise ValueError("blend_space: %r is not one of %s" % (blend_space, ", ".join(BLEND_SPACES)))
     dev = base.device
     plan = DenseWindows(dataset, dev, stride, blend)
     W, T, F = plan.W, plan.T, plan.F
@@ -650,13 +669,13 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics)
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
 
 
-def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics):
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None):
     """dense_infer behind its argument checks: the nets are in eval mode."""
     dev = base.device
     W, T, F = plan.W, plan.T, plan.F
@@ -679,8 +698,15 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             win_lo[s * T:(s + B) * T].copy_(lo.reshape(B * T, 24))
         # every frame from its windows
         up_f, lo_f, spread = f32(F, 45), f32(F, 24), f32(F)
-        ops.blend_windows(win_up, plan, up_f, spread)
-        ops.blend_windows(win_lo, plan, lo_f)
+        if blend_space is not None:
+            L_up, L_lo = bone_lengths(plan.bone_set)
+        if blend_space == "bones":
+            fell = torch.zeros((2, F), dtype=torch.int32, device=dev)
+            ops.blend_bones(win_up, plan, skeleton.WALK_UPPER, L_up, up_f, spread, fell[0])
+            ops.blend_bones(win_lo, plan, skeleton.WALK_LOWER, L_lo, lo_f, None, fell[1])
+        else:
+            ops.blend_windows(win_up, plan, up_f, spread)
+            ops.blend_windows(win_lo, plan, lo_f)
         tgt_f = plan.src["target"]                                 # [F, 63]
         cov = np.flatnonzero(plan.covered)
         Fc = len(cov)
@@ -691,7 +717,7 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             spread_c = ops.gather_rows(spread.view(F, 1), cidx, f32(Fc, 1))
         full = metrics == "full"
         WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
-        log = torch.zeros((3 + T, max(43, WA)), dtype=torch.float32, device=dev)
+        log = torch.zeros((3 + T + (2 if blend_space is not None else 0), max(43, WA)), dtype=torch.float32, device=dev)
         E = f32(Fc, 43)
         hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
         ops.colsum(E, log[0, :43])
@@ -701,7 +727,16 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         Ew = f32(W * T, 43)
         hip.call("pose_errors", win_up, win_lo, tgt_w, W * T, Ew)
         ops.colsum(Ew, log[2, :43])
-        ops.colsum_phase(Ew, T, log[3:, :43])
+        ops.colsum_phase(Ew, T, log[3:3 + T, :43])
+        if blend_space is not None:
+            # deviation from the body's bone lengths, blended frames and window rows: columns 0..19 of two more rows of the log
+            D, Dw = f32(Fc, 20), f32(W * T, 20)
+            ops.bone_length_dev(up_c, skeleton.WALK_UPPER, L_up, D[:, :14])
+            ops.bone_length_dev(lo_c, skeleton.WALK_LOWER, L_lo, D[:, 14:])
+            ops.bone_length_dev(win_up, skeleton.WALK_UPPER, L_up, Dw[:, :14])
+            ops.bone_length_dev(win_lo, skeleton.WALK_LOWER, L_lo, Dw[:, 14:])
+            ops.colsum(D, log[3 + T, :20])
+            ops.colsum(Dw, log[4 + T, :20])
         if full:
             thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
             A = f32(Fc, WA)
@@ -711,9 +746,14 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     out = log.cpu().numpy().astype(np.float64)                     # the figures' one device -> host read
     summary = _error_summary(out[0, :43], Fc)
     summary.update(_error_summary(out[2, :43], W * T, "single_"))
-    summary["position_cm"] = out[3:, :21].mean(axis=1) / W * 100
+    summary["position_cm"] = out[3:3 + T, :21].mean(axis=1) / W * 100
     summary["spread_cm"] = float(out[1, 0]) / Fc * 100
     summary.update(windows=W, frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=blend, frame_no=T)
+    if blend_space is not None:
+        # (the fallback counts are integers per frame: they come down with the per-frame arrays, in their one read)
+        fallback = fell.cpu().numpy().sum(axis=0, dtype=np.int32) if blend_space == "bones" else np.zeros(F, dtype=np.int32)
+        summary.update(bone_dev_cm=float(out[3 + T, :20].mean()) / Fc * 100, single_bone_dev_cm=float(out[4 + T, :20].mean()) / (W * T) * 100,
+                       degenerate_bones=int(fallback.sum()), blend_space=blend_space)
     if full:
         spans = [(a, b) for a, b in zip(plan.rec_off[:-1], plan.rec_off[1:]) if b - a >= T]      # the covered recordings, whole
         acc = _accel_over_sequences(dev, up_f, lo_f, tgt_f, spans)
@@ -736,6 +776,8 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     arrays = dict(pred=pred, covered=plan.covered.astype(np.int32), spread=spread.cpu().numpy(), recording=plan.frame_rec,
                   frame_in_recording=plan.frame_in_recording, target=tgt_f.cpu().numpy().reshape(F, 21, 3),
                   upper=up_h, lower=lo_h, win_up=win_up, win_lo=win_lo, plan=plan)
+    if blend_space is not None:
+        arrays["fallback"] = fallback
     return summary, arrays
 
 
@@ -761,8 +803,9 @@ class Evaluator(_Base):
         self.model.load(cfg.model_lower_path)
         self.model.eval()
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
+        space = getattr(cfg, "blend_space", None)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
-                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics())
+                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space)
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -772,6 +815,9 @@ class Evaluator(_Base):
             s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
         print("Error by window position(cm): {}".format(s["position_cm"]))
         print("Window Disagreement(cm): {}".format(s["spread_cm"]))
+        if space is not None:
+            print("Bone Length Deviation(cm): blended {} single-window {} (degenerate bones {})".format(
+                s["bone_dev_cm"], s["single_bone_dev_cm"], s["degenerate_bones"]))
         print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
             s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
         if self._metrics() == "full":
@@ -780,8 +826,9 @@ class Evaluator(_Base):
         self.last_metrics = s
         path = getattr(cfg, "save_pred", None)
         if path:
+            more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
             np.savez(path, stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]),
-                     **{k: arrays[k] for k in DENSE_SAVED})
+                     **{k: arrays[k] for k in DENSE_SAVED}, **more)
             print("Per-frame skeletons saved in {}".format(path))
         return s
 

@@ -18,6 +18,20 @@ UPPER_MAP = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 16, 20]
 LOWER_MAP = [12, 13, 14, 15, 16, 17, 18, 19]
 HAND_MAP = [7, 6, 11, 10]
 KINECT_SELECTION = [0, 1, 2, 3, 4, 5, 6, 7, 11, 12, 13, 14, 18, 19, 20, 21, 22, 23, 24, 25, 26]
+
+
+def _walk(bones, joint_map):
+    """[parent, child] pairs in the 21-joint numbering -> (child, parent) rows in the numbering of a net's own row (joint_map)."""
+    return np.asarray([[joint_map.index(c), joint_map.index(p)] for p, c in bones], dtype=np.int32)
+
+
+# Walk tables of the bone-length-preserving blend (ops.blend_bones): (child, parent) per bone in the numbering of the net's own row,
+# parents before children as the nets' forward kinematics place them (csrc/geom.hip make_plan); bone k has row k of the body's bone set.
+WALK_UPPER = _walk(BONES_UPPER, UPPER_MAP)          # one tree rooted at the head (joint 20, slot 14): 14 bones, body rows 0..13
+WALK_LOWER = _walk(BONES_LOWER, LOWER_MAP)          # a forest rooted at the two hips (joints 12 and 16, slots 0 and 4): 6 bones
+WALK_UPPER_ROWS = tuple(range(0, len(BONES_UPPER)))
+WALK_LOWER_ROWS = tuple(range(len(BONES_UPPER), len(BONES_ALL)))
+
 GCN_EDGES = [(0, 12), (0, 13), (0, 1), (1, 2), (2, 3), (2, 4), (2, 8), (3, 14), (4, 5), (5, 6), (6, 7), (8, 9),
              (9, 10), (10, 11)]
 
