@@ -880,6 +880,18 @@ int mmego_grad_sqnorm(void* stream, const float* g, long n, const long* skip, in
 int mmego_adam_step_clipped(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
                             double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
                             const double* part, int npart, double max_norm, double* stats);
+/* The two steps above with an exponential moving average of the weights kept in the same launch (csrc/optim_ema.hip).  The Adam part
+ * is the plain one: the same p, g, m, v, state give the same bits in p, m, v, state (and stats, and the same ticket behaviour) as
+ * mmego_adam_step / mmego_adam_step_clipped.  ema: n device floats, 16-byte aligned, not overlapping p; for every element the update
+ * touches, ema = fmaf(omd, p_new - ema, ema) in fp32 with omd = (float)(1 - ema_decay) and p_new the parameter just stored.  Elements
+ * inside a skip range keep their ema bit for bit, and so does every element of a step that the clipped form skips as non-finite.
+ * 0 < ema_decay < 1 (NaN is refused); a refused call launches nothing. */
+int mmego_adam_step_ema(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
+                        float* ema, double ema_decay);
+int mmego_adam_step_clipped_ema(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                                double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
+                                const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay);
 
 #ifdef __cplusplus
 }

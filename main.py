@@ -12,7 +12,9 @@ available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam
 --imu_lr F] (stage 3 trains all three nets end to end on that sum: IMU_Net through Upper_Net's and Lower_Net's head-pose gradients),
 --imu_dropout P (the IMU_Net that is TRAINED -- stage 1, --finetune_imu or --finetune_all -- gets nn.LSTM(dropout=P) between its BiLSTM layers), --clip_grad_norm X (every
 trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
-"Grad norm" line per net and epoch; `inf` only measures), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
+"Grad norm" line per net and epoch; `inf` only measures), --ema_decay D (every trained net keeps an exponential moving average of its
+weights at decay D, updated inside its fused Adam launch; each epoch's evaluation, model selection and early stopping run on the averaged
+weights; the checkpoints keep the raw weights and the averaged nets are written beside them under EMA/), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
 UpperNetwlocal with the anchor branch -- the net trained by --train --network Upper_Net, the class the Upper checkpoint is loaded into by
 --train --network Lower_Net and --infer), --metrics {reference,full} (full: beside the reference's figures, the evaluation pass of --infer
 and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
@@ -82,6 +84,12 @@ def build_parser():
                    help="--train: clip every trained net's gradient to this global norm ahead of its Adam step (one clip_grad_norm_ per "
                         "optimiser, on the SUM-loss gradient of the global minibatch), skip a step whose gradient is not finite, and print "
                         "the norms once per epoch; `inf` measures without clipping (default: no clipping)")
+    p.add_argument("--ema_decay", type=float,
+                   help="--train: every trained net keeps an exponential moving average of its weights, ema += (1 - D)(w - ema) after each "
+                        "Adam step, D in (0, 1), starting from the weights the run starts from; each epoch's evaluation pass, model "
+                        "selection and early stopping use the averaged weights.  Checkpoints keep the raw weights (the average travels in "
+                        "the optimiser state, so --resume continues it without the flag); the averaged nets are written in the "
+                        "reference's format beside them, in an EMA folder (default: no averaging)")
     p.add_argument("--upper_variant", type=str, choices=["global", "wlocal"], default=None,
                    help="which net Upper_Net is: global (default: UpperNet) or wlocal (UpperNetwlocal, with the anchor branch).  --train "
                         "--network Upper_Net trains it (with --finetune_imu, --imu_lr, --imu_dropout, --clip_grad_norm, --resume and "
@@ -190,6 +198,16 @@ def check_clip_grad_norm(parser, args):
         parser.error("--clip_grad_norm goes with --train only (it bounds the optimiser's step)")
 
 
+def check_ema_decay(parser, args):
+    """--ema_decay belongs to a training run and is a decay strictly between 0 and 1."""
+    if args.ema_decay is None:
+        return
+    if not 0.0 < args.ema_decay < 1.0:                 # (false for NaN as well)
+        parser.error("--ema_decay is the decay of the weight average: it has to lie in (0, 1), got %r" % (args.ema_decay,))
+    if args.infer or not args.train:
+        parser.error("--ema_decay goes with --train only (it averages the weights an optimiser updates)")
+
+
 def check_finetune_upper(parser, args, world):
     """--finetune_upper fits one arrangement only; everything else is refused before any work starts.  (--gt_head_pose is fine: the
     head pose is not what is trained.)"""
@@ -242,6 +260,7 @@ def check_finetune(parser, args, world):
     check_finetune_upper(parser, args, world)
     check_imu_dropout(parser, args)
     check_clip_grad_norm(parser, args)
+    check_ema_decay(parser, args)
     check_frame_store(parser, args)
     check_dense(parser, args)
     if not args.finetune_imu:
@@ -287,6 +306,7 @@ def apply_overrides(args):
     Config.upper_lr = args.upper_lr
     Config.finetune_all = bool(args.finetune_all)
     Config.clip_grad_norm = args.clip_grad_norm
+    Config.ema_decay = args.ema_decay
     Config.window_jitter = bool(args.window_jitter)
     Config.point_keep = args.point_keep
     Config.seed = args.seed

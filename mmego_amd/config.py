@@ -55,6 +55,7 @@ class _Common:
     point_keep = None           # --point_keep: clouds re-packed on the device per minibatch, each return kept with this probability (None: the loader's packing)
     seed = None                 # --seed, as main.py got it (None: 0 for what FrameStore draws)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
+    ema_decay = None            # --ema_decay: every trained net keeps a weight average at this decay; evaluation uses it (None: off)
 
 
 class Config(_Common):

@@ -6,6 +6,8 @@ That gives: one fused Adam launch per step, one RCCL all-reduce per step (refere
 Processor/Train/Train_Upper.py:60,181-182 steps 54 tensors one by one), and float4-aligned weights for
 the GEMM kernels.  state_dict keys/shapes are untouched, so shipped checkpoints load unchanged.
 """
+import contextlib
+
 import torch
 
 from . import hip
@@ -106,19 +108,32 @@ class FusedAdam:
     max_grad_norm (None: off): torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) ahead of every step, over THIS net's
     gradients, as two launches and no host read (mmego_grad_sqnorm, mmego_adam_step_clipped).  A step whose gradient norm is not
     finite is skipped on the device -- weights, moments and step count stay as they are -- and counted; `grad_stats()` reads the
-    norms and counts seen since the last `reset_grad_stats()`.  float("inf") measures without ever clipping."""
+    norms and counts seen since the last `reset_grad_stats()`.  float("inf") measures without ever clipping.
+
+    ema_decay (None: off; else d in (0, 1)): an exponential moving average of the weights, `ema`, a second flat buffer in the layout
+    of `flat_p`, updated by the step's own launch (mmego_adam_step_ema, mmego_adam_step_clipped_ema): ema <- ema + (1 - d)(p_new - ema)
+    for every element the update touches.  DEFINITION: ema_0 is the weights as they are when the optimiser's buffers are built, which
+    is its first use (step, state_dict, load_state_dict, averaged) -- for fine-tuning from a checkpoint, the checkpoint.  So there is
+    no bias correction and no first step that differs; parameters that never train, and steps skipped as non-finite, keep ema equal to
+    the weights.  Buffers of the module (BatchNorm running statistics) are not averaged: they are running averages already.
+    `averaged()` evaluates with the average in place of the weights, `ema_state_dict()` is the module's state_dict with it."""
 
     STAT_KEYS = ("last", "sum", "max", "steps", "clipped", "skipped")
 
-    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError("max_grad_norm has to be > 0 (or None: no clipping), got %r" % (max_grad_norm,))
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:            # (false for NaN as well)
+            raise ValueError("ema_decay has to lie in (0, 1) (or None: no weight average), got %r" % (ema_decay,))
         self.flat = flat
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.m = self.v = self.state = self._ticket = None
         self._skip = None
         self._part = self._stats = None
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema = None
+        self._averaged = False            # inside averaged(): flat_p holds the average, ema the weights
 
     def _skip_ranges(self, f):
         """Element ranges of parameters that never receive a gradient (`module.never_trained()`, e.g. IMU_Net.fc3):
@@ -146,6 +161,10 @@ class FusedAdam:
             self.state = torch.zeros(3, dtype=torch.float64, device=f.device)
             self._ticket = torch.zeros(1, dtype=torch.int32, device=f.device)
             self._part = self._stats = None
+            self.ema = None
+        if self.ema_decay is not None and self.ema is None:
+            # (ema_0 = the weights as they are now; built before the first step, so before anything captures its address)
+            self.ema = f.flat_p.clone()
         if self.max_grad_norm is not None and self._part is None:
             # (only a clipping optimiser owns these; built before the first step, so before anything captures their addresses)
             self._part = torch.zeros(hip.lib().mmego_grad_norm_nblk(f.flat_p.numel()), dtype=torch.float64, device=f.device)
@@ -153,17 +172,21 @@ class FusedAdam:
         return f
 
     def step(self):
+        if self._averaged:
+            raise RuntimeError("FusedAdam.step() inside averaged(): the parameters hold the average, not the weights to update")
         f = self._ensure()
         skip = self._skip_ranges(f)
         ranges = (skip if skip is not False else None, skip.numel() // 2 if skip is not False else 0)
+        # (with a weight average: the same launch under its _ema name, the average and its decay behind the plain arguments)
+        sfx, avg = ("", ()) if self.ema_decay is None else ("_ema", (self.ema, self.ema_decay))
         if self.max_grad_norm is None:
-            hip.call("adam_step", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
-                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket)
+            hip.call("adam_step" + sfx, f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
+                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket, *avg)
         else:
             hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
-            hip.call("adam_step_clipped", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
+            hip.call("adam_step_clipped" + sfx, f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
                      float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket,
-                     self._part, self._part.numel(), self.max_grad_norm, self._stats)
+                     self._part, self._part.numel(), self.max_grad_norm, self._stats, *avg)
         # the update went through raw pointers (no tensor._version bump): tell the net to drop derived copies of its weights
         changed = getattr(f.module, "weights_changed", None)
         if changed is not None:
@@ -171,6 +194,46 @@ class FusedAdam:
 
     def zero_grad(self):
         pass  # every backward overwrites the flat gradient buffer
+
+    def _exchange(self, f):
+        """Exchange the CONTENTS of flat_p and ema (HIP graphs and the nets' parameter views hold the addresses) and have the net drop
+        what it derived from the old contents."""
+        keep = f.flat_p.clone()
+        f.flat_p.copy_(self.ema)
+        self.ema.copy_(keep)
+        changed = getattr(f.module, "weights_changed", None)
+        if changed is not None:
+            changed()
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the context the module runs on the averaged weights; on exit the weights are back bit for bit (an exchange, no
+        arithmetic).  Not re-entrant, and no step() inside."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdam.averaged(): this optimiser keeps no weight average (ema_decay=None)")
+        if self._averaged:
+            raise RuntimeError("FusedAdam.averaged() is not re-entrant: the parameters already hold the average")
+        f = self._ensure()
+        self._exchange(f)
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._exchange(f)
+            self._averaged = False
+
+    def ema_state_dict(self):
+        """The module's state_dict() with every parameter taken from the average (copies).  Buffers -- BatchNorm running statistics and
+        step counters -- are the live ones: they are not averaged."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdam.ema_state_dict(): this optimiser keeps no weight average (ema_decay=None)")
+        f = self._ensure()
+        src = f.flat_p if self._averaged else self.ema
+        sd = f.module.state_dict()
+        shapes = {n: p.shape for n, p in f.module.named_parameters()}
+        for name, off, k in self.layout():
+            sd[name] = src[off:off + k].view(shapes[name]).clone()
+        return sd
 
     def grad_stats(self):
         """The gradient norms of the steps since the last reset, from ONE device read: {"last", "sum", "max", "steps", "clipped",
@@ -201,15 +264,22 @@ class FusedAdam:
     def state_dict(self):
         """Moments and step counters (host copies) + hyper-parameters + the layout the moments are stored in: everything a
         bit-exact resume needs, also after the flat layout of the net has changed."""
+        if self._averaged:
+            raise RuntimeError("FusedAdam.state_dict() inside averaged(): weights and average are exchanged")
         self._ensure()
-        return {"m": self.m.cpu(), "v": self.v.cpu(), "state": self.state.cpu(), "lr": self.lr, "betas": tuple(self.betas),
-                "eps": self.eps, "weight_decay": self.weight_decay, "layout": self.layout(), "max_grad_norm": self.max_grad_norm}
+        sd = {"m": self.m.cpu(), "v": self.v.cpu(), "state": self.state.cpu(), "lr": self.lr, "betas": tuple(self.betas),
+              "eps": self.eps, "weight_decay": self.weight_decay, "layout": self.layout(), "max_grad_norm": self.max_grad_norm}
+        if self.ema_decay is not None:     # (an optimiser without an average writes the state it always wrote)
+            sd["ema"], sd["ema_decay"] = self.ema.cpu(), self.ema_decay
+        return sd
 
     def load_state_dict(self, sd):
         """Moments are matched to parameters BY NAME through the saved layout; a state saved under another flat order lands on
         the right parameters.  A state without a layout (written before r03) is only accepted where no ambiguity exists: the net
         has no layout of its own (registration order then and now).  Anything else is refused -- equal element counts say
         nothing about where a parameter's moments are."""
+        if self._averaged:
+            raise RuntimeError("FusedAdam.load_state_dict() inside averaged(): weights and average are exchanged")
         f = self._ensure()
         cur = self.layout()
         saved = sd.get("layout")
@@ -229,16 +299,24 @@ class FusedAdam:
             missing = sorted({n for n, _, _ in cur} ^ {n for n, _, _ in saved})
             raise ValueError("optimizer state belongs to another net: parameters differ (%s%s)" %
                              (", ".join(missing[:4]) or "shapes", " ..." if len(missing) > 4 else ""))
+        if sd.get("ema_decay") is not None:     # (as max_grad_norm: the saved value wins, and a state with an average switches averaging on)
+            self.ema_decay = float(sd["ema_decay"])
+            self._ensure()                      # (the average's buffer, should the state switch averaging on)
+        carried = [("m", self.m), ("v", self.v)] + ([("ema", self.ema)] if sd.get("ema_decay") is not None else [])
         if saved == cur and sd["m"].numel() == f.flat_p.numel():
-            self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+            for key, dst in carried:
+                dst.copy_(sd[key])
         else:
             where = {n: o for n, o, _ in saved}
-            m_new, v_new = torch.zeros(f.flat_p.numel()), torch.zeros(f.flat_p.numel())
-            for n, o, k in cur:
-                so = where[n]
-                m_new[o:o + k] = sd["m"][so:so + k]
-                v_new[o:o + k] = sd["v"][so:so + k]
-            self.m.copy_(m_new); self.v.copy_(v_new)
+            for key, dst in carried:
+                new = torch.zeros(f.flat_p.numel())
+                for n, o, k in cur:
+                    so = where[n]
+                    new[o:o + k] = sd[key][so:so + k]
+                dst.copy_(new)
+        if self.ema_decay is not None and sd.get("ema_decay") is None:
+            self.ema.copy_(f.flat_p)
+            print("[mmego_amd] optimizer state carries no weight average: the average (decay %g) restarts from the loaded weights" % self.ema_decay)
         self.state.copy_(sd["state"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
         if "max_grad_norm" in sd:          # (as lr: the saved value wins, a resumed run clips as the run it continues; a state from

@@ -9,6 +9,7 @@ same stdout lines for `--infer`.  Plotting (matplotlib/seaborn) is out of scope.
 Data parallel (not in the reference): when launched under torch.distributed.run each rank trains on its
 own shard of every epoch's shuffled order; gradients are summed with one RCCL all-reduce per step.
 """
+import contextlib
 import os
 import types
 
@@ -62,6 +63,7 @@ class _Base:
     # The trainer's optimisers, keyed like train_step.TRAINED ("opt": the stage's own net, "imu_opt", "upper_opt"): ONE set, handed to
     # the step of every minibatch size, read by the grad-norm report and the checkpoint (a trainer's __init__ makes it a dict)
     _opts = types.MappingProxyType({})
+    _resume = None                # (the train state --resume loaded: load_train_state; a trainer's __init__ starts it as None too)
     weight_decay = 0.0            # of "opt" (stage 1: coupled 1e-3)
     last_metrics = None           # (--metrics full: aligned_summary of the last evaluation pass; eval_model's return value stays the reference's)
     net_name = None               # what "opt" trains, as the grad-norm report calls it
@@ -198,21 +200,38 @@ class _Base:
         that is where a --resume state is loaded."""
         if "opt" not in self._opts:
             self._opts["opt"] = FusedAdam(model.flat(), lr=self.learning_rate, weight_decay=self.weight_decay,
-                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None))
+                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None), ema_decay=getattr(self.cfg, "ema_decay", None))
             if self._resume is not None:
                 self._opts["opt"].load_state_dict(self._resume["optimizer"])
         return self._opts["opt"]
 
-    def save_beside(self, epoch, folder, net):
+    def save_beside(self, epoch, folder, net, state_dict=None):
         """A second trained net beside the stage's checkpoint, same file name, in a folder of its own (--finetune_imu: IMU_Net,
-        --finetune_upper: Upper_Net, --finetune_all: both)."""
+        --finetune_upper: Upper_Net, --finetune_all: both); ``state_dict``: written instead of ``net``'s own (--ema_decay: the averaged
+        weights, under EMA/)."""
         if self.rank != 0:
             return None
         folder = os.path.join(_TRAIN_DIR, "model", str(self.Idx), folder)
         os.makedirs(folder, exist_ok=True)
         path = os.path.join(folder, "epoch{}_batch{}frame{}lr{}.pth".format(epoch, self.batchsize, self.frame_no, self.learning_rate))
-        torch.save(net.state_dict(), path)
+        torch.save(net.state_dict() if state_dict is None else state_dict, path)
         return path
+
+    def _averaging(self):
+        """[(optimiser key, optimiser)] of the trainer's optimisers that keep a weight average (--ema_decay, or a resumed state's)."""
+        return [(o, self._opts[o]) for o, _ in TRAINED if o in self._opts and self._opts[o].ema_decay is not None]
+
+    def _save_averaged(self, epoch, model, also_saved):
+        """--ema_decay: beside every file just saved, the same net with its averaged weights (FusedAdam.ema_state_dict: reference format,
+        loads wherever the raw file loads) under the same name in EMA/ -- EMA/IMU_Net/, EMA/Upper_Net/ for the nets saved beside."""
+        if self.rank != 0:
+            return
+        opts = dict(self._averaging())
+        targets = [("opt", "EMA", model)] + [({"IMU_Net": "imu_opt", "Upper_Net": "upper_opt"}[folder], "EMA/" + folder, net)
+                                             for folder, net in also_saved]
+        for key, folder, net in targets:
+            if key in opts:
+                self.save_beside(epoch, folder, net, state_dict=opts[key].ema_state_dict())
 
     def _epochs(self, model, train, evaluate, report, also_saved=()):
         """The epoch loop of every trainer (reference Train_Upper.py:90-132, Train_Lower.py:110-153, Train_IMU.py:90-112).  ``train()``: one
@@ -224,6 +243,12 @@ class _Base:
             ts = self.load_train_state(self.cfg.resume_path, model)
             if ts["early"] is not None:
                 early.counter, early.best_score = ts["early"]
+        # --ema_decay (a resumed run: the decay its optimiser state carries, the flag need not be repeated)
+        decay = getattr(self.cfg, "ema_decay", None)
+        if self._resume is not None and self._resume["optimizer"].get("ema_decay") is not None:
+            decay = self._resume["optimizer"]["ema_decay"]
+        if decay is not None and self.rank == 0:
+            print("[mmego_amd] weight averaging: decay %g; evaluation and early stopping use the averaged weights" % decay)
         out = None
         names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
         for epoch in range(self.start_epoch, self.num_epochs):
@@ -235,7 +260,12 @@ class _Base:
             # sticky word: read once per epoch (the training pass has just synchronised for its log) -- never train on silently
             blocks.seq_xcd_raise()
             sync_replicas(model, self.pg, params=False)            # BatchNorm running statistics: rank 0's, on every rank
-            out = evaluate()
+            # (--ema_decay: the evaluation pass -- the report, model selection and early stopping with it -- runs on every trained net's
+            #  averaged weights; the contents are exchanged back, bit for bit, before anything is saved or trained further)
+            with contextlib.ExitStack() as averaged:
+                for _, opt in self._averaging():
+                    averaged.enter_context(opt.averaged())
+                out = evaluate()
             eval_loss, eval_loss_l = out[0], out[1]
             if self.rank == 0:
                 self.lossfile.write("%d %f\n" % (epoch + 1, eval_loss))
@@ -251,6 +281,7 @@ class _Base:
                 self.save_models(epoch, model, self._main_opt(model), early)
                 for folder, net in also_saved:
                     self.save_beside(epoch, folder, net)
+                self._save_averaged(epoch, model, also_saved)
             if stop:
                 print("Early stopping")
                 break
@@ -333,7 +364,8 @@ class _StageTrainer(_Base):
                            use_graph=not pipelined, finetune_imu=self.finetune_imu,
                            imu_lr=self.learning_rate if imu_lr is None else imu_lr,
                            finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
-                           clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts)
+                           clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts,
+                           ema_decay=getattr(self.cfg, "ema_decay", None))
             st.engine = None
             if pipelined:
                 st.imu_next = torch.empty((B, self.frame_no) + tuple(self._train_dev.shape["imu"][1:]), dtype=torch.float32,

@@ -261,12 +261,16 @@ class StageStep(_Engine):
     optimisers and learning rates.  Data parallel, the all-reduce precedes ``opt.step()``: every rank clips the summed gradient by the
     same norm.
 
+    ``ema_decay`` (None: off): every optimiser this step builds keeps an exponential moving average of ITS net's weights at that decay
+    (FusedAdam(ema_decay=...)), updated inside its own Adam launch -- which runs outside the captured body, so the graph is the one
+    without the option.  Data parallel, no collective: replicas with bit-equal parameters compute bit-equal averages.
+
     ``optimisers`` (a dict keyed "opt" / "imu_opt" / "upper_opt"): the ones in it are used as they are, the missing ones are built and
     put into it -- a trainer hands ONE dict to the steps of all its minibatch sizes, so every optimiser is built once."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
-                 clip_grad_norm=None, optimisers=None):
+                 clip_grad_norm=None, optimisers=None, ema_decay=None):
         assert stage in ("upper", "lower")
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
@@ -276,7 +280,7 @@ class StageStep(_Engine):
 
         def opt_for(key, trained, lr, weight_decay):
             if opts.get(key) is None:
-                opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+                opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema_decay=ema_decay)
             return opts[key]
         self.imu_opt = self.upper_opt = None
         if self.finetune_upper:
@@ -427,9 +431,11 @@ class ImuStep(_Engine):
     position loss (sum), backward through the two BiLSTM(512) stacks, Adam with coupled weight decay -- with static
     buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound)."""
 
-    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None):
+    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None, ema_decay=None):
         self.net = net
-        self.opt = opt if opt is not None else FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        # (clip_grad_norm, ema_decay: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=...); one handed in is used as it is)
+        self.opt = opt if opt is not None else FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
+                                                         ema_decay=ema_decay)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
