@@ -750,7 +750,8 @@ typedef struct MmegoBnRef {
  * 1x1 convs -> mix = 1: Z [F*V][(K+1) cout] = zr, Y [F*V][cout] = einsum('nkctv,kvw->nctw', z, A . importance), recY / recR
  * [mmego_gcn_front_nrec(F)][cout]: records of Y and of the residual columns of Z (4 frames = 4 V rows per record); mix = 0: the
  * closing 1x1 conv, stored transposed outT[b][nout][T*V] (GCN.py:351-353, the re-viewed layout).  cin in {<32 with in_mode 0, 32,
- * 64, 128}; nout a multiple of 32 (<= 384 with cin <= 64). */
+ * 64, 128}; nout a multiple of 32 (<= 384 with cin <= 64; in_mode 0: cin <= 8, nout <= 128 and nout * cin <= 512); mix = 1 with
+ * cin >= 32: cout in {32, 64, 128}. */
 typedef struct MmegoGcnFront {
   const float* X1; long ld1; const float* X2; long ld2; int in_mode;
   MmegoBnRef bn1, bn2;
@@ -774,7 +775,7 @@ int mmego_tconv_train(void* stream, const float* X, long ldx, const MmegoBnRef* 
                       long ldy, float* act, float* out_rec, int B, int T, int V, int Cin, int Cout, int taps);
 int mmego_tconv_bwd_stats(void* stream, const float* dY, long lddy, const float* Wp, float* dAct, long ldda, const float* ymix,
                           long ldym, const float* state, float* bw_rec, int B, int T, int V, int Cin, int Cout, int taps);
-/* Sequence-tiled forms of the two calls above for T*V <= 128 rows per sequence and Cin in {32, 64, 128} (mmego_tconv_seq_ok): one
+/* Sequence-tiled forms of the two calls above for T*V <= 127 rows per sequence and Cin in {32, 64, 128} (mmego_tconv_seq_ok): one
  * workgroup per (sequence, 32 output columns), the sequence's rows staged in LDS once for all taps, weights Wf fragment-major per tap
  * (mmego_pack_multi kind 2: 2 * taps * Co * Ci floats, the forward image then the input-gradient image); out_rec / bw_rec are per
  * SEQUENCE: [B][Cout], T*V rows per record. */

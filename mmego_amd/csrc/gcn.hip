@@ -587,7 +587,7 @@ extern "C" int mmego_tconv_bwd_stats(void* stream, const float* dY, long lddy, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Temporal convolution, SEQUENCE-TILED (training shape: T V <= 128 rows per sequence).  The 9 taps of a (t, v) row reach only rows
+// Temporal convolution, SEQUENCE-TILED (training shape: T V < 128 rows per sequence).  The 9 taps of a (t, v) row reach only rows
 // of the same sequence, so a workgroup takes ONE sequence and a 32-column slice of the output: the sequence's (activated) input
 // rows go to LDS once -- not once per tap -- and every tap is the same tile read 15 d rows further down, rows outside the sequence
 // masked to zero.  The weights come fragment-major per tap (mmego_pack_multi kind 2): a wave fetches its B operand straight into

@@ -67,7 +67,7 @@ __device__ __forceinline__ void tile_out(const float* lds, int S, float* g, long
 
 // (mean, M2) records of `ncol` columns (a power of two <= 256) of an LDS tile over its nv valid rows: thread (column, row part) takes
 // every P-th row (shifted sums, four loads in flight), the parts are added in a fixed order through `scr` (GF_NT * 2 floats).
-// rows16: the tile keeps 16 rows per frame of V (row V a dummy).  Ends with the records stored (no trailing barrier).
+// rows16: the tile keeps 16 rows per frame of V (rows V .. 15 dummies).  Ends with the records stored (no trailing barrier).
 __device__ __forceinline__ void tile_records(const float* base, int S, int ncol, int nv, int V, bool rows16, float* scr, float2* rec) {
   const int tid = threadIdx.x, P = GF_NT / ncol;
   const int cid = tid & (ncol - 1), part = tid / ncol;
@@ -79,7 +79,7 @@ __device__ __forceinline__ void tile_records(const float* base, int S, int ncol,
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int q = rr + u * P < nv ? rr + u * P : 0;
-      d[u] = col[(rows16 ? q + q / V : q) * S] - shift;
+      d[u] = col[(rows16 ? q + (q / V) * (16 - V) : q) * S] - shift;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) { const float dd = rr + u * P < nv ? d[u] : 0.f; s1 += dd; s2 = __builtin_fmaf(dd, dd, s2); }
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(GF_NT) void gcn_front_kernel(GcnFrontD p) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {                      // (ys keeps 16 rows per frame, zs V)
           const int q = rr + u * P < nv ? rr + u * P : 0;
-          d[u] = col[(res ? q : q + q / V) * S] - shift;
+          d[u] = col[(res ? q : q + (q / V) * (16 - V)) * S] - shift;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) { const float dd = rr + u * P < nv ? d[u] : 0.f; s1 += dd; s2 = __builtin_fmaf(dd, dd, s2); }
@@ -608,8 +608,8 @@ __global__ __launch_bounds__(256) void graph_dA_fused_kernel(GraphDAFusedD p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int V = p.V, Kk = p.Kk, C = p.C, KC = Kk * C;
   const int ZS = KC + 4, YS = C + 4;                     // row strides: 16-byte aligned rows, lanes 16 apart in k hit other banks
-  float* zs = sm;                                        // [16][ZS] z of the frame (row 15: zero), later dz
-  float* ys = zs + 16 * ZS;                              // [16][YS] dy
+  float* zs = sm;                                        // [16][ZS] z of the frame (rows V .. 15: zero), later dz
+  float* ys = zs + 16 * ZS;                              // [16][YS] dy (rows V .. 15: zero -- the dz product reads all 16)
   float* c12 = ys + 16 * YS;                             // [2][C]
   float* stl = c12 + 2 * C;                              // [4][C]
   float* dAs = stl + 4 * C;                              // [4 waves][256] partial dA tiles
@@ -651,8 +651,8 @@ __global__ __launch_bounds__(256) void graph_dA_fused_kernel(GraphDAFusedD p) {
   asm volatile("" : "+v"(sv[0]), "+v"(sv[1]));
   if (tid < 4 * C) stl[tid] = sv[0];
   if (tid + 256 < 4 * C) stl[tid + 256] = sv[1];
-  for (int i = tid; i < ZS; i += 256) zs[15 * ZS + i] = 0.f;
-  for (int i = tid; i < YS; i += 256) ys[15 * YS + i] = 0.f;
+  for (int i = tid; i < (16 - V) * ZS; i += 256) zs[V * ZS + i] = 0.f;
+  for (int i = tid; i < (16 - V) * YS; i += 256) ys[V * YS + i] = 0.f;
   __syncthreads();
   const float2 tot = bwd_finish<256>(C, p.G * V, red, c12);
   __syncthreads();
@@ -725,8 +725,8 @@ __global__ __launch_bounds__(256) void graph_dA_fused_kernel(GraphDAFusedD p) {
         *reinterpret_cast<f32x4*>(p.dZ + (g * V + i / zc4) * p.lddz + 4 * (i % zc4)) = o[u];
       }
     }
-    __syncthreads();                                      // (zs row 15 was overwritten with dz's dummy row: zero it again below)
-    for (int i = tid; i < ZS; i += 256) zs[15 * ZS + i] = 0.f;
+    __syncthreads();                                      // (zs rows V .. 15 were overwritten with dz's dummy rows: zero them again below)
+    for (int i = tid; i < (16 - V) * ZS; i += 256) zs[V * ZS + i] = 0.f;
   }
 #undef GDF_ISSUE
   // partial dA of this workgroup: D[i = v][j = w], lane (lo = w, hi): rows v = 4 hi + reg
@@ -884,7 +884,12 @@ extern "C" int mmego_gcn_front(void* stream, const MmegoGcnFront* h) {
   }
   const bool scalar = p.cin < 32;
   MMEGO_REQUIRE(scalar == (p.in_mode == 0) || !scalar);
+  // (the scalar path keeps W in 512 floats of LDS, one element per thread, and the bias in 128 behind them,
+  // and its input tile has a row stride of 8 floats)
+  MMEGO_REQUIRE(!scalar || ((long)p.nout * p.cin <= 512 && p.nout <= 128 && p.cin <= 8));
   const bool phased = !scalar && p.mix;
+  // (the phased path computes cout / 32 column tiles per part and takes its records with tile_records: ncol a power of two)
+  MMEGO_REQUIRE(!phased || ((p.cout % 32) == 0 && (p.cout & (p.cout - 1)) == 0));
   const int NCT = p.nout / 32, nctw = phased ? p.Kk + 1 : (NCT + 3) / 4, nk = scalar ? 0 : p.cin / 32;
   const int XS = (nk ? p.cin : 4) + 4, ZS = phased ? p.cout + 16 : (p.mix ? p.nout + 16 : p.nout + 1), YS = p.cout + 4;
   const int tail = 64 * XS > 64 * YS ? 64 * XS : 64 * YS;
