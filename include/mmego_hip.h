@@ -216,7 +216,8 @@ int mmego_lstm_step(void* stream, int ndir, int Bn, int H, int first, const floa
 /* Whole-sequence H=64 bidirectional LSTM layer (Upper_Net.py:333, Lower_Net.py:91, Upper_Net.py:210).
  * xproj_d rows are (b*T+t) with row stride xs; out rows (b*T+t) with row stride os, direction d in
  * columns [64d, 64d+64).  Optional stashes for backward (all or none): gates_d [T][B][64][4] (the four gate activations
- * i, f, g, o of a hidden unit side by side: a private format between this call and mmego_lstm64_backward, 16-byte aligned),
+ * i, f, g, o of a hidden unit side by side: a private format between this call and mmego_lstm64_backward, 16-byte aligned -- checked
+ * by both calls and their _multi forms: the stash is stored and loaded 16 bytes at a time),
  * cst_d [T][B][64], hprev_d [(b*T+t)][64].
  * drop_y / drop_mask (both or neither; out's layout): nn.LSTM(dropout=drop_p)'s inverted inter-layer dropout applied while the
  * outputs are stored -- drop_mask = 0 or 1/(1-p) per element from a counter-based hash of (element index, seed_ctr[0], salt),
@@ -322,7 +323,9 @@ int mmego_fc_relu_bf16_frag_tm(void* stream, const float* X, long ldx, const flo
 /* ---- IMU_Net stage-1 training pieces (imu_train.hip): reference Processor/Train/Train_IMU.py:21-34,114-149 -------
  * Pointwise LSTM cell backward of one timestep, both directions: dh = dout + dh_rec (dh_rec may be NULL), reads the
  * stashed gates / cell states, writes the pre-activation gate gradients dgates_d [Bn][4H] (row stride dgs) and updates
- * dc_d [Bn][H] in place (zero it before the last timestep).  cprev_d NULL means c_{t-1} = 0. */
+ * dc_d [Bn][H] in place (zero it before the last timestep).  cprev_d NULL means c_{t-1} = 0.  Only dout and dgates take a
+ * row stride (dos, dgs: time slices of [Bn][T][2H] / [Bn][T][8H] buffers); gst_d has the FIXED row stride 4H of mmego_lstm_step's
+ * stash, and cst_d, cprev_d, dh_rec_d, dc_d are dense [Bn][H]. */
 int mmego_lstm_cell_backward(void* stream, int ndir, int Bn, int H, const float* dout0, const float* dout1, long dos,
                              const float* dhrec0, const float* dhrec1, const float* gst0, const float* gst1,
                              const float* cst0, const float* cst1, const float* cprev0, const float* cprev1, float* dc0,

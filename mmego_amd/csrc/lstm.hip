@@ -230,6 +230,7 @@ extern "C" int mmego_lstm64_forward(void* stream, int B, int T, const float* xpr
   MMEGO_REQUIRE(B > 0 && T > 0 && xproj0 && xproj1 && whh0 && whh1 && out);
   MMEGO_REQUIRE((((uintptr_t)whh0 | (uintptr_t)whh1) & 15) == 0);
   MMEGO_REQUIRE((gates0 == nullptr) == (cst0 == nullptr) && (gates1 == nullptr) == (cst1 == nullptr));
+  MMEGO_REQUIRE((((uintptr_t)gates0 | (uintptr_t)gates1) & 15) == 0);      // the gate stash is stored as f32x4
   Lstm64P p;
   p.xproj[0] = xproj0; p.xproj[1] = xproj1; p.xs = xs;
   p.whh[0] = whh0; p.whh[1] = whh1;
@@ -402,6 +403,7 @@ extern "C" int mmego_lstm64_backward(void* stream, int B, int T, const float* do
                                      float* dgates1, long dgs) {
   MMEGO_REQUIRE(B > 0 && T > 0 && dout && gates0 && gates1 && cst0 && cst1 && whh0 && whh1 && dgates0 && dgates1);
   MMEGO_REQUIRE((((uintptr_t)whh0 | (uintptr_t)whh1) & 15) == 0);
+  MMEGO_REQUIRE((((uintptr_t)gates0 | (uintptr_t)gates1) & 15) == 0);      // the gate stash is loaded as f32x4
   Lstm64BwdP p;
   p.dout = dout; p.dos = dos;
   p.gates[0] = gates0; p.gates[1] = gates1; p.cst[0] = cst0; p.cst[1] = cst1;
@@ -428,6 +430,7 @@ extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const MmegoLstm64
     const MmegoLstm64Fwd& p = h[i];
     MMEGO_REQUIRE(p.B == B && p.T == T && B > 0 && T > 0 && p.xproj[0] && p.xproj[1] && p.whh[0] && p.whh[1] && p.out);
     MMEGO_REQUIRE((((uintptr_t)p.whh[0] | (uintptr_t)p.whh[1]) & 15) == 0);
+    MMEGO_REQUIRE((((uintptr_t)p.gates[0] | (uintptr_t)p.gates[1]) & 15) == 0);
     MMEGO_REQUIRE((p.drop_mask == nullptr) == (p.drop_y == nullptr) && (p.drop_mask != nullptr) == dr);
     MMEGO_REQUIRE(!p.drop_mask || (p.seed_ctr && p.drop_p > 0.f && p.drop_p < 1.f && (long)B * T * p.os < (1L << 32)));
     MMEGO_REQUIRE((p.gates[0] != nullptr) == st_ && (p.gates[1] != nullptr) == st_ && (p.cst[0] != nullptr) == st_ && (p.cst[1] != nullptr) == st_ &&
@@ -463,6 +466,7 @@ extern "C" int mmego_lstm64_backward_multi(void* stream, int n, const MmegoLstm6
     MMEGO_REQUIRE(p.B == B && p.T == T && B > 0 && T > 0 && p.dout && p.gates[0] && p.gates[1] && p.cst[0] && p.cst[1] && p.whh[0] && p.whh[1] &&
                   p.dgates[0] && p.dgates[1]);
     MMEGO_REQUIRE((((uintptr_t)p.whh[0] | (uintptr_t)p.whh[1]) & 15) == 0);
+    MMEGO_REQUIRE((((uintptr_t)p.gates[0] | (uintptr_t)p.gates[1]) & 15) == 0);
     m.p[i] = l64_param<Lstm64BwdP>(p);
   }
   for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = m.p[0];

@@ -5,8 +5,19 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// rcp / v_exp_f32 based activations: a few ulp from the libm forms at a fraction of their instruction count (libm expf is ~15 VALU
-// instructions; a step kernel's cell update evaluates 40 of them per lane).  sigmoidf_ of common.h is the libm form, for other users.
+// rcp / v_exp_f32 based activations at a fraction of the libm forms' instruction count (libm expf is ~15 VALU instructions; a step
+// kernel's cell update evaluates 40 of them per lane).  sigmoidf_ of common.h is the libm form, for other users.
+// Accuracy (u = 2^-24; derivation in tests/lstm_ref.py, held by tests/test_lstm_kernels_gpu.py, figures in NOTES.md "Float64 tests of
+// the LSTM recurrence kernels"), with v_exp_f32 and v_rcp_f32 taken as 1 ulp each:
+//   fast_sigmoid  RELATIVE error <= (1 - s)(1.23 |x| + 2) u + 3 u: the rounding of x * log2(e) and of the fp32 constant grow with |x|
+//                 where s is small (18 u at x = -20, 64 u at x = -80 in an fp32 emulation; 2-3 u for |x| <= 1); the ABSOLUTE error
+//                 stays below 1.6 u everywhere.  exp overflows to inf for x < -88.7: s = 0 exactly, where sigmoid < 2^-126.
+//   fast_tanh     ABSOLUTE error <= 2 r ((1 - r)(2.45 |x| + 2) + 3) u + |t| u with r = sigmoid(-2x): at most 4 u (2.4e-7), at x = 0
+//                 (emulation: 3.1 u).  It is NOT a few ulp of tanh near zero: t = 1 - 2r cancels, so for |x| < 1e-3 the relative
+//                 error reaches 1e-2 and beyond (|x| < 2^-24 may come out as 0 or with the wrong sign).  Harmless for the cell -- g
+//                 and tanh(c) enter sums and products of order-1 terms -- but nothing may divide by it or take its logarithm.
+// Saturation is exact: a sigmoid gate is 1.0f from x = 17 on (1 - g exactly 0 in the backward) and 0.0f below -88.7, and tanh is
+// +-1.0f beyond |x| = 9.1 (1 - tc^2 exactly 0).
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
