@@ -130,6 +130,25 @@ int mmego_gather_rows(void* stream, const float* X, long nsrc, long W, const lon
  * frame_idx lying inside the offset array. */
 int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
                       int pc_no, int max_n, float keep_p, unsigned long long seed, float* out);
+/* mmego_pack_frames with radar-return noise (data.FrameStore under --point_noise / --point_noise_v): keep, place and convert as above,
+ * from the same two streams -- with the same seed and keep_p the same returns land in the same slots and the zero rows are the same
+ * rows -- and every kept return is perturbed before its row is written.  Return j (its number inside its frame) of output frame q:
+ *   KN      = dropout_key(seed, 0x4e4f4953)                      -- a third stream of the launch
+ *   b       = key(KN, q, j)
+ *   h(c, i) = hash32(b + (unsigned)(4 c + i + 1))  (mod 2^32)    -- c = 0, 1, 2: x, y, z; c = 3: velocity; i = 0 .. 3
+ *   s_c     = sum_i (h(c, i) >> 10)                              -- four 22-bit integers, s_c < 2^24
+ *   z_c     = (float)((int)s_c - 8388606) * C                    -- C = 0x1.bb67aep-22f (bits 0x34ddb3d7: fp32 nearest to sqrt(3) 2^-22)
+ *   v'_c    = v_c + sigma_c * z_c                                -- sigma_c = sigma_xyz for c < 3, sigma_v for c = 3
+ * z_c is the centred sum of four uniforms (Irwin-Hall): mean 0, variance 1 - 2^-44, support +-2 sqrt(3) (about +-3.46), so the jitter is
+ * bell-shaped and clipped by construction.  The int -> float conversion is exact, the product and the sum are two separately rounded fp32
+ * operations (never a fused multiply-add): tests/point_noise_ref.py restates every bit in integer and fp32 numpy arithmetic, which a
+ * Box-Muller Gaussian would not allow.  A component whose sigma is 0 is copied, not computed (-0.0 + 0.0 * z would lose the sign).  r is
+ * formed from the perturbed x, y, z; intensity is never touched.  The noise is a function of (seed, q, j): it depends neither on which
+ * other returns were kept nor on the slot, and a frame listed twice gets two independent draws.  No LDS beyond mmego_pack_frames'.
+ * Refused: what mmego_pack_frames refuses, and a sigma that is negative, NaN or infinite.  sigma_xyz = sigma_v = 0: mmego_pack_frames'
+ * output, bit for bit. */
+int mmego_pack_frames_noise(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
+                            int pc_no, int max_n, float keep_p, unsigned long long seed, float sigma_xyz, float sigma_v, float* out);
 /* Dense inference (blend.hip; processors.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
  * src [nrows][C] contiguous; the cover of frame f = 0 .. F-1 is the CSR list k in [cov_off[f], cov_off[f+1]) (int64 offsets) of source
  * rows cov_row[k] (int32) with weights cov_w[k]:

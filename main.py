@@ -20,7 +20,9 @@ UpperNetwlocal with the anchor branch -- the net trained by --train --network Up
 and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
 rotation, shift and scale, PCK and the acceleration error on the device -- pose error apart from placement error; printed only, the log
 files keep their format), --window_jitter (every epoch each training window moves to a valid start within +-(frame_no-1) frames of its
-own) and --point_keep P (every minibatch's clouds are packed afresh on the device, each radar return kept with probability P): what a
+own), --point_keep P (every minibatch's clouds are packed afresh on the device, each radar return kept with probability P) and
+--point_noise S / --point_noise_v S (that device packing also jitters every kept return: x, y, z by a bell-shaped draw of standard deviation
+S metres, clipped at +-3.46 S, with r recomputed from the result, and the Doppler velocity likewise in its own units): what a
 run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched; --infer --dense [--stride S --blend
 {mean,triangle} --blend_space {joints,bones} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
 apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
@@ -109,6 +111,15 @@ def build_parser():
                    help="--train --network Upper_Net / Lower_Net: every minibatch's point clouds are packed afresh on the device from the "
                         "raw radar returns, each return kept with probability P in (0, 1] (1: only the packing is re-drawn); draws are "
                         "functions of (--seed, epoch, minibatch).  Evaluation stays on the loader's packing")
+    p.add_argument("--point_noise", type=float,
+                   help="--train --network Upper_Net / Lower_Net: metres, the standard deviation of the jitter on x, y and z of every radar "
+                        "return, added on the device while every minibatch's clouds are packed afresh (without --point_keep every return "
+                        "is kept and only the packing is re-drawn); a centred sum of four uniforms, so no draw lies beyond +-3.46 S; r is "
+                        "recomputed from the result.  Draws are functions of (--seed, epoch, minibatch).  Evaluation stays on the "
+                        "loader's packing")
+    p.add_argument("--point_noise_v", type=float,
+                   help="--train --network Upper_Net / Lower_Net: the same on the Doppler velocity of every radar return, in the "
+                        "recordings' units")
     p.add_argument("--dense", action="store_true",
                    help="--infer only: sliding-window inference over whole recordings -- overlapping frame_no-frame windows --stride frames "
                         "apart (tail-anchored, plus one window at every recording's head), every frame's pose blended on the device from "
@@ -152,17 +163,24 @@ def check_dense(parser, args):
 
 
 def check_frame_store(parser, args):
-    """--window_jitter and --point_keep change what a training run is trained on: they go with --train, and --point_keep with a net
-    that reads points."""
-    if not args.window_jitter and args.point_keep is None:
+    """--window_jitter, --point_keep, --point_noise and --point_noise_v change what a training run is trained on: they go with --train,
+    and the three that touch the points with a net that reads points."""
+    noise = [flag for flag in ("point_noise", "point_noise_v") if getattr(args, flag) is not None]
+    if not args.window_jitter and args.point_keep is None and not noise:
         return
     if args.point_keep is not None and not 0.0 < args.point_keep <= 1.0:          # (false for NaN as well)
         parser.error("--point_keep is the probability that a radar return is kept: it has to lie in (0, 1], got %r" % (args.point_keep,))
+    for flag in noise:
+        if not 0.0 < getattr(args, flag) < float("inf"):                         # (false for NaN as well)
+            parser.error("--%s is the standard deviation of the jitter on a radar return: it has to be finite and > 0, got %r"
+                         % (flag, getattr(args, flag)))
     if args.infer or not args.train:
-        parser.error("--window_jitter and --point_keep go with --train only: evaluation runs on the reference's test windows with the "
-                     "loader's packing")
+        parser.error("--window_jitter, --point_keep, --point_noise and --point_noise_v go with --train only: evaluation runs on the "
+                     "reference's test windows with the loader's packing")
     if args.point_keep is not None and args.network == "IMU_Net":
         parser.error("--point_keep does not go with --network IMU_Net: stage 1 reads no points (--window_jitter does)")
+    if noise and args.network == "IMU_Net":
+        parser.error("--%s does not go with --network IMU_Net: stage 1 reads no points (--window_jitter does)" % noise[0])
 
 
 def check_metrics(parser, args):
@@ -309,6 +327,7 @@ def apply_overrides(args):
     Config.ema_decay = args.ema_decay
     Config.window_jitter = bool(args.window_jitter)
     Config.point_keep = args.point_keep
+    Config.point_noise, Config.point_noise_v = args.point_noise, args.point_noise_v
     Config.seed = args.seed
     for c in both:
         c.upper_variant = args.upper_variant or "global"

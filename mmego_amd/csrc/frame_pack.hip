@@ -1,11 +1,14 @@
 // Point clouds packed on the device: raw radar returns -> [pc_no][6] frames, a fresh random packing per output frame
-// (data.pack_points' layout and distribution; data.FrameStore under --point_keep).  The recipe is the comment of
-// mmego_pack_frames in include/mmego_hip.h; tests/frame_pack_ref.py restates it in numpy.
+// (data.pack_points' layout and distribution; data.FrameStore under --point_keep), with or without noise on every kept return
+// (--point_noise, --point_noise_v).  The recipes are the comments of mmego_pack_frames and mmego_pack_frames_noise in
+// include/mmego_hip.h; tests/frame_pack_ref.py and tests/point_noise_ref.py restate them in numpy.
 #include "common.h"
 
 #define FP_WAVES 4                       // one wave per output frame, four per workgroup
 #define FP_SALT_KEEP 0x4b454550u         // the launch's keep stream
 #define FP_SALT_ORDER 0x4f524452u        // the launch's ordering stream
+#define FP_SALT_NOISE 0x4e4f4953u        // the launch's noise stream (mmego_pack_frames_noise)
+#define FP_NOISE_SCALE 0x1.bb67aep-22f   // fp32 nearest to sqrt(3) 2^-22: the centred sum of four 22-bit uniforms -> unit variance
 
 // one output row from one raw point: (x, y, z, intensity, velocity) -> (x, y, z, r, velocity, intensity)
 __device__ __forceinline__ void fp_row(float* __restrict__ dst, const float* __restrict__ p) {
@@ -16,12 +19,38 @@ __device__ __forceinline__ void fp_row(float* __restrict__ dst, const float* __r
   d[2] = make_float2(p[4], p[3]);
 }
 
+// z_c of the header's recipe: the centred sum of the four 22-bit draws h(c, 0 .. 3) of the return whose noise key is b, scaled to
+// unit variance.  The sum stays below 2^24, so its conversion is exact.
+__device__ __forceinline__ float fp_noise_z(unsigned b, unsigned c) {
+  unsigned s = 0;
+#pragma unroll
+  for (unsigned i = 0; i < 4; ++i) s += hash32(b + (4u * c + i + 1u)) >> 10;
+  return (float)((int)s - 8388606) * FP_NOISE_SCALE;
+}
+
+// fp_row of the perturbed point: x, y, z += sigma_xyz z_0..2 and velocity += sigma_v z_3, each as one rounded product and one rounded
+// sum (no fma: tests/point_noise_ref.py restates the bits); a channel whose sigma is 0 is copied, so that a -0.0 keeps its sign.
+__device__ __forceinline__ void fp_row_noise(float* __restrict__ dst, const float* __restrict__ p, unsigned b, float sigma_xyz,
+                                             float sigma_v) {
+  float v[5] = {p[0], p[1], p[2], p[3], p[4]};
+  if (sigma_xyz != 0.f) {
+#pragma unroll
+    for (unsigned c = 0; c < 3; ++c) v[c] = __fadd_rn(v[c], __fmul_rn(sigma_xyz, fp_noise_z(b, c)));
+  }
+  if (sigma_v != 0.f) v[4] = __fadd_rn(v[4], __fmul_rn(sigma_v, fp_noise_z(b, 3)));
+  fp_row(dst, v);
+}
+
 // LDS per wave: keys[m] (m = max(max_n, pc_no): the ordering keys of the slots, or of the survivors), then kept[max_n] (the
 // survivors' point numbers in increasing order).  Every wave meets the two workgroup barriers, whatever its frame holds; a wave
 // behind the last output frame packs an empty frame into its own LDS slice and writes nothing.
+// NOISE (mmego_pack_frames_noise) differs at the row write only: the kept return j of output frame q is perturbed under key(KN, q, j).
+// The sigmas come last, so that the plain instantiation reads the arguments it read before them.
+template <bool NOISE>
 __global__ __launch_bounds__(64 * FP_WAVES) void pack_frames_kernel(const float* __restrict__ pts, const long long* __restrict__ off,
                                                                    const long long* __restrict__ fidx, long nout, int pc_no, int max_n,
-                                                                   int m, float keep_p, unsigned long long seed, float* __restrict__ out) {
+                                                                   int m, float keep_p, unsigned long long seed, float* __restrict__ out,
+                                                                   float sigma_xyz, float sigma_v) {
   extern __shared__ unsigned fp_lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned* keys = fp_lds + (size_t)wave * (m + max_n);
@@ -74,6 +103,12 @@ __global__ __launch_bounds__(64 * FP_WAVES) void pack_frames_kernel(const float*
   // rank by counting: every lane compares its items' (key, index) with all of them (broadcast LDS reads).  Survivors are stored in
   // increasing point number, so the tie-break by position is the tie-break by point number.
   float* o = out + (size_t)q * pc_no * 6;
+  const unsigned fn = NOISE ? hash32(dropout_key(seed, FP_SALT_NOISE) ^ hq) : 0u;
+  auto row = [&](float* dst, unsigned j) {                         // the row of the frame's return j
+    const float* p = pts + (base + j) * 5;
+    if constexpr (NOISE) fp_row_noise(dst, p, hash32(fn ^ j), sigma_xyz, sigma_v);
+    else fp_row(dst, p);
+  };
   for (int i = lane; i < items; i += 64) {
     const unsigned k = keys[i];
     int r = 0;
@@ -82,9 +117,9 @@ __global__ __launch_bounds__(64 * FP_WAVES) void pack_frames_kernel(const float*
       r += (kt < k || (kt == k && t < i)) ? 1 : 0;
     }
     if (sub) {
-      if (r < pc_no) fp_row(o + (size_t)r * 6, pts + (base + kept[i]) * 5);
+      if (r < pc_no) row(o + (size_t)r * 6, kept[i]);
     } else if (r < cnt) {
-      fp_row(o + (size_t)i * 6, pts + (base + kept[r]) * 5);
+      row(o + (size_t)i * 6, kept[r]);
     } else {
       float2* d = (float2*)(o + (size_t)i * 6);
       d[0] = d[1] = d[2] = make_float2(0.f, 0.f);
@@ -92,8 +127,10 @@ __global__ __launch_bounds__(64 * FP_WAVES) void pack_frames_kernel(const float*
   }
 }
 
-extern "C" int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
-                                 int pc_no, int max_n, float keep_p, unsigned long long seed, float* out) {
+// What both entry points refuse, and the launch: sigma 0, 0 without NOISE is mmego_pack_frames.
+template <bool NOISE>
+static int pack_frames_launch(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout, int pc_no,
+                              int max_n, float keep_p, unsigned long long seed, float sigma_xyz, float sigma_v, float* out) {
   MMEGO_REQUIRE(pts && frame_off && frame_idx && out && nout >= 1 && nout < (1L << 31));
   MMEGO_REQUIRE(pc_no >= 1 && pc_no <= 1024 && max_n >= 1 && max_n <= 16384);
   MMEGO_REQUIRE(keep_p > 0.f && keep_p <= 1.f);                    // (false for a NaN as well)
@@ -101,9 +138,23 @@ extern "C" int mmego_pack_frames(void* stream, const float* pts, const long long
   const int m = max_n > pc_no ? max_n : pc_no;
   const size_t lds = (size_t)FP_WAVES * (size_t)(m + max_n) * sizeof(unsigned);
   MMEGO_REQUIRE(lds <= 64 * 1024);
-  if (int e = mmego_allow_lds<pack_frames_kernel>(lds)) return e;
-  hipLaunchKernelGGL(pack_frames_kernel, dim3((unsigned)cdiv(nout, FP_WAVES)), dim3(64 * FP_WAVES), lds, (hipStream_t)stream, pts, frame_off,
-                     frame_idx, nout, pc_no, max_n, m, keep_p, seed, out);
+  if (int e = mmego_allow_lds<pack_frames_kernel<NOISE>>(lds)) return e;
+  hipLaunchKernelGGL(pack_frames_kernel<NOISE>, dim3((unsigned)cdiv(nout, FP_WAVES)), dim3(64 * FP_WAVES), lds, (hipStream_t)stream, pts,
+                     frame_off, frame_idx, nout, pc_no, max_n, m, keep_p, seed, out, sigma_xyz, sigma_v);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
+}
+
+extern "C" int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
+                                 int pc_no, int max_n, float keep_p, unsigned long long seed, float* out) {
+  return pack_frames_launch<false>(stream, pts, frame_off, frame_idx, nout, pc_no, max_n, keep_p, seed, 0.f, 0.f, out);
+}
+
+extern "C" int mmego_pack_frames_noise(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
+                                       int pc_no, int max_n, float keep_p, unsigned long long seed, float sigma_xyz, float sigma_v,
+                                       float* out) {
+  MMEGO_REQUIRE(sigma_xyz >= 0.f && sigma_xyz < INFINITY && sigma_v >= 0.f && sigma_v < INFINITY);      // (false for a NaN as well)
+  if (sigma_xyz == 0.f && sigma_v == 0.f)                          // nothing to add: the plain kernel, the same bytes
+    return pack_frames_launch<false>(stream, pts, frame_off, frame_idx, nout, pc_no, max_n, keep_p, seed, 0.f, 0.f, out);
+  return pack_frames_launch<true>(stream, pts, frame_off, frame_idx, nout, pc_no, max_n, keep_p, seed, sigma_xyz, sigma_v, out);
 }

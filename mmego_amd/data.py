@@ -307,8 +307,12 @@ class FrameStore:
       point_keep   every gather packs the raw returns of its frames afresh on the device (mmego_pack_frames): each return kept with
                    probability point_keep, the survivors at random slots (or a random ordered subsample of them), as pack_points does
                    once per load on the host.  1.0 only re-draws the packing.
+      point_noise, point_noise_v   (finite floats > 0) the same per-gather packing with every kept return perturbed inside the packer
+                   (mmego_pack_frames_noise): x, y, z by point_noise z, the Doppler velocity by point_noise_v z, z of unit variance and
+                   support +-2 sqrt(3); r follows the perturbed x, y, z.  Without point_keep every return is kept (keep_p = 1: the
+                   packing is re-drawn, as under point_keep = 1).
 
-    Both off: the reference's windows and the loader's packing -- gather() returns what DeviceArrays(dataset).gather() returns.
+    All off: the reference's windows and the loader's packing -- gather() returns what DeviceArrays(dataset).gather() returns.
     The start draws come from a RandomState of their own seeded by (seed, epoch), the packing seeds from (seed, epoch, minibatch
     number): neither touches the RNG of the minibatch order, every data-parallel rank draws the same starts, and a run resumed
     at an epoch continues the same sequence.  ``index`` of gather / gather_field_into holds training-window numbers, as for
@@ -317,7 +321,7 @@ class FrameStore:
     UNUSED, TRAIN, TEST = 0, 1, 2
     FIELDS = DeviceArrays.FIELDS
 
-    def __init__(self, dataset, device, jitter=False, point_keep=None, seed=0):
+    def __init__(self, dataset, device, jitter=False, point_keep=None, seed=0, point_noise=None, point_noise_v=None):
         import torch
         from . import ops
         if getattr(dataset, "frame_packed_", None) is None:
@@ -326,8 +330,15 @@ class FrameStore:
             raise ValueError("FrameStore serves the training split of a PosePC(train=True)")
         if point_keep is not None and not 0.0 < float(point_keep) <= 1.0:
             raise ValueError("point_keep is a probability in (0, 1], got %r" % (point_keep,))
+        for name, v in (("point_noise", point_noise), ("point_noise_v", point_noise_v)):
+            if v is not None and not 0.0 < float(v) < float("inf"):          # (false for NaN as well)
+                raise ValueError("%s is a standard deviation, finite and > 0 (None: no noise), got %r" % (name, v))
         self.device, self.n = device, len(dataset)
         self.jitter, self.point_keep, self.seed = bool(jitter), None if point_keep is None else float(point_keep), int(seed)
+        self.point_noise = None if point_noise is None else float(point_noise)
+        self.point_noise_v = None if point_noise_v is None else float(point_noise_v)
+        self.noisy = self.point_noise is not None or self.point_noise_v is not None
+        self.repack = self.point_keep is not None or self.noisy          # `data` is packed per gather from the raw returns
         self.L, self.pc_no = L, pc_no = int(dataset.frame_no), int(dataset.pc_no)
         self.F = F = len(dataset.frame_npts_)
         # who owns a frame: the one PosePC knows both sides of the split
@@ -362,7 +373,7 @@ class FrameStore:
         npts = np.asarray(dataset.frame_npts_, dtype=np.int64)
         self.max_n = int(npts.max()) if F else 1
         self.pts = self.off = None
-        if self.point_keep is not None:
+        if self.repack:
             if pc_no > ops.PACK_FRAMES_MAX_PC_NO or self.max_n > ops.pack_frames_max_n(pc_no):
                 raise ValueError("a frame of %d points at pc_no = %d is beyond what mmego_pack_frames' 64 KB of LDS hold (at most %d points)"
                                  % (self.max_n, pc_no, ops.pack_frames_max_n(pc_no)))
@@ -407,8 +418,12 @@ class FrameStore:
             if z is None:
                 z = self._zero_idx[B] = torch.zeros(B, dtype=torch.int64, device=self.device)
             return ops.gather_rows(self.src["skl"], z, dst.view(B, -1))
-        if name == "data" and self.point_keep is not None:
-            return ops.pack_frames(self.pts, self.off, fidx, dst.view(B * self.L, self.pc_no, 6), self.max_n, self.point_keep, pack_seed)
+        if name == "data" and self.repack:
+            keep = 1.0 if self.point_keep is None else self.point_keep
+            if self.noisy:
+                return ops.pack_frames_noise(self.pts, self.off, fidx, dst.view(B * self.L, self.pc_no, 6), self.max_n, keep, pack_seed,
+                                             self.point_noise or 0.0, self.point_noise_v or 0.0)
+            return ops.pack_frames(self.pts, self.off, fidx, dst.view(B * self.L, self.pc_no, 6), self.max_n, keep, pack_seed)
         return ops.gather_rows(self.src[name], fidx, dst.view(B * self.L, self.width[name]))
 
     def gather(self, index):
@@ -430,7 +445,7 @@ class FrameStore:
 
     def gather_field_into(self, name, index, out):
         """One field of the windows `index`, at this epoch's starts, into a caller-owned buffer (DeviceArrays.gather_field_into)."""
-        if name == "data" and self.point_keep is not None:
+        if name == "data" and self.repack:
             raise ValueError("the re-drawn clouds belong to gather(): their seed is its minibatch counter")
         fidx, B = self._upload(index)
         self._field(name, fidx, B, out, 0)

@@ -629,10 +629,7 @@ def pack_frames_max_n(pc_no):
     return max(0, min(words // 2, words - int(pc_no)))
 
 
-def pack_frames(pts, frame_off, frame_idx, out, max_n, keep_p, seed):
-    """out[q] [pc_no, 6] = a fresh random packing of the raw points [P, 5] of frame frame_idx[q] (int64 CSR offsets frame_off; every
-    index has to lie in [0, len(frame_off) - 1): the caller's to check, the index lives on the device), each point kept with probability
-    keep_p (mmego_pack_frames: the recipe is in the header).  The same ``seed`` (an integer below 2^64) gives the same output."""
+def _pack_frames_check(pts, frame_off, frame_idx, out):
     _chk(pts, 2)
     if not (pts.is_contiguous() and pts.shape[1] == 5 and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
             and out.dim() == 3 and out.shape[2] == 6):
@@ -642,8 +639,26 @@ def pack_frames(pts, frame_off, frame_idx, out, max_n, keep_p, seed):
             raise ValueError("pack_frames needs contiguous int64 device offsets and frame numbers")
     if frame_idx.numel() != out.shape[0] or frame_off.numel() < 2:
         raise ValueError("pack_frames shape mismatch")
+
+
+def pack_frames(pts, frame_off, frame_idx, out, max_n, keep_p, seed):
+    """out[q] [pc_no, 6] = a fresh random packing of the raw points [P, 5] of frame frame_idx[q] (int64 CSR offsets frame_off; every
+    index has to lie in [0, len(frame_off) - 1): the caller's to check, the index lives on the device), each point kept with probability
+    keep_p (mmego_pack_frames: the recipe is in the header).  The same ``seed`` (an integer below 2^64) gives the same output."""
+    _pack_frames_check(pts, frame_off, frame_idx, out)
     hip.call("pack_frames", pts, frame_off, frame_idx, frame_idx.numel(), out.shape[1], int(max_n), float(keep_p),
              int(seed) & 0xFFFFFFFFFFFFFFFF, out)
+    return out
+
+
+def pack_frames_noise(pts, frame_off, frame_idx, out, max_n, keep_p, seed, sigma_xyz, sigma_v):
+    """pack_frames -- the same returns in the same slots for the same ``seed`` and ``keep_p`` -- with every kept return perturbed before
+    its row is written: x, y, z by sigma_xyz z and the velocity by sigma_v z, z a centred sum of four uniforms of unit variance and
+    support +-2 sqrt(3) drawn per (seed, output frame, return, channel); r is formed from the perturbed x, y, z and the intensity is
+    copied (mmego_pack_frames_noise: the recipe is in the header).  A sigma of 0 leaves its channels' bits alone."""
+    _pack_frames_check(pts, frame_off, frame_idx, out)
+    hip.call("pack_frames_noise", pts, frame_off, frame_idx, frame_idx.numel(), out.shape[1], int(max_n), float(keep_p),
+             int(seed) & 0xFFFFFFFFFFFFFFFF, float(sigma_xyz), float(sigma_v), out)
     return out
 
 

@@ -93,31 +93,36 @@ class _Base:
             model.seed_counter().bitwise_xor_((self.rank * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF)
 
     def _frame_store_options(self):
-        """(--window_jitter, --point_keep): either one makes the training split a data.FrameStore instead of DeviceArrays."""
-        keep = getattr(self.cfg, "point_keep", None)
-        return bool(getattr(self.cfg, "window_jitter", False)), None if keep is None else float(keep)
+        """(--window_jitter, --point_keep, (--point_noise, --point_noise_v)): any of them makes the training split a data.FrameStore
+        instead of DeviceArrays."""
+        keep, noise = getattr(self.cfg, "point_keep", None), [getattr(self.cfg, k, None) for k in ("point_noise", "point_noise_v")]
+        return (bool(getattr(self.cfg, "window_jitter", False)), None if keep is None else float(keep),
+                tuple(None if v is None else float(v) for v in noise))
 
     def _load_splits(self):
         """The two PosePC splits; the training one keeps its per-frame clouds when a FrameStore is going to serve it."""
-        jitter, keep = self._frame_store_options()
-        self.train_data = PosePC(batch_length=self.frame_no, keep_frames=jitter or keep is not None)
+        jitter, keep, noise = self._frame_store_options()
+        self.train_data = PosePC(batch_length=self.frame_no, keep_frames=jitter or keep is not None or noise != (None, None))
         self.test_data = PosePC(train=False, batch_length=self.frame_no)
         self._epoch = 0               # (the epoch _epochs is in: what a FrameStore draws its window starts and packing seeds from)
 
     def _train_arrays(self):
         """The training split in HBM, uploaded at the first training pass: finished windows (DeviceArrays: the reference's windows, the
-        loader's packing), or -- --window_jitter / --point_keep -- frames (FrameStore), told which epoch begins."""
+        loader's packing), or -- --window_jitter / --point_keep / --point_noise / --point_noise_v -- frames (FrameStore), told which epoch begins."""
         if self._train_dev is None:
-            jitter, keep = self._frame_store_options()
-            if not jitter and keep is None:
+            jitter, keep, noise = self._frame_store_options()
+            if not jitter and keep is None and noise == (None, None):
                 self._train_dev = DeviceArrays(self.train_data, self.device)
             else:
                 fs = self._train_dev = FrameStore(self.train_data, self.device, jitter=jitter, point_keep=keep,
-                                                  seed=getattr(self.cfg, "seed", None) or 0)
+                                                  seed=getattr(self.cfg, "seed", None) or 0, point_noise=noise[0], point_noise_v=noise[1])
                 if self.rank == 0:
+                    said = "" if keep is None else "; clouds re-drawn per minibatch, point_keep %g" % keep
+                    if noise != (None, None):
+                        said += "%s; return noise sigma %s" % ("; clouds re-drawn per minibatch" if keep is None else "", ", ".join(
+                            "%s %g" % (n, v) for n, v in zip(("xyz", "velocity"), noise) if v is not None))
                     print("[mmego_amd] frame store: %d frames, %d valid window starts (%d training windows, %d of them movable)%s%s"
-                          % (fs.F, len(fs.valid_starts()), fs.n, fs.n_movable, "; window jitter on" if jitter else "",
-                             "" if keep is None else "; clouds re-drawn per minibatch, point_keep %g" % keep))
+                          % (fs.F, len(fs.valid_starts()), fs.n, fs.n_movable, "; window jitter on" if jitter else "", said))
         if isinstance(self._train_dev, FrameStore):
             self._train_dev.begin_epoch(self._epoch)
         return self._train_dev
