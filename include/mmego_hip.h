@@ -149,6 +149,28 @@ int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off
  * output, bit for bit. */
 int mmego_pack_frames_noise(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
                             int pc_no, int max_n, float keep_p, unsigned long long seed, float sigma_xyz, float sigma_v, float* out);
+/* Head-pose noise (pose_noise.hip; train_step.StageStep under pose_noise_deg / pose_noise_t, processors._epoch_eval and dense_infer under
+ * pose_noise): row i = 0 .. n-1 of the head poses R [n][3][3] (row-major) and t [n][3] perturbed into R_out, t_out.  seed_word is ONE
+ * int64 word ON THE DEVICE, read by the kernel: a launch captured into a HIP graph sees the word the host wrote before the replay (the
+ * convention of mmego_seed_take / mmego_lstm_dropout).  ids (int64 on the device, may be NULL) gives every row its draw number
+ * d = ids[i], else d = i: rows with one draw number get one draw.  With hash32 and dropout_key as in csrc/common.h:
+ *   K       = dropout_key((unsigned long long)seed_word[0], 0x504F5345)         -- the launch's stream
+ *   b       = hash32(K ^ hash32((unsigned)d))                                    -- the row's word
+ *   z_c     = mmego_pack_frames_noise's z_c of b, c = 0 .. 5                     -- six draws of unit variance, |z_c| <= 2 sqrt(3)
+ *   w       = (sigma_deg pi / 180) (z_0, z_1, z_2) in double, theta = |w|
+ *   E       = I + a [w]x + b' [w]x^2,  a = sin(theta) / theta,  b' = (1 - cos(theta)) / theta^2;  for theta < 1e-3 the series
+ *             a = 1 - theta^2/6 + theta^4/120,  b' = 1/2 - theta^2/24 + theta^4/720
+ *   R_out   = (float)(E R): products and sums in double, one float store per entry
+ *   t_out_c = (float)((double)t_c + sigma_t z_{3+c})
+ * E multiplies from the left: a rotation on the head-frame side of R (xyz - t); w being isotropic, composing on the other side has the
+ * same distribution.  sigma_deg is the standard deviation of the rotation vector PER AXIS, in degrees: the RMS rotation angle is
+ * sqrt(3) sigma_deg and no row turns by more than 6 sigma_deg; sigma_t is in t's units and no component moves by more than 3.47 sigma_t.
+ * sigma_deg == 0 copies R bit for bit, sigma_t == 0 copies t bit for bit.  One thread per row, no LDS, no atomics; two launches with one
+ * word give the same bytes.  Refused (non-zero, nothing launched): a null R, t, R_out, t_out or seed_word; n < 1 (or >= 2^40); a sigma
+ * that is negative, NaN or infinite; both sigmas 0; a seed_word or ids that is not 8-byte aligned; an output that overlaps an input other
+ * than R_out == R or t_out == t exactly (a thread reads its row before it writes it); R_out overlapping t_out. */
+int mmego_pose_jitter(void* stream, const float* R, const float* t, long n, double sigma_deg, double sigma_t,
+                      const long long* seed_word, const long long* ids, float* R_out, float* t_out);
 /* Dense inference (blend.hip; processors.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
  * src [nrows][C] contiguous; the cover of frame f = 0 .. F-1 is the CSR list k in [cov_off[f], cov_off[f+1]) (int64 offsets) of source
  * rows cov_row[k] (int32) with weights cov_w[k]:

@@ -27,7 +27,13 @@ run is trained on, from the frame-major device store data.FrameStore; evaluation
 {mean,triangle} --blend_space {joints,bones} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
 apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
 by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons; --blend_space bones
-blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again), --pose_noise_deg D /
+--pose_noise_t S (the head pose Upper_Net and Lower_Net get -- the recording's under --gt_head_pose, else the frozen IMU_Net's -- is
+perturbed per frame on the device: a random rotation whose rotation vector has standard deviation D degrees per axis, never beyond 6 D in
+all, and a random shift of standard deviation S metres per component, never beyond 3.47 S.  With --train --network Upper_Net / Lower_Net
+the draw is renewed every minibatch inside the captured step, as a function of (--seed, epoch, minibatch, rank), and the epoch evaluation
+is untouched; with --infer and --infer --dense it is a sensitivity instrument -- how much joint error a degree or a centimetre of
+head-pose error costs -- and one "Head Pose Noise" line follows the figures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -120,6 +126,16 @@ def build_parser():
     p.add_argument("--point_noise_v", type=float,
                    help="--train --network Upper_Net / Lower_Net: the same on the Doppler velocity of every radar return, in the "
                         "recordings' units")
+    p.add_argument("--pose_noise_deg", type=float,
+                   help="--train --network Upper_Net / Lower_Net, or --infer [--dense]: degrees, the standard deviation PER AXIS of a random "
+                        "rotation vector applied to every frame's head pose before the nets see it (RMS rotation angle sqrt(3) D, never "
+                        "beyond 6 D; a centred sum of four uniforms per axis).  Training: re-drawn every minibatch on the device from "
+                        "(--seed, epoch, minibatch, rank), so --resume continues the sequence; the epoch evaluation is untouched.  --infer: "
+                        "drawn from --seed; --dense gives a frame one pose error in every window that serves it.  Not with "
+                        "--finetune_imu / --finetune_all (no gradient flows through the perturbation)")
+    p.add_argument("--pose_noise_t", type=float,
+                   help="the same on the head position: metres, the standard deviation per component of a random shift (never beyond "
+                        "3.47 S).  Either flag may be given without the other")
     p.add_argument("--dense", action="store_true",
                    help="--infer only: sliding-window inference over whole recordings -- overlapping frame_no-frame windows --stride frames "
                         "apart (tail-anchored, plus one window at every recording's head), every frame's pose blended on the device from "
@@ -181,6 +197,29 @@ def check_frame_store(parser, args):
         parser.error("--point_keep does not go with --network IMU_Net: stage 1 reads no points (--window_jitter does)")
     if noise and args.network == "IMU_Net":
         parser.error("--%s does not go with --network IMU_Net: stage 1 reads no points (--window_jitter does)" % noise[0])
+
+
+def check_pose_noise(parser, args):
+    """--pose_noise_deg and --pose_noise_t perturb the head pose that Upper_Net and Lower_Net are given: they go with a run that gives
+    them one as data."""
+    given = [flag for flag in ("pose_noise_deg", "pose_noise_t") if getattr(args, flag) is not None]
+    if not given:
+        return
+    for flag in given:
+        if not 0.0 < getattr(args, flag) < float("inf"):                         # (false for NaN as well)
+            parser.error("--%s is the standard deviation of the head-pose noise: it has to be finite and > 0, got %r"
+                         % (flag, getattr(args, flag)))
+    flag = given[0]
+    if not (args.train or args.infer):
+        parser.error("--%s goes with --train (--network Upper_Net / Lower_Net) or --infer: nothing else runs a net on a head pose" % flag)
+    if args.network == "IMU_Net":
+        parser.error("--%s does not go with --network IMU_Net: stage 1 is given no head pose, it estimates one" % flag)
+    for ft in ("finetune_imu", "finetune_all"):
+        if getattr(args, ft):
+            parser.error("--%s cannot be combined with --%s: that run trains the head pose, and no gradient flows through the perturbation"
+                         % (flag, ft))
+    if args.vis:
+        parser.error("--%s does not go with --vis" % flag)
 
 
 def check_metrics(parser, args):
@@ -281,6 +320,7 @@ def check_finetune(parser, args, world):
     check_ema_decay(parser, args)
     check_frame_store(parser, args)
     check_dense(parser, args)
+    check_pose_noise(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -329,6 +369,10 @@ def apply_overrides(args):
     Config.point_keep = args.point_keep
     Config.point_noise, Config.point_noise_v = args.point_noise, args.point_noise_v
     Config.seed = args.seed
+    for c in both:
+        c.pose_noise_deg, c.pose_noise_t = args.pose_noise_deg, args.pose_noise_t
+    if args.pose_noise_deg is not None or args.pose_noise_t is not None:
+        ConfigDemo.seed = args.seed                  # (--infer under the flags: the draws' seed)
     for c in both:
         c.upper_variant = args.upper_variant or "global"
         c.metrics = args.metrics

@@ -55,6 +55,8 @@ class _Common:
     point_keep = None           # --point_keep: clouds re-packed on the device per minibatch, each return kept with this probability (None: the loader's packing)
     point_noise = None          # --point_noise: metres, standard deviation of the jitter the device packer adds to x, y, z of every kept return per minibatch; r follows (None: none)
     point_noise_v = None        # --point_noise_v: the same on the Doppler velocity, in the recordings' units (None: none)
+    pose_noise_deg = None       # --pose_noise_deg: degrees per axis, standard deviation of the random rotation vector applied to every frame's head pose (None: none)
+    pose_noise_t = None         # --pose_noise_t: metres per component, standard deviation of the random shift of every frame's head position (None: none)
     seed = None                 # --seed, as main.py got it (None: 0 for what FrameStore draws)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
     ema_decay = None            # --ema_decay: every trained net keeps a weight average at this decay; evaluation uses it (None: off)

@@ -3,12 +3,12 @@
 // (--point_noise, --point_noise_v).  The recipes are the comments of mmego_pack_frames and mmego_pack_frames_noise in
 // include/mmego_hip.h; tests/frame_pack_ref.py and tests/point_noise_ref.py restate them in numpy.
 #include "common.h"
+#include "noise_draw.h"                  // fp_noise_z, FP_NOISE_SCALE: the draw mmego_pose_jitter shares
 
 #define FP_WAVES 4                       // one wave per output frame, four per workgroup
 #define FP_SALT_KEEP 0x4b454550u         // the launch's keep stream
 #define FP_SALT_ORDER 0x4f524452u        // the launch's ordering stream
 #define FP_SALT_NOISE 0x4e4f4953u        // the launch's noise stream (mmego_pack_frames_noise)
-#define FP_NOISE_SCALE 0x1.bb67aep-22f   // fp32 nearest to sqrt(3) 2^-22: the centred sum of four 22-bit uniforms -> unit variance
 
 // one output row from one raw point: (x, y, z, intensity, velocity) -> (x, y, z, r, velocity, intensity)
 __device__ __forceinline__ void fp_row(float* __restrict__ dst, const float* __restrict__ p) {
@@ -17,15 +17,6 @@ __device__ __forceinline__ void fp_row(float* __restrict__ dst, const float* __r
   d[0] = make_float2(x, y);
   d[1] = make_float2(z, sqrtf(x * x + y * y + z * z));
   d[2] = make_float2(p[4], p[3]);
-}
-
-// z_c of the header's recipe: the centred sum of the four 22-bit draws h(c, 0 .. 3) of the return whose noise key is b, scaled to
-// unit variance.  The sum stays below 2^24, so its conversion is exact.
-__device__ __forceinline__ float fp_noise_z(unsigned b, unsigned c) {
-  unsigned s = 0;
-#pragma unroll
-  for (unsigned i = 0; i < 4; ++i) s += hash32(b + (4u * c + i + 1u)) >> 10;
-  return (float)((int)s - 8388606) * FP_NOISE_SCALE;
 }
 
 // fp_row of the perturbed point: x, y, z += sigma_xyz z_0..2 and velocity += sigma_v z_3, each as one rounded product and one rounded

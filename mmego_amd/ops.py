@@ -662,6 +662,34 @@ def pack_frames_noise(pts, frame_off, frame_idx, out, max_n, keep_p, seed, sigma
     return out
 
 
+def pose_jitter(R, t, sigma_deg, sigma_t, word, R_out, t_out, ids=None):
+    """(R_out, t_out) = the head poses R [..., 3, 3], t [..., 3] each perturbed by a random rotation (rotation vector of standard
+    deviation sigma_deg degrees per axis, never beyond 6 sigma_deg in all) and a random shift (sigma_t per component, never beyond
+    3.47 sigma_t), drawn from ``word`` -- ONE int64 word on the device, read by the kernel, so a captured launch draws afresh once the
+    word is rewritten -- and the row's draw number: ids[i] (int64 on the device, one per row) or the row number (mmego_pose_jitter: the
+    recipe is in the header).  A sigma of 0 copies its half bit for bit; both 0 are refused.  R_out may be R and t_out may be t."""
+    for x, tail, what in ((R, (3, 3), "R"), (t, (3,), "t"), (R_out, (3, 3), "R_out"), (t_out, (3,), "t_out")):
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape[-len(tail):]) == tail
+                and x.dim() > len(tail)):
+            raise ValueError("pose_jitter: %s is a contiguous fp32 tensor [..., %s]" % (what, ", ".join(map(str, tail))))
+    n = R.numel() // 9
+    if n < 1 or t.numel() != 3 * n or R_out.numel() != 9 * n or t_out.numel() != 3 * n:
+        raise ValueError("pose_jitter: R %s, t %s, R_out %s and t_out %s do not hold one and the same number of poses"
+                         % tuple(tuple(x.shape) for x in (R, t, R_out, t_out)))
+    if not (isinstance(word, torch.Tensor) and word.dtype == torch.int64 and word.numel() >= 1 and word.is_contiguous()
+            and word.device.type == "cuda"):
+        raise TypeError("pose_jitter needs an int64 device seed word")
+    if ids is not None:
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and ids.is_contiguous() and ids.device.type == "cuda"):
+            raise TypeError("pose_jitter: ids are contiguous int64 draw numbers on the device")
+        if ids.numel() != n:
+            raise ValueError("pose_jitter: %d ids for %d poses" % (ids.numel(), n))
+    for x in (R, t, R_out, t_out):
+        _chk(x, x.dim())
+    hip.call("pose_jitter", R, t, n, float(sigma_deg), float(sigma_t), word, ids, R_out, t_out)
+    return R_out, t_out
+
+
 def relu_mask_(G, H):
     G, H = _rows(G), _rows(H)
     hip.call("relu_mask", G, G.stride(0), H, H.stride(0), G.shape[0], G.shape[1])

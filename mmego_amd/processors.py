@@ -18,7 +18,7 @@ import torch
 
 from . import blocks, hip, ops, skeleton
 from .config import Config, ConfigDemo
-from .data import DeviceArrays, FrameStore, PosePC, batch_indices
+from .data import DeviceArrays, FrameStore, PosePC, _mix64, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam
 from .nets_local import UpperNetwlocal
@@ -33,6 +33,41 @@ _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_
 UPPER_VARIANTS = {"global": UpperNet, "wlocal": UpperNetwlocal}          # --upper_variant -> the class behind "Upper_Net"
 METRICS = ("reference", "full")                                          # --metrics
 PCK_THRESHOLDS_CM = (5.0, 10.0, 15.0)                                    # --metrics full: PCK of the absolute joint errors
+
+
+POSE_NOISE_SALT = 0x504F5345                                             # the head-pose draws' stream among what _mix64 derives from --seed
+
+
+def pose_noise_key(seed, epoch, minibatch, rank=None):
+    """The key of one minibatch's head-pose draw (--pose_noise_deg / --pose_noise_t): a pure function of (seed, epoch, minibatch number
+    [, rank]), so --resume continues the sequence with no saved state and the ranks of a data-parallel run draw differently.  rank None:
+    the evaluation passes' key, which has no rank.  -> the 63 bits mmego_pose_jitter's int64 device word takes."""
+    words = (int(seed), int(epoch), int(minibatch)) + (() if rank is None else (int(rank),))
+    return _mix64(*words, POSE_NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
+
+
+def pose_noise_of(cfg):
+    """(deg, t, seed) of a run's --pose_noise_deg / --pose_noise_t (a missing sigma: 0.0; a missing --seed: 0, as --point_noise treats
+    it), or None without the flags."""
+    deg, t = getattr(cfg, "pose_noise_deg", None), getattr(cfg, "pose_noise_t", None)
+    if deg is None and t is None:
+        return None
+    return (0.0 if deg is None else float(deg), 0.0 if t is None else float(t), int(getattr(cfg, "seed", None) or 0))
+
+
+def pose_noise_line(pose_noise):
+    return "Head Pose Noise: rotation {} deg per axis, translation {} m, seed {}".format(*pose_noise)
+
+
+def _jitter_pose(scratch, R, t, pose_noise, key, ids=None):
+    """An evaluation minibatch's head pose perturbed out of place (buffers and the device word kept in ``scratch`` per shape)."""
+    R, t = R.contiguous(), t.contiguous()
+    slot = ("pose_noise",) + tuple(R.shape)
+    if slot not in scratch:
+        scratch[slot] = (torch.empty_like(R), torch.empty_like(t), torch.zeros(1, dtype=torch.int64, device=R.device))
+    R_n, t_n, word = scratch[slot]
+    word.fill_(int(key))
+    return ops.pose_jitter(R, t, pose_noise[0], pose_noise[1], word, R_n, t_n, ids=ids)
 
 
 def upper_variant_of(state_dict):
@@ -60,6 +95,7 @@ class _Base:
     """Shared set-up: directories, frozen IMU_Net (or ground-truth head pose), datasets."""
     finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
     finetune_upper = False        # (--finetune_upper: likewise)
+    pose_noise = None             # (--pose_noise_deg, --pose_noise_t: (deg, t, seed), set by the stage trainers from the config)
     # The trainer's optimisers, keyed like train_step.TRAINED ("opt": the stage's own net, "imu_opt", "upper_opt"): ONE set, handed to
     # the step of every minibatch size, read by the grad-norm report and the checkpoint (a trainer's __init__ makes it a dict)
     _opts = types.MappingProxyType({})
@@ -338,6 +374,14 @@ class _StageTrainer(_Base):
         if self.finetune_upper and self._upper_variant() != "global":
             raise SystemExit("--upper_variant wlocal: --finetune_upper / --finetune_all train a plain UpperNet only (UpperNetwlocal stays "
                              "frozen in stage 3)")
+        self.pose_noise = pose_noise_of(cfg)                           # (--pose_noise_deg, --pose_noise_t: (deg, t, seed) or None)
+        if self.pose_noise is not None:
+            if self.finetune_imu:
+                raise SystemExit("--pose_noise_deg / --pose_noise_t perturb a head pose that is data: not with --finetune_imu / --finetune_all, "
+                                 "which train it")
+            if self.rank == 0:
+                print("[mmego_amd] head-pose noise: rotation %g deg per axis, translation %g m, re-drawn per minibatch from (seed %d, epoch, "
+                      "minibatch, rank); evaluation untouched" % self.pose_noise)
         self.model_IMU = self._load_imu()
         self._opts = {}
         self._load_splits()
@@ -370,7 +414,8 @@ class _StageTrainer(_Base):
                            imu_lr=self.learning_rate if imu_lr is None else imu_lr,
                            finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
                            clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts,
-                           ema_decay=getattr(self.cfg, "ema_decay", None))
+                           ema_decay=getattr(self.cfg, "ema_decay", None),
+                           **({} if self.pose_noise is None else dict(pose_noise_deg=self.pose_noise[0], pose_noise_t=self.pose_noise[1])))
             st.engine = None
             if pipelined:
                 st.imu_next = torch.empty((B, self.frame_no) + tuple(self._train_dev.shape["imu"][1:]), dtype=torch.float32,
@@ -404,6 +449,8 @@ class _StageTrainer(_Base):
             tgt = b["target"]
             if st.static is None or st.static["x_src"].data_ptr() != b["data"].data_ptr():
                 st.bind(b["data"], b["imu"], b["skl"], tgt, R_gt=b["R_R0R"])
+            if self.pose_noise is not None:                             # this minibatch's head-pose draw (the word the captured launch reads)
+                st.set_pose_key(pose_noise_key(self.pose_noise[2], self._epoch, i, self.rank))
             if st.engine is None:
                 st.step()
             else:
@@ -521,7 +568,7 @@ class LowerTrainer(_StageTrainer):
         return out
 
 
-def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference"):
+def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference", pose_noise=None):
     """One evaluation pass with ONE host synchronisation: -> float64 array [n_minibatches, W] of per-frame MEANS per minibatch.
     lower_net None: W = 30, the columns of mmego_pose_errors_upper; else W = 45: the 43 columns of mmego_pose_errors, then the
     Lower stage's L1(sum) loss per frame and its mean joint distance.  The split is uploaded once per dataset object
@@ -529,7 +576,9 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
     metrics="full": the same launches, and per minibatch one mmego_pose_errors_aligned launch (the 21 joints with a Lower_Net, the 15
     upper joints without) with its colsum, and -- for T >= 3 -- one mmego_pose_accel_errors launch with its colsum over the sequences,
     into further columns of the same device log: W is followed by the 3 J + 3 + len(PCK_THRESHOLDS_CM) columns of
-    mmego_pose_errors_aligned (per-frame means) and J columns of acceleration error (per-sequence means; NaN when T < 3)."""
+    mmego_pose_errors_aligned (per-frame means) and J columns of acceleration error (per-sequence means; NaN when T < 3).
+    pose_noise=(deg, t, seed): every minibatch's head pose is perturbed before the nets see it (ops.pose_jitter under
+    pose_noise_key(seed, 0, minibatch number), rows numbered within the minibatch): what head-pose error costs in joint error."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
     dev = base.device
@@ -561,6 +610,8 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
             h0, c0, E = scratch[key]
             tgt, body = b["target"], b["skl"]
             R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
+            if pose_noise is not None:
+                R, t = _jitter_pose(scratch, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, i))
             up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]      # (an UpperNet or an UpperNetwlocal)
             lo = None
             if lower_net is None:
@@ -622,12 +673,13 @@ def metrics_line(s):
                 " ".join("@%gcm %.4f" % (c, v) for c, v in s["pck"].items()), acc)
 
 
-def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference"):
+def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference", pose_noise=None):
     """IMU -> Upper -> Lower over a data split (reference Processor/Test/Demo_test.py:71-184, Train_Lower.py:232-332); returns
     (reference-style tuple, summary dict).  Device-resident split, one host read per pass (_epoch_eval).  metrics="full": the same
-    tuple and summary keys from the same launches, and the summary also holds aligned_summary's keys for the 21 joints."""
+    tuple and summary keys from the same launches, and the summary also holds aligned_summary's keys for the 21 joints.
+    pose_noise=(deg, t, seed): _epoch_eval's keyword."""
     cfg = base.cfg
-    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics)
+    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics, pose_noise=pose_noise)
     eval_loss = float(np.mean(m[:, 43]))
     accu_l, accu_up, accu_lo = m[:, :21].mean(axis=1), m[:, 41], m[:, 42]
     accu_ll, angle_ll = m[:, :21].mean(axis=0), m[:, 21:41].mean(axis=0)
@@ -670,7 +722,8 @@ def bone_lengths(bone_set):
     return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
 
 
-def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None):
+def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
+                pose_noise=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -690,6 +743,9 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     adds to the summary bone_dev_cm, the mean over the covered frames and the 20 bones of | |bone| - L_b | on the blended rows (upper 14
     from the upper rows, lower 6 from the lower rows; mmego_bone_length_dev), single_bone_dev_cm, the same over the window rows,
     degenerate_bones, the bones that took mmego_blend_bones' fallback (0 for "joints"), and blend_space; and to the arrays fallback [F].
+    pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
+    whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
+    pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
     The figures come down in one read; the per-frame arrays in one each."""
     from .data import DenseWindows
     if metrics not in METRICS:
@@ -706,13 +762,13 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space)
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
 
 
-def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None):
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None):
     """dense_infer behind its argument checks: the nets are in eval mode."""
     dev = base.device
     W, T, F = plan.W, plan.T, plan.F
@@ -720,6 +776,8 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     win_up, win_lo = f32(W * T, 45), f32(W * T, 24)
     with torch.no_grad():
         state = {}
+        if pose_noise is not None:
+            row_frame = torch.as_tensor(np.ascontiguousarray(plan.row_frame, dtype=np.int64)).to(dev)      # [W T]: every row's frame
         for s in range(0, W, batch_size):
             idx = np.arange(s, min(s + batch_size, W))
             b = plan.gather(idx)                                   # fresh copies: the nets transform `data` in place (Q1)
@@ -729,6 +787,8 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             h0, c0 = state[B]
             tgt, body = b["target"], b["skl"]
             R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
+            if pose_noise is not None:
+                R, t = _jitter_pose(state, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, 0), ids=row_frame[s * T:(s + B) * T])
             up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]
             lo, _ = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
             win_up[s * T:(s + B) * T].copy_(up.reshape(B * T, 45))
@@ -842,7 +902,8 @@ class Evaluator(_Base):
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
         space = getattr(cfg, "blend_space", None)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
-                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space)
+                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space,
+                                pose_noise=pose_noise_of(cfg))
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -862,11 +923,16 @@ class Evaluator(_Base):
             print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
         self.last_metrics = s
         path = getattr(cfg, "save_pred", None)
+        noise = pose_noise_of(cfg)
         if path:
             more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
+            if noise is not None:
+                more.update(pose_noise_deg=np.float64(noise[0]), pose_noise_t=np.float64(noise[1]), pose_noise_seed=np.int64(noise[2]))
             np.savez(path, stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]),
                      **{k: arrays[k] for k in DENSE_SAVED}, **more)
             print("Per-frame skeletons saved in {}".format(path))
+        if noise is not None:
+            print(pose_noise_line(noise))
         return s
 
     def _print_aligned(self, s):
@@ -884,7 +950,9 @@ class Evaluator(_Base):
     def eval_model(self):
         self.model.load(self.cfg.model_lower_path)
         self.model.eval()
-        out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics())
+        noise = pose_noise_of(self.cfg)
+        out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics(),
+                               pose_noise=noise)
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -893,6 +961,8 @@ class Evaluator(_Base):
         if self._metrics() == "full":
             self.last_metrics = s
             self._print_aligned(s)
+        if noise is not None:
+            print(pose_noise_line(noise))
         return out
 
     def eval_all_skeleton(self):

@@ -266,12 +266,33 @@ class StageStep(_Engine):
     without the option.  Data parallel, no collective: replicas with bit-equal parameters compute bit-equal averages.
 
     ``optimisers`` (a dict keyed "opt" / "imu_opt" / "upper_opt"): the ones in it are used as they are, the missing ones are built and
-    put into it -- a trainer hands ONE dict to the steps of all its minibatch sizes, so every optimiser is built once."""
+    put into it -- a trainer hands ONE dict to the steps of all its minibatch sizes, so every optimiser is built once.
+
+    ``pose_noise_deg`` / ``pose_noise_t`` (None: off; either alone is fine): the head pose the stage's nets get -- the recording's, the
+    frozen IMU_Net's, or the shared / prefetched ``pose`` buffers -- is perturbed per frame inside the body by one mmego_pose_jitter
+    launch (ops.pose_jitter: a rotation vector of standard deviation pose_noise_deg degrees per axis, a shift of pose_noise_t per
+    component), OUT of place into a pair of buffers the step owns per bound minibatch size: warm_up runs the body more than once on
+    the same inputs, and noise applied in place would compound.  The draw is a function of ``pose_word``, an int64 device word the
+    kernel reads: callers write it between steps with ``set_pose_key(k)``, outside the graph, so every replay draws afresh and a
+    resumed run continues the sequence.  The engines around a stage run it unchanged: the launch is part of the stage's body, and
+    each stage has its own word.  There is no backward through the perturbation: a stage that TRAINS the pose (finetune_imu, with or
+    without finetune_upper) refuses the options; finetune_upper alone is fine, its pose is data.  With both None the step launches
+    what it launched before and owns no extra buffer."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
-                 clip_grad_norm=None, optimisers=None, ema_decay=None):
+                 clip_grad_norm=None, optimisers=None, ema_decay=None, pose_noise_deg=None, pose_noise_t=None):
         assert stage in ("upper", "lower")
+        self.pose_noise = None
+        if pose_noise_deg is not None or pose_noise_t is not None:
+            if finetune_imu:
+                raise ValueError("StageStep: pose_noise_deg / pose_noise_t perturb a head pose that is DATA; finetune_imu trains it, and "
+                                 "there is no backward through the perturbation")
+            sig = tuple(0.0 if v is None else float(v) for v in (pose_noise_deg, pose_noise_t))
+            if not all(0.0 <= v < float("inf") for v in sig) or sig == (0.0, 0.0):
+                raise ValueError("StageStep: pose_noise_deg / pose_noise_t are finite and >= 0, one of them > 0, got %r, %r"
+                                 % (pose_noise_deg, pose_noise_t))
+            self.pose_noise = sig
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
         self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
         self.finetune_imu = bool(finetune_imu)
@@ -315,6 +336,9 @@ class StageStep(_Engine):
         self.loss2 = torch.zeros(2, dtype=torch.float32, device=dev)   # [L1 sum, sum of per-joint Euclidean distances]
         self.loss = self.loss2[:1]
         self.last_pred = None
+        if self.pose_noise is not None:
+            self.pose_word = torch.zeros(1, dtype=torch.int64, device=dev)      # the draw's key: set_pose_key
+            self._pose_out = {}                                        # (B, T) -> (R_n, t_n)
         if self.finetune_upper:                                        # (loss2 stays the Lower stage's pair: the trainers log it)
             self.upper_jmap = torch.tensor(UPPER_MAP, dtype=torch.int32, device=dev)
             self.upper_loss2 = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -342,8 +366,22 @@ class StageStep(_Engine):
             if self.finetune_upper:
                 self.upper_frozen.loss_hook = None
 
+    def set_pose_key(self, k):
+        """The key of the next step's head-pose draw (its low 63 bits): written between steps, outside the graph."""
+        self.pose_word.fill_(int(k) & 0x7FFFFFFFFFFFFFFF)
+
     def _head_pose(self, s, B, T):
-        """(R, t) of the minibatch: the trained IMU_Net's, the shared pose, the frozen IMU_Net's, or the recording's."""
+        """(R, t) of the minibatch: the trained IMU_Net's, the shared pose, the frozen IMU_Net's, or the recording's -- under pose_noise_deg /
+        pose_noise_t the perturbed copy of it in the step's own buffers."""
+        R, t = self._clean_head_pose(s, B, T)
+        if self.pose_noise is None:
+            return R, t
+        R_n, t_n = self._pose_out[(B, T)]
+        return ops.pose_jitter(R.contiguous().view(B, T, 3, 3), t.contiguous().view(B, T, 3), self.pose_noise[0], self.pose_noise[1],
+                               self.pose_word, R_n, t_n)
+
+    def _clean_head_pose(self, s, B, T):
+        """The pose as its source gives it."""
         if self.finetune_imu:
             from . import imu_train
             return imu_train.forward_train(self.imu, s["imu"])
@@ -417,6 +455,8 @@ class StageStep(_Engine):
                            t_gt=torch.empty(B, T, 3, device=dev))
         if self.finetune_upper:
             self.static["dl_up"] = torch.empty(B, T, 15, 3, device=dev)
+        if self.pose_noise is not None and (B, T) not in self._pose_out:
+            self._pose_out[(B, T)] = (torch.empty(B, T, 3, 3, device=dev), torch.empty(B, T, 3, device=dev))
         self.graph = None
 
     def _mutable_state(self):
