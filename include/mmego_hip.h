@@ -627,7 +627,19 @@ int mmego_pool128_backward(void* stream, const float* Z, long ldz, long rows, co
 
 /* ---- pooling / attention / graph (pool.hip) -------------------------------------------------------
  * Softmax-attention pooling over the P points of each of G groups (Upper_Net.py:285-301,163-177,
- * IMU_Net.py:79-80). */
+ * IMU_Net.py:79-80).  X [G, P, C] contiguous, w [C], b one float or NULL (0); vec [G, C], attn [G, P]; P <= 8192.
+ * No operand has to be aligned; alignment only picks the kernel (tests/pool_ref.py mirrors the choice, tests/test_pool_kernels_gpu.py
+ * runs every branch against float64):
+ *   forward   C % 4 == 0 and X, w, vec on 16-byte addresses: the register kernel for P <= 32, C <= 1024, else the LDS kernel while
+ *             its tile, (P C + P) * 4 bytes, is at most 96 KB; anything else -- C % 4 != 0, one of the three a float off, a larger
+ *             tile -- takes the plain two-pass kernel.  attn is never read or written in 16-byte pieces.
+ *   backward  C % 4 == 0, C < 256 dividing 256 or C >= 256, X on a 16-byte address and a tile, (P C + 2 P + PG C) * 4 bytes with
+ *             PG = 256 / min(C, 256), of at most 64 KB: the LDS kernel; else the plain one.  w, attn, dvec, dX, pdw, pdb may lie
+ *             anywhere.  attn is read as given (the forward's output); pdw [G, C] and pdb [G] are per-group partial gradients.
+ *   Both tile limits are on the DYNAMIC LDS alone: each LDS kernel holds 8,224 bytes of static arrays on top (at most 104.5 KB and
+ *   72.2 KB per workgroup of a CU's 160 KB), so the launchers raise the kernels' dynamic-LDS limit before they launch.
+ * All kernels add in a fixed order: two launches on the same operands give the same bits; the kernels of one entry point agree to
+ * rounding, not to the bit. */
 int mmego_attn_pool_forward(void* stream, const float* X, const float* w, const float* b, long G, int P, int C,
                             float* vec, float* attn);
 int mmego_attn_pool_backward(void* stream, const float* X, const float* w, const float* attn, const float* dvec, long G,

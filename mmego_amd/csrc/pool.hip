@@ -797,6 +797,9 @@ extern "C" int mmego_attn_pool_backward(void* stream, const float* X, const floa
     const int TCc = C < 256 ? C : 256, PG = 256 / TCc;
     const size_t tile = ((size_t)P * C + 2 * P + (size_t)PG * C) * sizeof(float);
     if ((C % 4) == 0 && (256 % TCc) == 0 && tile <= 64 * 1024 && (((uintptr_t)X) & 15) == 0) {
+      // (the kernel's static arrays -- dvs, ps, red: 8,224 bytes -- come on top of the tile: past 57,312 bytes of tile the workgroup
+      //  asks for more than 64 KB in all, 71,648 bytes at P = 120, C = 128; the limit is raised as for the forward)
+      if (int e = mmego_allow_lds<attn_pool_bwd_lds_kernel>(tile)) return e;
       hipLaunchKernelGGL(attn_pool_bwd_lds_kernel, dim3((unsigned)G), dim3(256), tile, (hipStream_t)stream, X, w, attn, dvec, P, C, dX,
                          pdw, pdb);
       MMEGO_LAUNCH_CHECK();
