@@ -950,6 +950,34 @@ int mmego_adam_step_clipped_ema(void* stream, float* p, const float* g, float* m
                                 double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
                                 const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay);
 
+/* ---- learning-rate schedule inside the step (optim_sched.hip) -----------------------------------------
+ * The four steps above with the rate computed by the launch itself from the step count, so that a captured graph replays another
+ * rate every step and a step skipped as non-finite consumes no schedule step.  With t = state[0] + 1 the step about to be taken,
+ * all in double:
+ *   w = t / W where W > 0 and t < W, else exactly 1;  s = max(0, t - W);  x = min(s, D) / D;
+ *   d = 1 (constant) | r + (1 - r)(1 + cos(pi x)) / 2 (cosine) | r + (1 - r)(1 - x) (linear) | max(r, g^floor(s / E)) (step),
+ *   d exactly 1 where s == 0;   lr_t = lr * (w * d);   from there the step is the one above at lr_t, bit for bit.
+ * state: FOUR device doubles {t, lr_t / (1 - b1^t), sqrt(1 - b2^t), lr_t}, 8-byte aligned; state[3] is the rate of the last step taken.
+ * part == NULL (then npart 0, stats NULL): the plain step, else the clipped one; ema == NULL (then ema_decay 0): no weight average.
+ * sched: a HOST struct, copied into the kernel arguments.  Refused (nothing is launched): whatever the corresponding entry point
+ * above refuses, sched == NULL, kind outside 0..3, reserved != 0, W negative / fractional / not finite, for cosine and linear D < 1 /
+ * fractional / not finite, r outside [0, 1), for step E < 1 / fractional / not finite or g outside (0, 1].
+ * (Declared as a tagged struct with its typedef behind it: hip.parse_tagged_structs reads this form.) */
+struct MmegoLrSchedule {
+  int kind;          /* 0 constant, 1 cosine, 2 linear, 3 step */
+  int reserved;      /* 0 */
+  double warmup;     /* W >= 0, integer-valued: optimiser steps of linear warm-up (0: none) */
+  double span;       /* D >= 1, integer-valued: steps the decay takes behind the warm-up (cosine, linear) */
+  double floor;      /* r in [0, 1): the decay's end value as a fraction of lr (step: its lower bound) */
+  double every;      /* step: E >= 1, integer-valued */
+  double gamma;      /* step: g in (0, 1] */
+};
+typedef struct MmegoLrSchedule MmegoLrSchedule;
+int mmego_adam_step_sched(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
+                          const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay,
+                          const MmegoLrSchedule* sched);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,9 @@ available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam
 trained net's gradient is clipped to the global norm X ahead of its Adam step; steps with a non-finite gradient are skipped; one
 "Grad norm" line per net and epoch; `inf` only measures), --ema_decay D (every trained net keeps an exponential moving average of its
 weights at decay D, updated inside its fused Adam launch; each epoch's evaluation, model selection and early stopping run on the averaged
-weights; the checkpoints keep the raw weights and the averaged nets are written beside them under EMA/), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
+weights; the checkpoints keep the raw weights and the averaged nets are written beside them under EMA/), --lr_schedule {cosine,linear,step}
+[--lr_warmup N --lr_min_ratio R --lr_decay_steps N --lr_step_every N --lr_step_gamma G] (every trained net's learning rate follows a warm-up
+and a decay over its optimiser's step count, computed inside its fused Adam launch; --lr_warmup alone: warm-up, then constant), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
 UpperNetwlocal with the anchor branch -- the net trained by --train --network Upper_Net, the class the Upper checkpoint is loaded into by
 --train --network Lower_Net and --infer), --metrics {reference,full} (full: beside the reference's figures, the evaluation pass of --infer
 and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
@@ -98,6 +100,18 @@ def build_parser():
                         "selection and early stopping use the averaged weights.  Checkpoints keep the raw weights (the average travels in "
                         "the optimiser state, so --resume continues it without the flag); the averaged nets are written in the "
                         "reference's format beside them, in an EMA folder (default: no averaging)")
+    p.add_argument("--lr_schedule", type=str, choices=["cosine", "linear", "step"], default=None,
+                   help="--train: every trained net's learning rate follows this schedule over its optimiser's step count, computed inside "
+                        "the fused Adam launch (skipped steps consume none): cosine / linear decay to --lr_min_ratio x lr over "
+                        "--lr_decay_steps steps (default: the rest of the run), or step (x --lr_step_gamma every --lr_step_every steps, "
+                        "not below --lr_min_ratio).  --resume continues the saved schedule without the flags (default: constant)")
+    p.add_argument("--lr_warmup", type=int, help="--train: linear warm-up over the first N >= 1 optimiser steps (step 1 at lr / N, step N "
+                                                  "the first at the full rate), ahead of --lr_schedule's decay or, alone, of a constant rate")
+    p.add_argument("--lr_min_ratio", type=float, help="--lr_schedule: where the decay ends, as a fraction of lr, in [0, 1) (default 0)")
+    p.add_argument("--lr_decay_steps", type=int, help="--lr_schedule cosine / linear: the N >= 1 optimiser steps the decay takes behind "
+                                                       "the warm-up (default: epochs x minibatches per epoch - warm-up)")
+    p.add_argument("--lr_step_every", type=int, help="--lr_schedule step: decay every N >= 1 optimiser steps behind the warm-up")
+    p.add_argument("--lr_step_gamma", type=float, help="--lr_schedule step: the factor of each decay, in (0, 1]")
     p.add_argument("--upper_variant", type=str, choices=["global", "wlocal"], default=None,
                    help="which net Upper_Net is: global (default: UpperNet) or wlocal (UpperNetwlocal, with the anchor branch).  --train "
                         "--network Upper_Net trains it (with --finetune_imu, --imu_lr, --imu_dropout, --clip_grad_norm, --resume and "
@@ -265,6 +279,35 @@ def check_ema_decay(parser, args):
         parser.error("--ema_decay goes with --train only (it averages the weights an optimiser updates)")
 
 
+def check_lr_schedule(parser, args):
+    """The --lr_* options belong to a training run; each belongs to the kinds that read it and lies in its range."""
+    given = [f for f in ("lr_schedule", "lr_warmup", "lr_min_ratio", "lr_decay_steps", "lr_step_every", "lr_step_gamma")
+             if getattr(args, f) is not None]
+    if not given:
+        return
+    if args.infer or not args.train:
+        parser.error("--%s goes with --train only (it schedules the optimiser's learning rate)" % given[0])
+    for f in ("lr_warmup", "lr_decay_steps", "lr_step_every"):
+        if getattr(args, f) is not None and getattr(args, f) < 1:
+            parser.error("--%s is a number of optimiser steps: it has to be >= 1, got %r" % (f, getattr(args, f)))
+    if args.lr_min_ratio is not None:
+        if args.lr_schedule is None:
+            parser.error("--lr_min_ratio is where --lr_schedule's decay ends; without --lr_schedule nothing decays")
+        if not 0.0 <= args.lr_min_ratio < 1.0:         # (false for NaN as well)
+            parser.error("--lr_min_ratio is a fraction of the learning rate: it has to lie in [0, 1), got %r" % (args.lr_min_ratio,))
+    if args.lr_decay_steps is not None and args.lr_schedule not in ("cosine", "linear"):
+        parser.error("--lr_decay_steps is the length of a cosine or linear decay: it goes with --lr_schedule cosine / linear only")
+    for f in ("lr_step_every", "lr_step_gamma"):
+        if getattr(args, f) is not None and args.lr_schedule != "step":
+            parser.error("--%s belongs to --lr_schedule step only" % f)
+    if args.lr_schedule == "step":
+        for f in ("lr_step_every", "lr_step_gamma"):
+            if getattr(args, f) is None:
+                parser.error("--lr_schedule step needs --lr_step_every and --lr_step_gamma: --%s is missing" % f)
+        if not 0.0 < args.lr_step_gamma <= 1.0:        # (false for NaN as well)
+            parser.error("--lr_step_gamma is the factor of each decay: it has to lie in (0, 1], got %r" % (args.lr_step_gamma,))
+
+
 def check_finetune_upper(parser, args, world):
     """--finetune_upper fits one arrangement only; everything else is refused before any work starts.  (--gt_head_pose is fine: the
     head pose is not what is trained.)"""
@@ -318,6 +361,7 @@ def check_finetune(parser, args, world):
     check_imu_dropout(parser, args)
     check_clip_grad_norm(parser, args)
     check_ema_decay(parser, args)
+    check_lr_schedule(parser, args)
     check_frame_store(parser, args)
     check_dense(parser, args)
     check_pose_noise(parser, args)
@@ -365,6 +409,8 @@ def apply_overrides(args):
     Config.finetune_all = bool(args.finetune_all)
     Config.clip_grad_norm = args.clip_grad_norm
     Config.ema_decay = args.ema_decay
+    Config.lr_schedule, Config.lr_warmup, Config.lr_min_ratio = args.lr_schedule, args.lr_warmup, args.lr_min_ratio
+    Config.lr_decay_steps, Config.lr_step_every, Config.lr_step_gamma = args.lr_decay_steps, args.lr_step_every, args.lr_step_gamma
     Config.window_jitter = bool(args.window_jitter)
     Config.point_keep = args.point_keep
     Config.point_noise, Config.point_noise_v = args.point_noise, args.point_noise_v

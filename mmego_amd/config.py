@@ -59,6 +59,12 @@ class _Common:
     pose_noise_t = None         # --pose_noise_t: metres per component, standard deviation of the random shift of every frame's head position (None: none)
     seed = None                 # --seed, as main.py got it (None: 0 for what FrameStore draws)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
+    lr_schedule = None          # --lr_schedule: cosine | linear | step; every trained net's rate follows it inside its Adam launch (None: constant)
+    lr_warmup = None            # --lr_warmup: optimiser steps of linear warm-up (None: none)
+    lr_min_ratio = None         # --lr_min_ratio: the decay's end as a fraction of lr (None: 0)
+    lr_decay_steps = None       # --lr_decay_steps: the span of a cosine / linear decay (None: the rest of the run)
+    lr_step_every = None        # --lr_step_every, --lr_step_gamma: the step decay
+    lr_step_gamma = None
     ema_decay = None            # --ema_decay: every trained net keeps a weight average at this decay; evaluation uses it (None: off)
 
 

@@ -65,8 +65,11 @@ __device__ __forceinline__ float clipped_grad(float g, float cf) {
 // The clipped step around its update loop (optim.hip describes both above adam_clipped_kernel).  Prologue: EVERY workgroup sums the
 // records of pass 1 in the same fixed order and leaves the new state in sh[0..2], the norm in sh[3], c before the clamp in sh[4];
 // `norm` and `finite` are then in scope.  Epilogue: the workgroup that draws the last ticket stores the state and keeps the statistics.
-#define ADAM_CLIPPED_PROLOGUE                                                                                                    \
-  __shared__ double sh[9];       /* [0..2] the new state, [3] norm, [4] c before the clamp, [5..8] the waves' sums */            \
+// NSH / NBC, RATE, STATE3: the hooks of optim_sched.hip, whose kernels compute the step's rate themselves.  RATE stands behind `t` and
+// declares the `lr` that the lines below it read (the kernels without a schedule have `lr` as a kernel argument and an empty RATE);
+// it keeps the rate in one more word of the shared array (NSH / NBC: its length), which STATE3 stores as state[3] with the other three.
+#define ADAM_CLIPPED_PROLOGUE_(NSH, RATE)                                                                                        \
+  __shared__ double sh[NSH];     /* [0..2] the new state, [3] norm, [4] c before the clamp, [5..8] the waves' sums */            \
   double acc = 0.0;                                                                                                              \
   for (int j = threadIdx.x; j < npart; j += 256) acc += part[j];                                                                 \
   acc = wave_sum_d(acc);                                                                                                         \
@@ -75,6 +78,7 @@ __device__ __forceinline__ float clipped_grad(float g, float cf) {
   if (threadIdx.x == 0) {                                                                                                        \
     const double norm = sqrt(((sh[5] + sh[6]) + sh[7]) + sh[8]);                                                                 \
     const double t = state[0] + 1.0;                                                                                             \
+    RATE                                                                                                                         \
     sh[0] = t;                                                                                                                   \
     sh[1] = lr / (1.0 - pow(beta1, t));                                                                                          \
     sh[2] = sqrt(1.0 - pow(beta2d, t));                                                                                          \
@@ -84,13 +88,15 @@ __device__ __forceinline__ float clipped_grad(float g, float cf) {
   __syncthreads();                                                                                                               \
   const double norm = sh[3];                                                                                                     \
   const bool finite = norm < (double)INFINITY;           /* (false for NaN as well) */
-#define ADAM_CLIPPED_EPILOGUE                                                                                                    \
+#define ADAM_CLIPPED_PROLOGUE ADAM_CLIPPED_PROLOGUE_(9, )
+#define ADAM_CLIPPED_EPILOGUE_(STATE3)                                                                                           \
   if (threadIdx.x == 0) {                                                                                                        \
     if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) {                                                                            \
       stats[0] = norm;                                                                                                           \
       stats[3] += 1.0;                                                                                                           \
       if (finite) {                                                                                                              \
         state[0] = sh[0]; state[1] = sh[1]; state[2] = sh[2];                                                                    \
+        STATE3                                                                                                                   \
         stats[1] += norm;                                                                                                        \
         stats[2] = norm > stats[2] ? norm : stats[2];                                                                            \
         if (sh[4] < 1.0) stats[4] += 1.0;                                                                                        \
@@ -100,13 +106,15 @@ __device__ __forceinline__ float clipped_grad(float g, float cf) {
       *ticket = 0;                                                                                                               \
     }                                                                                                                            \
   }
+#define ADAM_CLIPPED_EPILOGUE ADAM_CLIPPED_EPILOGUE_()
 
 // The plain step around its loop: thread 0 forms the new state (bc[0] = t, bc[1] = step_size, bc[2] = sqrt(1 - b2^t)) from state[0] = t-1;
 // the workgroup whose ticket add comes last stores it (optim.hip, above adam_kernel).
-#define ADAM_PLAIN_PROLOGUE                                                                                                      \
-  __shared__ double bc[3];                                                                                                       \
+#define ADAM_PLAIN_PROLOGUE_(NBC, RATE)                                                                                          \
+  __shared__ double bc[NBC];                                                                                                     \
   if (threadIdx.x == 0) {                                                                                                        \
     const double t = state[0] + 1.0;                                                                                             \
+    RATE                                                                                                                         \
     bc[0] = t;                                                                                                                   \
     bc[1] = lr / (1.0 - pow(beta1, t));                                                                                          \
     bc[2] = sqrt(1.0 - pow(beta2d, t));                                                                                          \
@@ -114,18 +122,26 @@ __device__ __forceinline__ float clipped_grad(float g, float cf) {
   __syncthreads();                                                                                                               \
   const float step_size = (float)bc[1];                                                                                          \
   const float bc2_sqrt = (float)bc[2];
-#define ADAM_PLAIN_EPILOGUE                                                                                                      \
+#define ADAM_PLAIN_PROLOGUE ADAM_PLAIN_PROLOGUE_(3, )
+#define ADAM_PLAIN_EPILOGUE_(STATE3)                                                                                             \
   if (threadIdx.x == 0) {                                                                                                        \
     if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) {                                                                            \
       state[0] = bc[0]; state[1] = bc[1]; state[2] = bc[2];                                                                      \
+      STATE3                                                                                                                     \
       *ticket = 0;                                                                                                               \
     }                                                                                                                            \
   }
+#define ADAM_PLAIN_EPILOGUE ADAM_PLAIN_EPILOGUE_()
 
 // ---- host side of the launchers ---------------------------------------------------------------------------------------------
 static inline int ew_blocks(long total) {
   long b = (total + 255) / 256;
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+
+// The weight average's arguments: 0 < decay < 1 (NaN fails both comparisons) and an aligned buffer.
+static inline bool ema_args_ok(const float* ema, double ema_decay) {
+  return ema && ((uintptr_t)ema & 15) == 0 && ema_decay > 0.0 && ema_decay < 1.0;
 }
 
 // The HOST array of [begin, end) element ranges -> float4 units; false where a range is malformed.

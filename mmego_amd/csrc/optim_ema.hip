@@ -35,11 +35,6 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
   ADAM_PLAIN_EPILOGUE
 }
 
-// 0 < decay < 1 (NaN fails both comparisons) and an aligned buffer.
-static inline bool ema_args_ok(const float* ema, double ema_decay) {
-  return ema && ((uintptr_t)ema & 15) == 0 && ema_decay > 0.0 && ema_decay < 1.0;
-}
-
 extern "C" int mmego_adam_step_ema(void* stream, float* p, const float* g, float* m, float* v, long n, double* state,
                                    double lr, double beta1, double beta2, double eps, double weight_decay, const long* skip,
                                    int nskip, int* ticket, float* ema, double ema_decay) {

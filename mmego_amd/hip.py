@@ -71,6 +71,13 @@ def parse_structs(text):
     return structs
 
 
+def parse_tagged_structs(text):
+    """-> {C name: class} for every `struct MmegoX { ... }; typedef struct MmegoX MmegoX;` (the tag declared first, the typedef
+    behind it): the same members and the same reader as parse_structs, which is handed the one-statement spelling."""
+    found = re.findall(r"(?<!typedef )struct (\w+) \{(.*?)\};\s*typedef struct \1 \1;", text, flags=re.S)
+    return parse_structs("\n".join("typedef struct %s {%s} %s;" % (n, body, n) for n, body in found))
+
+
 def parse_header(path=HEADER):
     return parse_protos(header_text(path))
 
@@ -83,7 +90,7 @@ def check_gemm_desc(protos, desc):
 
 
 _protos = parse_header()
-_structs = parse_structs(header_text())
+_structs = dict(parse_structs(header_text()), **parse_tagged_structs(header_text()))      # (the second: LrSchedule)
 globals().update((c.__name__, c) for c in _structs.values())    # GemmDesc, BnRef, GcnFront, Pack, DwRed, Lstm64Fwd, Lstm64Bwd, Slab
 _GEMM_PARAMS = [n for _, n in _protos["mmego_gemm"][1:]]
 _lib = None

@@ -102,6 +102,113 @@ class FlatParams:
                 p.grad = self._gviews[id(p)]
 
 
+class LrSchedule:
+    """A learning-rate schedule over the optimiser's step count, evaluated inside the Adam launch (mmego_adam_step_sched; the header
+    spells the multiplier out).  An immutable value: kind "constant" | "cosine" | "linear" | "step"; warmup W >= 0 steps of linear
+    warm-up (step 1 at lr / W, step W the first at the full rate); span D >= 1, the steps a cosine or linear decay takes behind the
+    warm-up; floor r in [0, 1), where the decay ends as a fraction of lr (step: its lower bound); every E >= 1 and gamma g in (0, 1]
+    of the step decay.  Validation is the C side's.  `multiplier(t)` is the same arithmetic in Python floats, for what the host prints."""
+
+    KINDS = ("constant", "cosine", "linear", "step")
+    FIELDS = ("kind", "warmup", "span", "floor", "every", "gamma")
+
+    def __init__(self, kind="constant", warmup=0, span=None, floor=0.0, every=None, gamma=None):
+        def steps(name, val, least):
+            try:
+                ok = float(val) >= least and float(val) <= 2.0 ** 53 and float(val) == int(val)
+            except (TypeError, ValueError, OverflowError):
+                ok = False
+            if not ok:
+                raise ValueError("LrSchedule: %s has to be a whole number of steps >= %d, got %r" % (name, least, val))
+            return int(val)
+        if kind not in self.KINDS:
+            raise ValueError("LrSchedule: kind has to be one of %s, got %r" % (", ".join(self.KINDS), kind))
+        self.kind = kind
+        self.warmup = steps("warmup", warmup, 0)
+        try:
+            self.floor = float(floor)
+        except (TypeError, ValueError):
+            self.floor = float("nan")
+        if not 0.0 <= self.floor < 1.0:            # (false for NaN as well)
+            raise ValueError("LrSchedule: floor has to lie in [0, 1), got %r" % (floor,))
+        self.span = self.every = self.gamma = None
+        if kind in ("cosine", "linear"):
+            self.span = steps("span", span, 1)
+        elif span is not None:
+            raise ValueError("LrSchedule: span belongs to the cosine and linear kinds, not to %s" % kind)
+        if kind == "step":
+            self.every = steps("every", every, 1)
+            try:
+                self.gamma = float(gamma)
+            except (TypeError, ValueError):
+                self.gamma = float("nan")
+            if not 0.0 < self.gamma <= 1.0:
+                raise ValueError("LrSchedule: gamma has to lie in (0, 1], got %r" % (gamma,))
+        elif every is not None or gamma is not None:
+            raise ValueError("LrSchedule: every and gamma belong to the step kind, not to %s" % kind)
+
+    def c_struct(self):
+        """The MmegoLrSchedule of this schedule (a host struct; the entry point copies it into the kernel arguments)."""
+        return hip.LrSchedule(kind=self.KINDS.index(self.kind), reserved=0, warmup=float(self.warmup), span=float(self.span or 0),
+                              floor=self.floor, every=float(self.every or 0), gamma=float(self.gamma or 0.0))
+
+    def multiplier(self, t):
+        """lr_t / lr of step t >= 1, in float64."""
+        import math
+        t, W = float(t), float(self.warmup)
+        w = t / W if W > 0 and t < W else 1.0
+        s = t - W
+        if not s > 0.0:
+            return w
+        if self.kind in ("cosine", "linear"):
+            x = min(s, float(self.span)) / float(self.span)
+            shape = (1.0 + math.cos(math.pi * x)) / 2.0 if self.kind == "cosine" else 1.0 - x
+            return self.floor + (1.0 - self.floor) * shape
+        if self.kind == "step":
+            return max(self.floor, self.gamma ** math.floor(s / float(self.every)))
+        return 1.0
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @classmethod
+    def from_dict(cls, d):
+        if set(d) != set(cls.FIELDS):
+            raise ValueError("LrSchedule.from_dict: expected the keys %s, got %s" % (", ".join(cls.FIELDS), ", ".join(sorted(map(str, d)))))
+        return cls(**d)
+
+    def __eq__(self, other):
+        return isinstance(other, LrSchedule) and self.to_dict() == other.to_dict()
+
+    def __hash__(self):
+        return hash(tuple(self.to_dict().items()))
+
+    def describe(self):
+        """`<kind>, warm-up W steps, span D steps, floor r[, every E gamma g]` (the trainers' start line)."""
+        text = "%s, warm-up %d steps, span %s steps, floor %g" % (self.kind, self.warmup, "-" if self.span is None else "%d" % self.span, self.floor)
+        return text + (", every %d gamma %g" % (self.every, self.gamma) if self.kind == "step" else "")
+
+    def __repr__(self):
+        return "LrSchedule(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.FIELDS)
+
+
+def lr_schedule_of(cfg, epochs, steps_per_epoch):
+    """The LrSchedule a run's options ask for (--lr_schedule, --lr_warmup, --lr_min_ratio, --lr_decay_steps, --lr_step_every,
+    --lr_step_gamma as config attributes); None where none is given.  A cosine or linear decay without --lr_decay_steps spans the rest
+    of the run: epochs x steps_per_epoch (the optimiser steps of one epoch of THIS run) - warmup, at least 1."""
+    kind, warmup = getattr(cfg, "lr_schedule", None), getattr(cfg, "lr_warmup", None)
+    if kind is None and warmup is None:
+        return None
+    kind, warmup = kind or "constant", warmup or 0
+    kw = {}
+    if kind in ("cosine", "linear"):
+        span = getattr(cfg, "lr_decay_steps", None)
+        kw["span"] = max(1, int(epochs) * int(steps_per_epoch) - int(warmup)) if span is None else span
+    if kind == "step":
+        kw.update(every=getattr(cfg, "lr_step_every", None), gamma=getattr(cfg, "lr_step_gamma", None))
+    return LrSchedule(kind, warmup=warmup, floor=getattr(cfg, "lr_min_ratio", None) or 0.0, **kw)
+
+
 class FusedAdam:
     """torch.optim.Adam semantics (betas 0.9/0.999, eps 1e-8, coupled weight decay) in one launch.
 
@@ -116,11 +223,19 @@ class FusedAdam:
     is its first use (step, state_dict, load_state_dict, averaged) -- for fine-tuning from a checkpoint, the checkpoint.  So there is
     no bias correction and no first step that differs; parameters that never train, and steps skipped as non-finite, keep ema equal to
     the weights.  Buffers of the module (BatchNorm running statistics) are not averaged: they are running averages already.
-    `averaged()` evaluates with the average in place of the weights, `ema_state_dict()` is the module's state_dict with it."""
+    `averaged()` evaluates with the average in place of the weights, `ema_state_dict()` is the module's state_dict with it.
+
+    lr_schedule (None: off; else an LrSchedule): the rate of step t is lr * schedule.multiplier(t), computed by the step's own launch from
+    the step count on the device (mmego_adam_step_sched, for all four forms above), so a captured graph replays another rate every step
+    and a step skipped as non-finite consumes no schedule step.  `state` then has a fourth double, the rate of the last step taken
+    (`current_lr()`).  Assigning `lr` between steps still changes nothing under a captured graph: the schedule is the way to move it."""
 
     STAT_KEYS = ("last", "sum", "max", "steps", "clipped", "skipped")
 
-    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
+    def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
+                 lr_schedule=None):
+        if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+            raise ValueError("lr_schedule has to be a params.LrSchedule (or None: a constant rate), got %r" % (lr_schedule,))
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError("max_grad_norm has to be > 0 (or None: no clipping), got %r" % (max_grad_norm,))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:            # (false for NaN as well)
@@ -134,6 +249,8 @@ class FusedAdam:
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema = None
         self._averaged = False            # inside averaged(): flat_p holds the average, ema the weights
+        self.lr_schedule = lr_schedule
+        self._sched = None if lr_schedule is None else lr_schedule.c_struct()      # (kept alive: a recorded launch holds the object)
 
     def _skip_ranges(self, f):
         """Element ranges of parameters that never receive a gradient (`module.never_trained()`, e.g. IMU_Net.fc3):
@@ -158,7 +275,7 @@ class FusedAdam:
         if self.m is None or self.m.device != f.device or self.m.numel() != f.flat_p.numel():
             self.m = torch.zeros_like(f.flat_p)
             self.v = torch.zeros_like(f.flat_p)
-            self.state = torch.zeros(3, dtype=torch.float64, device=f.device)
+            self.state = torch.zeros(3 if self.lr_schedule is None else 4, dtype=torch.float64, device=f.device)
             self._ticket = torch.zeros(1, dtype=torch.int32, device=f.device)
             self._part = self._stats = None
             self.ema = None
@@ -179,7 +296,16 @@ class FusedAdam:
         ranges = (skip if skip is not False else None, skip.numel() // 2 if skip is not False else 0)
         # (with a weight average: the same launch under its _ema name, the average and its decay behind the plain arguments)
         sfx, avg = ("", ()) if self.ema_decay is None else ("_ema", (self.ema, self.ema_decay))
-        if self.max_grad_norm is None:
+        if self.lr_schedule is not None:
+            # (one entry point for the four forms: absent record buffers select the plain step, an absent average the step without one)
+            clip = (None, 0, 0.0, None)
+            if self.max_grad_norm is not None:
+                hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
+                clip = (self._part, self._part.numel(), self.max_grad_norm, self._stats)
+            hip.call("adam_step_sched", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
+                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket,
+                     *clip, *(avg or (None, 0.0)), self._sched)
+        elif self.max_grad_norm is None:
             hip.call("adam_step" + sfx, f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
                      float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket, *avg)
         else:
@@ -191,6 +317,15 @@ class FusedAdam:
         changed = getattr(f.module, "weights_changed", None)
         if changed is not None:
             changed()
+
+    def current_lr(self):
+        """The rate of the last step taken (one device read: state[3]); before the first step, the rate the first step will take.
+        Without a schedule: lr."""
+        if self.lr_schedule is None:
+            return float(self.lr)
+        self._ensure()
+        t, _, _, rate = self.state.tolist()
+        return rate if t > 0 and rate > 0 else float(self.lr) * self.lr_schedule.multiplier(t + 1)
 
     def zero_grad(self):
         pass  # every backward overwrites the flat gradient buffer
@@ -271,6 +406,8 @@ class FusedAdam:
               "eps": self.eps, "weight_decay": self.weight_decay, "layout": self.layout(), "max_grad_norm": self.max_grad_norm}
         if self.ema_decay is not None:     # (an optimiser without an average writes the state it always wrote)
             sd["ema"], sd["ema_decay"] = self.ema.cpu(), self.ema_decay
+        if self.lr_schedule is not None:
+            sd["lr_schedule"] = self.lr_schedule.to_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -280,6 +417,13 @@ class FusedAdam:
         nothing about where a parameter's moments are."""
         if self._averaged:
             raise RuntimeError("FusedAdam.load_state_dict() inside averaged(): weights and average are exchanged")
+        if sd.get("lr_schedule") is not None:
+            theirs = LrSchedule.from_dict(sd["lr_schedule"])
+            if theirs != self.lr_schedule:
+                raise ValueError("optimizer state was saved under the learning-rate schedule %r, this optimiser was built with %r: "
+                                 "build it with the saved one" % (theirs, self.lr_schedule))
+        elif sd["state"].numel() != 3:
+            raise ValueError("optimizer state has %d state words and names no learning-rate schedule" % sd["state"].numel())
         f = self._ensure()
         cur = self.layout()
         saved = sd.get("layout")
@@ -317,7 +461,9 @@ class FusedAdam:
         if self.ema_decay is not None and sd.get("ema_decay") is None:
             self.ema.copy_(f.flat_p)
             print("[mmego_amd] optimizer state carries no weight average: the average (decay %g) restarts from the loaded weights" % self.ema_decay)
-        self.state.copy_(sd["state"])
+        # (a three-word state into a scheduled optimiser: the schedule takes up at the saved step count; state[3] is 0 until its first step)
+        self.state.zero_()
+        self.state[:sd["state"].numel()].copy_(sd["state"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
         if "max_grad_norm" in sd:          # (as lr: the saved value wins, a resumed run clips as the run it continues; a state from
             self.max_grad_norm = None if sd["max_grad_norm"] is None else float(sd["max_grad_norm"])    # before the key: ours stays)

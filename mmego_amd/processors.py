@@ -20,7 +20,7 @@ from . import blocks, hip, ops, skeleton
 from .config import Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, _mix64, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
-from .params import FusedAdam
+from .params import FusedAdam, LrSchedule, lr_schedule_of
 from .nets_local import UpperNetwlocal
 from .train_step import TRAINED, ImuStep, PipelinedStages, StageStep, broadcast_flag, call_upper, empty_step, shard_of, sync_replicas
 from .utils import EarlyStopping
@@ -236,12 +236,49 @@ class _Base:
         print("[mmego_amd] resumed from %s at epoch %d" % (path, self.start_epoch))
         return ts
 
+    def _lr_schedule(self):
+        """The run's learning-rate schedule (params.LrSchedule; None: a constant rate), worked out ONCE, ahead of the first optimiser:
+        from the options, a decay without --lr_decay_steps spanning the rest of the run.  Under --resume the schedule the optimiser
+        state carries wins, as lr and ema_decay do, and options that name another one end the run.  Says the start line (rank 0)."""
+        if not hasattr(self, "_lr_sched"):
+            sched = None
+            if getattr(self.cfg, "lr_schedule", None) is not None or getattr(self.cfg, "lr_warmup", None) is not None:
+                per_epoch = -(-len(self.train_data) // (self.batchsize * self.world))      # (global minibatches: the optimiser steps of an epoch)
+                sched = lr_schedule_of(self.cfg, self.num_epochs, per_epoch)
+            saved = None if self._resume is None else self._resume["optimizer"].get("lr_schedule")
+            if self._resume is not None:
+                saved = None if saved is None else LrSchedule.from_dict(saved)
+                if sched is not None and sched != saved:
+                    raise SystemExit("--resume: the training state was saved under %s, and the --lr_* options name %r: leave them out (the "
+                                     "saved schedule is continued) or start a new run"
+                                     % ("no learning-rate schedule" if saved is None else "the learning-rate schedule %r" % (saved,), sched))
+                sched = saved
+            self._lr_sched = sched
+            if sched is not None and self.rank == 0:
+                print("[mmego_amd] learning-rate schedule: %s" % sched.describe())
+        return self._lr_sched
+
+    def _report_lr(self):
+        """With a schedule: after an epoch's training pass, one line per trained net with the rate of its last step (one device double per
+        optimiser), to stdout and log-eval.txt."""
+        if self._lr_schedule() is None or self.rank != 0:
+            return
+        names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
+        for o, _ in TRAINED:
+            if o in self._opts and self._opts[o].lr_schedule is not None:
+                line = "LR ({}): {:.9g}".format(names[o], self._opts[o].current_lr())
+                print(line)
+                if getattr(self, "evalfile", None) is not None:
+                    self.evalfile.write(line + "\n")
+                    self.evalfile.flush()
+
     def _main_opt(self, model):
         """The optimiser of the trainer's own net: built ONCE -- by the first step or the first empty-shard step, whichever comes -- and
         that is where a --resume state is loaded."""
         if "opt" not in self._opts:
             self._opts["opt"] = FusedAdam(model.flat(), lr=self.learning_rate, weight_decay=self.weight_decay,
-                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None), ema_decay=getattr(self.cfg, "ema_decay", None))
+                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None), ema_decay=getattr(self.cfg, "ema_decay", None),
+                                          lr_schedule=self._lr_schedule())
             if self._resume is not None:
                 self._opts["opt"].load_state_dict(self._resume["optimizer"])
         return self._opts["opt"]
@@ -290,6 +327,7 @@ class _Base:
             decay = self._resume["optimizer"]["ema_decay"]
         if decay is not None and self.rank == 0:
             print("[mmego_amd] weight averaging: decay %g; evaluation and early stopping use the averaged weights" % decay)
+        self._lr_schedule()                                        # (the start line, and a refusal, ahead of the first epoch)
         out = None
         names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
         for epoch in range(self.start_epoch, self.num_epochs):
@@ -297,6 +335,7 @@ class _Base:
             self._epoch = epoch
             trained = train()
             report_grad_norms(self.rank, [(names[o], self._opts[o]) for o, _ in TRAINED if o in self._opts])
+            self._report_lr()
             # a persistent rnn_slow launch of the frozen IMU_Net whose workgroups were not co-resident reports it only through a
             # sticky word: read once per epoch (the training pass has just synchronised for its log) -- never train on silently
             blocks.seq_xcd_raise()
@@ -414,7 +453,7 @@ class _StageTrainer(_Base):
                            imu_lr=self.learning_rate if imu_lr is None else imu_lr,
                            finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
                            clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts,
-                           ema_decay=getattr(self.cfg, "ema_decay", None),
+                           ema_decay=getattr(self.cfg, "ema_decay", None), lr_schedule=self._lr_schedule(),
                            **({} if self.pose_noise is None else dict(pose_noise_deg=self.pose_noise[0], pose_noise_t=self.pose_noise[1])))
             st.engine = None
             if pipelined:

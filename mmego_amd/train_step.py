@@ -265,6 +265,11 @@ class StageStep(_Engine):
     (FusedAdam(ema_decay=...)), updated inside its own Adam launch -- which runs outside the captured body, so the graph is the one
     without the option.  Data parallel, no collective: replicas with bit-equal parameters compute bit-equal averages.
 
+    ``lr_schedule`` (None: a constant rate; else a params.LrSchedule): every optimiser this step builds gets the SAME schedule over its
+    own base rate (``lr``, ``imu_lr``, ``upper_lr``) and computes its rate inside its own Adam launch from its own step count
+    (FusedAdam(lr_schedule=...)): the nets of a fine-tuning step warm up and decay together.  Data parallel, no collective: the step
+    counts of the ranks agree -- the clipped form decides to skip on the all-reduced gradient, which precedes ``opt.step()``.
+
     ``optimisers`` (a dict keyed "opt" / "imu_opt" / "upper_opt"): the ones in it are used as they are, the missing ones are built and
     put into it -- a trainer hands ONE dict to the steps of all its minibatch sizes, so every optimiser is built once.
 
@@ -281,7 +286,8 @@ class StageStep(_Engine):
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
-                 clip_grad_norm=None, optimisers=None, ema_decay=None, pose_noise_deg=None, pose_noise_t=None):
+                 clip_grad_norm=None, optimisers=None, ema_decay=None, pose_noise_deg=None, pose_noise_t=None,
+                 lr_schedule=None):
         assert stage in ("upper", "lower")
         self.pose_noise = None
         if pose_noise_deg is not None or pose_noise_t is not None:
@@ -301,7 +307,8 @@ class StageStep(_Engine):
 
         def opt_for(key, trained, lr, weight_decay):
             if opts.get(key) is None:
-                opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema_decay=ema_decay)
+                opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema_decay=ema_decay,
+                                      lr_schedule=lr_schedule)
             return opts[key]
         self.imu_opt = self.upper_opt = None
         if self.finetune_upper:
@@ -471,11 +478,13 @@ class ImuStep(_Engine):
     position loss (sum), backward through the two BiLSTM(512) stacks, Adam with coupled weight decay -- with static
     buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound)."""
 
-    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None, ema_decay=None):
+    def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None, ema_decay=None,
+                 lr_schedule=None):
         self.net = net
-        # (clip_grad_norm, ema_decay: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=...); one handed in is used as it is)
+        # (clip_grad_norm, ema_decay, lr_schedule: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=..., lr_schedule=...);
+        #  one handed in is used as it is)
         self.opt = opt if opt is not None else FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
-                                                         ema_decay=ema_decay)
+                                                         ema_decay=ema_decay, lr_schedule=lr_schedule)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
