@@ -171,6 +171,35 @@ int mmego_pack_frames_noise(void* stream, const float* pts, const long long* fra
  * than R_out == R or t_out == t exactly (a thread reads its row before it writes it); R_out overlapping t_out. */
 int mmego_pose_jitter(void* stream, const float* R, const float* t, long n, double sigma_deg, double sigma_t,
                       const long long* seed_word, const long long* ids, float* R_out, float* t_out);
+/* IMU sensor noise and bias (imu_noise.hip; train_step.ImuStep / StageStep under imu_noise, processors._epoch_eval and dense_infer under
+ * imu_noise): the IMU samples imu [n_rows][S][15] that IMU_Net reads perturbed into out.  A row is one frame, n_rows = B T rows in B
+ * windows of T (row i belongs to window i / T), a frame has S samples, a sample is 15 floats: the orientation O [3][3] row-major
+ * (channels 0 .. 8), the accelerometer (9 .. 11), the gyroscope (12 .. 14).  Every sample gets WHITE noise of its own and the BIAS of its
+ * window: an offset that is constant over the window's T S samples.  seed_word is ONE int64 word ON THE DEVICE, read by the kernel
+ * (mmego_pose_jitter's convention: a captured launch draws afresh once the host rewrites the word).  row_ids [n_rows] and win_ids
+ * [n_rows / T] (int64 on the device, either may be NULL) give the draw numbers d = row_ids[i], else i, and u = win_ids[i / T], else i / T.
+ * With hash32 and dropout_key as in csrc/common.h, for sample s = 0 .. S-1 of row i:
+ *   K_s = dropout_key((unsigned long long)seed_word[0], 0x494D554E),  K_w = dropout_key((unsigned long long)seed_word[0], 0x494D5542)
+ *   e   = (unsigned)(d S + s),  b_s = hash32(K_s ^ hash32(e))        -- the sample's word
+ *   b_w = hash32(K_w ^ hash32((unsigned)u))                          -- the window's word: every sample of every row of a window
+ *   z_s[c], z_w[c] = mmego_pack_frames_noise's z_c of b_s, b_w, c = 0 .. 8: rotation 0 .. 2, accelerometer 3 .. 5, gyroscope 6 .. 8
+ *   E_s = mmego_pose_jitter's E of (noise_rot_deg pi / 180) z_s[0..2],  E_w = the same of (bias_rot_deg pi / 180) z_w[0..2]
+ *   E   = E_s E_w: a 3 x 3 double product, every entry a three-term sum in column order; a factor whose sigma is 0 is left out exactly
+ *   O'  = (float)(E O), as mmego_pose_jitter's R_out (from the left, as there)
+ *   a'_k = (float)(((double)a_k + bias_acc z_w[3+k]) + noise_acc z_s[3+k]);  g'_k the same with bias_gyro, noise_gyro and channels 6+k
+ * Everything in double, one float rounding per output.  A group (orientation, accelerometer, gyroscope) both of whose sigmas are 0 is
+ * copied bit for bit.  Angles are degrees PER AXIS of the rotation vector, additive sigmas are in the recordings' units.  Bounds: no
+ * additive channel moves by more than 3.47 (bias + noise); neither rotation factor turns by more than 6 times its sigma.  One launch, one
+ * thread per sample (2048 workgroups of 256 at the most, strided beyond), no LDS, no atomics; out may be imu exactly (a thread reads its
+ * sample before it writes it); the output is a function of the input, the word and the ids: two launches under one word write the same
+ * bytes.  Refused (non-zero, nothing launched): a null imu, out or seed_word; n_rows < 1, T < 1, S < 1, n_rows % T != 0 (or n_rows S >=
+ * 2^40); a sigma that is negative, NaN or infinite; all six sigmas 0; a seed_word, row_ids or win_ids that is not 8-byte aligned; out
+ * overlapping imu other than out == imu exactly. */
+int mmego_imu_jitter(void* stream, const float* imu, long n_rows, int T, int S,
+                     double noise_rot_deg, double noise_acc, double noise_gyro,
+                     double bias_rot_deg, double bias_acc, double bias_gyro,
+                     const long long* seed_word, const long long* row_ids, const long long* win_ids,
+                     float* out);
 /* Dense inference (blend.hip; processors.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
  * src [nrows][C] contiguous; the cover of frame f = 0 .. F-1 is the CSR list k in [cov_off[f], cov_off[f+1]) (int64 offsets) of source
  * rows cov_row[k] (int32) with weights cov_w[k]:

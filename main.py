@@ -35,7 +35,11 @@ perturbed per frame on the device: a random rotation whose rotation vector has s
 all, and a random shift of standard deviation S metres per component, never beyond 3.47 S.  With --train --network Upper_Net / Lower_Net
 the draw is renewed every minibatch inside the captured step, as a function of (--seed, epoch, minibatch, rank), and the epoch evaluation
 is untouched; with --infer and --infer --dense it is a sensitivity instrument -- how much joint error a degree or a centimetre of
-head-pose error costs -- and one "Head Pose Noise" line follows the figures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+head-pose error costs -- and one "Head Pose Noise" line follows the figures), --imu_noise_rot_deg D / --imu_noise_acc S / --imu_noise_gyro S
+and --imu_bias_rot_deg D / --imu_bias_acc S / --imu_bias_gyro S (the 20 x 15 IMU samples per frame that IMU_Net reads are perturbed on the
+device: white noise drawn per sample, and a bias that stays constant over a window, each on the orientation -- a rotation, degrees per axis
+-- the accelerometer and the gyroscope; with --train, for every --network and with --finetune_imu / --finetune_all, re-drawn every
+minibatch inside the captured step; with --infer [--dense] a sensitivity instrument, one "IMU Noise" line following the figures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -43,7 +47,7 @@ import os
 
 import torch
 
-from mmego_amd.config import Config, ConfigDemo
+from mmego_amd.config import IMU_NOISE_FLAGS, Config, ConfigDemo
 
 
 def build_parser():
@@ -150,6 +154,24 @@ def build_parser():
     p.add_argument("--pose_noise_t", type=float,
                    help="the same on the head position: metres, the standard deviation per component of a random shift (never beyond "
                         "3.47 S).  Either flag may be given without the other")
+    p.add_argument("--imu_noise_rot_deg", type=float,
+                   help="--train (any --network that runs an IMU_Net, --finetune_imu / --finetune_all included) or --infer [--dense]: white "
+                        "noise on the ORIENTATION of every IMU sample IMU_Net reads -- degrees, the standard deviation PER AXIS of a random "
+                        "rotation vector, drawn anew for each of a frame's 20 samples (never beyond 6 D).  Training: re-drawn every minibatch "
+                        "on the device from (--seed, epoch, minibatch, rank), so --resume continues the sequence; the epoch evaluation is "
+                        "untouched.  --infer: drawn from --seed; --dense keeps a frame's white noise in every window that serves it.  Any "
+                        "subset of the six --imu_noise_* / --imu_bias_* flags may be given; not with --gt_head_pose (no IMU_Net runs) "
+                        "unless --train --network IMU_Net")
+    p.add_argument("--imu_noise_acc", type=float,
+                   help="the same on the accelerometer: the standard deviation per component of an added draw, in the recordings' units "
+                        "(never beyond 3.47 S)")
+    p.add_argument("--imu_noise_gyro", type=float, help="the same on the gyroscope")
+    p.add_argument("--imu_bias_rot_deg", type=float,
+                   help="a BIAS on the orientation: one random rotation per window (degrees per axis of its rotation vector), the same for "
+                        "all frame_no x 20 samples of the window, applied together with --imu_noise_rot_deg's; under --infer --dense a bias "
+                        "belongs to its window")
+    p.add_argument("--imu_bias_acc", type=float, help="a bias on the accelerometer: one offset per window and component, in the recordings' units")
+    p.add_argument("--imu_bias_gyro", type=float, help="the same on the gyroscope")
     p.add_argument("--dense", action="store_true",
                    help="--infer only: sliding-window inference over whole recordings -- overlapping frame_no-frame windows --stride frames "
                         "apart (tail-anchored, plus one window at every recording's head), every frame's pose blended on the device from "
@@ -234,6 +256,23 @@ def check_pose_noise(parser, args):
                          % (flag, ft))
     if args.vis:
         parser.error("--%s does not go with --vis" % flag)
+
+
+def check_imu_noise(parser, args):
+    """--imu_noise_* and --imu_bias_* perturb the samples IMU_Net reads: they go with a run in which one runs."""
+    given = [flag for flag in IMU_NOISE_FLAGS if getattr(args, flag) is not None]
+    if not given:
+        return
+    for flag in given:
+        if not 0.0 < getattr(args, flag) < float("inf"):                         # (false for NaN as well)
+            parser.error("--%s is a standard deviation of the IMU noise: it has to be finite and > 0, got %r" % (flag, getattr(args, flag)))
+    flag = given[0]
+    if not (args.train or args.infer):
+        parser.error("--%s goes with --train or --infer: nothing else runs an IMU_Net" % flag)
+    if args.vis:
+        parser.error("--%s does not go with --vis" % flag)
+    if args.gt_head_pose and not (args.train and args.network == "IMU_Net"):
+        parser.error("--%s cannot be combined with --gt_head_pose: the head pose comes from the recording there and no IMU_Net runs" % flag)
 
 
 def check_metrics(parser, args):
@@ -365,6 +404,7 @@ def check_finetune(parser, args, world):
     check_frame_store(parser, args)
     check_dense(parser, args)
     check_pose_noise(parser, args)
+    check_imu_noise(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -419,6 +459,11 @@ def apply_overrides(args):
         c.pose_noise_deg, c.pose_noise_t = args.pose_noise_deg, args.pose_noise_t
     if args.pose_noise_deg is not None or args.pose_noise_t is not None:
         ConfigDemo.seed = args.seed                  # (--infer under the flags: the draws' seed)
+    for c in both:
+        for flag in IMU_NOISE_FLAGS:
+            setattr(c, flag, getattr(args, flag))
+    if any(getattr(args, flag) is not None for flag in IMU_NOISE_FLAGS):
+        ConfigDemo.seed = args.seed                  # (likewise)
     for c in both:
         c.upper_variant = args.upper_variant or "global"
         c.metrics = args.metrics

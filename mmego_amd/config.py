@@ -9,6 +9,8 @@ import torch
 from . import skeleton as sk
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --imu_noise_* / --imu_bias_*: the six flags and configuration attributes, in the order of mmego_imu_jitter's sigmas
+IMU_NOISE_FLAGS = ("imu_noise_rot_deg", "imu_noise_acc", "imu_noise_gyro", "imu_bias_rot_deg", "imu_bias_acc", "imu_bias_gyro")
 
 
 def _default_device():
@@ -57,6 +59,12 @@ class _Common:
     point_noise_v = None        # --point_noise_v: the same on the Doppler velocity, in the recordings' units (None: none)
     pose_noise_deg = None       # --pose_noise_deg: degrees per axis, standard deviation of the random rotation vector applied to every frame's head pose (None: none)
     pose_noise_t = None         # --pose_noise_t: metres per component, standard deviation of the random shift of every frame's head position (None: none)
+    imu_noise_rot_deg = None    # --imu_noise_rot_deg: degrees per axis, white rotation noise on the orientation of every IMU sample IMU_Net reads (None: none)
+    imu_noise_acc = None        # --imu_noise_acc: white noise per accelerometer component, in the recordings' units (None: none)
+    imu_noise_gyro = None       # --imu_noise_gyro: the same on the gyroscope (None: none)
+    imu_bias_rot_deg = None     # --imu_bias_rot_deg: degrees per axis, one rotation per window applied to all its samples' orientations (None: none)
+    imu_bias_acc = None         # --imu_bias_acc: one offset per window and accelerometer component (None: none)
+    imu_bias_gyro = None        # --imu_bias_gyro: the same on the gyroscope (None: none)
     seed = None                 # --seed, as main.py got it (None: 0 for what FrameStore draws)
     clip_grad_norm = None       # --clip_grad_norm: every trained net's gradient is clipped to this global norm ahead of its Adam step (None: off)
     lr_schedule = None          # --lr_schedule: cosine | linear | step; every trained net's rate follows it inside its Adam launch (None: constant)

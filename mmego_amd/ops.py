@@ -690,6 +690,44 @@ def pose_jitter(R, t, sigma_deg, sigma_t, word, R_out, t_out, ids=None):
     return R_out, t_out
 
 
+def imu_jitter(imu, sigmas, word, out, T=None, row_ids=None, win_ids=None):
+    """out = the IMU samples imu [..., T, S, 15] (orientation 3 x 3, accelerometer, gyroscope) perturbed by white noise per sample and a
+    bias that is constant over a window of T frames.  ``sigmas`` = (noise_rot_deg, noise_acc, noise_gyro, bias_rot_deg, bias_acc,
+    bias_gyro): degrees per axis of the rotation vector, the additive ones in the recordings' units.  The draws come from ``word`` --
+    ONE int64 word on the device, read by the kernel, so a captured launch draws afresh once the word is rewritten -- and the draw
+    numbers: row_ids (int64 on the device, one per frame) or the frame's number, win_ids (one per window) or the window's number
+    (mmego_imu_jitter: the recipe is in the header).  T None: the third dimension from the end; T given: imu is [..., S, 15] and its
+    frames fall into windows of T.  A group both of whose sigmas are 0 is copied bit for bit; all six 0 are refused.  out may be imu.
+    -> out."""
+    for x, what in ((imu, "imu"), (out, "out")):
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 3 and x.shape[-1] == 15):
+            raise ValueError("imu_jitter: %s is a contiguous fp32 tensor [..., T, S, 15]" % what)
+    if tuple(out.shape) != tuple(imu.shape):
+        raise ValueError("imu_jitter: imu %s and out %s differ in shape" % (tuple(imu.shape), tuple(out.shape)))
+    S = int(imu.shape[-2])
+    n = imu.numel() // (15 * S) if S else 0
+    T = int(imu.shape[-3]) if T is None else int(T)
+    if n < 1 or T < 1 or n % T:
+        raise ValueError("imu_jitter: imu %s does not hold whole windows of T = %d frames" % (tuple(imu.shape), T))
+    sig = tuple(float(v) for v in sigmas)
+    if len(sig) != 6 or not all(0.0 <= v < float("inf") for v in sig) or not any(sig):
+        raise ValueError("imu_jitter: sigmas are six finite values >= 0, one of them > 0, got %r" % (tuple(sigmas),))
+    if not (isinstance(word, torch.Tensor) and word.dtype == torch.int64 and word.numel() >= 1 and word.is_contiguous()
+            and word.device.type == "cuda"):
+        raise TypeError("imu_jitter needs an int64 device seed word")
+    for ids, want, what in ((row_ids, n, "row_ids"), (win_ids, n // T, "win_ids")):
+        if ids is None:
+            continue
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and ids.is_contiguous() and ids.device.type == "cuda"):
+            raise TypeError("imu_jitter: %s are contiguous int64 draw numbers on the device" % what)
+        if ids.numel() != want:
+            raise ValueError("imu_jitter: %d %s for %d %s" % (ids.numel(), what, want, "frames" if what == "row_ids" else "windows"))
+    for x in (imu, out):
+        _chk(x, x.dim())
+    hip.call("imu_jitter", imu, n, T, S, *sig, word, row_ids, win_ids, out)
+    return out
+
+
 def relu_mask_(G, H):
     G, H = _rows(G), _rows(H)
     hip.call("relu_mask", G, G.stride(0), H, H.stride(0), G.shape[0], G.shape[1])

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import blocks, hip, ops, skeleton
-from .config import Config, ConfigDemo
+from .config import IMU_NOISE_FLAGS, Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, _mix64, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam, LrSchedule, lr_schedule_of
@@ -70,6 +70,42 @@ def _jitter_pose(scratch, R, t, pose_noise, key, ids=None):
     return ops.pose_jitter(R, t, pose_noise[0], pose_noise[1], word, R_n, t_n, ids=ids)
 
 
+IMU_NOISE_SALT = 0x494D554E                                              # the IMU draws' stream among what _mix64 derives from --seed
+
+
+def imu_noise_key(seed, epoch, minibatch, rank=None):
+    """The key of one minibatch's IMU noise and bias draws (--imu_noise_* / --imu_bias_*): pose_noise_key's construction under a salt of
+    its own, so a run with both options draws the two independently.  -> the 63 bits mmego_imu_jitter's int64 device word takes."""
+    words = (int(seed or 0), int(epoch), int(minibatch)) + (() if rank is None else (int(rank),))
+    return _mix64(*words, IMU_NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
+
+
+def imu_noise_of(cfg):
+    """((noise_rot_deg, noise_acc, noise_gyro, bias_rot_deg, bias_acc, bias_gyro), seed) of a run's --imu_noise_* / --imu_bias_* (a
+    missing sigma: 0.0; a missing --seed: 0), or None without the flags."""
+    given = [getattr(cfg, flag, None) for flag in IMU_NOISE_FLAGS]
+    if all(v is None for v in given):
+        return None
+    return tuple(0.0 if v is None else float(v) for v in given), int(getattr(cfg, "seed", None) or 0)
+
+
+def imu_noise_line(imu_noise):
+    sig, seed = imu_noise
+    return ("IMU Noise: white rotation {} deg per axis, accelerometer {}, gyroscope {}; bias rotation {} deg per axis, accelerometer {}, "
+            "gyroscope {}; seed {}").format(*sig, seed)
+
+
+def _jitter_imu(scratch, imu, imu_noise, key, row_ids=None, win_ids=None):
+    """An evaluation minibatch's IMU samples [B, T, S, 15] perturbed out of place (buffer and device word kept in ``scratch`` per shape)."""
+    imu = imu.contiguous()
+    slot = ("imu_noise",) + tuple(imu.shape)
+    if slot not in scratch:
+        scratch[slot] = (torch.empty_like(imu), torch.zeros(1, dtype=torch.int64, device=imu.device))
+    out, word = scratch[slot]
+    word.fill_(int(key))
+    return ops.imu_jitter(imu, imu_noise[0], word, out, row_ids=row_ids, win_ids=win_ids)
+
+
 def upper_variant_of(state_dict):
     """Which Upper net a state_dict belongs to, by its keys (the anchor branch and its combine head against the plain head); None: neither."""
     keys = list(state_dict)
@@ -96,6 +132,7 @@ class _Base:
     finetune_imu = False          # (--finetune_imu: set by the stage trainers from the config)
     finetune_upper = False        # (--finetune_upper: likewise)
     pose_noise = None             # (--pose_noise_deg, --pose_noise_t: (deg, t, seed), set by the stage trainers from the config)
+    imu_noise = None              # (--imu_noise_*, --imu_bias_*: (six sigmas, seed), set by the trainers from the config)
     # The trainer's optimisers, keyed like train_step.TRAINED ("opt": the stage's own net, "imu_opt", "upper_opt"): ONE set, handed to
     # the step of every minibatch size, read by the grad-norm report and the checkpoint (a trainer's __init__ makes it a dict)
     _opts = types.MappingProxyType({})
@@ -235,6 +272,14 @@ class _Base:
         self._resume = ts
         print("[mmego_amd] resumed from %s at epoch %d" % (path, self.start_epoch))
         return ts
+
+    def _say_imu_noise(self):
+        """The one line a training run under --imu_noise_* / --imu_bias_* prints when it starts."""
+        if self.rank == 0:
+            sig, seed = self.imu_noise
+            print("[mmego_amd] IMU noise: white rotation %g deg per axis, accelerometer %g, gyroscope %g; bias per window rotation %g deg per "
+                  "axis, accelerometer %g, gyroscope %g; re-drawn per minibatch from (seed %d, epoch, minibatch, rank); evaluation untouched"
+                  % (sig + (seed,)))
 
     def _lr_schedule(self):
         """The run's learning-rate schedule (params.LrSchedule; None: a constant rate), worked out ONCE, ahead of the first optimiser:
@@ -422,6 +467,11 @@ class _StageTrainer(_Base):
                 print("[mmego_amd] head-pose noise: rotation %g deg per axis, translation %g m, re-drawn per minibatch from (seed %d, epoch, "
                       "minibatch, rank); evaluation untouched" % self.pose_noise)
         self.model_IMU = self._load_imu()
+        self.imu_noise = imu_noise_of(cfg)                             # (--imu_noise_*, --imu_bias_*: (six sigmas, seed) or None)
+        if self.imu_noise is not None:
+            if self.model_IMU is None:
+                raise SystemExit("--imu_noise_* / --imu_bias_* perturb what IMU_Net reads: not with --gt_head_pose, where none runs")
+            self._say_imu_noise()
         self._opts = {}
         self._load_splits()
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -444,6 +494,9 @@ class _StageTrainer(_Base):
             pipelined = (self.model_IMU is not None and not self.finetune_imu and os.environ.get("MMEGO_PIPELINE_IMU", "1") != "0")
             # (--finetune_upper: the plain StageStep too -- the engines around a frozen IMU_Net forward refuse a stage with two trained nets)
             pipelined = pipelined and not self.finetune_upper
+            # (--imu_noise_* / --imu_bias_*: the plain StageStep too -- the noise launch sits in front of the stage's OWN IMU_Net forward,
+            #  inside its body, and a forward that ran one minibatch ahead would have to know the NEXT minibatch's key)
+            pipelined = pipelined and self.imu_noise is None
             imu_lr = getattr(self.cfg, "imu_lr", None)
             self._main_opt(self.model)
             # (one optimiser state per trained net for all batch sizes: the step takes what the dict holds and adds what it builds)
@@ -454,7 +507,8 @@ class _StageTrainer(_Base):
                            finetune_upper=self.finetune_upper, upper_lr=getattr(self.cfg, "upper_lr", None),
                            clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts,
                            ema_decay=getattr(self.cfg, "ema_decay", None), lr_schedule=self._lr_schedule(),
-                           **({} if self.pose_noise is None else dict(pose_noise_deg=self.pose_noise[0], pose_noise_t=self.pose_noise[1])))
+                           **({} if self.pose_noise is None else dict(pose_noise_deg=self.pose_noise[0], pose_noise_t=self.pose_noise[1])),
+                           **({} if self.imu_noise is None else dict(imu_noise=self.imu_noise[0])))
             st.engine = None
             if pipelined:
                 st.imu_next = torch.empty((B, self.frame_no) + tuple(self._train_dev.shape["imu"][1:]), dtype=torch.float32,
@@ -490,6 +544,8 @@ class _StageTrainer(_Base):
                 st.bind(b["data"], b["imu"], b["skl"], tgt, R_gt=b["R_R0R"])
             if self.pose_noise is not None:                             # this minibatch's head-pose draw (the word the captured launch reads)
                 st.set_pose_key(pose_noise_key(self.pose_noise[2], self._epoch, i, self.rank))
+            if self.imu_noise is not None:                              # and its IMU draws
+                st.set_imu_key(imu_noise_key(self.imu_noise[1], self._epoch, i, self.rank))
             if st.engine is None:
                 st.step()
             else:
@@ -607,7 +663,8 @@ class LowerTrainer(_StageTrainer):
         return out
 
 
-def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference", pose_noise=None):
+def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference", pose_noise=None,
+                imu_noise=None):
     """One evaluation pass with ONE host synchronisation: -> float64 array [n_minibatches, W] of per-frame MEANS per minibatch.
     lower_net None: W = 30, the columns of mmego_pose_errors_upper; else W = 45: the 43 columns of mmego_pose_errors, then the
     Lower stage's L1(sum) loss per frame and its mean joint distance.  The split is uploaded once per dataset object
@@ -617,9 +674,13 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
     into further columns of the same device log: W is followed by the 3 J + 3 + len(PCK_THRESHOLDS_CM) columns of
     mmego_pose_errors_aligned (per-frame means) and J columns of acceleration error (per-sequence means; NaN when T < 3).
     pose_noise=(deg, t, seed): every minibatch's head pose is perturbed before the nets see it (ops.pose_jitter under
-    pose_noise_key(seed, 0, minibatch number), rows numbered within the minibatch): what head-pose error costs in joint error."""
+    pose_noise_key(seed, 0, minibatch number), rows numbered within the minibatch): what head-pose error costs in joint error.
+    imu_noise=(six sigmas, seed): every minibatch's IMU samples are perturbed before IMU_Net reads them (ops.imu_jitter under
+    imu_noise_key(seed, 0, minibatch number), frames and windows numbered within the minibatch): what sensor error costs."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
+    if imu_noise is not None and imu_net is None:
+        raise ValueError("imu_noise perturbs what IMU_Net reads: this pass takes the head pose from the recording")
     dev = base.device
     arrays = DeviceArrays.of(dataset, dev)                  # (one copy per split, shared with eval_imu; ADVICE r03)
     todo = list(batch_indices(len(dataset), batch_size, shuffle, rng))
@@ -648,7 +709,8 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
                                 torch.empty((F, 43 if lower_net is not None else 30), dtype=torch.float32, device=dev))
             h0, c0, E = scratch[key]
             tgt, body = b["target"], b["skl"]
-            R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
+            imu = b["imu"] if imu_noise is None else _jitter_imu(scratch, b["imu"], imu_noise, imu_noise_key(imu_noise[1], 0, i))
+            R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
             if pose_noise is not None:
                 R, t = _jitter_pose(scratch, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, i))
             up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]      # (an UpperNet or an UpperNetwlocal)
@@ -712,13 +774,15 @@ def metrics_line(s):
                 " ".join("@%gcm %.4f" % (c, v) for c, v in s["pck"].items()), acc)
 
 
-def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference", pose_noise=None):
+def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference", pose_noise=None,
+                  imu_noise=None):
     """IMU -> Upper -> Lower over a data split (reference Processor/Test/Demo_test.py:71-184, Train_Lower.py:232-332); returns
     (reference-style tuple, summary dict).  Device-resident split, one host read per pass (_epoch_eval).  metrics="full": the same
     tuple and summary keys from the same launches, and the summary also holds aligned_summary's keys for the 21 joints.
-    pose_noise=(deg, t, seed): _epoch_eval's keyword."""
+    pose_noise=(deg, t, seed), imu_noise=(six sigmas, seed): _epoch_eval's keywords."""
     cfg = base.cfg
-    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics, pose_noise=pose_noise)
+    m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics, pose_noise=pose_noise,
+                    imu_noise=imu_noise)
     eval_loss = float(np.mean(m[:, 43]))
     accu_l, accu_up, accu_lo = m[:, :21].mean(axis=1), m[:, 41], m[:, 42]
     accu_ll, angle_ll = m[:, :21].mean(axis=0), m[:, 21:41].mean(axis=0)
@@ -762,7 +826,7 @@ def bone_lengths(bone_set):
 
 
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None):
+                pose_noise=None, imu_noise=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -785,6 +849,10 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
     whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
     pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
+    imu_noise=(six sigmas, seed): every window row's IMU samples are perturbed before IMU_Net reads them (ops.imu_jitter), under ONE key
+    for the whole pass (imu_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as row_ids and the plan's window
+    number as win_ids: a frame keeps its white noise in every window that serves it, a bias belongs to its window -- overlapping windows
+    see one frame under different offsets, as separately started estimators would -- and the result does not depend on batch_size.
     The figures come down in one read; the per-frame arrays in one each."""
     from .data import DenseWindows
     if metrics not in METRICS:
@@ -801,13 +869,13 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise)
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
 
 
-def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None):
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None, imu_noise=None):
     """dense_infer behind its argument checks: the nets are in eval mode."""
     dev = base.device
     W, T, F = plan.W, plan.T, plan.F
@@ -815,7 +883,11 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     win_up, win_lo = f32(W * T, 45), f32(W * T, 24)
     with torch.no_grad():
         state = {}
-        if pose_noise is not None:
+        if imu_noise is not None and imu_net is None:
+            raise ValueError("imu_noise perturbs what IMU_Net reads: this pass takes the head pose from the recording")
+        if imu_noise is not None:
+            win_no = torch.arange(W, dtype=torch.int64, device=dev)                                        # [W]: the plan's window numbers
+        if pose_noise is not None or imu_noise is not None:
             row_frame = torch.as_tensor(np.ascontiguousarray(plan.row_frame, dtype=np.int64)).to(dev)      # [W T]: every row's frame
         for s in range(0, W, batch_size):
             idx = np.arange(s, min(s + batch_size, W))
@@ -825,7 +897,11 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
                 state[B] = (torch.zeros((6, B, 64), device=dev), torch.zeros((6, B, 64), device=dev))
             h0, c0 = state[B]
             tgt, body = b["target"], b["skl"]
-            R, t = base.head_pose(imu_net, b["imu"], b["R_R0R"], tgt)
+            imu = b["imu"]
+            if imu_noise is not None:
+                imu = _jitter_imu(state, imu, imu_noise, imu_noise_key(imu_noise[1], 0, 0), row_ids=row_frame[s * T:(s + B) * T],
+                                  win_ids=win_no[s:s + B])
+            R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
             if pose_noise is not None:
                 R, t = _jitter_pose(state, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, 0), ids=row_frame[s * T:(s + B) * T])
             up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]
@@ -942,7 +1018,7 @@ class Evaluator(_Base):
         space = getattr(cfg, "blend_space", None)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space,
-                                pose_noise=pose_noise_of(cfg))
+                                pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg))
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -962,16 +1038,20 @@ class Evaluator(_Base):
             print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
         self.last_metrics = s
         path = getattr(cfg, "save_pred", None)
-        noise = pose_noise_of(cfg)
+        noise, imu_noise = pose_noise_of(cfg), imu_noise_of(cfg)
         if path:
             more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
             if noise is not None:
                 more.update(pose_noise_deg=np.float64(noise[0]), pose_noise_t=np.float64(noise[1]), pose_noise_seed=np.int64(noise[2]))
+            if imu_noise is not None:
+                more.update({flag: np.float64(v) for flag, v in zip(IMU_NOISE_FLAGS, imu_noise[0])}, imu_noise_seed=np.int64(imu_noise[1]))
             np.savez(path, stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]),
                      **{k: arrays[k] for k in DENSE_SAVED}, **more)
             print("Per-frame skeletons saved in {}".format(path))
         if noise is not None:
             print(pose_noise_line(noise))
+        if imu_noise is not None:
+            print(imu_noise_line(imu_noise))
         return s
 
     def _print_aligned(self, s):
@@ -989,9 +1069,9 @@ class Evaluator(_Base):
     def eval_model(self):
         self.model.load(self.cfg.model_lower_path)
         self.model.eval()
-        noise = pose_noise_of(self.cfg)
+        noise, imu_noise = pose_noise_of(self.cfg), imu_noise_of(self.cfg)
         out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics(),
-                               pose_noise=noise)
+                               pose_noise=noise, imu_noise=imu_noise)
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -1002,6 +1082,8 @@ class Evaluator(_Base):
             self._print_aligned(s)
         if noise is not None:
             print(pose_noise_line(noise))
+        if imu_noise is not None:
+            print(imu_noise_line(imu_noise))
         return out
 
     def eval_all_skeleton(self):
@@ -1021,6 +1103,9 @@ class ImuTrainer(_Base):
         if cfg.IMU_pretrained:
             self.model_IMU.load(cfg.model_IMU_path)
         self._dp_start(self.model_IMU)
+        self.imu_noise = imu_noise_of(cfg)                             # (--imu_noise_*, --imu_bias_*: (six sigmas, seed) or None)
+        if self.imu_noise is not None:
+            self._say_imu_noise()
         self._opts = {}
         self._load_splits()
         rep = os.path.join(_TRAIN_DIR, "report", str(self.Idx))
@@ -1036,7 +1121,7 @@ class ImuTrainer(_Base):
         losses = []
         pg = self.pg
         self._train_arrays()
-        for idx in batch_indices(len(self.train_data), self.batchsize * self.world, True, self._rng):
+        for i, idx in enumerate(batch_indices(len(self.train_data), self.batchsize * self.world, True, self._rng)):
             idx = idx[shard_of(self.rank, self.world)]
             if len(idx) == 0:       # nothing for this rank in a short last global minibatch: zero gradient, same update
                 empty_step(self.model_IMU, self._main_opt(self.model_IMU), pg)
@@ -1045,9 +1130,12 @@ class ImuTrainer(_Base):
             B, T = b["imu"].shape[0], b["imu"].shape[1]
             st = self._steps.get(B)
             if st is None:                                              # one graph per minibatch size, one optimiser
-                st = self._steps[B] = ImuStep(self.model_IMU, process_group=pg, use_graph=True, opt=self._main_opt(self.model_IMU))
+                st = self._steps[B] = ImuStep(self.model_IMU, process_group=pg, use_graph=True, opt=self._main_opt(self.model_IMU),
+                                              **({} if self.imu_noise is None else dict(imu_noise=self.imu_noise[0])))
             if st.static is None or st.static["imu"].data_ptr() != b["imu"].data_ptr():
                 st.bind(b["imu"], b["R_R0R"], b["target"])
+            if self.imu_noise is not None:                              # this minibatch's draws (the word the captured launch reads)
+                st.set_imu_key(imu_noise_key(self.imu_noise[1], self._epoch, i, self.rank))
             st.step()
             losses.append(st.loss.item() / B / T)
         return float(np.mean(losses))

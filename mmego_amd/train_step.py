@@ -209,6 +209,39 @@ class _Engine:
     def _losses(self):
         return self.loss
 
+    # -- imu_noise: the IMU samples perturbed on their way into the engine's IMU_Net (StageStep, ImuStep) ------------------------------
+    imu_noise = None
+
+    def _init_imu_noise(self, imu_noise, dev):
+        """``imu_noise`` checked and kept as six floats, with the device word of the draws and the output buffers per bound shape."""
+        if imu_noise is None:
+            return
+        try:
+            sig = tuple(float(v) for v in imu_noise)
+        except (TypeError, ValueError):
+            sig = ()
+        if len(sig) != 6 or not all(0.0 <= v < float("inf") for v in sig) or not any(sig):
+            raise ValueError("%s: imu_noise is (noise_rot_deg, noise_acc, noise_gyro, bias_rot_deg, bias_acc, bias_gyro), finite and >= 0, "
+                             "one of them > 0, got %r" % (type(self).__name__, imu_noise))
+        self.imu_noise = sig
+        self.imu_word = torch.zeros(1, dtype=torch.int64, device=dev)       # the draws' key: set_imu_key
+        self._imu_out = {}                                                  # the bound samples' shape -> their perturbed copy
+
+    def set_imu_key(self, k):
+        """The key of the next step's IMU noise and bias draws (its low 63 bits): written between steps, outside the graph."""
+        self.imu_word.fill_(int(k) & 0x7FFFFFFFFFFFFFFF)
+
+    def _bind_imu_out(self, imu):
+        if self.imu_noise is not None and tuple(imu.shape) not in self._imu_out:
+            self._imu_out[tuple(imu.shape)] = torch.empty_like(imu)
+
+    def _imu_samples(self, s):
+        """The minibatch's IMU samples as the IMU_Net gets them: the bound buffer, or under imu_noise its perturbed copy in the engine's
+        own buffer (one mmego_imu_jitter launch, part of the body; the bound buffer is never written)."""
+        if self.imu_noise is None:
+            return s["imu"]
+        return ops.imu_jitter(s["imu"], self.imu_noise, self.imu_word, self._imu_out[tuple(s["imu"].shape)])
+
 
 class _StagesEngine(_Engine):
     """An engine around several StageSteps (``stages``) whose gradients ``pair`` all-reduces: each stage trains its one net."""
@@ -282,13 +315,26 @@ class StageStep(_Engine):
     resumed run continues the sequence.  The engines around a stage run it unchanged: the launch is part of the stage's body, and
     each stage has its own word.  There is no backward through the perturbation: a stage that TRAINS the pose (finetune_imu, with or
     without finetune_upper) refuses the options; finetune_upper alone is fine, its pose is data.  With both None the step launches
-    what it launched before and owns no extra buffer."""
+    what it launched before and owns no extra buffer.
+
+    ``imu_noise`` (None: off; else (noise_rot_deg, noise_acc, noise_gyro, bias_rot_deg, bias_acc, bias_gyro), finite and >= 0, one of them
+    > 0): the IMU samples the stage's OWN IMU_Net reads -- trained (finetune_imu: imu_train.forward_train) or frozen -- are perturbed
+    inside the body by one mmego_imu_jitter launch (ops.imu_jitter: white noise per sample, a bias constant over each window), OUT of
+    place into a buffer the step owns per bound minibatch shape; the bound buffer is never written.  The draws are a function of
+    ``imu_word``, an int64 device word the kernel reads: callers write it between steps with ``set_imu_key(k)``, outside the graph.  The
+    gradient flows as it did: the perturbation sits in front of the net's input, which is data.  A stage with no IMU_Net of its own --
+    the recorded pose, or a ``pose`` shared or prefetched by somebody else (SharedImuStages, PipelinedStages) -- has nothing to perturb
+    and refuses the option, at construction or when such a ``pose`` is assigned.  With None the step launches what it launched before
+    and owns no extra buffer."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
                  clip_grad_norm=None, optimisers=None, ema_decay=None, pose_noise_deg=None, pose_noise_t=None,
-                 lr_schedule=None):
+                 lr_schedule=None, imu_noise=None):
         assert stage in ("upper", "lower")
+        if imu_noise is not None and (imu_net is None or pose is not None):
+            raise ValueError("StageStep: imu_noise perturbs what the stage's own IMU_Net reads; this stage has none (the recorded or a "
+                             "shared head pose)")
         self.pose_noise = None
         if pose_noise_deg is not None or pose_noise_t is not None:
             if finetune_imu:
@@ -300,7 +346,7 @@ class StageStep(_Engine):
                                  % (pose_noise_deg, pose_noise_t))
             self.pose_noise = sig
         self.stage, self.net, self.imu, self.upper_frozen = stage, net, imu_net, upper_frozen
-        self.pose = pose              # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement)
+        self._pose = pose             # (R, t) device buffers filled by somebody else (the "IMU-shared" arrangement): the ``pose`` property
         self.finetune_imu = bool(finetune_imu)
         self.finetune_upper = bool(finetune_upper)
         opts = {} if optimisers is None else optimisers
@@ -346,9 +392,21 @@ class StageStep(_Engine):
         if self.pose_noise is not None:
             self.pose_word = torch.zeros(1, dtype=torch.int64, device=dev)      # the draw's key: set_pose_key
             self._pose_out = {}                                        # (B, T) -> (R_n, t_n)
+        self._init_imu_noise(imu_noise, dev)
         if self.finetune_upper:                                        # (loss2 stays the Lower stage's pair: the trainers log it)
             self.upper_jmap = torch.tensor(UPPER_MAP, dtype=torch.int32, device=dev)
             self.upper_loss2 = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    @property
+    def pose(self):
+        return self._pose
+
+    @pose.setter
+    def pose(self, pose):
+        """The engines that fill the pose for a stage assign it here: under imu_noise that would drop the noise without a word."""
+        if pose is not None and self.imu_noise is not None:
+            raise ValueError("StageStep: imu_noise perturbs what the stage's own IMU_Net reads; a shared or prefetched head pose bypasses it")
+        self._pose = pose
 
     def _body(self):
         self._body_forward()
@@ -391,11 +449,11 @@ class StageStep(_Engine):
         """The pose as its source gives it."""
         if self.finetune_imu:
             from . import imu_train
-            return imu_train.forward_train(self.imu, s["imu"])
+            return imu_train.forward_train(self.imu, self._imu_samples(s))
         if self.pose is not None:
             return self.pose
         if self.imu is not None:
-            return self.imu(s["imu"])
+            return self.imu(self._imu_samples(s))
         ops.copy2d(s["target"].view(B * T, 63)[:, 60:63], s["t_gt"].view(B * T, 3))
         return s["R_gt"], s["t_gt"]
 
@@ -464,6 +522,7 @@ class StageStep(_Engine):
             self.static["dl_up"] = torch.empty(B, T, 15, 3, device=dev)
         if self.pose_noise is not None and (B, T) not in self._pose_out:
             self._pose_out[(B, T)] = (torch.empty(B, T, 3, 3, device=dev), torch.empty(B, T, 3, device=dev))
+        self._bind_imu_out(imu)
         self.graph = None
 
     def _mutable_state(self):
@@ -476,10 +535,14 @@ class StageStep(_Engine):
 class ImuStep(_Engine):
     """Stage-1 per-minibatch body (reference Processor/Train/Train_IMU.py:114-149): IMU_Net forward, geodesic + 100 x
     position loss (sum), backward through the two BiLSTM(512) stacks, Adam with coupled weight decay -- with static
-    buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound)."""
+    buffers, capturable into one HIP graph (the eager body is ~650 launches and CPU-launch bound).
+
+    ``imu_noise`` (None: off): StageStep's option of that name -- the bound IMU samples are perturbed by one mmego_imu_jitter launch in
+    front of the net's forward, out of place into a buffer the step owns per bound shape, under the device word ``imu_word`` that
+    ``set_imu_key(k)`` writes between steps.  With None the step launches what it launched before and owns no extra buffer."""
 
     def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None, ema_decay=None,
-                 lr_schedule=None):
+                 lr_schedule=None, imu_noise=None):
         self.net = net
         # (clip_grad_norm, ema_decay, lr_schedule: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=..., lr_schedule=...);
         #  one handed in is used as it is)
@@ -491,12 +554,14 @@ class ImuStep(_Engine):
         self.static = None
         dev = next(net.parameters()).device
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._init_imu_noise(imu_noise, dev)
 
     def bind(self, imu, R_gt, target):
         dev = imu.device
         B, T = imu.shape[0], imu.shape[1]
         self.static = dict(imu=imu, R_gt=R_gt, target=target, head=torch.empty(B, T, 3, device=dev),
                            dR=torch.empty(B, T, 3, 3, device=dev), dt=torch.empty(B, T, 3, device=dev))
+        self._bind_imu_out(imu)
         self.graph = None
 
     def _body(self):
@@ -505,7 +570,7 @@ class ImuStep(_Engine):
         B, T = s["imu"].shape[0], s["imu"].shape[1]
         with torch.no_grad():
             ops.copy2d(s["target"].view(B * T, 63)[:, 60:63], s["head"].view(B * T, 3))     # head joint = joint 20
-            R, t = imu_train.forward_train(self.net, s["imu"])
+            R, t = imu_train.forward_train(self.net, self._imu_samples(s))
             hip.call("imu_loss", R, t, s["R_gt"], s["head"], B * T, 1.0, self.loss, s["dR"], s["dt"])
             imu_train.backward(self.net, s["dR"], s["dt"])
 
