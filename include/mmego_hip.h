@@ -966,7 +966,7 @@ int mmego_grad_sqnorm(void* stream, const float* g, long n, const long* skip, in
 int mmego_adam_step_clipped(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
                             double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
                             const double* part, int npart, double max_norm, double* stats);
-/* The two steps above with an exponential moving average of the weights kept in the same launch (csrc/optim_ema.hip).  The Adam part
+/* The two steps above with an exponential moving average of the weights kept in the same launch (csrc/optim.hip, EMA).  The Adam part
  * is the plain one: the same p, g, m, v, state give the same bits in p, m, v, state (and stats, and the same ticket behaviour) as
  * mmego_adam_step / mmego_adam_step_clipped.  ema: n device floats, 16-byte aligned, not overlapping p; for every element the update
  * touches, ema = fmaf(omd, p_new - ema, ema) in fp32 with omd = (float)(1 - ema_decay) and p_new the parameter just stored.  Elements
@@ -979,7 +979,7 @@ int mmego_adam_step_clipped_ema(void* stream, float* p, const float* g, float* m
                                 double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
                                 const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay);
 
-/* ---- learning-rate schedule inside the step (optim_sched.hip) -----------------------------------------
+/* ---- learning-rate schedule inside the step (optim.hip, SCHED) -------------------------------------
  * The four steps above with the rate computed by the launch itself from the step count, so that a captured graph replays another
  * rate every step and a step skipped as non-finite consumes no schedule step.  With t = state[0] + 1 the step about to be taken,
  * all in double:

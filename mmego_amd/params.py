@@ -294,25 +294,20 @@ class FusedAdam:
         f = self._ensure()
         skip = self._skip_ranges(f)
         ranges = (skip if skip is not False else None, skip.numel() // 2 if skip is not False else 0)
-        # (with a weight average: the same launch under its _ema name, the average and its decay behind the plain arguments)
-        sfx, avg = ("", ()) if self.ema_decay is None else ("_ema", (self.ema, self.ema_decay))
+        common = (f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr), float(self.betas[0]),
+                  float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket)
+        clip = avg = ()
+        if self.max_grad_norm is not None:
+            hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
+            clip = (self._part, self._part.numel(), self.max_grad_norm, self._stats)
+        if self.ema_decay is not None:
+            avg = (self.ema, self.ema_decay)
         if self.lr_schedule is not None:
             # (one entry point for the four forms: absent record buffers select the plain step, an absent average the step without one)
-            clip = (None, 0, 0.0, None)
-            if self.max_grad_norm is not None:
-                hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
-                clip = (self._part, self._part.numel(), self.max_grad_norm, self._stats)
-            hip.call("adam_step_sched", f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
-                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket,
-                     *clip, *(avg or (None, 0.0)), self._sched)
-        elif self.max_grad_norm is None:
-            hip.call("adam_step" + sfx, f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
-                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket, *avg)
+            hip.call("adam_step_sched", *common, *(clip or (None, 0, 0.0, None)), *(avg or (None, 0.0)), self._sched)
         else:
-            hip.call("grad_sqnorm", f.flat_g, f.flat_g.numel(), *ranges, self._part, self._part.numel())
-            hip.call("adam_step_clipped" + sfx, f.flat_p, f.flat_g, self.m, self.v, f.flat_p.numel(), self.state, float(self.lr),
-                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), *ranges, self._ticket,
-                     self._part, self._part.numel(), self.max_grad_norm, self._stats, *avg)
+            # (an option's arguments stand behind the plain ones, under the name that says so)
+            hip.call("adam_step" + ("_clipped" if clip else "") + ("_ema" if avg else ""), *common, *clip, *avg)
         # the update went through raw pointers (no tensor._version bump): tell the net to drop derived copies of its weights
         changed = getattr(f.module, "weights_changed", None)
         if changed is not None:

@@ -21,65 +21,16 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmego_amd import hip, nets, ops  # noqa: E402
+from mmego_amd import hip, nets  # noqa: E402
+from adam_chain import CHAIN, Buffers, chain, dev  # noqa: E402
 
-dev = torch.device("cuda:0")
 hip.lib()
-ADAM = (3e-5, 0.9, 0.999, 1e-8, 1e-3)
-CHAIN = 16
-
-
-class Buffers:
-    def __init__(self, n):
-        g = torch.Generator(device=dev).manual_seed(n)
-        self.n = n
-        self.p, self.g = torch.randn(n, device=dev, generator=g), torch.randn(n, device=dev, generator=g) * 0.01
-        self.m, self.v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.state = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(hip.lib().mmego_grad_norm_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-
-    def plain(self):
-        hip.call("adam_step", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket)
-
-    def norm(self):
-        hip.call("grad_sqnorm", self.g, self.n, None, 0, self.part, self.part.numel())
-
-    def clipped(self):
-        hip.call("adam_step_clipped", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.part,
-                 self.part.numel(), 1.0, self.stats)
-
-    def pair(self):
-        self.norm()
-        self.clipped()
-
-
-def chain(fn):
-    """fn CHAIN times in a row as one HIP graph -> a function returning the GPU-side us per call (20 replays, wall clock)."""
-    fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with ops.capture(graph):
-        for _ in range(CHAIN):
-            fn()
-
-    def us(reps=20):
-        for _ in range(3):
-            graph.replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            graph.replay()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / (reps * CHAIN) * 1e6
-    return us
 
 
 def launches(n):
     b, tiny = Buffers(n), Buffers(4)
-    timers = {"boundary": chain(tiny.plain), "plain": chain(b.plain), "pair": chain(b.pair), "grad_sqnorm": chain(b.norm),
-              "adam_step_clipped": chain(b.clipped)}
+    timers = {"boundary": chain(tiny.form("adam_step")), "plain": chain(b.form("adam_step")), "pair": chain(b.pair),
+              "grad_sqnorm": chain(b.norm), "adam_step_clipped": chain(b.form("adam_step_clipped"))}
     runs = {k: [] for k in timers}
     for _ in range(3):
         for k, t in timers.items():

@@ -7,7 +7,7 @@ rounds, medians:
     (92.5 M: no buffer of either form survives in the Infinity Cache from one launch of the chain to the next): mmego_adam_step against
     mmego_adam_step_ema and mmego_adam_step_clipped against mmego_adam_step_clipped_ema (the update launch of the clipping pair; its
     records are written once, by one mmego_grad_sqnorm), as chains of 16 calls captured into one HIP graph (GPU-side time per call, the
-    dependent launch boundary behind each kernel included -- scripts/bench_clip_step.py's method).  The boundary itself: the same chain
+    dependent launch boundary behind each kernel included -- scripts/adam_chain.py).  The boundary itself: the same chain
     of plain steps on 4 floats.
     Yardstick, from the launch without the average measured in the same process: with <= without + (without - boundary) * 8 / 28 -- the
     time the launch's own achieved byte rate needs for 8 more bytes per parameter (28 B/param without, 36 with: the average is read
@@ -23,68 +23,16 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmego_amd import hip, nets, ops  # noqa: E402
+from mmego_amd import hip, nets  # noqa: E402
+from adam_chain import CHAIN, DECAY, Buffers, chain, dev  # noqa: E402
 
-dev = torch.device("cuda:0")
 hip.lib()
-ADAM = (3e-5, 0.9, 0.999, 1e-8, 1e-3)
-DECAY = 0.999
-CHAIN = 16
-
-
-class Buffers:
-    def __init__(self, n):
-        g = torch.Generator(device=dev).manual_seed(n)
-        self.n = n
-        self.p, self.g = torch.randn(n, device=dev, generator=g), torch.randn(n, device=dev, generator=g) * 0.01
-        self.m, self.v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.ema = self.p.clone()
-        self.state = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(hip.lib().mmego_grad_norm_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-        hip.call("grad_sqnorm", self.g, self.n, None, 0, self.part, self.part.numel())
-
-    def plain(self):
-        hip.call("adam_step", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket)
-
-    def plain_ema(self):
-        hip.call("adam_step_ema", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.ema, DECAY)
-
-    def clipped(self):
-        hip.call("adam_step_clipped", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.part,
-                 self.part.numel(), 1.0, self.stats)
-
-    def clipped_ema(self):
-        hip.call("adam_step_clipped_ema", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.part,
-                 self.part.numel(), 1.0, self.stats, self.ema, DECAY)
-
-
-def chain(fn):
-    """fn CHAIN times in a row as one HIP graph -> a function returning the GPU-side us per call (20 replays, wall clock)."""
-    fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with ops.capture(graph):
-        for _ in range(CHAIN):
-            fn()
-
-    def us(reps=20):
-        for _ in range(3):
-            graph.replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            graph.replay()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / (reps * CHAIN) * 1e6
-    return us
 
 
 def launches(n):
     b, tiny = Buffers(n), Buffers(4)
-    timers = {"boundary": chain(tiny.plain), "adam_step": chain(b.plain), "adam_step_ema": chain(b.plain_ema),
-              "adam_step_clipped": chain(b.clipped), "adam_step_clipped_ema": chain(b.clipped_ema)}
+    timers = dict({"boundary": chain(tiny.form("adam_step"))},
+                  **{k: chain(b.form(k)) for k in ("adam_step", "adam_step_ema", "adam_step_clipped", "adam_step_clipped_ema")})
     runs = {k: [] for k in timers}
     for _ in range(3):
         for k, t in timers.items():

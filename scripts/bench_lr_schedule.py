@@ -3,93 +3,30 @@ on alternating, five rounds, medians and the spread of the rounds beside them:
 
   python scripts/bench_lr_schedule.py OUT.json
 
-The launches without the option are the parent's: the kernels behind mmego_adam_step / mmego_adam_step_clipped are instruction for
-instruction what they were before the option existed (scripts/isa_diff.py), and a step without the option launches what it launched.
-
 (a) the launches alone, on Upper_Net's flat buffer (0.3 M floats: latency level) and on IMU_Net's (23.1 M): mmego_adam_step against
     mmego_adam_step_sched in its plain form, mmego_adam_step_clipped against the clipped form (its records written once, by one
     mmego_grad_sqnorm), as chains of 16 calls captured into one HIP graph (GPU-side time per call, the dependent launch boundary behind
-    each kernel included -- scripts/bench_ema_step.py's method).  The schedule is a cosine with warm-up, so every call takes the branch
+    each kernel included -- scripts/adam_chain.py).  The schedule is a cosine with warm-up, so every call takes the branch
     with the cos.  Expectation from the code: a handful of double operations in one lane per workgroup, nothing per element -- not
     measurable against the unscheduled launch.
 (b) the graph-replayed Upper step (train_step.StageStep, recorded head pose) at B=64, T=8, N=128 without and with the option."""
 import json
 import os
-import statistics
 import sys
 import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mmego_amd import hip, nets, ops  # noqa: E402
-from mmego_amd.params import LrSchedule  # noqa: E402
+from mmego_amd import hip, nets  # noqa: E402
+from adam_chain import CHAIN, ROUNDS, SCHED, Buffers, chain, dev, summary  # noqa: E402
 
-dev = torch.device("cuda:0")
 hip.lib()
-ADAM = (3e-5, 0.9, 0.999, 1e-8, 1e-3)
-SCHED = LrSchedule("cosine", warmup=100, span=100000, floor=0.1)
-CHAIN, ROUNDS = 16, 5
-
-
-class Buffers:
-    def __init__(self, n):
-        g = torch.Generator(device=dev).manual_seed(n)
-        self.n = n
-        self.p, self.g = torch.randn(n, device=dev, generator=g), torch.randn(n, device=dev, generator=g) * 0.01
-        self.m, self.v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.state = torch.zeros(4, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(hip.lib().mmego_grad_norm_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-        self.sched = SCHED.c_struct()
-        hip.call("grad_sqnorm", self.g, self.n, None, 0, self.part, self.part.numel())
-
-    def plain(self):
-        hip.call("adam_step", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket)
-
-    def plain_sched(self):
-        hip.call("adam_step_sched", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, None, 0, 0.0, None,
-                 None, 0.0, self.sched)
-
-    def clipped(self):
-        hip.call("adam_step_clipped", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.part,
-                 self.part.numel(), 1.0, self.stats)
-
-    def clipped_sched(self):
-        hip.call("adam_step_sched", self.p, self.g, self.m, self.v, self.n, self.state, *ADAM, None, 0, self.ticket, self.part,
-                 self.part.numel(), 1.0, self.stats, None, 0.0, self.sched)
-
-
-def chain(fn):
-    """fn CHAIN times in a row as one HIP graph -> a function returning the GPU-side us per call (20 replays, wall clock)."""
-    fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with ops.capture(graph):
-        for _ in range(CHAIN):
-            fn()
-
-    def us(reps=20):
-        for _ in range(3):
-            graph.replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            graph.replay()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / (reps * CHAIN) * 1e6
-    return us
-
-
-def summary(v):
-    return {"rounds": v, "median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
 def launches(n):
     b = Buffers(n)
-    timers = {"adam_step": chain(b.plain), "adam_step_sched": chain(b.plain_sched), "adam_step_clipped": chain(b.clipped),
-              "adam_step_sched_clipped": chain(b.clipped_sched)}
+    timers = {k: chain(b.form(k)) for k in ("adam_step", "adam_step_sched", "adam_step_clipped", "adam_step_sched_clipped")}
     runs = {k: [] for k in timers}
     for _ in range(ROUNDS):
         for k, t in timers.items():

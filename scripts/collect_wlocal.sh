@@ -12,7 +12,7 @@ rocprofv3 --kernel-trace --stats -d "$out/trace" -o bench -- python3 "$root/benc
 db=$(find "$out/trace" -name "*.db" | head -1)
 # 1 eager warm-up body + 1 capture (not executed) + 55 replays = 56 executed steps
 python3 "$root/scripts/prof_summary.py" "$db" 56 --grids > "$out/kernel_stats.csv"
-python3 "$root/scripts/trace_timeline.py" "$db" --marker adam_kernel > "$out/timeline.txt"
+python3 "$root/scripts/trace_timeline.py" "$db" --marker adam_step_kernel > "$out/timeline.txt"
 rm -rf "$out/trace"
 if [ "$2" == "pmc" ]; then
   for grp in "FETCH_SIZE" "WRITE_SIZE"; do

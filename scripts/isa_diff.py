@@ -1,7 +1,10 @@
 """Compare the gfx950 machine code of two builds of libmmego_hip.so kernel by kernel (no GPU needed): the check behind a refactor
 that must not change what any kernel computes.
 
-    python scripts/isa_diff.py OLD.so NEW.so
+    python scripts/isa_diff.py OLD.so NEW.so [--rename OLD_KERNEL=NEW_KERNEL ...]
+
+--rename (repeatable) pairs a kernel that changed its symbol with its predecessor: both sides are matched on the demangled name without
+its parameter list, e.g. --rename 'adam_kernel=adam_step_kernel<false, false, false>', and the pair gets one verdict like any other.
 
 Per kernel symbol one verdict:
   identical  the instruction text is equal (addresses and encodings dropped).
@@ -13,6 +16,7 @@ Per kernel symbol one verdict:
 Exit status 0 when both libraries hold the same kernel symbols and none is DIFFERENT."""
 import collections
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -20,6 +24,7 @@ import tempfile
 from isa_pk_scan import OBJDUMP, device_code_objects
 
 READELF = OBJDUMP.replace("llvm-objdump", "llvm-readelf")
+CXXFILT = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")       # (only --rename needs it)
 SCHEDULE_ONLY = ("s_nop", "s_waitcnt")
 META_EQUAL = ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "group_segment_fixed_size")
 META_REGS = ("vgpr_count", "agpr_count", "sgpr_count")
@@ -56,8 +61,8 @@ def kernels(lib):
                 cur[0].append((ins.strip(), enc.split(":")[-1].split("<")[0].split()))
     for ins, _ in out.values():
         # the fill between one kernel's last instruction and the next kernel's aligned start is not code: zero words (they decode
-        # as v_cndmask_b32 v0, s0, v0, vcc) and s_code_end
-        while ins and (ins[-1][0].startswith("s_code_end") or set(ins[-1][1]) <= {"00000000"}):
+        # as v_cndmask_b32 v0, s0, v0, vcc), s_code_end, and behind the last kernel of a section a run of s_nop
+        while ins and (ins[-1][0].startswith(("s_code_end", "s_nop")) or set(ins[-1][1]) <= {"00000000"}):
             ins.pop()
         ins[:] = [i for i, _ in ins]
     return out
@@ -89,8 +94,21 @@ def verdict(old, new):
     return ("DIFFERENT" if why else "reordered"), "; ".join(why + ([regs] if regs else []))
 
 
-def main(old_lib, new_lib):
+def short_names(symbols):
+    """-> {demangled name without return type and parameter list: symbol}"""
+    symbols = sorted(symbols)
+    txt = subprocess.run([CXXFILT], input="\n".join(symbols), capture_output=True, text=True, check=True).stdout
+    return {re.sub(r"^void ", "", d).split("(")[0]: s for s, d in zip(symbols, txt.splitlines())}
+
+
+def main(old_lib, new_lib, renames=()):
     old, new = kernels(old_lib), kernels(new_lib)
+    old_short, new_short = (short_names(old), short_names(new)) if renames else ({}, {})
+    for was, now in renames:
+        if was not in old_short or now not in new_short:
+            sys.exit("--rename %s=%s: no such kernel in %s" % (was, now, old_lib if was not in old_short else new_lib))
+        label = "%s -> %s" % (was, now)
+        old[label], new[label] = old.pop(old_short[was]), new.pop(new_short[now])
     counts = collections.Counter()
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
@@ -104,6 +122,13 @@ def main(old_lib, new_lib):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        if i + 1 >= len(args) or "=" not in args[i + 1]:
+            sys.exit(__doc__)
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], renames))

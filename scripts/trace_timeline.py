@@ -1,7 +1,7 @@
 """Ordered timeline of the LAST step in a rocprofv3 --kernel-trace database of `bench.py --trace-only [--sequential]`:
 per kernel its start offset, duration and the gap since the previous kernel's end (all in us).
 usage: python scripts/trace_timeline.py <results.db> [--marker KERNEL_SUBSTRING [--per-step N]]
-(--marker: a step starts at every N-th launch of the kernels matching the substring -- e.g. `--marker adam_kernel` for
+(--marker: a step starts at every N-th launch of the kernels matching the substring -- e.g. `--marker adam_step_kernel` for
 `bench.py --wlocal-only --trace-only`, whose step ends with its Adam launch)"""
 import re
 import sqlite3

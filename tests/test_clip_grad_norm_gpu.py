@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from adam_helpers import ADAM, AdamSet as _Set, same_bits as _same_bits
 from conftest import ROOT
 from oracle import geometry as geo
 from step_helpers import entry_points as _entry_points
@@ -31,7 +32,6 @@ TRIP_FLOATS = 1024          # one workgroup's footprint per grid-stride trip: 25
 UNROLL = 4                  # trips whose loads the kernel issues together (csrc/optim.hip GN_UNROLL)
 MAX_NBLK = 1024             # the most records mmego_grad_norm_nblk returns (csrc/optim.hip GN_MAX_BLOCKS)
 SECOND_TRIP_N = MAX_NBLK * TRIP_FLOATS + 4      # 1048580: the smallest n at which a workgroup (the first) takes a second trip
-ADAM = (3e-5, 0.9, 0.999, 1e-8)
 
 
 @pytest.fixture(scope="module")
@@ -45,15 +45,6 @@ def dev():
 def _nblk(n):
     from mmego_amd import hip
     return hip.lib().mmego_grad_norm_nblk(n)
-
-
-def _bits(t):
-    return t.contiguous().cpu().view(torch.int32)
-
-
-def _same_bits(a, b):
-    """torch.equal on the bit patterns (NaN-safe, and -0.0 is not 0.0)."""
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _records(dev, g, skip=None, pad=8):
@@ -72,38 +63,6 @@ def _cf(norm, max_norm):
     c = max_norm / (norm + 1e-6)
     c = 1.0 if c > 1.0 else c
     return float(np.float32(c))
-
-
-class _Set:
-    """p, m, v, state, ticket (+ records and statistics) of one optimiser on the device."""
-
-    def __init__(self, dev, p0):
-        n = p0.numel()
-        self.n = n
-        self.p, self.m, self.v = p0.clone().to(dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.state = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-
-    def plain(self, g, wd, skip=None):
-        from mmego_amd import hip
-        hip.call("adam_step", self.p, g, self.m, self.v, self.n, self.state, *ADAM, wd, skip, 0 if skip is None else skip.numel() // 2,
-                 self.ticket)
-
-    def clipped(self, g, wd, max_norm, skip=None):
-        from mmego_amd import hip
-        ns = 0 if skip is None else skip.numel() // 2
-        hip.call("grad_sqnorm", g, self.n, skip, ns, self.part, self.part.numel())
-        hip.call("adam_step_clipped", self.p, g, self.m, self.v, self.n, self.state, *ADAM, wd, skip, ns, self.ticket, self.part,
-                 self.part.numel(), max_norm, self.stats)
-
-    def snapshot(self):
-        torch.cuda.synchronize()
-        return [t.clone() for t in (self.p, self.m, self.v, self.state)]
-
-    def same_as(self, other):
-        return all(_same_bits(a, b) for a, b in zip(self.snapshot(), other.snapshot() if isinstance(other, _Set) else other))
 
 
 def _schedule(n, seed=5):
@@ -168,7 +127,7 @@ def test_skip_ranges(dev, fill):
     s = _Set(dev, p0)
     s.m.fill_(0.25), s.v.fill_(0.5)
     before = s.snapshot()
-    s.clipped(g.to(dev), 1e-3, 1.0, skip)
+    s.step(g.to(dev), 1e-3, max_norm=1.0, skip=skip)
     after = s.snapshot()
     ins = inside.to(dev)
     for a, b in zip(before[:3], after[:3]):
@@ -186,7 +145,7 @@ def test_update_equals_plain_step_on_the_scaled_gradient(dev, wd):
     norms = []
     for step, g in enumerate(grads, 1):
         g = g.to(dev)
-        a.clipped(g, wd, 1.0)
+        a.step(g, wd, max_norm=1.0)
         torch.cuda.synchronize()
         norm = a.stats[0].item()
         norms.append(norm)
@@ -194,8 +153,8 @@ def test_update_equals_plain_step_on_the_scaled_gradient(dev, wd):
         assert abs(norm - want) <= (n + 4) * U * want
         cf = _cf(norm, 1.0)
         assert (cf < 1.0) == (step >= 2), (step, norm, cf)
-        b.plain(g * torch.tensor(cf, dtype=torch.float32, device=dev), wd)
-        assert a.same_as(b), (wd, step)
+        b.step(g * torch.tensor(cf, dtype=torch.float32, device=dev), wd)
+        assert a.same_adam(b), (wd, step)
         assert a.ticket.item() == 0
     print("clip schedule norms:", " ".join("%.4g" % x for x in norms))
     assert 0.5 < norms[0] < 0.8 and 5e3 < norms[4] < 8e3
@@ -212,9 +171,9 @@ def test_threshold_out_of_reach_is_the_plain_step(dev, max_norm):
         a, b = _Set(dev, p0), _Set(dev, p0)
         for step, g in enumerate(grads, 1):
             g = g.to(dev)
-            a.clipped(g, wd, max_norm)
-            b.plain(g, wd)
-            assert a.same_as(b), (wd, step)
+            a.step(g, wd, max_norm=max_norm)
+            b.step(g, wd)
+            assert a.same_adam(b), (wd, step)
         assert a.stats[4].item() == 0 and a.stats[3].item() == 5 and a.stats[5].item() == 0
 
 
@@ -234,7 +193,7 @@ def test_against_torch_clip_grad_norm_and_adam(dev, wd):
         opt.step()
         free_p.grad = g.clone()
         free.step()
-        a.clipped(g.to(dev), wd, 1.0)
+        a.step(g.to(dev), wd, max_norm=1.0)
         err = float((a.p.cpu() - ref_p.detach()).abs().max())
         apart = float((ref_p.detach() - free_p.detach()).abs().max())
         print("clipped adam wd %g step %d: %.3e from torch, clipped and unclipped torch %.3e apart" % (wd, step, err, apart))
@@ -250,24 +209,24 @@ def test_non_finite_gradient_skips_the_step(dev):
     p0, grads = _schedule(n)
     a, b = _Set(dev, p0), _Set(dev, p0)
     wd = 1e-3
-    a.clipped(grads[2].to(dev), wd, 1.0)
+    a.step(grads[2].to(dev), wd, max_norm=1.0)
     keep = a.snapshot()
     assert a.state[0].item() == 1
     for k, bad in enumerate((float("inf"), float("nan")), 1):
         g = grads[3].clone()
         g[1234] = bad
-        a.clipped(g.to(dev), wd, 1.0)
-        assert a.same_as(keep), bad
+        a.step(g.to(dev), wd, max_norm=1.0)
+        assert a.same_adam(keep), bad
         assert a.ticket.item() == 0 and a.stats[5].item() == k and a.stats[3].item() == 1 + k
         assert not math.isfinite(a.stats[0].item())
-    a.clipped(grads[3].to(dev), wd, 1.0)
+    a.step(grads[3].to(dev), wd, max_norm=1.0)
     torch.cuda.synchronize()
     assert a.state[0].item() == 2 and a.stats[5].item() == 2 and a.stats[3].item() == 4 and a.stats[4].item() == 2
     assert math.isfinite(a.stats[1].item()) and math.isfinite(a.stats[2].item())
     # the same two finite steps without the bad ones in between
     for i in (2, 3):
-        b.clipped(grads[i].to(dev), wd, 1.0)
-    assert a.same_as(b)
+        b.step(grads[i].to(dev), wd, max_norm=1.0)
+    assert a.same_adam(b)
 
 
 # ---- 6. capture ---------------------------------------------------------------------------------------------------------------------------
@@ -277,17 +236,17 @@ def test_captured_pair_replays_as_three_eager_steps(dev):
     p0, grads = _schedule(n)
     a, b = _Set(dev, p0), _Set(dev, p0)
     for g in grads[1:4]:
-        a.clipped(g.to(dev), 1e-3, 1.0)
+        a.step(g.to(dev), 1e-3, max_norm=1.0)
     torch.cuda.synchronize()
     gbuf = torch.zeros(n, device=dev)
     graph = torch.cuda.CUDAGraph()
     with ops.capture(graph):
-        b.clipped(gbuf, 1e-3, 1.0)
+        b.step(gbuf, 1e-3, max_norm=1.0)
     assert b.state[0].item() == 0                                             # (capturing executes nothing)
     for g in grads[1:4]:
         gbuf.copy_(g)
         graph.replay()
-    assert a.same_as(b) and torch.equal(a.stats, b.stats) and b.state[0].item() == 3 and b.stats[4].item() == 3
+    assert a.same_adam(b) and torch.equal(a.stats, b.stats) and b.state[0].item() == 3 and b.stats[4].item() == 3
 
 
 # ---- 7. refusals --------------------------------------------------------------------------------------------------------------------------
@@ -395,7 +354,7 @@ class _HostClip:
 
 
 def _prologue_sum(part):
-    """adam_clipped_kernel's fixed order over the records, in numpy float64."""
+    """The fixed order of the clipped step's prologue (adam_step_kernel, CLIP) over the records, in numpy float64."""
     x = np.zeros(256 * ((part.numel() + 255) // 256))
     x[:part.numel()] = part.numpy()
     lanes = np.zeros(256)

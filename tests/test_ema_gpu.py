@@ -1,4 +1,4 @@
-"""GPU: the fused Adam steps with a weight average (csrc/optim_ema.hip: mmego_adam_step_ema, mmego_adam_step_clipped_ema), FusedAdam's
+"""GPU: the fused Adam steps with a weight average (csrc/optim.hip: mmego_adam_step_ema, mmego_adam_step_clipped_ema), FusedAdam's
 ema_decay / averaged() / ema_state_dict(), the step engines' ema_decay and `main.py --train --ema_decay`.
 
 Sizes: 4 floats (one float4, one lane), 1028 (a partial workgroup), 2 097 156 = 524 289 float4: the launch is capped at 2048 workgroups
@@ -14,12 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+from adam_helpers import ADAM, AdamSet as _Set, grads as _seeded, same_bits as _same_bits
 from conftest import ROOT
 from step_helpers import entry_points as _entry_points
 
 pytestmark = pytest.mark.gpu
 
-ADAM = (3e-5, 0.9, 0.999, 1e-8)
 SIZES = [4, 1028, 2048 * 256 * 4 + 4]
 SENTINEL = -7.5
 EPS = 2.0 ** -23
@@ -33,53 +33,9 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _bits(t):
-    return t.contiguous().cpu().view(torch.int32)
-
-
-def _same_bits(a, b):
-    """torch.equal on the bit patterns (NaN-safe, and -0.0 is not 0.0)."""
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _grads(dev, n, steps=3, seed=5):
-    """(p0, [g_1 .. g_steps]) on the device: seeded, a fresh gradient per step."""
-    g = torch.Generator(device=dev).manual_seed(seed + n)
-    return torch.randn(n, device=dev, generator=g), [torch.randn(n, device=dev, generator=g) * 0.1 for _ in range(steps)]
-
-
-class _Set:
-    """p, m, v, state, ticket, the records and statistics of the clipped step and the average of one optimiser, on the device."""
-
-    def __init__(self, dev, p0):
-        from mmego_amd import hip
-        n = self.n = p0.numel()
-        self.p, self.m, self.v = p0.clone(), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.ema = p0.clone()
-        self.state = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(hip.lib().mmego_grad_norm_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-
-    def step(self, g, wd, decay=None, max_norm=None, skip=None):
-        """One step through the entry point that (decay, max_norm) select."""
-        from mmego_amd import hip
-        ns = 0 if skip is None else skip.numel() // 2
-        avg = () if decay is None else (self.ema, decay)
-        sfx = "" if decay is None else "_ema"
-        if max_norm is None:
-            hip.call("adam_step" + sfx, self.p, g, self.m, self.v, self.n, self.state, *ADAM, wd, skip, ns, self.ticket, *avg)
-        else:
-            hip.call("grad_sqnorm", g, self.n, skip, ns, self.part, self.part.numel())
-            hip.call("adam_step_clipped" + sfx, self.p, g, self.m, self.v, self.n, self.state, *ADAM, wd, skip, ns, self.ticket, self.part,
-                     self.part.numel(), max_norm, self.stats, *avg)
-
-    def snapshot(self, ema=False):
-        torch.cuda.synchronize()
-        return [t.clone() for t in (self.p, self.m, self.v, self.state) + ((self.ema,) if ema else ())]
-
-    def same_adam(self, other):
-        return all(_same_bits(a, b) for a, b in zip(self.snapshot(), other.snapshot()))
+def _grads(dev, n):
+    """(p0, [g_1, g_2, g_3]) on the device."""
+    return _seeded(dev, n, 3)
 
 
 # ---- 1. the Adam part is the plain step, plain and clipped ----------------------------------------------------------------------------------

@@ -204,7 +204,10 @@ def test_the_entry_point_is_declared():
     names = [n for _, n in protos["mmego_adam_step_clipped_ema"]]
     assert [n for _, n in protos["mmego_adam_step_sched"]] == names + ["sched"]
     assert [t for t, _ in protos["mmego_adam_step_sched"]] == [t for t, _ in protos["mmego_adam_step_clipped_ema"]] + [ctypes.c_void_p]
-    assert os.path.exists(os.path.join(os.path.dirname(hip.HEADER), "..", "mmego_amd", "csrc", "optim_sched.hip"))
+    with open(os.path.join(os.path.dirname(hip.HEADER), "..", "mmego_amd", "csrc", "optim.hip")) as fh:
+        src = fh.read()
+    for name in ("mmego_adam_step", "mmego_adam_step_clipped", "mmego_adam_step_ema", "mmego_adam_step_clipped_ema", "mmego_adam_step_sched"):
+        assert name + "(" in src, name
 
 
 def test_fused_adam_state_carries_the_schedule():

@@ -1,4 +1,4 @@
-"""GPU: the fused Adam steps with a learning-rate schedule evaluated inside the launch (csrc/optim_sched.hip: mmego_adam_step_sched),
+"""GPU: the fused Adam steps with a learning-rate schedule evaluated inside the launch (csrc/optim.hip: mmego_adam_step_sched),
 FusedAdam's lr_schedule / current_lr(), the step engines' lr_schedule and `main.py --train --lr_schedule`.
 
 Sizes as tests/test_ema_gpu.py: 4 floats (one lane), 1028 (a partial workgroup), 2 097 156 (exactly one lane takes a second grid-stride
@@ -16,14 +16,13 @@ import numpy as np
 import pytest
 import torch
 
+from adam_helpers import ADAM, LR, AdamSet as _Set, grads as _seeded, same_bits as _same_bits
 from conftest import ROOT
 from lr_schedule_ref import mult_ref
 from step_helpers import entry_points as _entry_points
 
 pytestmark = pytest.mark.gpu
 
-LR = 3e-5
-ADAM = (LR, 0.9, 0.999, 1e-8)
 SIZES = [4, 1028, 2048 * 256 * 4 + 4]
 SENTINEL = -7.5
 BOUND = 1e-14
@@ -56,69 +55,9 @@ def _ref(kind, t):
     return mult_ref(kind, t, **KINDS[kind][1])
 
 
-def _same_bits(a, b):
-    """torch.equal on the bit patterns (NaN-safe, and -0.0 is not 0.0), on the device."""
-    it = torch.int32 if a.dtype == torch.float32 else torch.int64
-    return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
-
-
-_grad_cache = {}
-
-
-def _grads(dev, n, seed=5):
-    """(p0, [g_1 .. g_7]) on the device: seeded, a fresh gradient per step; computed once per size and never written."""
-    if n not in _grad_cache:
-        g = torch.Generator(device=dev).manual_seed(seed + n)
-        _grad_cache[n] = (torch.randn(n, device=dev, generator=g), [torch.randn(n, device=dev, generator=g) * 0.1 for _ in range(STEPS)])
-    return _grad_cache[n]
-
-
-class _Set:
-    """p, m, v, state (``words`` doubles), ticket, the records and statistics of the clipped step and the average of one optimiser."""
-
-    def __init__(self, dev, p0, words):
-        from mmego_amd import hip
-        n = self.n = p0.numel()
-        self.p, self.m, self.v = p0.clone(), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self.ema = p0.clone()
-        self.state = torch.zeros(words, dtype=torch.float64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.part = torch.zeros(hip.lib().mmego_grad_norm_nblk(n), dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
-
-    def step(self, g, wd, decay=None, max_norm=None, lr=LR):
-        """One step through the EXISTING entry point that (decay, max_norm) select, at the rate ``lr``."""
-        from mmego_amd import hip
-        avg = () if decay is None else (self.ema, decay)
-        sfx = "" if decay is None else "_ema"
-        if max_norm is None:
-            hip.call("adam_step" + sfx, self.p, g, self.m, self.v, self.n, self.state, lr, *ADAM[1:], wd, None, 0, self.ticket, *avg)
-        else:
-            hip.call("grad_sqnorm", g, self.n, None, 0, self.part, self.part.numel())
-            hip.call("adam_step_clipped" + sfx, self.p, g, self.m, self.v, self.n, self.state, lr, *ADAM[1:], wd, None, 0, self.ticket,
-                     self.part, self.part.numel(), max_norm, self.stats, *avg)
-
-    def sched_step(self, g, wd, sched, decay=None, max_norm=None):
-        """One step through mmego_adam_step_sched in the form that (decay, max_norm) select."""
-        from mmego_amd import hip
-        clip = (None, 0, 0.0, None)
-        if max_norm is not None:
-            hip.call("grad_sqnorm", g, self.n, None, 0, self.part, self.part.numel())
-            clip = (self.part, self.part.numel(), max_norm, self.stats)
-        avg = (None, 0.0) if decay is None else (self.ema, decay)
-        hip.call("adam_step_sched", self.p, g, self.m, self.v, self.n, self.state, *ADAM, wd, None, 0, self.ticket, *clip, *avg, sched)
-
-    def tensors(self):
-        return (self.p, self.m, self.v, self.ema, self.stats)
-
-    def same(self, other):
-        """p, m, v, ema, stats and state[0..2] equal as bit patterns."""
-        torch.cuda.synchronize()
-        return all(_same_bits(a, b) for a, b in zip(self.tensors(), other.tensors())) and _same_bits(self.state[:3], other.state[:3])
-
-    def snapshot(self):
-        torch.cuda.synchronize()
-        return [t.clone() for t in self.tensors() + (self.state,)]
+def _grads(dev, n):
+    """(p0, [g_1 .. g_7]) on the device."""
+    return _seeded(dev, n, STEPS)
 
 
 def _max_norm(form, grads):
@@ -213,11 +152,11 @@ def test_non_finite_gradient_consumes_no_schedule_step(dev, n, kind):
     sched = _sched(kind)
     a = _Set(dev, p0, 4)
     a.sched_step(grads[0], 1e-3, sched, decay=0.9, max_norm=1.0)
-    keep = a.snapshot()
+    keep = a.snapshot(stats=True, ema=True)
     g = grads[1].clone()
     g[n - 3] = float("inf")
     a.sched_step(g, 1e-3, sched, decay=0.9, max_norm=1.0)
-    after = a.snapshot()
+    after = a.snapshot(stats=True, ema=True)
     for i, (x, y) in enumerate(zip(after, keep)):
         if i != 4:                                                          # (everything but the statistics, all four state words included)
             assert _same_bits(x, y), i
