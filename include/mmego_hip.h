@@ -1007,6 +1007,26 @@ int mmego_adam_step_sched(void* stream, float* p, const float* g, float* m, floa
                           const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay,
                           const MmegoLrSchedule* sched);
 
+/* ---- shaped weight decay inside the step (optim.hip, DECAY) ----------------------------------------
+ * Every option of the steps above in one entry point, plus a mask of what decays and the decoupled (AdamW) form.  The arguments
+ * are mmego_adam_step_sched's with its conventions (part == NULL: not clipped, ema == NULL: no average); sched == NULL selects the
+ * unscheduled step (state: three doubles), else state has four.
+ * decay_mask: one bit per float4 of the flat buffer in 64-bit words, word w bit b covering float4 64 w + b: (n / 4 + 63) / 64 device
+ * words, 8-byte aligned, read only; bits beyond n / 4 in the last word are ignored.  NULL: every element decays.  An element whose
+ * bit is clear is updated as with weight_decay = 0; an element inside a skip range is untouched whatever its bit.
+ * decoupled == 0: where the bit is set the gradient of the update is g + weight_decay * p (g * cf under clipping), as in the steps
+ * above -- with a NULL or all-set mask the call is bit for bit the corresponding entry point above.
+ * decoupled == 1: with lr_t the rate of this step (the scheduled one where sched is given) and dw = (float)(lr_t * weight_decay),
+ * the product formed in double, where the bit is set p' = fmaf(-dw, p, p) -- p - dw p rounded ONCE, not p * (1 - dw) -- and the
+ * Adam update then runs on p' with the gradient alone: from p' the step is the one above at weight_decay = 0, bit for bit.  The
+ * clip factor scales the raw gradient only, a step skipped as non-finite decays nothing, ema takes the final parameter.
+ * Refused (nothing is launched): whatever mmego_adam_step_sched refuses (but a NULL sched), a decay_mask off an 8-byte boundary,
+ * weight_decay negative, infinite or NaN, decoupled outside {0, 1}. */
+int mmego_adam_step_decay(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip, int* ticket,
+                          const double* part, int npart, double max_norm, double* stats, float* ema, double ema_decay,
+                          const MmegoLrSchedule* sched, const unsigned long long* decay_mask, int decoupled);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,9 @@ trained net's gradient is clipped to the global norm X ahead of its Adam step; s
 weights at decay D, updated inside its fused Adam launch; each epoch's evaluation, model selection and early stopping run on the averaged
 weights; the checkpoints keep the raw weights and the averaged nets are written beside them under EMA/), --lr_schedule {cosine,linear,step}
 [--lr_warmup N --lr_min_ratio R --lr_decay_steps N --lr_step_every N --lr_step_gamma G] (every trained net's learning rate follows a warm-up
-and a decay over its optimiser's step count, computed inside its fused Adam launch; --lr_warmup alone: warm-up, then constant), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
+and a decay over its optimiser's step count, computed inside its fused Adam launch; --lr_warmup alone: warm-up, then constant),
+--weight_decay W [--decay_mode {l2,adamw} --no_decay_1d] (the weight decay of every trained net in place of the reference's, coupled or
+decoupled at the rate of the step, optionally leaving biases and normalisation parameters out, inside its fused Adam launch), --upper_variant {global,wlocal} (which net "Upper_Net" is: UpperNet, or
 UpperNetwlocal with the anchor branch -- the net trained by --train --network Upper_Net, the class the Upper checkpoint is loaded into by
 --train --network Lower_Net and --infer), --metrics {reference,full} (full: beside the reference's figures, the evaluation pass of --infer
 and of --train --network Upper_Net / Lower_Net also takes root-relative, rigid-aligned and Procrustes-aligned joint errors, the fit's
@@ -116,6 +118,14 @@ def build_parser():
                                                        "the warm-up (default: epochs x minibatches per epoch - warm-up)")
     p.add_argument("--lr_step_every", type=int, help="--lr_schedule step: decay every N >= 1 optimiser steps behind the warm-up")
     p.add_argument("--lr_step_gamma", type=float, help="--lr_schedule step: the factor of each decay, in (0, 1]")
+    p.add_argument("--weight_decay", type=float,
+                   help="--train: the weight decay W >= 0 of every net the run trains, in place of the reference's (IMU_Net 1e-3, Upper_Net "
+                        "and Lower_Net 0), applied inside the fused Adam launch.  --resume continues the saved setting without the flags")
+    p.add_argument("--decay_mode", type=str, choices=["l2", "adamw"], default=None,
+                   help="--weight_decay: l2 (default: W x weight joins the gradient, as torch.optim.Adam does) or adamw (decoupled: the "
+                        "weight shrinks by lr_t x W ahead of the update, lr_t the rate of the step, the scheduled one under --lr_schedule)")
+    p.add_argument("--no_decay_1d", action="store_true",
+                   help="--weight_decay: parameters with at most one dimension (biases, BatchNorm scales and shifts, LSTM biases) do not decay")
     p.add_argument("--upper_variant", type=str, choices=["global", "wlocal"], default=None,
                    help="which net Upper_Net is: global (default: UpperNet) or wlocal (UpperNetwlocal, with the anchor branch).  --train "
                         "--network Upper_Net trains it (with --finetune_imu, --imu_lr, --imu_dropout, --clip_grad_norm, --resume and "
@@ -347,6 +357,19 @@ def check_lr_schedule(parser, args):
             parser.error("--lr_step_gamma is the factor of each decay: it has to lie in (0, 1], got %r" % (args.lr_step_gamma,))
 
 
+def check_weight_decay(parser, args):
+    """--weight_decay, --decay_mode and --no_decay_1d belong to a training run; the last two shape the first; W is finite and >= 0."""
+    given = [f for f in ("weight_decay", "decay_mode") if getattr(args, f) is not None] + (["no_decay_1d"] if args.no_decay_1d else [])
+    if not given:
+        return
+    if args.infer or not args.train:
+        parser.error("--%s goes with --train only (it shapes the optimiser's weight decay)" % given[0])
+    if args.weight_decay is None:
+        parser.error("--%s shapes --weight_decay's decay; without --weight_decay the run keeps the reference's" % given[0])
+    if not 0.0 <= args.weight_decay < float("inf"):    # (false for NaN as well)
+        parser.error("--weight_decay is a decay strength: it has to be finite and >= 0, got %r" % (args.weight_decay,))
+
+
 def check_finetune_upper(parser, args, world):
     """--finetune_upper fits one arrangement only; everything else is refused before any work starts.  (--gt_head_pose is fine: the
     head pose is not what is trained.)"""
@@ -401,6 +424,7 @@ def check_finetune(parser, args, world):
     check_clip_grad_norm(parser, args)
     check_ema_decay(parser, args)
     check_lr_schedule(parser, args)
+    check_weight_decay(parser, args)
     check_frame_store(parser, args)
     check_dense(parser, args)
     check_pose_noise(parser, args)
@@ -451,6 +475,7 @@ def apply_overrides(args):
     Config.ema_decay = args.ema_decay
     Config.lr_schedule, Config.lr_warmup, Config.lr_min_ratio = args.lr_schedule, args.lr_warmup, args.lr_min_ratio
     Config.lr_decay_steps, Config.lr_step_every, Config.lr_step_gamma = args.lr_decay_steps, args.lr_step_every, args.lr_step_gamma
+    Config.weight_decay, Config.decay_mode, Config.no_decay_1d = args.weight_decay, args.decay_mode, bool(args.no_decay_1d)
     Config.window_jitter = bool(args.window_jitter)
     Config.point_keep = args.point_keep
     Config.point_noise, Config.point_noise_v = args.point_noise, args.point_noise_v

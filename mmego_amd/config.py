@@ -74,6 +74,9 @@ class _Common:
     lr_step_every = None        # --lr_step_every, --lr_step_gamma: the step decay
     lr_step_gamma = None
     ema_decay = None            # --ema_decay: every trained net keeps a weight average at this decay; evaluation uses it (None: off)
+    weight_decay = None         # --weight_decay: the decay of every net the run trains (None: the reference's, IMU_Net 1e-3 and the others 0)
+    decay_mode = None           # --decay_mode: l2 (coupled, the reference's) | adamw (decoupled, follows the scheduled rate) (None: l2)
+    no_decay_1d = False         # --no_decay_1d: biases, BatchNorm scales and shifts and LSTM biases do not decay
 
 
 class Config(_Common):

@@ -15,6 +15,12 @@
 //          though, lives in state[0] on the device.  The one lane per workgroup that forms the bias corrections first forms
 //          lr_t = lr * (w(t) * d(t)) (include/mmego_hip.h spells w and d out; all of it in double), and the step is the
 //          unscheduled one at lr_t.  A handful of double operations (one cos or pow) in one lane per workgroup, nothing per element.
+//   DECAY  weight decay a user can shape (FusedAdam(decoupled=..., no_decay=...), --weight_decay / --decay_mode / --no_decay_1d): a
+//          mask of one bit per float4 says which elements decay at all, and a host flag selects the decoupled (AdamW) form,
+//          p' = fmaf(-dw, p, p) with dw = (float)(lr_t * weight_decay) formed in double by the lane that forms the bias corrections,
+//          ahead of an update whose gradient carries no decay term.  A wave's 64 lanes cover float4 64 k .. 64 k + 63 in every trip,
+//          so the wave reads ONE 8-byte mask word per trip through a wave-uniform index and lane l tests bit l: 8 B per 64 float4,
+//          1/32 B/param against 28.  Without DECAY the step is the coupled one over every element, as it always was.
 // The options do not touch each other's arithmetic: p, m, v, state[0..2] (and stats, ema) of any form are bit for bit those of the
 // form without an option, called with the same rate.
 #include <math.h>
@@ -78,6 +84,7 @@ struct AdamArgs {
   const double* part; int npart; double max_norm; double* stats;      // CLIP: the records of pass 1
   float* ema; float omd;                                              // EMA
   MmegoLrSchedule sched;                                              // SCHED
+  const unsigned long long* mask; int decoupled; double wdd;          // DECAY: bit b of word w covers float4 64 w + b (NULL: all set)
 };
 
 // g * cf as ONE rounded fp32 product: the empty asm keeps it out of any fused multiply-add with what follows.
@@ -106,8 +113,11 @@ __device__ __forceinline__ double lr_multiplier(const MmegoLrSchedule& sc, doubl
 // The update itself.  CLIP: the gradient is the fp32 product g * cf, rounded once on its own; otherwise g as it lies there.  EMA: every
 // element the update touches moves its average towards the NEW parameter (still in its register) by one explicit fp32 fma; an element
 // in a skip range leaves the loop before the average is read.
-template <bool CLIP, bool EMA>
-__device__ __forceinline__ void adam_update(const AdamArgs& a, float cf, float step_size, float bc2_sqrt) {
+// DECAY: `decays` is this float4's mask bit.  Coupled: the decay term joins the gradient where the bit is set, as above; decoupled: the
+// parameter is scaled first, by ONE explicit fmaf (p - dw p rounded once; NOT p * (1 - dw), whose fp32 factor has a handful of values
+// near 1 and would quantise the decay), and the update runs on it with the gradient alone.  A clear bit is the step at weight_decay 0.
+template <bool CLIP, bool EMA, bool DECAY>
+__device__ __forceinline__ void adam_update(const AdamArgs& a, float cf, float step_size, float bc2_sqrt, float dw) {
   float4* __restrict__ p4 = reinterpret_cast<float4*>(a.p);
   const float4* __restrict__ g4 = reinterpret_cast<const float4*>(a.g);
   float4* __restrict__ m4 = reinterpret_cast<float4*>(a.m);
@@ -121,6 +131,16 @@ __device__ __forceinline__ void adam_update(const AdamArgs& a, float cf, float s
     if (skipped) continue;      // a tensor that never receives a gradient (torch.optim.Adam skips grad=None)
     float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee;
     if constexpr (EMA) ee = e4[i];
+    bool decays = true;
+    if constexpr (DECAY) {
+      // i >> 6 is the same in all 64 lanes of a wave (i = 256 * (blockIdx.x + trip * gridDim.x) + threadIdx.x): taken from the first
+      // active lane it is a scalar.  The mask is never written while a step runs: read through the constant address space, so the
+      // stores to p, m, v cannot be taken to alias it, the word arrives by one scalar 8-byte load per wave and trip
+      typedef const __attribute__((address_space(4))) unsigned long long* ConstWords;
+      const long w = __builtin_amdgcn_readfirstlane((int)(i >> 6));
+      const unsigned long long word = a.mask ? ((ConstWords)a.mask)[w] : ~0ull;
+      decays = (word >> (threadIdx.x & 63)) & 1ull;
+    }
     float* pa = reinterpret_cast<float*>(&pp);
     float* ga = reinterpret_cast<float*>(&gg);
     float* ma = reinterpret_cast<float*>(&mm);
@@ -130,7 +150,15 @@ __device__ __forceinline__ void adam_update(const AdamArgs& a, float cf, float s
     for (int k = 0; k < 4; ++k) {
       float gr = ga[k];
       if constexpr (CLIP) gr = clipped_grad(ga[k], cf);
-      if (a.weight_decay != 0.f) gr = gr + a.weight_decay * pa[k];
+      if constexpr (DECAY) {
+        if (a.decoupled) {
+          if (decays && dw != 0.f) pa[k] = fmaf(-dw, pa[k], pa[k]);
+        } else if (decays && a.weight_decay != 0.f) {
+          gr = gr + a.weight_decay * pa[k];
+        }
+      } else {
+        if (a.weight_decay != 0.f) gr = gr + a.weight_decay * pa[k];
+      }
       // torch: exp_avg.lerp_(grad, 1-beta1) == m + (g - m) * (1 - beta1)
       ma[k] = ma[k] + (gr - ma[k]) * a.omb1;
       va[k] = va[k] * a.beta2 + a.omb2 * gr * gr;
@@ -155,11 +183,15 @@ __device__ __forceinline__ void adam_update(const AdamArgs& a, float cf, float s
 // step count does not advance and no schedule step is consumed.  The workgroup that draws the last ticket also keeps the statistics:
 // stats[0] this step's norm, [1] sum of the finite norms, [2] their maximum, [3] steps seen, [4] steps with c < 1, [5] steps
 // skipped as non-finite, [6..7] reserved.
-template <bool CLIP, bool EMA, bool SCHED>
+// DECAY.  The lane that forms the bias corrections also forms dw = (float)(lr_t * weight_decay) in double -- lr_t the rate of THIS step,
+// the scheduled one under SCHED, which under a captured graph exists nowhere but here -- and shares it beside step_size.  The clip
+// factor scales the raw gradient only; a step skipped as non-finite decays nothing (the update does not run); the average takes the
+// final parameter.
+template <bool CLIP, bool EMA, bool SCHED, bool DECAY>
 __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
-  // [0..2] the new state; CLIP: [3] norm, [4] c before the clamp, [5..8] the waves' sums; SCHED: the rate in one more word
-  constexpr int NORM = 3, C = 4, WAVES = 5, RATE = CLIP ? 9 : 3;
-  __shared__ double sh[3 + SCHED + (CLIP ? 6 : 0)];
+  // [0..2] the new state; CLIP: [3] norm, [4] c before the clamp, [5..8] the waves' sums; SCHED: the rate in one more word; DECAY: dw in one more
+  constexpr int NORM = 3, C = 4, WAVES = 5, RATE = CLIP ? 9 : 3, DW = RATE + SCHED;
+  __shared__ double sh[3 + SCHED + (CLIP ? 6 : 0) + DECAY];
   if constexpr (CLIP) {
     double acc = 0.0;
     for (int j = threadIdx.x; j < a.npart; j += 256) acc += a.part[j];
@@ -174,6 +206,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
     sh[0] = t;
     sh[1] = lr / (1.0 - pow(a.beta1, t));
     sh[2] = sqrt(1.0 - pow(a.beta2d, t));
+    if constexpr (DECAY) sh[DW] = (double)(float)(lr * a.wdd);
     if constexpr (CLIP) {
       const double norm = sqrt(((sh[WAVES] + sh[WAVES + 1]) + sh[WAVES + 2]) + sh[WAVES + 3]);
       sh[NORM] = norm;
@@ -189,7 +222,9 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamArgs a) {
     finite = norm < (double)INFINITY;      // (false for NaN as well)
     cf = (float)(sh[C] > 1.0 ? 1.0 : sh[C]);
   }
-  if (finite) adam_update<CLIP, EMA>(a, cf, (float)sh[1], (float)sh[2]);
+  float dw = 0.f;
+  if constexpr (DECAY) dw = (float)sh[DW];
+  if (finite) adam_update<CLIP, EMA, DECAY>(a, cf, (float)sh[1], (float)sh[2], dw);
   if (threadIdx.x == 0) {
     if (atomicAdd(a.ticket, 1) == (int)gridDim.x - 1) {
       if constexpr (CLIP) {
@@ -278,7 +313,7 @@ static inline void adam_clip_args(AdamArgs* a, const double* part, int npart, do
 // The one launcher: every form's checks stand here once (what only mmego_adam_step_sched's convention adds -- absent options spelled as
 // NULL / 0 -- it checks itself), then the members that are derived from the host values beside `a`: n4, the skip ranges, omd, the schedule.
 static int adam_launch(void* stream, AdamArgs a, bool clip, bool ema, bool sched, long n, const long* skip, int nskip, double ema_decay,
-                       const MmegoLrSchedule* sc) {
+                       const MmegoLrSchedule* sc, bool decay = false) {
   MMEGO_REQUIRE(a.p && a.g && a.m && a.v && a.state && a.ticket && n > 0 && (n % 4) == 0);
   MMEGO_REQUIRE(adam_skip_ranges(&a.skip, skip, nskip, n));
   MMEGO_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0);
@@ -297,11 +332,13 @@ static int adam_launch(void* stream, AdamArgs a, bool clip, bool ema, bool sched
     a.sched = *sc;
   }
   a.n4 = n / 4;
-  static void (*const form[8])(AdamArgs) = {                                    // [CLIP * 4 + EMA * 2 + SCHED]
-      adam_step_kernel<false, false, false>, adam_step_kernel<false, false, true>, adam_step_kernel<false, true, false>,
-      adam_step_kernel<false, true, true>,   adam_step_kernel<true, false, false>, adam_step_kernel<true, false, true>,
-      adam_step_kernel<true, true, false>,   adam_step_kernel<true, true, true>};
-  hipLaunchKernelGGL(form[clip * 4 + ema * 2 + sched], dim3(ew_blocks(a.n4)), dim3(256), 0, (hipStream_t)stream, a);
+#define ADAM_FORMS(D)                                                                                                          \
+  adam_step_kernel<false, false, false, D>, adam_step_kernel<false, false, true, D>, adam_step_kernel<false, true, false, D>,  \
+      adam_step_kernel<false, true, true, D>, adam_step_kernel<true, false, false, D>, adam_step_kernel<true, false, true, D>, \
+      adam_step_kernel<true, true, false, D>, adam_step_kernel<true, true, true, D>
+  static void (*const form[16])(AdamArgs) = {ADAM_FORMS(false), ADAM_FORMS(true)};      // [DECAY * 8 + CLIP * 4 + EMA * 2 + SCHED]
+#undef ADAM_FORMS
+  hipLaunchKernelGGL(form[decay * 8 + clip * 4 + ema * 2 + sched], dim3(ew_blocks(a.n4)), dim3(256), 0, (hipStream_t)stream, a);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -350,4 +387,23 @@ extern "C" int mmego_adam_step_sched(void* stream, float* p, const float* g, flo
   adam_clip_args(&a, part, npart, max_norm, stats);
   a.ema = ema;
   return adam_launch(stream, a, part != NULL, ema != NULL, true, n, skip, nskip, ema_decay, sched);
+}
+
+// Every option in one entry point: mmego_adam_step_sched's arguments and conventions, sched == NULL the unscheduled step (three state
+// words), then the decay mask (NULL: every element decays) and the decoupled flag.
+extern "C" int mmego_adam_step_decay(void* stream, float* p, const float* g, float* m, float* v, long n, double* state, double lr,
+                                     double beta1, double beta2, double eps, double weight_decay, const long* skip, int nskip,
+                                     int* ticket, const double* part, int npart, double max_norm, double* stats, float* ema,
+                                     double ema_decay, const MmegoLrSchedule* sched, const unsigned long long* decay_mask,
+                                     int decoupled) {
+  if (!part) MMEGO_REQUIRE(npart == 0 && !stats);
+  if (!ema) MMEGO_REQUIRE(ema_decay == 0.0);
+  MMEGO_REQUIRE(((uintptr_t)decay_mask & 7) == 0);
+  MMEGO_REQUIRE(weight_decay >= 0.0 && weight_decay < (double)INFINITY);      // (NaN fails the first comparison)
+  MMEGO_REQUIRE(decoupled == 0 || decoupled == 1);
+  AdamArgs a = adam_args(p, g, m, v, state, lr, beta1, beta2, eps, weight_decay, ticket);
+  adam_clip_args(&a, part, npart, max_norm, stats);
+  a.ema = ema;
+  a.mask = decay_mask; a.decoupled = decoupled; a.wdd = weight_decay;
+  return adam_launch(stream, a, part != NULL, ema != NULL, sched != NULL, n, skip, nskip, ema_decay, sched, true);
 }

@@ -209,8 +209,64 @@ def lr_schedule_of(cfg, epochs, steps_per_epoch):
     return LrSchedule(kind, warmup=warmup, floor=getattr(cfg, "lr_min_ratio", None) or 0.0, **kw)
 
 
+def decay_mask_words(layout, no_decay=()):
+    """The decay mask of a flat buffer (mmego_adam_step_decay's ``decay_mask``) as a numpy uint64 array, on the host: one bit per float4,
+    word w bit b covering float4 64 w + b, set where the element decays.  ``layout``: (name, offset, numel) triples in buffer order, as
+    FusedAdam.layout() gives them -- every tensor starts on a float4 boundary (ALIGN) and owns its padding, so a float4 belongs to one
+    tensor; ``no_decay``: the names whose tensors do not decay.  A name that is not in the layout is a ValueError.  ceil(n4 / 64) words;
+    the bits beyond n4 in the last one are clear."""
+    import numpy as np
+    layout = [(str(n), int(o), int(k)) for n, o, k in layout]
+    unknown = sorted(set(no_decay) - {n for n, _, _ in layout})
+    if unknown:
+        raise ValueError("no_decay names parameters this net does not have: %s" % ", ".join(unknown))
+    spans = [(n, o, o + (k + ALIGN - 1) // ALIGN * ALIGN) for n, o, k in layout]
+    if any(o % ALIGN for _, o, _ in spans):
+        raise ValueError("decay_mask_words: every tensor has to start on a multiple of %d floats" % ALIGN)
+    n4 = max([hi for _, _, hi in spans] + [0]) // ALIGN
+    bits = np.ones(n4, dtype=np.uint8)
+    skip = set(no_decay)
+    for n, lo, hi in spans:
+        if n in skip:
+            bits[lo // ALIGN:hi // ALIGN] = 0
+    padded = np.zeros((n4 + 63) // 64 * 64, dtype=np.uint8)
+    padded[:n4] = bits
+    return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
+
+
+def resolve_no_decay(module, no_decay):
+    """FusedAdam's ``no_decay`` as a sorted tuple of parameter names: None -> (), "1d" -> every parameter with at most one dimension (biases,
+    BatchNorm weight and bias, LSTM biases), an iterable of names -> those; a name the module does not have is a ValueError."""
+    if no_decay is None:
+        return ()
+    named = list(module.named_parameters())
+    if isinstance(no_decay, str):
+        if no_decay != "1d":
+            raise ValueError("no_decay has to be None, \"1d\" or an iterable of parameter names, got %r" % (no_decay,))
+        return tuple(sorted(n for n, p in named if p.dim() <= 1))
+    names = sorted({str(n) for n in no_decay})
+    unknown = sorted(set(names) - {n for n, _ in named})
+    if unknown:
+        raise ValueError("no_decay names parameters this net does not have: %s" % ", ".join(unknown))
+    return tuple(names)
+
+
+def describe_decay(decoupled, no_decay):
+    """`adamw|l2, all tensors decay | N tensors left out` (both sides of a refusal's message)."""
+    return "%s, %s" % ("adamw (decoupled)" if decoupled else "l2 (coupled)",
+                       "every tensor decays" if not no_decay else "no decay for %d tensors (%s%s)" % (
+                           len(no_decay), ", ".join(no_decay[:3]), ", ..." if len(no_decay) > 3 else ""))
+
+
 class FusedAdam:
     """torch.optim.Adam semantics (betas 0.9/0.999, eps 1e-8, coupled weight decay) in one launch.
+
+    decoupled (False: the coupled L2 form above): torch.optim.AdamW's decay, p <- p - lr_t * weight_decay * p ahead of an update whose
+    gradient carries no decay term, lr_t the rate of the step (the scheduled one under lr_schedule: the decay follows the schedule).
+    no_decay (None: every tensor decays; "1d": every parameter with at most one dimension -- biases, BatchNorm weight and bias, LSTM
+    biases; or an iterable of parameter names): tensors that are updated as with weight_decay = 0, in either form.  Both go through
+    mmego_adam_step_decay (a bit mask over the flat buffer, built once on the host: decay_mask_words); an optimiser with neither makes
+    exactly the calls below.  A state_dict carries them only where they are not the defaults.
 
     max_grad_norm (None: off): torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) ahead of every step, over THIS net's
     gradients, as two launches and no host read (mmego_grad_sqnorm, mmego_adam_step_clipped).  A step whose gradient norm is not
@@ -233,7 +289,7 @@ class FusedAdam:
     STAT_KEYS = ("last", "sum", "max", "steps", "clipped", "skipped")
 
     def __init__(self, flat, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
-                 lr_schedule=None):
+                 lr_schedule=None, decoupled=False, no_decay=None):
         if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
             raise ValueError("lr_schedule has to be a params.LrSchedule (or None: a constant rate), got %r" % (lr_schedule,))
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
@@ -251,6 +307,11 @@ class FusedAdam:
         self._averaged = False            # inside averaged(): flat_p holds the average, ema the weights
         self.lr_schedule = lr_schedule
         self._sched = None if lr_schedule is None else lr_schedule.c_struct()      # (kept alive: a recorded launch holds the object)
+        if decoupled not in (False, True, 0, 1):
+            raise ValueError("decoupled has to be True (AdamW's decay) or False (the coupled L2 form), got %r" % (decoupled,))
+        self.decoupled = bool(decoupled)
+        self.no_decay = resolve_no_decay(flat.module, no_decay)      # (sorted names; (): every tensor decays)
+        self._mask = None
 
     def _skip_ranges(self, f):
         """Element ranges of parameters that never receive a gradient (`module.never_trained()`, e.g. IMU_Net.fc3):
@@ -279,6 +340,11 @@ class FusedAdam:
             self._ticket = torch.zeros(1, dtype=torch.int32, device=f.device)
             self._part = self._stats = None
             self.ema = None
+            self._mask = None
+        if self.no_decay and self._mask is None:
+            # (one bit per float4, clear over the tensors that do not decay; built before the first step, so before anything captures its address)
+            words = decay_mask_words(self._layout_of(f), self.no_decay)
+            self._mask = torch.from_numpy(words.view("int64")).to(f.device)
         if self.ema_decay is not None and self.ema is None:
             # (ema_0 = the weights as they are now; built before the first step, so before anything captures its address)
             self.ema = f.flat_p.clone()
@@ -302,7 +368,11 @@ class FusedAdam:
             clip = (self._part, self._part.numel(), self.max_grad_norm, self._stats)
         if self.ema_decay is not None:
             avg = (self.ema, self.ema_decay)
-        if self.lr_schedule is not None:
+        if self.decoupled or self._mask is not None:
+            # (every option in one entry point; a NULL schedule is the unscheduled step, a NULL mask decays everything)
+            hip.call("adam_step_decay", *common, *(clip or (None, 0, 0.0, None)), *(avg or (None, 0.0)), self._sched, self._mask,
+                     int(self.decoupled))
+        elif self.lr_schedule is not None:
             # (one entry point for the four forms: absent record buffers select the plain step, an absent average the step without one)
             hip.call("adam_step_sched", *common, *(clip or (None, 0, 0.0, None)), *(avg or (None, 0.0)), self._sched)
         else:
@@ -387,9 +457,19 @@ class FusedAdam:
     def layout(self):
         """The fingerprint of the flat layout: (parameter name, offset, numel) in buffer order.  The order inside the flat buffers
         is the net's own business (`flat_param_order`) and has changed between rounds, so a saved optimizer state carries it."""
-        f = self._ensure()
+        return self._layout_of(self._ensure())
+
+    @staticmethod
+    def _layout_of(f):
         names = {id(p): n for n, p in f.module.named_parameters()}
         return [(names[id(p)], int(off), int(p.numel())) for p, off in zip(f.params, f.offsets)]
+
+    def decay_counts(self):
+        """(tensors, elements) that weight decay reaches: everything but the no_decay tensors and those that never train."""
+        f = self._ensure()
+        dead = {id(p) for p in getattr(f.module, "never_trained", lambda: ())()}
+        left = [p for n, p in f.module.named_parameters() if n not in set(self.no_decay) and id(p) not in dead]
+        return len(left), sum(p.numel() for p in left)
 
     def state_dict(self):
         """Moments and step counters (host copies) + hyper-parameters + the layout the moments are stored in: everything a
@@ -403,6 +483,10 @@ class FusedAdam:
             sd["ema"], sd["ema_decay"] = self.ema.cpu(), self.ema_decay
         if self.lr_schedule is not None:
             sd["lr_schedule"] = self.lr_schedule.to_dict()
+        if self.decoupled:                 # (likewise: only what is not the default)
+            sd["decoupled"] = True
+        if self.no_decay:
+            sd["no_decay"] = list(self.no_decay)
         return sd
 
     def load_state_dict(self, sd):
@@ -419,6 +503,10 @@ class FusedAdam:
                                  "build it with the saved one" % (theirs, self.lr_schedule))
         elif sd["state"].numel() != 3:
             raise ValueError("optimizer state has %d state words and names no learning-rate schedule" % sd["state"].numel())
+        theirs = (bool(sd.get("decoupled", False)), tuple(sorted(str(n) for n in (sd.get("no_decay") or ()))))
+        if (self.decoupled, self.no_decay) not in ((False, ()), theirs):
+            raise ValueError("optimizer state was saved under the weight decay [%s], this optimiser was built with [%s]: build it with "
+                             "the saved one, or with neither option" % (describe_decay(*theirs), describe_decay(self.decoupled, self.no_decay)))
         f = self._ensure()
         cur = self.layout()
         saved = sd.get("layout")
@@ -453,6 +541,10 @@ class FusedAdam:
                     so = where[n]
                     new[o:o + k] = sd[key][so:so + k]
                 dst.copy_(new)
+        if (self.decoupled, self.no_decay) != theirs:      # (as lr and ema_decay: the saved values win; a state without the keys is coupled, all-decay)
+            self.decoupled, self.no_decay = theirs[0], resolve_no_decay(f.module, theirs[1])
+            self._mask = None
+            self._ensure()
         if self.ema_decay is not None and sd.get("ema_decay") is None:
             self.ema.copy_(f.flat_p)
             print("[mmego_amd] optimizer state carries no weight average: the average (decay %g) restarts from the loaded weights" % self.ema_decay)

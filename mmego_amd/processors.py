@@ -20,7 +20,7 @@ from . import blocks, hip, ops, skeleton
 from .config import IMU_NOISE_FLAGS, Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, _mix64, batch_indices
 from .nets import IMUNet, LowerNet, UpperNet
-from .params import FusedAdam, LrSchedule, lr_schedule_of
+from .params import FusedAdam, LrSchedule, describe_decay, lr_schedule_of, resolve_no_decay
 from .nets_local import UpperNetwlocal
 from .train_step import TRAINED, ImuStep, PipelinedStages, StageStep, broadcast_flag, call_upper, empty_step, shard_of, sync_replicas
 from .utils import EarlyStopping
@@ -317,16 +317,54 @@ class _Base:
                     self.evalfile.write(line + "\n")
                     self.evalfile.flush()
 
+    def _decay_options(self):
+        """--weight_decay / --decay_mode / --no_decay_1d as (W or None: the reference's decays, FusedAdam's decoupled, its no_decay)."""
+        w = getattr(self.cfg, "weight_decay", None)
+        if w is None:
+            return None, False, None
+        return float(w), getattr(self.cfg, "decay_mode", None) == "adamw", "1d" if getattr(self.cfg, "no_decay_1d", False) else None
+
+    def _say_decay(self):
+        """Under the decay options (or a resumed state that carries them): one line per trained net, once, when its optimisers exist."""
+        opts = [(o, self._opts[o]) for o, _ in TRAINED if o in self._opts]
+        if getattr(self, "_decay_said", False) or not opts:
+            return
+        self._decay_said = True
+        if self._decay_options()[0] is None and not any(opt.decoupled or opt.no_decay for _, opt in opts):
+            return
+        names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
+        for o, opt in opts:
+            if self.rank == 0:
+                tensors, elements = opt.decay_counts()
+                print("[mmego_amd] weight decay (%s): %s, W %g; %d of %d tensors and %d of %d elements decay"
+                      % (names[o], "adamw" if opt.decoupled else "l2", opt.weight_decay, tensors, len(opt.flat.params), elements,
+                         sum(p.numel() for p in opt.flat.params)))
+
     def _main_opt(self, model):
         """The optimiser of the trainer's own net: built ONCE -- by the first step or the first empty-shard step, whichever comes -- and
         that is where a --resume state is loaded."""
         if "opt" not in self._opts:
-            self._opts["opt"] = FusedAdam(model.flat(), lr=self.learning_rate, weight_decay=self.weight_decay,
-                                          max_grad_norm=getattr(self.cfg, "clip_grad_norm", None), ema_decay=getattr(self.cfg, "ema_decay", None),
-                                          lr_schedule=self._lr_schedule())
+            w, decoupled, no_decay = self._decay_options()
+            opt = self._opts["opt"] = FusedAdam(model.flat(), lr=self.learning_rate, weight_decay=self.weight_decay if w is None else w,
+                                                max_grad_norm=getattr(self.cfg, "clip_grad_norm", None), ema_decay=getattr(self.cfg, "ema_decay", None),
+                                                lr_schedule=self._lr_schedule(), decoupled=decoupled, no_decay=no_decay)
             if self._resume is not None:
-                self._opts["opt"].load_state_dict(self._resume["optimizer"])
+                self._check_resumed_decay(model)
+                opt.load_state_dict(self._resume["optimizer"])
         return self._opts["opt"]
+
+    def _check_resumed_decay(self, model):
+        """--resume: the saved decay is continued without the flags, as lr and ema_decay are; flags that name another one end the run."""
+        w, decoupled, no_decay = self._decay_options()
+        if w is None or self._resume is None:
+            return
+        sd = self._resume["optimizer"]
+        saved = (float(sd["weight_decay"]), bool(sd.get("decoupled", False)), tuple(sorted(sd.get("no_decay") or ())))
+        named = (w, decoupled, resolve_no_decay(model, no_decay))
+        if saved != named:
+            raise SystemExit("--resume: the training state was saved under the weight decay [W %g, %s], and the --weight_decay / --decay_mode "
+                             "/ --no_decay_1d options name [W %g, %s]: leave them out (the saved setting is continued) or start a new run"
+                             % (saved[0], describe_decay(*saved[1:]), named[0], describe_decay(*named[1:])))
 
     def save_beside(self, epoch, folder, net, state_dict=None):
         """A second trained net beside the stage's checkpoint, same file name, in a folder of its own (--finetune_imu: IMU_Net,
@@ -373,6 +411,7 @@ class _Base:
         if decay is not None and self.rank == 0:
             print("[mmego_amd] weight averaging: decay %g; evaluation and early stopping use the averaged weights" % decay)
         self._lr_schedule()                                        # (the start line, and a refusal, ahead of the first epoch)
+        self._check_resumed_decay(model)                           # (likewise a refusal)
         out = None
         names = {"opt": self.net_name, "imu_opt": "IMU_Net", "upper_opt": "Upper_Net"}
         for epoch in range(self.start_epoch, self.num_epochs):
@@ -499,6 +538,8 @@ class _StageTrainer(_Base):
             pipelined = pipelined and self.imu_noise is None
             imu_lr = getattr(self.cfg, "imu_lr", None)
             self._main_opt(self.model)
+            w, decoupled, no_decay = self._decay_options()
+            decay = {} if w is None else dict(weight_decay=w, imu_weight_decay=w, decoupled=decoupled, no_decay=no_decay)
             # (one optimiser state per trained net for all batch sizes: the step takes what the dict holds and adds what it builds)
             st = StageStep(self.stage, self.model, None if pipelined else self.model_IMU,
                            upper_frozen=getattr(self, "Upper_net", None), lr=self.learning_rate, process_group=pg,
@@ -508,7 +549,8 @@ class _StageTrainer(_Base):
                            clip_grad_norm=getattr(self.cfg, "clip_grad_norm", None), optimisers=self._opts,
                            ema_decay=getattr(self.cfg, "ema_decay", None), lr_schedule=self._lr_schedule(),
                            **({} if self.pose_noise is None else dict(pose_noise_deg=self.pose_noise[0], pose_noise_t=self.pose_noise[1])),
-                           **({} if self.imu_noise is None else dict(imu_noise=self.imu_noise[0])))
+                           **({} if self.imu_noise is None else dict(imu_noise=self.imu_noise[0])), **decay)
+            self._say_decay()
             st.engine = None
             if pipelined:
                 st.imu_next = torch.empty((B, self.frame_no) + tuple(self._train_dev.shape["imu"][1:]), dtype=torch.float32,
@@ -1132,6 +1174,7 @@ class ImuTrainer(_Base):
             if st is None:                                              # one graph per minibatch size, one optimiser
                 st = self._steps[B] = ImuStep(self.model_IMU, process_group=pg, use_graph=True, opt=self._main_opt(self.model_IMU),
                                               **({} if self.imu_noise is None else dict(imu_noise=self.imu_noise[0])))
+                self._say_decay()
             if st.static is None or st.static["imu"].data_ptr() != b["imu"].data_ptr():
                 st.bind(b["imu"], b["R_R0R"], b["target"])
             if self.imu_noise is not None:                              # this minibatch's draws (the word the captured launch reads)

@@ -325,12 +325,16 @@ class StageStep(_Engine):
     gradient flows as it did: the perturbation sits in front of the net's input, which is data.  A stage with no IMU_Net of its own --
     the recorded pose, or a ``pose`` shared or prefetched by somebody else (SharedImuStages, PipelinedStages) -- has nothing to perturb
     and refuses the option, at construction or when such a ``pose`` is assigned.  With None the step launches what it launched before
-    and owns no extra buffer."""
+    and owns no extra buffer.
+
+    ``decoupled`` / ``no_decay`` (False / None: the coupled decay over every tensor): FusedAdam's options of those names, handed to every
+    optimiser this step builds -- ``no_decay`` is "1d" or names; a list of names has to fit every trained net, so several nets take "1d".
+    The decay of each net stays ``weight_decay`` / ``imu_weight_decay``.  With the defaults every optimiser makes the calls it made."""
 
     def __init__(self, stage, net, imu_net, upper_frozen=None, lr=3e-5, weight_decay=0.0, process_group=None,
                  use_graph=True, pose=None, finetune_imu=False, imu_lr=None, imu_weight_decay=0.001, finetune_upper=False, upper_lr=None,
                  clip_grad_norm=None, optimisers=None, ema_decay=None, pose_noise_deg=None, pose_noise_t=None,
-                 lr_schedule=None, imu_noise=None):
+                 lr_schedule=None, imu_noise=None, decoupled=False, no_decay=None):
         assert stage in ("upper", "lower")
         if imu_noise is not None and (imu_net is None or pose is not None):
             raise ValueError("StageStep: imu_noise perturbs what the stage's own IMU_Net reads; this stage has none (the recorded or a "
@@ -354,7 +358,7 @@ class StageStep(_Engine):
         def opt_for(key, trained, lr, weight_decay):
             if opts.get(key) is None:
                 opts[key] = FusedAdam(trained.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema_decay=ema_decay,
-                                      lr_schedule=lr_schedule)
+                                      lr_schedule=lr_schedule, decoupled=decoupled, no_decay=no_decay)
             return opts[key]
         self.imu_opt = self.upper_opt = None
         if self.finetune_upper:
@@ -542,12 +546,12 @@ class ImuStep(_Engine):
     ``set_imu_key(k)`` writes between steps.  With None the step launches what it launched before and owns no extra buffer."""
 
     def __init__(self, net, lr=1e-4, weight_decay=0.001, process_group=None, use_graph=True, clip_grad_norm=None, opt=None, ema_decay=None,
-                 lr_schedule=None, imu_noise=None):
+                 lr_schedule=None, imu_noise=None, decoupled=False, no_decay=None):
         self.net = net
-        # (clip_grad_norm, ema_decay, lr_schedule: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=..., lr_schedule=...);
-        #  one handed in is used as it is)
+        # (clip_grad_norm, ema_decay, lr_schedule, decoupled, no_decay: of the optimiser built here -- FusedAdam(max_grad_norm=..., ema_decay=...,
+        #  lr_schedule=..., decoupled=..., no_decay=...); one handed in is used as it is)
         self.opt = opt if opt is not None else FusedAdam(net.flat(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
-                                                         ema_decay=ema_decay, lr_schedule=lr_schedule)
+                                                         ema_decay=ema_decay, lr_schedule=lr_schedule, decoupled=decoupled, no_decay=no_decay)
         self.pg = process_group
         self.use_graph = use_graph
         self.graph = None
