@@ -246,6 +246,40 @@ int mmego_blend_bones(void* stream, const float* src, long nrows, int J, const l
  * Refused: null pointers, n < 1 or >= 2^26, J outside [1, 21], NB outside [1, J - 1], ldx < 3 J, ldo < NB. */
 int mmego_bone_length_dev(void* stream, const float* X, long ldx, long n, int J, const int* bones, const float* bone_len, int NB,
                           float* out, long ldo);
+/* Dense inference's temporal smoothing (smooth.hip; processors.dense_infer with smooth=(H, order, taper)): a zero-phase local-polynomial
+ * filter along the frames.  src [F][C] (row stride lds), seg [F] (int32) the segment of every frame (-1: none), w [2 H + 1] (float,
+ * positive and finite; the host makes the taper, ops.smooth_frames checks it) the weights of the taps k = -H .. H.  Per frame f:
+ *   tap k is VALID when 0 <= f + k < F and seg[f + k] == seg[f] >= 0; n of them;
+ *   n <= 1 (seg[f] < 0, or f alone in its segment): dst[f, :C] = src[f, :C] bit for bit, moved[f] = 0;   otherwise
+ *   deg = min(D, n - 1);  S_m = sum over the valid taps of w_k k^m, m = 0 .. 2 deg, in double;
+ *   A = the first row of the inverse of the moment matrix [S_{i+j}] (i, j <= deg), in closed form by cofactors;
+ *   c_k = w_k (A . [1, k, k^2][:deg + 1])   -- the weights with which the weighted least-squares polynomial of degree deg through the
+ *         valid taps is evaluated at k = 0; sum_k c_k = 1;
+ *   dst[f, c] = (float) sum_k c_k src[f + k, c], c < C, in double over the valid taps in ascending k; the columns of dst[f] (row
+ *         stride ldd) beyond C are not touched;
+ *   moved[f] (may be NULL; needs C % 3 == 0, J = C / 3) = sqrt(sum_j |y_j - x_j|^2 / J), y the filtered row as doubles, before its
+ *         rounding, x = src[f]: the RMS distance over the joints that the filter moved the frame.
+ * No atomics, sums in a fixed order: two launches give the same bits.  One wave per frame; lane = tap for the coefficients (2 H + 1 <=
+ * 63), lane = column for the sums (C <= 64).  Refused: a null src, seg, w or dst, F < 1 or >= 2^31, C outside [1, 64], lds or ldd < C, H
+ * outside [1, 31], D outside [0, 2], moved with C % 3 != 0, dst rows that overlap the src rows (the filter cannot run in place). */
+int mmego_smooth_frames(void* stream, const float* src, long lds, long F, int C, const int* seg, const float* w, int H, int D,
+                        float* dst, long ldd, float* moved);
+/* The same filter with every bone's length kept (processors.dense_infer under blend_space="bones"): src [F][3 J] holds skeletons of J
+ * joints, bones [NB][2] and bone_len [NB] are mmego_blend_bones' walk table and lengths.  Per frame, with n, deg and c_k as above:
+ *   n <= 1: the row bit for bit, moved 0, fallback 0;   otherwise
+ *   a root r:            pos_r = sum_k c_k x_kr, mmego_smooth_frames' own arithmetic: those columns carry the same bits;
+ *   bone b = (c, p):     s = sum_k c_k (x_kc - x_kp), every difference formed in double, ascending k;
+ *                        u = s / |s| where |s| > 1e-9 L_b, else -- the FALLBACK, counted in fallback[f]; c_k can be negative for deg 2,
+ *                        so the sum can cancel -- the normalised bone x_c - x_p of frame f itself (tap 0), or the zero vector where
+ *                        that is zero too;   pos_c = pos_p + L_b u, the bones taken in their listed order;
+ *   dst[f, 3 j + i] = (float) pos_j[i];   moved[f] (may be NULL) as above against pos;   fallback[f] (int32, may be NULL) = the number
+ *   of bones of the frame that took the fallback.
+ * Every filtered bone has length L_b up to the rounding of its two endpoints.  One wave per frame; lane = tap, then lane = joint, the
+ * parent's position handed over by wave shuffles.  Refused: a null src, seg, w or dst, F < 1 or >= 2^31, J outside [1, 21], lds or ldd <
+ * 3 J, H outside [1, 31], D outside [0, 2], NB outside [0, J - 1], null bones or bone_len with NB > 0, dst rows that overlap the src rows.
+ * The caller answers for the bone list (ops.smooth_bones checks it on the host); a bone that names a joint outside [0, J) is left out. */
+int mmego_smooth_bones(void* stream, const float* src, long lds, long F, int J, const int* seg, const float* w, int H, int D,
+                       const int* bones, const float* bone_len, int NB, float* dst, long ldd, float* moved, int* fallback);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

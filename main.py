@@ -4,6 +4,7 @@
   python main.py --train --network {IMU_Net,Upper_Net,Lower_Net} [--epochs N --lr F --batch_size N --device cuda:0
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
   python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones} --save_pred PATH]]
+  python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -31,7 +32,10 @@ run is trained on, from the frame-major device store data.FrameStore; evaluation
 {mean,triangle} --blend_space {joints,bones} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
 apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
 by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons; --blend_space bones
-blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again), --pose_noise_deg D /
+blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again; --smooth H [--smooth_order D
+--smooth_taper {box,gauss}] then filters every recording's stitched frames along time on the device, a zero-phase local polynomial of
+degree D over +-H frames -- of bone directions under --blend_space bones -- and prints the blended frames' figures and the mean
+displacement beside the smoothed ones'), --pose_noise_deg D /
 --pose_noise_t S (the head pose Upper_Net and Lower_Net get -- the recording's under --gt_head_pose, else the frozen IMU_Net's -- is
 perturbed per frame on the device: a random rotation whose rotation vector has standard deviation D degrees per axis, never beyond 6 D in
 all, and a random shift of standard deviation S metres per component, never beyond 3.47 S.  With --train --network Upper_Net / Lower_Net
@@ -201,13 +205,30 @@ def build_parser():
     p.add_argument("--save_pred", type=str,
                    help="--dense: write the per-frame arrays to this .npz -- pred [F, 21, 3] (NaN where no window covers the frame: "
                         "recordings shorter than frame_no), covered, spread, recording, frame_in_recording, target, stride, blend, frame_no")
+    p.add_argument("--smooth", type=int, metavar="H",
+                   help="--dense: smooth every recording's stitched poses along time on the device, after the blend -- a zero-phase "
+                        "local-polynomial filter over the frames f-H .. f+H of the same recording, H in [1, 31] (off by default).  Under "
+                        "--blend_space bones the bone directions are filtered and the frames stay rigid.  The figures above are then the "
+                        "smoothed frames'; three more lines give the blended frames' error, the mean displacement and (--metrics full) the "
+                        "unsmoothed acceleration error, and --save_pred's file gains pred_unsmoothed, moved, smooth_window, smooth_order, "
+                        "smooth_taper")
+    p.add_argument("--smooth_order", type=int, choices=[0, 1, 2], default=None,
+                   help="--smooth: degree of the local polynomial (default 2; 0 is a weighted moving average)")
+    p.add_argument("--smooth_taper", type=str, choices=["box", "gauss"], default=None,
+                   help="--smooth: weights of the frames of the window -- box (ones) or gauss (default: exp(-2 k^2 / H^2), sigma H / 2)")
     return p
 
 
 def check_dense(parser, args):
-    """--dense is a mode of --infer; --stride, --blend, --blend_space and --save_pred belong to it."""
+    """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred and the --smooth flags belong to it."""
+    for flag in ("smooth_order", "smooth_taper"):
+        if getattr(args, flag) is not None and args.smooth is None and args.dense:
+            parser.error("--%s belongs to --smooth H: without --smooth nothing is filtered" % flag)
+    if args.smooth is not None and not 1 <= args.smooth <= 31:
+        parser.error("--smooth is the filter's half-width in frames: it has to lie in [1, 31] (2 H + 1 taps fit one wave), got %d"
+                     % args.smooth)
     if not args.dense:
-        for flag in ("stride", "blend", "blend_space", "save_pred"):
+        for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper"):
             if getattr(args, flag) is not None:
                 parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % flag)
         return
@@ -494,6 +515,8 @@ def apply_overrides(args):
         c.metrics = args.metrics
     ConfigDemo.dense, ConfigDemo.stride, ConfigDemo.blend = bool(args.dense), args.stride, args.blend or "mean"
     ConfigDemo.save_pred, ConfigDemo.dense_batch_size, ConfigDemo.blend_space = args.save_pred, args.batch_size, args.blend_space
+    ConfigDemo.smooth = None if args.smooth is None else (args.smooth, 2 if args.smooth_order is None else args.smooth_order,
+                                                          args.smooth_taper or "gauss")
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

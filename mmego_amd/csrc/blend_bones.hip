@@ -11,12 +11,6 @@
 
 #define BB_WAVES 4                       // one wave per output frame, four per workgroup (no barrier: a wave behind F leaves)
 
-// lane `from`'s double for every lane: the two halves of the double, one 32-bit wave shuffle each
-__device__ __forceinline__ double shfl_d(double v, int from) {
-  const int lo = __shfl(__double2loint(v), from, 64), hi = __shfl(__double2hiint(v), from, 64);
-  return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(64 * BB_WAVES) void blend_bones_kernel(const float* __restrict__ src, long nrows, int J,
                                                                    const long long* __restrict__ cov_off,
                                                                    const int* __restrict__ cov_row, const float* __restrict__ cov_w,

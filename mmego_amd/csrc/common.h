@@ -43,6 +43,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// lane `from`'s double for every lane: the two halves of the double, one 32-bit wave shuffle each (blend_bones.hip, smooth.hip)
+__device__ __forceinline__ double shfl_d(double v, int from) {
+  const int lo = __shfl(__double2loint(v), from, 64), hi = __shfl(__double2hiint(v), from, 64);
+  return __hiloint2double(hi, lo);
+}
 
 // Counter-based dropout RNG: element i of a call keeps its value when a 24-bit hash of (i, call key) is >= p.  The call key
 // mixes the device-side seed counter (advanced once per training forward by mmego_inc_i64) with a per-call-site salt.

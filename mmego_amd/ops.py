@@ -572,6 +572,84 @@ def bone_length_dev(X, bones, bone_len, out):
     return out
 
 
+SMOOTH_MAX_H = 31           # smooth.hip SM_MAX_H: one lane per tap, 2 H + 1 <= 63
+
+_smooth_w_dev = {}
+
+
+def _smooth_on(src, seg, weights, order, dst, moved, C_max, who):
+    """What the two smoothing launches share, checked on the HOST: src [F, C] and dst [F, >= C] row tensors that share no byte, the
+    weight table (host floats: odd length 2 H + 1 with H in [1, 31], every weight finite and > 0; uploaded once per table and device),
+    order in {0, 1, 2}, seg (an int32 host array or device tensor of length F; a host array is uploaded), moved (optional): one
+    contiguous float per frame, of rows of 3-vectors.  -> (seg, w, H, order, F, C, lds, ldd)."""
+    import numpy as np
+    src, dst = _rows(src), _rows(dst)
+    F, C = src.shape
+    if F < 1 or not 1 <= C <= C_max or (F > 1 and src.stride(0) < C):
+        raise ValueError("%s needs a source of at least one row of 1 to %d columns, got %s" % (who, C_max, tuple(src.shape)))
+    if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
+        raise ValueError("%s: dst is %s for %d frames of %d columns" % (who, tuple(dst.shape), F, C))
+    lds, ldd = max(src.stride(0), C), max(dst.stride(0), C)
+    s0, d0 = src.data_ptr(), dst.data_ptr()
+    if s0 < d0 + 4 * ((F - 1) * ldd + C) and d0 < s0 + 4 * ((F - 1) * lds + C):
+        raise ValueError("%s: dst overlaps src; the filter reads the rows around the one it writes and cannot run in place" % who)
+    wt = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights)
+    if wt.ndim != 1 or wt.dtype.kind != "f" or len(wt) % 2 == 0 or not 1 <= len(wt) // 2 <= SMOOTH_MAX_H:
+        raise ValueError("%s: the weights are a table of 2 H + 1 floats with H in [1, %d], got %s" % (who, SMOOTH_MAX_H, wt.shape))
+    wt = np.ascontiguousarray(wt, dtype=np.float32)
+    if not (np.isfinite(wt).all() and (wt > 0).all()):
+        raise ValueError("%s: every weight has to be finite and > 0" % who)
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
+        raise ValueError("%s: order (the polynomial's degree) is 0, 1 or 2, got %r" % (who, order))
+    if isinstance(seg, np.ndarray):
+        if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) != F:
+            raise ValueError("%s: seg is one int32 per frame (%d), got %s %s" % (who, F, seg.dtype, seg.shape))
+        seg = torch.as_tensor(np.ascontiguousarray(seg)).to(src.device)
+    elif not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 1 and seg.numel() == F
+              and seg.is_contiguous()):
+        raise ValueError("%s: seg is one contiguous int32 per frame (%d), a host array or a device tensor" % (who, F))
+    if moved is not None:
+        _chk(moved, 1)
+        if moved.numel() != F or not moved.is_contiguous() or C % 3:
+            raise ValueError("%s: moved is one contiguous float per frame, of rows of 3-vectors" % who)
+    key = (wt.tobytes(), str(src.device))
+    wd = _smooth_w_dev.get(key)
+    if wd is None:
+        if len(_smooth_w_dev) >= 64:
+            _smooth_w_dev.clear()
+        wd = _smooth_w_dev[key] = torch.as_tensor(wt).to(src.device)
+    return seg, wd, len(wt) // 2, int(order), F, C, lds, ldd
+
+
+def smooth_frames(src, seg, weights, order, dst, moved=None):
+    """dst[f, :C] = the zero-phase local-polynomial filter of the rows of src [F, C <= 64] along the frames (mmego_smooth_frames; the
+    recipe is in the header): the weighted least-squares polynomial of degree min(order, valid taps - 1) through the rows f - H .. f + H
+    of frame f's own segment, evaluated at f.  ``seg`` [F] int32 names every frame's segment (-1: none; such a frame, and one alone in
+    its segment, keeps its row bit for bit); ``weights`` the 2 H + 1 tap weights (host floats, processors.smooth_weights); ``order`` 0, 1
+    or 2.  moved [F] (optional, C % 3 == 0): the RMS distance over the joints between the filtered and the source row.  Everything is
+    checked on the host first (ValueError); dst must not overlap src, and may be wider than C: its other columns stay."""
+    seg, w, H, order, F, C, lds, ldd = _smooth_on(src, seg, weights, order, dst, moved, BLEND_MAX_C, "smooth_frames")
+    hip.call("smooth_frames", src, lds, F, C, seg, w, H, order, dst, ldd, moved)
+    return dst
+
+
+def smooth_bones(src, seg, weights, order, walk, lengths, dst, moved=None, fallback=None):
+    """The same filter for rows of rigid skeletons, src [F, 3 J] with J <= 21 (mmego_smooth_bones): the roots filtered as smooth_frames
+    filters them, every bone's direction filtered, set to ``lengths`` and laid along ``walk`` ([NB, 2] host integers (child, parent),
+    parents first; checked as blend_bones checks them) -- the filtered frames are rigid skeletons again.  fallback [F] int32 (optional):
+    the bones per frame whose filtered direction cancelled and that kept the frame's own direction."""
+    if src.dim() == 2 and src.shape[1] % 3:
+        raise ValueError("smooth_bones needs rows of 3-vectors, got %s" % (tuple(src.shape),))
+    seg, w, H, order, F, C, lds, ldd = _smooth_on(src, seg, weights, order, dst, moved, 3 * BONES_MAX_J, "smooth_bones")
+    bd, ld, NB = _bones_on(walk, lengths, C // 3, src.device, "smooth_bones")
+    if fallback is not None:
+        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
+                and fallback.numel() == F and fallback.is_contiguous()):
+            raise ValueError("smooth_bones: fallback is one contiguous int32 device word per frame")
+    hip.call("smooth_bones", src, lds, F, C // 3, seg, w, H, order, bd, ld, NB, dst, ldd, moved, fallback)
+    return dst
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

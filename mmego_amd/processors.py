@@ -867,8 +867,35 @@ def bone_lengths(bone_set):
     return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
 
 
+SMOOTH_TAPERS = ("box", "gauss")
+
+
+def smooth_weights(H, taper):
+    """The tap weights w[2 H + 1] (float32, k = -H .. H) of dense inference's temporal filter (ops.smooth_frames): "box" ones, "gauss"
+    exp(-2 k^2 / H^2) -- a Gaussian of sigma H / 2, 0.135 at the window's ends -- computed in float64 and rounded once."""
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= ops.SMOOTH_MAX_H:
+        raise ValueError("smooth: the half-width is an integer number of frames in [1, %d], got %r" % (ops.SMOOTH_MAX_H, H))
+    if taper not in SMOOTH_TAPERS:
+        raise ValueError("smooth: taper %r is not one of %s" % (taper, ", ".join(SMOOTH_TAPERS)))
+    k = np.arange(-int(H), int(H) + 1, dtype=np.float64)
+    return (np.ones(len(k)) if taper == "box" else np.exp(-2.0 * k * k / float(H * H))).astype(np.float32)
+
+
+def _check_smooth(smooth):
+    """smooth = (H, order, taper) of dense_infer, or None.  -> the tuple with plain ints."""
+    if smooth is None:
+        return None
+    if not (isinstance(smooth, (tuple, list)) and len(smooth) == 3):
+        raise ValueError("smooth: (H, order, taper), got %r" % (smooth,))
+    H, order, taper = smooth
+    smooth_weights(H, taper)
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
+        raise ValueError("smooth: order (the polynomial's degree) is 0, 1 or 2, got %r" % (order,))
+    return int(H), int(order), taper
+
+
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None):
+                pose_noise=None, imu_noise=None, smooth=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -895,12 +922,23 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for the whole pass (imu_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as row_ids and the plan's window
     number as win_ids: a frame keeps its white noise in every window that serves it, a bias belongs to its window -- overlapping windows
     see one frame under different offsets, as separately started estimators would -- and the result does not depend on batch_size.
+    smooth=(H, order, taper): the pass's last stage, a zero-phase local-polynomial filter along time over every recording's stitched
+    blended frames (ops.smooth_frames; under blend_space="bones" ops.smooth_bones with the walk tables and bone lengths of the blend, so
+    the frames stay rigid): frame f becomes the value at f of the weighted least-squares polynomial of degree ``order`` (0, 1, 2) through
+    the frames f - H .. f + H of its own recording, weights smooth_weights(H, taper); uncovered frames take no part and stay as they
+    are.  Everything above then runs on the smoothed frames unchanged, and the blended frames' figures are kept beside them: the summary
+    gains unsmoothed_all_cm, unsmoothed_upper_cm, unsmoothed_lower_cm, unsmoothed_rot_deg, unsmoothed_per_joint_cm (and
+    unsmoothed_accel_cm under metrics="full"), moved_cm, the mean over the covered frames of the RMS distance over the upper joints that
+    the filter moved a frame, smooth itself and smooth_fallback, the bones that kept their own frame's direction (0 in the column
+    form); the arrays gain pred_unsmoothed [F, 21, 3] and moved [F].  None (the default): no launch, no key, the bytes of the pass
+    without the argument.
     The figures come down in one read; the per-frame arrays in one each."""
     from .data import DenseWindows
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
     if blend_space is not None and blend_space not in BLEND_SPACES:
         raise ValueError("blend_space: %r is not one of %s" % (blend_space, ", ".join(BLEND_SPACES)))
+    smooth = _check_smooth(smooth)
     dev = base.device
     plan = DenseWindows(dataset, dev, stride, blend)
     W, T, F = plan.W, plan.T, plan.F
@@ -911,13 +949,14 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise)
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise, smooth)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
 
 
-def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None, imu_noise=None):
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None, imu_noise=None,
+                smooth=None):
     """dense_infer behind its argument checks: the nets are in eval mode."""
     dev = base.device
     W, T, F = plan.W, plan.T, plan.F
@@ -961,6 +1000,21 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         else:
             ops.blend_windows(win_up, plan, up_f, spread)
             ops.blend_windows(win_lo, plan, lo_f)
+        if smooth is not None:
+            # along time, recording by recording: a frame's segment is its recording, an uncovered frame has none
+            H, order, taper = smooth
+            up_b, lo_b = up_f, lo_f                                # the blended frames: their figures are kept beside the smoothed ones'
+            seg = np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)
+            seg = torch.as_tensor(seg).to(dev)
+            wts = smooth_weights(H, taper)
+            up_f, lo_f, moved = f32(F, 45), f32(F, 24), f32(F)
+            if blend_space == "bones":
+                fell_s = torch.zeros((2, F), dtype=torch.int32, device=dev)
+                ops.smooth_bones(up_b, seg, wts, order, skeleton.WALK_UPPER, L_up, up_f, moved, fell_s[0])
+                ops.smooth_bones(lo_b, seg, wts, order, skeleton.WALK_LOWER, L_lo, lo_f, None, fell_s[1])
+            else:
+                ops.smooth_frames(up_b, seg, wts, order, up_f, moved)
+                ops.smooth_frames(lo_b, seg, wts, order, lo_f)
         tgt_f = plan.src["target"]                                 # [F, 63]
         cov = np.flatnonzero(plan.covered)
         Fc = len(cov)
@@ -971,7 +1025,8 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             spread_c = ops.gather_rows(spread.view(F, 1), cidx, f32(Fc, 1))
         full = metrics == "full"
         WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
-        log = torch.zeros((3 + T + (2 if blend_space is not None else 0), max(43, WA)), dtype=torch.float32, device=dev)
+        n_log = 3 + T + (2 if blend_space is not None else 0)      # (smooth: two more rows behind these)
+        log = torch.zeros((n_log + (2 if smooth is not None else 0), max(43, WA)), dtype=torch.float32, device=dev)
         E = f32(Fc, 43)
         hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
         ops.colsum(E, log[0, :43])
@@ -991,6 +1046,16 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             ops.bone_length_dev(win_lo, skeleton.WALK_LOWER, L_lo, Dw[:, 14:])
             ops.colsum(D, log[3 + T, :20])
             ops.colsum(Dw, log[4 + T, :20])
+        if smooth is not None:
+            # the blended frames before the filter: the same error kernel; and how far the filter moved a frame
+            up_bc, lo_bc, moved_c = up_b, lo_b, moved.view(F, 1)
+            if Fc < F:
+                up_bc, lo_bc = (ops.gather_rows(x, cidx, f32(Fc, x.shape[1])) for x in (up_b, lo_b))
+                moved_c = ops.gather_rows(moved.view(F, 1), cidx, f32(Fc, 1))
+            Eb = f32(Fc, 43)
+            hip.call("pose_errors", up_bc, lo_bc, tgt_c, Fc, Eb)
+            ops.colsum(Eb, log[n_log, :43])
+            ops.colsum(moved_c, log[n_log + 1, :1])
         if full:
             thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
             A = f32(Fc, WA)
@@ -1008,11 +1073,18 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         fallback = fell.cpu().numpy().sum(axis=0, dtype=np.int32) if blend_space == "bones" else np.zeros(F, dtype=np.int32)
         summary.update(bone_dev_cm=float(out[3 + T, :20].mean()) / Fc * 100, single_bone_dev_cm=float(out[4 + T, :20].mean()) / (W * T) * 100,
                        degenerate_bones=int(fallback.sum()), blend_space=blend_space)
+    if smooth is not None:
+        summary.update(_error_summary(out[n_log, :43], Fc, "unsmoothed_"))
+        smooth_fallback = int(fell_s.cpu().numpy().sum()) if blend_space == "bones" else 0
+        summary.update(moved_cm=float(out[n_log + 1, 0]) / Fc * 100, smooth=smooth, smooth_fallback=smooth_fallback)
     if full:
         spans = [(a, b) for a, b in zip(plan.rec_off[:-1], plan.rec_off[1:]) if b - a >= T]      # the covered recordings, whole
         acc = _accel_over_sequences(dev, up_f, lo_f, tgt_f, spans)
         m = np.concatenate([alog.cpu().numpy().astype(np.float64) / Fc, np.full(21, np.nan) if acc is None else acc])[None]
         summary.update(aligned_summary(m, 21))
+        if smooth is not None:
+            acc = _accel_over_sequences(dev, up_b, lo_b, tgt_f, spans)
+            summary["unsmoothed_accel_cm"] = None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100     # (aligned_summary's mean)
         summary["single_accel_cm"] = None
         if plan.stride == T:
             # the reference's windows of a recording are its last len // T windows: consecutive rows of the window tensors
@@ -1027,11 +1099,18 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     pred[:, list(base.cfg.upper_joint_map)] = up_h
     pred[:, list(base.cfg.lower_joint_map)] = lo_h                 # lower overwrites the shared hips (Demo_test.py:121-123)
     pred[plan.covered == 0] = np.nan
+    if smooth is not None:
+        pred_b = np.zeros((F, 21, 3), dtype=np.float32)
+        pred_b[:, list(base.cfg.upper_joint_map)] = up_b.cpu().numpy().reshape(F, 15, 3)
+        pred_b[:, list(base.cfg.lower_joint_map)] = lo_b.cpu().numpy().reshape(F, 8, 3)
+        pred_b[plan.covered == 0] = np.nan
     arrays = dict(pred=pred, covered=plan.covered.astype(np.int32), spread=spread.cpu().numpy(), recording=plan.frame_rec,
                   frame_in_recording=plan.frame_in_recording, target=tgt_f.cpu().numpy().reshape(F, 21, 3),
                   upper=up_h, lower=lo_h, win_up=win_up, win_lo=win_lo, plan=plan)
     if blend_space is not None:
         arrays["fallback"] = fallback
+    if smooth is not None:
+        arrays.update(pred_unsmoothed=pred_b, moved=moved.cpu().numpy())
     return summary, arrays
 
 
@@ -1051,16 +1130,18 @@ class Evaluator(_Base):
         self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no, keep_frames=bool(getattr(cfg, "dense", False)))
 
     def eval_dense(self):
-        """`--infer --dense [--stride S --blend B --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
+        """`--infer --dense [--stride S --blend B --smooth H --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
         (the reference's five lines for the blend first), the per-frame skeletons written when asked for.  -> the summary."""
         cfg = self.cfg
         self.model.load(cfg.model_lower_path)
         self.model.eval()
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
         space = getattr(cfg, "blend_space", None)
+        smooth = getattr(cfg, "smooth", None)
+        more_args = {} if smooth is None else dict(smooth=smooth)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space,
-                                pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg))
+                                pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg), **more_args)
         print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
         print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
         print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
@@ -1083,6 +1164,9 @@ class Evaluator(_Base):
         noise, imu_noise = pose_noise_of(cfg), imu_noise_of(cfg)
         if path:
             more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
+            if smooth is not None:
+                more.update(pred_unsmoothed=arrays["pred_unsmoothed"], moved=arrays["moved"], smooth_window=np.int64(smooth[0]),
+                            smooth_order=np.int64(smooth[1]), smooth_taper=np.asarray(smooth[2]))
             if noise is not None:
                 more.update(pose_noise_deg=np.float64(noise[0]), pose_noise_t=np.float64(noise[1]), pose_noise_seed=np.int64(noise[2]))
             if imu_noise is not None:
@@ -1094,6 +1178,13 @@ class Evaluator(_Base):
             print(pose_noise_line(noise))
         if imu_noise is not None:
             print(imu_noise_line(imu_noise))
+        if smooth is not None:
+            print("Unsmoothed (blended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+                s["unsmoothed_all_cm"], s["unsmoothed_upper_cm"], s["unsmoothed_lower_cm"], s["unsmoothed_rot_deg"]))
+            print("Smoothing Displacement(cm): {} (window +-{} frames, order {}, {}; degenerate bones {})".format(
+                s["moved_cm"], s["smooth"][0], s["smooth"][1], s["smooth"][2], s["smooth_fallback"]))
+            if self._metrics() == "full":
+                print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
         return s
 
     def _print_aligned(self, s):
