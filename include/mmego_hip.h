@@ -246,6 +246,47 @@ int mmego_blend_bones(void* stream, const float* src, long nrows, int J, const l
  * Refused: null pointers, n < 1 or >= 2^26, J outside [1, 21], NB outside [1, J - 1], ldx < 3 J, ldo < NB. */
 int mmego_bone_length_dev(void* stream, const float* X, long ldx, long n, int J, const int* bones, const float* bone_len, int NB,
                           float* out, long ldo);
+/* The blend in ROTATION space (blend_rot.hip; processors.dense_infer under blend_space="rot"): every bone's world-frame rotation
+ * averaged over the cover, the nets' forward kinematics run once on the averages.  src [nrows][3 J] and the cover are
+ * mmego_blend_bones'; q [nrows][NQ][9] holds the rotations the net predicted for every row (row-major 3 x 3, head frame), Rh [nrows][9]
+ * the head rotation every row was run with (the head-to-world transform is p <- Rh^T p + t); bones [NB][2] (int32, on the device) is
+ * mmego_blend_bones' walk table, rot_idx [NB] (int32) names the one of a row's NQ rotations that turns bone b, body [NB][3] (float) the
+ * rest bone vectors.  Per frame, with its valid entries k (those whose row r_k lies in [0, nrows)) in CSR order, their weights w_k and
+ * W = sum_k w_k:
+ *   no valid entry, or W == 0: a zero row, zero quaternions, spread 0, rot_spread 0, fallback 0;   otherwise
+ *   bone b = (c, p):     A_k = Rh[r_k]^T q[r_k][rot_idx[b]], the bone's world rotation in entry k;  S = sum_k w_k A_k;
+ *                        Qbar_b = the proper rotation that maximises tr(Q^T S) -- the weighted chordal mean of the A_k, Markley's
+ *                        quaternion mean: its unit quaternion (w, x, y, z) is the eigenvector of the largest eigenvalue of the
+ *                        symmetric 4 x 4 matrix (S 1-indexed)
+ *                          [ S11+S22+S33   S32-S23       S13-S31       S21-S12     ]
+ *                          [ .             S11-S22-S33   S12+S21       S13+S31     ]
+ *                          [ .             .            -S11+S22-S33   S23+S32     ]
+ *                          [ .             .             .            -S11-S22+S33 ]
+ *                        by cyclic Jacobi sweeps (a single rotation has the eigenvalues 3 W and three times -W);
+ *                        where the two largest eigenvalues lie no more than 1e-9 W apart the mean has no direction: the FALLBACK,
+ *                        counted in fallback[f], is the quaternion, by the same route, of the A_k of the entry with the largest weight
+ *                        (the first such on ties);   the quaternion's sign is canonical: its first non-zero component is positive;
+ *   quat[f, b] = (float4) that quaternion: one 16-byte store;
+ *   exactly one valid entry: dst[f] is its row of src, bit for bit, and rot_spread[f] = 0;   otherwise
+ *   a root r:            pos_r = (sum_k w_k x_kr) / W, mmego_blend_windows' own arithmetic: those columns carry the same bits;
+ *   bone b = (c, p):     pos_c = pos_p + Qbar_b body_b, the bones taken in their listed order;
+ *   dst[f, 3 j + i] = (float) pos_j[i]: positions stay doubles until this one store; the columns of dst[f] beyond 3 J are not touched;
+ *   spread[f] (may be NULL) = mmego_blend_windows' spread against pos, the rigid positions before their rounding;
+ *   rot_spread[f] (may be NULL) = sqrt(sum_b sum_k w_k theta_kb^2 / (NB W)) in radians, theta_kb the angle of D = Qbar_b^T A_k taken as
+ *                        atan2(|v|, (tr D - 1) / 2), v = (D32 - D23, D13 - D31, D21 - D12) / 2: how much the windows disagree about the
+ *                        frame's rotations;
+ *   fallback[f] (int32, may be NULL) = the number of bones of the frame that took the fallback.
+ * Every blended bone has the length |body_b| up to the rounding of its two endpoints.  All arithmetic in double from the fp32 inputs, no
+ * atomics, no LDS, sums in a fixed order: two launches give the same bits.  One wave per frame, one lane per joint (the bone whose child
+ * it is), the parent's position handed over by wave shuffles.  Rh is NOT checked to be a proper rotation: the nets' and the loader's head
+ * rotations are, and a q or Rh that is only a rotation up to fp32 rounding is projected by the mean itself.  Refused: a null src, q, Rh,
+ * cov_off, cov_row, cov_w, bones, rot_idx, body, dst or quat, F < 1 or >= 2^31, nrows < 0 or >= 2^31, J outside [2, 21], NB outside
+ * [1, J - 1], NQ outside [1, 64], ldd < 3 J, a quat that is not 16-byte aligned.  The caller answers for the cover and the bone list as
+ * for mmego_blend_bones and for rot_idx lying in [0, NQ) (ops.blend_rot checks all three on the host); a bone that names a joint outside
+ * [0, J) or a rotation outside [0, NQ) is left out: its child stays a root and its quaternion is not written. */
+int mmego_blend_rot(void* stream, const float* src, long nrows, int J, const float* q, int NQ, const float* Rh,
+                    const long long* cov_off, const int* cov_row, const float* cov_w, long F, const int* bones, const int* rot_idx,
+                    const float* body, int NB, float* dst, long ldd, float* quat, float* spread, float* rot_spread, int* fallback);
 /* Dense inference's temporal smoothing (smooth.hip; processors.dense_infer with smooth=(H, order, taper)): a zero-phase local-polynomial
  * filter along the frames.  src [F][C] (row stride lds), seg [F] (int32) the segment of every frame (-1: none), w [2 H + 1] (float,
  * positive and finite; the host makes the taper, ops.smooth_frames checks it) the weights of the taps k = -H .. H.  Per frame f:

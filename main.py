@@ -3,7 +3,7 @@
 
   python main.py --train --network {IMU_Net,Upper_Net,Lower_Net} [--epochs N --lr F --batch_size N --device cuda:0
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
-  python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones} --save_pred PATH]]
+  python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones,rot} --save_pred PATH]]
   python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
@@ -29,10 +29,13 @@ own), --point_keep P (every minibatch's clouds are packed afresh on the device, 
 --point_noise S / --point_noise_v S (that device packing also jitters every kept return: x, y, z by a bell-shaped draw of standard deviation
 S metres, clipped at +-3.46 S, with r recomputed from the result, and the Doppler velocity likewise in its own units): what a
 run is trained on, from the frame-major device store data.FrameStore; evaluation is untouched; --infer --dense [--stride S --blend
-{mean,triangle} --blend_space {joints,bones} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
+{mean,triangle} --blend_space {joints,bones,rot} --save_pred PATH] (sliding-window inference over whole recordings: the three nets run over overlapping windows S frames
 apart, every frame's pose is blended on the device from the windows that cover it, the blended and the single-window errors, the error
 by position in the window and the windows' disagreement are printed, and PATH receives the per-frame skeletons; --blend_space bones
-blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again; --smooth H [--smooth_order D
+blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again; --blend_space rot averages
+the world rotations both nets predicted for every bone over the windows and runs the nets' forward kinematics once on the averages --
+rigid frames too, with the twist about every bone kept -- prints the windows' rotational disagreement in degrees and adds a unit
+quaternion per bone and frame (rot), rot_spread and the rest bones (bone_vectors) to PATH; it does not go with --smooth; --smooth H [--smooth_order D
 --smooth_taper {box,gauss}] then filters every recording's stitched frames along time on the device, a zero-phase local polynomial of
 degree D over +-H frames -- of bone directions under --blend_space bones -- and prints the blended frames' figures and the mean
 displacement beside the smoothed ones'), --pose_noise_deg D /
@@ -196,11 +199,16 @@ def build_parser():
     p.add_argument("--blend", type=str, choices=["mean", "triangle"], default=None,
                    help="--dense: weight of a window's prediction for a frame -- mean (default: 1) or triangle (min(p + 1, frame_no - p) at "
                         "position p: the window's middle counts most)")
-    p.add_argument("--blend_space", type=str, choices=["joints", "bones"], default=None,
+    p.add_argument("--blend_space", type=str, choices=["joints", "bones", "rot"], default=None,
                    help="--dense: what is blended over a frame's windows -- joints (default: every joint's 3-vector on its own; where the "
                         "windows disagree about a bone's direction the blended bone comes out shorter) or bones (every bone's direction, set "
                         "to the body's bone length and laid along the kinematic tree from the blended roots: the frames stay rigid "
-                        "skeletons).  Given, either value prints one more line, the blended and single-window deviation from the bone "
+                        "skeletons) or rot (every bone's world rotation as the nets predicted it, averaged over the windows -- the weighted "
+                        "chordal mean -- and the nets' forward kinematics run once on the averages: rigid frames with the twist about every "
+                        "bone kept; one more line gives the windows' rotational disagreement in degrees, and --save_pred's file gains rot "
+                        "[F, 20, 4], a unit quaternion (w, x, y, z) per bone and frame in the world frame, rot_spread [F] and bone_vectors "
+                        "[20, 3], the rest bones: rot applied to bone_vectors from pred's roots gives pred.  Not with --smooth).  Given, any "
+                        "value prints one more line, the blended and single-window deviation from the bone "
                         "lengths, and adds blend_space and degenerate_bones to --save_pred's file")
     p.add_argument("--save_pred", type=str,
                    help="--dense: write the per-frame arrays to this .npz -- pred [F, 21, 3] (NaN where no window covers the frame: "
@@ -227,6 +235,9 @@ def check_dense(parser, args):
     if args.smooth is not None and not 1 <= args.smooth <= 31:
         parser.error("--smooth is the filter's half-width in frames: it has to lie in [1, 31] (2 H + 1 taps fit one wave), got %d"
                      % args.smooth)
+    if args.dense and args.blend_space == "rot" and args.smooth is not None:
+        parser.error("--smooth does not go with --blend_space rot: the filter runs on joint positions, so the saved rotations would not "
+                     "be filtered with the positions (filtering rotations along time is not provided)")
     if not args.dense:
         for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper"):
             if getattr(args, flag) is not None:

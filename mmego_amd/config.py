@@ -92,7 +92,7 @@ class ConfigDemo(_Common):
     dense = False               # --dense: sliding-window inference over whole recordings (processors.dense_infer)
     stride = None               # --stride: frames between window starts (None: frame_no // 2)
     blend = "mean"              # --blend: mean or triangle
-    blend_space = None          # --blend_space: joints or bones (None: joints, without the bone-length figures)
+    blend_space = None          # --blend_space: joints, bones or rot (None: joints, without the bone-length figures)
     smooth = None               # --smooth H [--smooth_order D --smooth_taper T]: (H, D, T), the dense pass's temporal filter (None: off)
     save_pred = None            # --save_pred: .npz of the per-frame skeletons
     dense_batch_size = None     # --batch_size under --dense: windows per minibatch (None: 64)

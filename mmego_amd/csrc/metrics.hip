@@ -13,10 +13,8 @@
 // of holding them: the 4 x 4 matrix and its eigenvectors are 32 doubles, and every array below is indexed by constants only, so
 // nothing lives in scratch memory.  Every sum runs over the joints (the frames of a sequence) in index order: two launches, same bits.
 #include "common.h"
+#include "quat_eig.h"        // MT_HD, MT_SWEEPS, mt_top_eigenpair: the cyclic Jacobi eigen-solver (shared with blend_rot.hip)
 
-#define MT_HD __host__ __device__ __forceinline__
-
-#define MT_SWEEPS 10       // cyclic Jacobi converges quadratically; a 4 x 4 matrix is at rounding level after 5 or 6 sweeps
 #define MT_MAX_THR 8
 
 // Joint j of the J compared ones: prediction and target as doubles.
@@ -36,72 +34,6 @@ MT_HD void mt_joint(const float* __restrict__ upper, const float* __restrict__ l
   }
   p[0] = (double)ps[0]; p[1] = (double)ps[1]; p[2] = (double)ps[2];
   g[0] = (double)gs[0]; g[1] = (double)gs[1]; g[2] = (double)gs[2];
-}
-
-// One Jacobi rotation of the symmetric a in the (P, Q) plane, accumulated into the eigenvector columns of v.  A rotation whose
-// off-diagonal element is zero, or vanishes against both diagonal elements, is skipped (theta = (a_qq - a_pp) / (2 a_pq) would
-// overflow when squared); where it only vanishes against their difference, t = a_pq / (a_qq - a_pp) is the small-angle limit.
-template <int P, int Q>
-MT_HD void mt_rotate(double (&a)[4][4], double (&v)[4][4]) {
-  const double apq = a[P][Q];
-  const double big = 100.0 * fabs(apq);
-  if (apq == 0.0 || (fabs(a[P][P]) + big == fabs(a[P][P]) && fabs(a[Q][Q]) + big == fabs(a[Q][Q]))) {
-    a[P][Q] = a[Q][P] = 0.0;
-    return;
-  }
-  const double h = a[Q][Q] - a[P][P];
-  double t;
-  if (fabs(h) + big == fabs(h)) {
-    t = apq / h;
-  } else {
-    const double theta = 0.5 * h / apq;
-    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-    if (theta < 0.0) t = -t;
-  }
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-  a[P][P] -= t * apq;
-  a[Q][Q] += t * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (r != P && r != Q) {
-      const double x = a[r][P], y = a[r][Q];
-      a[r][P] = a[P][r] = x - s * (y + tau * x);
-      a[r][Q] = a[Q][r] = y + s * (x - tau * y);
-    }
-    const double x = v[r][P], y = v[r][Q];
-    v[r][P] = x - s * (y + tau * x);
-    v[r][Q] = y + s * (x - tau * y);
-  }
-}
-
-// Largest eigenvalue of the symmetric a (destroyed) and its unit eigenvector q.  Of equal diagonal elements the first one wins, so the
-// zero matrix gives q = (1, 0, 0, 0): the identity.
-MT_HD double mt_top_eigenpair(double (&a)[4][4], double* q) {
-  double v[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[r][c] = r == c ? 1.0 : 0.0;
-#pragma unroll 1
-  for (int sweep = 0; sweep < MT_SWEEPS; ++sweep) {
-    mt_rotate<0, 1>(a, v); mt_rotate<0, 2>(a, v); mt_rotate<0, 3>(a, v);
-    mt_rotate<1, 2>(a, v); mt_rotate<1, 3>(a, v); mt_rotate<2, 3>(a, v);
-  }
-  double lam = a[0][0];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) q[r] = v[r][0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    const bool up = a[k][k] > lam;
-    lam = up ? a[k][k] : lam;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) q[r] = up ? v[r][k] : q[r];
-  }
-  const double n = sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));      // (1 up to rounding: the columns of v are rotations of I)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) q[r] /= n;
-  return lam;
 }
 
 // One frame's row of mmego_pose_errors_aligned (the layout is in include/mmego_hip.h).

@@ -572,6 +572,74 @@ def bone_length_dev(X, bones, bone_len, out):
     return out
 
 
+_rot_dev = {}
+
+
+def blend_rot(src, q, Rh, cover, bones, rot_idx, body, dst, quat, spread=None, rot_spread=None, fallback=None):
+    """dst[f, :3 J] = the blend in rotation space of the rows that cover frame f (mmego_blend_rot; the recipe is in the header): per bone
+    the weighted chordal mean of the world rotations Rh^T q of the cover, the roots as blend_windows blends them, the rest bones ``body``
+    laid along the means over ``bones``; quat [F, NB, 4] receives the means as unit quaternions (w, x, y, z) of canonical sign.
+    src [nrows, 3 J] the rows' joints (J <= 21), q [nrows, NQ, 9] (or [nrows, NQ, 3, 3]) the rows' rotations, Rh [nrows, 9] (or
+    [nrows, 3, 3]) the head rotation each row ran with; bones [NB, 2] host integers (child, parent), parents first, rot_idx [NB] host
+    integers in [0, NQ), body [NB, 3] host floats with no zero vector.  spread [F] (optional) as blend_windows', against the rigid
+    positions; rot_spread [F] (optional) the windows' weighted RMS rotational distance from the mean in radians; fallback [F] int32
+    (optional) the bones per frame whose mean was degenerate.  Every tensor is contiguous float32 on src's device.  Cover, bones,
+    rot_idx and body are checked on the host first; a refused call leaves every output untouched.  dst may be wider than 3 J: its other
+    columns stay."""
+    import numpy as np
+    _chk(src, 2)
+    dst = _rows(dst)
+    nrows, C = src.shape
+    if not src.is_contiguous() or C % 3 or not 2 <= C // 3 <= BONES_MAX_J:
+        raise ValueError("blend_rot needs a contiguous source of 2 to %d 3-vectors a row, got %s" % (BONES_MAX_J, tuple(src.shape)))
+    for name, t in (("q", q), ("Rh", Rh), ("quat", quat)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == src.device and t.is_contiguous()):
+            raise ValueError("blend_rot: %s is a contiguous float32 tensor on the source's device" % name)
+    if q.dim() not in (3, 4) or q.shape[0] != nrows or q.shape[1] < 1 or q.numel() != nrows * q.shape[1] * 9:
+        raise ValueError("blend_rot: q is [%d, NQ, 9], one 3 x 3 rotation per row and bone, got %s" % (nrows, tuple(q.shape)))
+    NQ = q.shape[1]
+    if Rh.dim() not in (2, 3) or Rh.shape[0] != nrows or Rh.numel() != nrows * 9:
+        raise ValueError("blend_rot: Rh is [%d, 9], one head rotation per row, got %s" % (nrows, tuple(Rh.shape)))
+    bv = np.asarray(body.detach().cpu() if isinstance(body, torch.Tensor) else body)
+    if bv.ndim != 2 or bv.shape[1] != 3 or bv.dtype.kind != "f":
+        raise ValueError("blend_rot: body is [NB, 3] floats, one rest vector per bone")
+    bv = np.ascontiguousarray(bv, dtype=np.float32)
+    if not np.isfinite(bv).all():
+        raise ValueError("blend_rot: bone lengths have to be finite and positive")
+    bd, _, NB = _bones_on(bones, np.linalg.norm(bv.astype(np.float64), axis=1), C // 3, src.device, "blend_rot")
+    if NB < 1:
+        raise ValueError("blend_rot: at least one bone")
+    ri = np.asarray(rot_idx)
+    if ri.ndim != 1 or len(ri) != NB or not np.issubdtype(ri.dtype, np.integer):
+        raise ValueError("blend_rot: rot_idx is one integer per bone (%d)" % NB)
+    if ri.min() < 0 or ri.max() >= NQ:
+        raise IndexError("blend_rot: rot_idx names rotations outside the %d of a row" % NQ)
+    off, row, w, F = _cover_on(cover, nrows, src.device)
+    if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
+        raise ValueError("blend_rot: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
+    if quat.numel() != F * NB * 4 or quat.shape[0] != F or quat.data_ptr() % 16:
+        raise ValueError("blend_rot: quat is [%d, %d, 4], 16-byte aligned, got %s" % (F, NB, tuple(quat.shape)))
+    for name, t in (("spread", spread), ("rot_spread", rot_spread)):
+        if t is not None:
+            _chk(t, 1)
+            if t.numel() != F or not t.is_contiguous() or t.device != src.device:
+                raise ValueError("blend_rot: %s is one contiguous float per frame" % name)
+    if fallback is not None:
+        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
+                and fallback.numel() == F and fallback.is_contiguous()):
+            raise ValueError("blend_rot: fallback is one contiguous int32 device word per frame")
+    ri = np.ascontiguousarray(ri, dtype=np.int32)
+    key = (ri.tobytes(), bv.tobytes(), str(src.device))
+    rd = _rot_dev.get(key)
+    if rd is None:
+        if len(_rot_dev) >= 64:
+            _rot_dev.clear()
+        rd = _rot_dev[key] = (torch.as_tensor(ri).to(src.device), torch.as_tensor(bv).to(src.device))
+    hip.call("blend_rot", src, nrows, C // 3, q, NQ, Rh, off, row, w, F, bd, rd[0], rd[1], NB, dst, max(dst.stride(0), C), quat, spread,
+             rot_spread, fallback)
+    return dst
+
+
 SMOOTH_MAX_H = 31           # smooth.hip SM_MAX_H: one lane per tap, 2 H + 1 <= 63
 
 _smooth_w_dev = {}

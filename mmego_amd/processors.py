@@ -857,7 +857,7 @@ def _accel_over_sequences(dev, up, lo, tgt, spans):
     return (Acc.cpu().numpy().astype(np.float64) * wt[:, None]).sum(axis=0) / wt.sum()
 
 
-BLEND_SPACES = ("joints", "bones")
+BLEND_SPACES = ("joints", "bones", "rot")
 
 
 def bone_lengths(bone_set):
@@ -915,6 +915,15 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     adds to the summary bone_dev_cm, the mean over the covered frames and the 20 bones of | |bone| - L_b | on the blended rows (upper 14
     from the upper rows, lower 6 from the lower rows; mmego_bone_length_dev), single_bone_dev_cm, the same over the window rows,
     degenerate_bones, the bones that took mmego_blend_bones' fallback (0 for "joints"), and blend_space; and to the arrays fallback [F].
+    "rot" blends in rotation space (mmego_blend_rot): both nets' rotations q and the head rotation R every row ran with (after any pose
+    noise) are kept per window row, every bone's world rotation R^T q is averaged over the cover (the weighted chordal mean), and the
+    nets' forward kinematics lays the rest bones of the campaign's bone set along the averages from the vector-blended roots -- rigid
+    frames as under "bones", with the twist about every bone kept.  The summary gains rot_spread_deg, the mean over the covered frames
+    of the windows' RMS rotational distance from the mean over the 14 upper bones, and degenerate_bones counts mmego_blend_rot's
+    fallback; the arrays gain rot [F, 20, 4], the unit quaternions (w, x, y, z) of the blended WORLD rotations in BONES_ALL order (NaN
+    where uncovered), rot_spread [F] in radians, bone_vectors [20, 3] -- pred's bones are rot applied to bone_vectors -- and, still on
+    the device, win_q_up [W T, 14, 9], win_q_lo [W T, 6, 9] and win_R [W T, 9]; none of these is allocated in another space.  "rot"
+    with smooth is refused (ValueError): the rotations would not be filtered with the positions.
     pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
     whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
     pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
@@ -939,6 +948,9 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     if blend_space is not None and blend_space not in BLEND_SPACES:
         raise ValueError("blend_space: %r is not one of %s" % (blend_space, ", ".join(BLEND_SPACES)))
     smooth = _check_smooth(smooth)
+    if blend_space == "rot" and smooth is not None:
+        raise ValueError("smooth: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
+                         "filtered with them; filtering rotations along time is not done here")
     dev = base.device
     plan = DenseWindows(dataset, dev, stride, blend)
     W, T, F = plan.W, plan.T, plan.F
@@ -962,6 +974,9 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     W, T, F = plan.W, plan.T, plan.F
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     win_up, win_lo = f32(W * T, 45), f32(W * T, 24)
+    rot = blend_space == "rot"
+    if rot:                                                        # every window row's rotations and the head rotation it ran with
+        win_q_up, win_q_lo, win_R = f32(W * T, 14, 9), f32(W * T, 6, 9), f32(W * T, 9)
     with torch.no_grad():
         state = {}
         if imu_noise is not None and imu_net is None:
@@ -985,10 +1000,14 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
             if pose_noise is not None:
                 R, t = _jitter_pose(state, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, 0), ids=row_frame[s * T:(s + B) * T])
-            up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[0]
-            lo, _ = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
+            up, q_up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[:2]
+            lo, q_lo = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
             win_up[s * T:(s + B) * T].copy_(up.reshape(B * T, 45))
             win_lo[s * T:(s + B) * T].copy_(lo.reshape(B * T, 24))
+            if rot:
+                win_q_up[s * T:(s + B) * T].copy_(q_up.reshape(B * T, 14, 9))
+                win_q_lo[s * T:(s + B) * T].copy_(q_lo.reshape(B * T, 6, 9))
+                win_R[s * T:(s + B) * T].copy_(R.reshape(B * T, 9))           # (after any pose noise: what the row was run with)
         # every frame from its windows
         up_f, lo_f, spread = f32(F, 45), f32(F, 24), f32(F)
         if blend_space is not None:
@@ -997,6 +1016,14 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             fell = torch.zeros((2, F), dtype=torch.int32, device=dev)
             ops.blend_bones(win_up, plan, skeleton.WALK_UPPER, L_up, up_f, spread, fell[0])
             ops.blend_bones(win_lo, plan, skeleton.WALK_LOWER, L_lo, lo_f, None, fell[1])
+        elif rot:
+            fell = torch.zeros((2, F), dtype=torch.int32, device=dev)
+            quat_up, quat_lo, rot_spread = f32(F, 14, 4), f32(F, 6, 4), f32(F)
+            bone_vectors = np.ascontiguousarray(np.asarray(plan.bone_set, dtype=np.float32).reshape(20, 3))
+            ops.blend_rot(win_up, win_q_up, win_R, plan, skeleton.WALK_UPPER, skeleton.ROT_UPPER, bone_vectors[list(skeleton.WALK_UPPER_ROWS)],
+                          up_f, quat_up, spread, rot_spread, fell[0])
+            ops.blend_rot(win_lo, win_q_lo, win_R, plan, skeleton.WALK_LOWER, skeleton.ROT_LOWER, bone_vectors[list(skeleton.WALK_LOWER_ROWS)],
+                          lo_f, quat_lo, None, None, fell[1])
         else:
             ops.blend_windows(win_up, plan, up_f, spread)
             ops.blend_windows(win_lo, plan, lo_f)
@@ -1025,7 +1052,7 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             spread_c = ops.gather_rows(spread.view(F, 1), cidx, f32(Fc, 1))
         full = metrics == "full"
         WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
-        n_log = 3 + T + (2 if blend_space is not None else 0)      # (smooth: two more rows behind these)
+        n_log = 3 + T + (2 if blend_space is not None else 0) + (1 if rot else 0)      # (smooth: two more rows behind these)
         log = torch.zeros((n_log + (2 if smooth is not None else 0), max(43, WA)), dtype=torch.float32, device=dev)
         E = f32(Fc, 43)
         hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
@@ -1046,6 +1073,9 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             ops.bone_length_dev(win_lo, skeleton.WALK_LOWER, L_lo, Dw[:, 14:])
             ops.colsum(D, log[3 + T, :20])
             ops.colsum(Dw, log[4 + T, :20])
+        if rot:
+            rot_spread_c = rot_spread.view(F, 1) if Fc == F else ops.gather_rows(rot_spread.view(F, 1), cidx, f32(Fc, 1))
+            ops.colsum(rot_spread_c, log[5 + T, :1])
         if smooth is not None:
             # the blended frames before the filter: the same error kernel; and how far the filter moved a frame
             up_bc, lo_bc, moved_c = up_b, lo_b, moved.view(F, 1)
@@ -1070,9 +1100,11 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
     summary.update(windows=W, frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=blend, frame_no=T)
     if blend_space is not None:
         # (the fallback counts are integers per frame: they come down with the per-frame arrays, in their one read)
-        fallback = fell.cpu().numpy().sum(axis=0, dtype=np.int32) if blend_space == "bones" else np.zeros(F, dtype=np.int32)
+        fallback = fell.cpu().numpy().sum(axis=0, dtype=np.int32) if blend_space in ("bones", "rot") else np.zeros(F, dtype=np.int32)
         summary.update(bone_dev_cm=float(out[3 + T, :20].mean()) / Fc * 100, single_bone_dev_cm=float(out[4 + T, :20].mean()) / (W * T) * 100,
                        degenerate_bones=int(fallback.sum()), blend_space=blend_space)
+    if rot:
+        summary["rot_spread_deg"] = float(np.degrees(out[5 + T, 0] / Fc))
     if smooth is not None:
         summary.update(_error_summary(out[n_log, :43], Fc, "unsmoothed_"))
         smooth_fallback = int(fell_s.cpu().numpy().sum()) if blend_space == "bones" else 0
@@ -1109,6 +1141,11 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
                   upper=up_h, lower=lo_h, win_up=win_up, win_lo=win_lo, plan=plan)
     if blend_space is not None:
         arrays["fallback"] = fallback
+    if rot:
+        quats = np.concatenate([quat_up.cpu().numpy(), quat_lo.cpu().numpy()], axis=1)      # [F, 20, 4] in BONES_ALL order
+        quats[plan.covered == 0] = np.nan
+        arrays.update(rot=quats, rot_spread=rot_spread.cpu().numpy(), bone_vectors=bone_vectors, win_q_up=win_q_up, win_q_lo=win_q_lo,
+                      win_R=win_R)
     if smooth is not None:
         arrays.update(pred_unsmoothed=pred_b, moved=moved.cpu().numpy())
     return summary, arrays
@@ -1154,6 +1191,8 @@ class Evaluator(_Base):
         if space is not None:
             print("Bone Length Deviation(cm): blended {} single-window {} (degenerate bones {})".format(
                 s["bone_dev_cm"], s["single_bone_dev_cm"], s["degenerate_bones"]))
+        if space == "rot":
+            print("Window Rotational Disagreement(°): {}".format(s["rot_spread_deg"]))
         print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
             s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
         if self._metrics() == "full":
@@ -1164,6 +1203,8 @@ class Evaluator(_Base):
         noise, imu_noise = pose_noise_of(cfg), imu_noise_of(cfg)
         if path:
             more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
+            if space == "rot":
+                more.update(rot=arrays["rot"], rot_spread=arrays["rot_spread"], bone_vectors=arrays["bone_vectors"])
             if smooth is not None:
                 more.update(pred_unsmoothed=arrays["pred_unsmoothed"], moved=arrays["moved"], smooth_window=np.int64(smooth[0]),
                             smooth_order=np.int64(smooth[1]), smooth_taper=np.asarray(smooth[2]))

@@ -31,6 +31,11 @@ WALK_UPPER = _walk(BONES_UPPER, UPPER_MAP)          # one tree rooted at the hea
 WALK_LOWER = _walk(BONES_LOWER, LOWER_MAP)          # a forest rooted at the two hips (joints 12 and 16, slots 0 and 4): 6 bones
 WALK_UPPER_ROWS = tuple(range(0, len(BONES_UPPER)))
 WALK_LOWER_ROWS = tuple(range(len(BONES_UPPER), len(BONES_ALL)))
+# Which of a net's rotations turns bone k (ops.blend_rot): Upper_Net's q [., 14, 3, 3] is indexed by the child's slot in its own row
+# (the head, slot 14, is no bone's child), Lower_Net's q [., 6, 3, 3] by the child's position among the six leg joints below the hips.
+ROT_UPPER = [int(c) for c in WALK_UPPER[:, 0]]
+LOWER_ROT_MAP = sorted(c for _, c in BONES_LOWER)   # [13, 14, 15, 17, 18, 19]: the leg joints in joint order (Lower_Net.py:29)
+ROT_LOWER = [LOWER_ROT_MAP.index(c) for _, c in BONES_LOWER]
 
 GCN_EDGES = [(0, 12), (0, 13), (0, 1), (1, 2), (2, 3), (2, 4), (2, 8), (3, 14), (4, 5), (5, 6), (6, 7), (8, 9),
              (9, 10), (10, 11)]
