@@ -24,6 +24,11 @@ extern "C" {
  * C[b](m,n) (+)= sum_k A[b](m,k) * B[b](k,n) (+ bias[n]) (relu).  A(m,k) = A[m*sam + k*sak + b*sAb],
  * B(k,n) = B[k*sbk + n*sbn + b*sBb], C(m,n) = C[m*scm + n*scn + b*sCb].  nsplit > 1 splits K into slabs
  * in `splitk_ws` (nsplit*nbatch*M*N floats) that are then summed in a fixed order (deterministic).
+ * Order of the epilogue, the same in every kernel and in the split-K reducer:
+ *   C = cmulop( C_old + relu( sum_k A B + bias ) )
+ * -- bias first, then ReLU (relu == 1 only), then the old C is added (accumulate == 1 only: the ReLU does NOT cover it), then cmul
+ * (relu 0 / 1: times cmul; relu == 2: 0 where cmul <= 0).  accumulate == 2 (nsplit > 1, nbatch == 1, no bias, no relu): the slabs stay
+ * in splitk_ws for the caller to sum and C is not written.
  * Replaces: nn.Linear / Conv1d(k=1) / Conv2d(1x1, 9x1) / Conv3d forward and their weight/input
  * gradients -- Net/Upper_Net.py:242-301,343-364, Net/Lower_Net.py:40-72,95-123, Net/GCN.py:46-60,
  * and the LSTM input projections of Net/IMU_Net.py:58-62. */
@@ -40,7 +45,9 @@ int mmego_gemm(void* stream, const float* A, long sam, long sak, const float* B,
                int relu, int accumulate, float* splitk_ws, int nsplit, long sBiasb, const float* cmul, float* asum);
 /* Several INDEPENDENT products in one launch: each entry is one mmego_gemm argument set.  When all of them are small-tile products
  * of one operand orientation (what mmego_gemm would hand to its K-quartered kernel, unsplit), they share a launch -- grid.z is cut
- * into the products' ranges --; otherwise they run as n mmego_gemm calls in order.  Same results either way.  For the leaf
+ * into the products' ranges --; otherwise they run as n mmego_gemm calls in order.  Same results either way; an entry whose options
+ * mmego_gemm refuses (null A / B / C, a size < 1, relu outside 0..2 or 2 without cmul, accumulate == 2 on an unsplit, batched, biased
+ * or relu product, cmul or sBiasb with nsplit > 1) makes the call a bad argument before any entry is launched.  For the leaf
  * products of a backward pass (weight gradients of a BiLSTM stack: the reference's autograd computes them per parameter, e.g.
  * Net/Upper_Net.py:333), which otherwise sit one behind the other in a dependent chain of small kernels. */
 typedef struct MmegoGemmDesc {

@@ -506,18 +506,25 @@ __global__ __launch_bounds__(256) void gemm128_nt_kernel(const float* __restrict
   }
 }
 
+// The argument checks of mmego_gemm that do not depend on the kernel choice (mmego_gemm_group applies them to every entry before it
+// launches anything).
+static bool gemm_args_ok(const float* A, const float* B, const float* C, const float* bias, int M, int N, int K, int nbatch, int relu,
+                         int accumulate, int nsplit, long sBiasb, const float* cmul) {
+  if (!(A && B && C && M > 0 && N > 0 && K > 0 && nbatch > 0 && nsplit >= 1)) return false;
+  // accumulate == 2: DEFERRED split-K -- the slabs (and the slab row sums behind them) stay in splitk_ws[nsplit][M*N] (+ [nsplit][M])
+  // and C is not touched; mmego_slab_reduce (kind 0) adds them later, together with a backward pass's other partial products
+  if (accumulate == 2 && !(nsplit > 1 && nbatch == 1 && !bias && !relu)) return false;
+  if (cmul && nsplit != 1) return false;
+  if (!(relu == 0 || relu == 1 || (relu == 2 && cmul))) return false;
+  return sBiasb == 0 || nsplit == 1;                  // (the split-K reducer applies one shared bias)
+}
+
 extern "C" int mmego_gemm(void* stream, const float* A, long sam, long sak, const float* B, long sbk, long sbn,
                           float* C, long scm, long scn, const float* bias, int M, int N, int K, int nbatch, long sAb,
                           long sBb, long sCb, int relu, int accumulate, float* splitk_ws, int nsplit, long sBiasb,
                           const float* cmul, float* asum) {
-  MMEGO_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && nbatch > 0 && nsplit >= 1);
-  // accumulate == 2: DEFERRED split-K -- the slabs (and the slab row sums behind them) stay in splitk_ws[nsplit][M*N] (+ [nsplit][M])
-  // and C is not touched; mmego_slab_reduce (kind 0) adds them later, together with a backward pass's other partial products
+  MMEGO_REQUIRE(gemm_args_ok(A, B, C, bias, M, N, K, nbatch, relu, accumulate, nsplit, sBiasb, cmul));
   const bool defer = accumulate == 2;
-  MMEGO_REQUIRE(!defer || (nsplit > 1 && nbatch == 1 && !bias && !relu));
-  MMEGO_REQUIRE(!cmul || nsplit == 1);
-  MMEGO_REQUIRE(relu == 0 || relu == 1 || (relu == 2 && cmul));
-  MMEGO_REQUIRE(sBiasb == 0 || nsplit == 1);          // (the split-K reducer applies one shared bias)
   hipStream_t st = (hipStream_t)stream;
   // Large-tile kernels (gemm_tile.hip): 64-aligned shapes with enough work units to be worth a 64x64+ tile, any operand
   // orientation whose contiguous index has unit stride and 16-B aligned rows.
@@ -663,6 +670,11 @@ extern "C" int mmego_gemm_group(void* stream, int n, const MmegoGemmDesc* d) {
   MMEGO_REQUIRE(n >= 1 && d);
   constexpr long tile_min_other = GEMM_TILE_MIN_OTHER;
   constexpr int kq_max = GEMM_KQ_MAX;
+  // an entry mmego_gemm refuses is refused here as well, whichever way the group runs, and before any entry has been launched
+  for (int i = 0; i < n; ++i) {
+    const MmegoGemmDesc& a = d[i];
+    MMEGO_REQUIRE(gemm_args_ok(a.A, a.B, a.C, a.bias, a.M, a.N, a.K, a.nbatch, a.relu, a.accumulate, a.nsplit, a.sBiasb, a.cmul));
+  }
   bool ok = n >= 2 && n <= GEMM_GROUP_MAX;
   const bool akc = d[0].sak == 1, bkc = d[0].sbk == 1;
   GemmGroup g;
@@ -670,7 +682,6 @@ extern "C" int mmego_gemm_group(void* stream, int n, const MmegoGemmDesc* d) {
   int z = 0;
   for (int i = 0; ok && i < n; ++i) {
     const MmegoGemmDesc& a = d[i];
-    if (!(a.A && a.B && a.C && a.M > 0 && a.N > 0 && a.K > 0 && a.nbatch > 0)) return MMEGO_EBADARG;
     const long units64 = (long)(a.M / 64) * (a.N / 64) * a.nbatch;
     const long wgs64 = (long)cdiv(a.M, 64) * cdiv(a.N, 64) * a.nbatch;
     ok = a.nsplit == 1 && (a.sak == 1) == akc && (a.sbk == 1) == bkc && !(akc && bkc) && units64 < tile_min_other &&

@@ -245,6 +245,7 @@ def chain_split(M, N, K):
 
 
 _KQ_MAX = 512               # gemm.hip GEMM_KQ_MAX
+_TILE_MIN_OTHER = 256       # gemm.hip GEMM_TILE_MIN_OTHER
 _PAIR_SPLIT_WGS = 512
 
 
@@ -253,7 +254,7 @@ def asum_ok(M, N, K, nsplit, nbatch=1, over_tile=False):
     can return the row sums of its A operand beside the product."""
     kchunk = -(-(-(-K // nsplit)) // 16) * 16
     wgs64 = ((M + 63) // 64) * ((N + 63) // 64) * nsplit * nbatch
-    tile = M % 64 == 0 and N % 64 == 0 and K % 64 == 0 and (M // 64) * (N // 64) * nsplit * nbatch >= 256
+    tile = M % 64 == 0 and N % 64 == 0 and K % 64 == 0 and (M // 64) * (N // 64) * nsplit * nbatch >= _TILE_MIN_OTHER
     return wgs64 <= _KQ_MAX and kchunk >= 64 and (over_tile or not tile) and M * N < (1 << 16)
 
 
