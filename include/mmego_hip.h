@@ -328,6 +328,45 @@ int mmego_smooth_frames(void* stream, const float* src, long lds, long F, int C,
  * The caller answers for the bone list (ops.smooth_bones checks it on the host); a bone that names a joint outside [0, J) is left out. */
 int mmego_smooth_bones(void* stream, const float* src, long lds, long F, int J, const int* seg, const float* w, int H, int D,
                        const int* bones, const float* bone_len, int NB, float* dst, long ldd, float* moved, int* fallback);
+/* Dense inference's floor (floor.hip; processors.dense_infer with floor=(mode, contact_cm, margin_cm)).  Both kernels read rows of the 8
+ * lower joints, [rows][24]: local joints 0..3 are the global joints 12..15, local 4..7 the global 16..19, so the legs are (hip, knee,
+ * ankle, foot) = (0, 1, 2, 3) and (4, 5, 6, 7) and the feet local 3 and 7.  ground [rows][4] is every row's plane (a, b, c, d) in the
+ * frame of the row's own joints; with n = (a, b, c), nh = n / |n| and dh = d / |n| the height of a point is h(x) = nh . x + dh, in double.
+ * seg [rows] (int32): < 0 marks a row that takes no part.
+ * mmego_floor_stats: lo [rows][24] (row stride ldl) the predicted lower joints, tgt [rows][63] (row stride ldt) the 21-joint target,
+ * contact [rows][2] the recorded contact flags as floats, H > 0 the contact height in metres; out [rows][22] (packed), 11 columns per
+ * foot k, foot 0 first -- foot 0 is local joint 3, target joint 15 and contact[, 0]; foot 1 local 7, target joint 19 and contact[, 1].
+ * With hp = h(predicted foot), ht = h(target foot), c the flag, every comparison strict:
+ *   0 |hp - ht|   1 max(0, -hp)   2 [hp < 0]   3 [hp < H]   4 [hp < H] c   5 c   6 c max(0, hp)
+ *   7 max(0, -ht)   8 [ht < 0]   9 [ht < H]   10 [ht < H] c
+ * A row with seg < 0, or whose |n| is not > 1e-6, writes 22 zeros: the column sums (mmego_colsum) are sums over the rows that count.
+ * Refused: a null pointer, rows < 1 or >= 2^31, ldl < 24, ldt < 63, H not finite or not > 0.
+ * mmego_floor_clamp: dst[r, :24] (row stride ldd; the columns beyond stay) = src[r, :24] (row stride lds) with every leg raised whose
+ * foot or ankle lies under h = margin (metres, >= 0).  dst is src itself (then ldd == lds) or shares no byte with it.  A row with
+ * seg < 0 or |n| <= 1e-6 is copied bit for bit, lifted 0; the bad plane counts a fallback for both legs.  The hips are always copied
+ * bit for bit.  Per leg (Hp, K, A, T):
+ *   lift = max(0, margin - h(T), margin - h(A));  lift == 0: the leg's nine floats are copied bit for bit;  otherwise
+ *   A' = A + lift nh;  l1 = |K - Hp|, l2 = |A - K|, v = A' - Hp, D = |v|, u = v / D;  D <= 1e-9: the leg stays, one FALLBACK;
+ *   Dc = min(max(D, |l1 - l2| + 1e-6 (l1 + l2)), (l1 + l2)(1 - 1e-6));  Dc != D: one FALLBACK -- the target is out of reach, the ankle
+ *        lands at reach along u and the floor is not guaranteed there;
+ *   a = (l1^2 - l2^2 + Dc^2) / (2 Dc), b = sqrt(max(0, l1^2 - a^2));
+ *   w = (K - Hp) minus its component along u;  |w| < 1e-4 l1 (or 0): (T - A) the same way;  that < 1e-4 |T - A| (or 0): the coordinate
+ *        axis with the smallest |u_i|, the first on ties, the same way;  wh = w / |w|;
+ *   K' = Hp + a u + b wh,  A'' = Hp + Dc u,  T' = A'' + (T - A), the foot from the ankle as stored.
+ *   A solve that is not finite (a leg without length) leaves the leg as it was: one FALLBACK, no lift.
+ *   The three joints are stored as floats.  Where that rounding leaves h(A'') or h(T'), taken in double from the stored floats, under
+ *   the margin on a leg without fallback, the solve is repeated with the lift raised by what is missing plus 2^-22 of the largest
+ *   coordinate (more than the rounding of a height), at most twice: the stored feet are not under the margin, and lifted reports the
+ *   lift that was applied, within 1e-6 of the recipe's.
+ * |K' - Hp| = l1, |A'' - K'| = l2 and T' - A'' = T - A; without a fallback h(A'') = h(A) + lift, h(T') = h(T) + lift, both >= margin up
+ * to rounding.  lifted [rows] (float, may be NULL): the larger of the two legs' lifts, 0 where neither moved; fallback [rows] (int32,
+ * may be NULL): the legs that fell back, 0..2.  One thread per row, no atomics: two launches give the same bits.  Refused: a null src,
+ * ground, seg or dst, rows < 1 or >= 2^31, lds or ldd < 24, a margin that is not finite or < 0, dst rows that overlap the src rows
+ * without being them. */
+int mmego_floor_stats(void* stream, const float* lo, long ldl, const float* tgt, long ldt, const float* ground, const float* contact,
+                      const int* seg, long rows, double H, float* out);
+int mmego_floor_clamp(void* stream, const float* src, long lds, const float* ground, const int* seg, long rows, double margin, float* dst,
+                      long ldd, float* lifted, int* fallback);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

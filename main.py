@@ -5,6 +5,7 @@
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
   python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones,rot} --save_pred PATH]]
   python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
+  python main.py --infer --dense --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -38,7 +39,11 @@ rigid frames too, with the twist about every bone kept -- prints the windows' ro
 quaternion per bone and frame (rot), rot_spread and the rest bones (bone_vectors) to PATH; it does not go with --smooth; --smooth H [--smooth_order D
 --smooth_taper {box,gauss}] then filters every recording's stitched frames along time on the device, a zero-phase local polynomial of
 degree D over +-H frames -- of bone directions under --blend_space bones -- and prints the blended frames' figures and the mean
-displacement beside the smoothed ones'), --pose_noise_deg D /
+displacement beside the smoothed ones'; --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M] reads every frame's recorded
+floor plane and foot-contact flags, prints how often and how deep the saved feet lie under the floor, how well "foot lower than H cm"
+reproduces the recorded contacts and how far the flagged feet hover, each beside the recorded skeleton's own figure, and under clamp
+first raises every leg whose foot or ankle lies under M cm on the device, a two-bone solve that keeps the frame's bone lengths; it comes
+behind the blend and the filter, and clamp does not go with --blend_space rot), --pose_noise_deg D /
 --pose_noise_t S (the head pose Upper_Net and Lower_Net get -- the recording's under --gt_head_pose, else the frozen IMU_Net's -- is
 perturbed per frame on the device: a random rotation whose rotation vector has standard deviation D degrees per axis, never beyond 6 D in
 all, and a random shift of standard deviation S metres per component, never beyond 3.47 S.  With --train --network Upper_Net / Lower_Net
@@ -224,14 +229,39 @@ def build_parser():
                    help="--smooth: degree of the local polynomial (default 2; 0 is a weighted moving average)")
     p.add_argument("--smooth_taper", type=str, choices=["box", "gauss"], default=None,
                    help="--smooth: weights of the frames of the window -- box (ones) or gauss (default: exp(-2 k^2 / H^2), sigma H / 2)")
+    p.add_argument("--floor", type=str, choices=["measure", "clamp"], default=None,
+                   help="--dense: hold the saved feet against every frame's recorded floor plane (given in the frame of the frame's own "
+                        "joints; it comes from the recording, as the head pose does under --gt_head_pose) and the recorded foot-contact "
+                        "flags, behind the blend and --smooth.  measure prints the foot height error, the floor penetration rate and "
+                        "depth, precision and recall of 'foot lower than --floor_contact_cm' against the flags and the hover of the "
+                        "flagged feet, with the recorded skeleton's own figures beside them; clamp first raises every leg whose foot or "
+                        "ankle lies under --floor_margin_cm (a two-bone solve on the device that keeps the frame's bone lengths), reports "
+                        "the clamped frames and keeps the unclamped figures beside them (not with --blend_space rot).  --save_pred's file "
+                        "gains foot_height, ground, foot_contact, floor_mode, floor_contact_cm, floor_margin_cm, and under clamp "
+                        "pred_unclamped, lifted, floor_fallback")
+    p.add_argument("--floor_contact_cm", type=float, default=None, metavar="H",
+                   help="--floor: a foot lower than H cm above the floor counts as in contact (default 6, between the flagged and the "
+                        "unflagged feet of the 21 frames the test fixture stores; no claim for the full data)")
+    p.add_argument("--floor_margin_cm", type=float, default=None, metavar="M",
+                   help="--floor clamp: feet and ankles are raised to M cm above the floor (default 0)")
     return p
 
 
 def check_dense(parser, args):
-    """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred and the --smooth flags belong to it."""
+    """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred, the --smooth and the --floor flags belong to it."""
     for flag in ("smooth_order", "smooth_taper"):
         if getattr(args, flag) is not None and args.smooth is None and args.dense:
             parser.error("--%s belongs to --smooth H: without --smooth nothing is filtered" % flag)
+    for flag in ("floor_contact_cm", "floor_margin_cm"):
+        if getattr(args, flag) is not None and args.floor is None and args.dense:
+            parser.error("--%s belongs to --floor {measure,clamp}: without --floor nothing reads the floor" % flag)
+    if args.floor_contact_cm is not None and not 0.0 < args.floor_contact_cm < float("inf"):
+        parser.error("--floor_contact_cm is a height in centimetres, finite and > 0, got %r" % args.floor_contact_cm)
+    if args.floor_margin_cm is not None and not 0.0 <= args.floor_margin_cm < float("inf"):
+        parser.error("--floor_margin_cm is a height in centimetres, finite and >= 0, got %r" % args.floor_margin_cm)
+    if args.dense and args.blend_space == "rot" and args.floor == "clamp":
+        parser.error("--floor clamp does not go with --blend_space rot: the clamp moves joint positions, so the saved rotations would no "
+                     "longer produce pred (--floor measure goes with every space)")
     if args.smooth is not None and not 1 <= args.smooth <= 31:
         parser.error("--smooth is the filter's half-width in frames: it has to lie in [1, 31] (2 H + 1 taps fit one wave), got %d"
                      % args.smooth)
@@ -239,7 +269,8 @@ def check_dense(parser, args):
         parser.error("--smooth does not go with --blend_space rot: the filter runs on joint positions, so the saved rotations would not "
                      "be filtered with the positions (filtering rotations along time is not provided)")
     if not args.dense:
-        for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper"):
+        for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper", "floor", "floor_contact_cm",
+                     "floor_margin_cm"):
             if getattr(args, flag) is not None:
                 parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % flag)
         return
@@ -528,6 +559,8 @@ def apply_overrides(args):
     ConfigDemo.save_pred, ConfigDemo.dense_batch_size, ConfigDemo.blend_space = args.save_pred, args.batch_size, args.blend_space
     ConfigDemo.smooth = None if args.smooth is None else (args.smooth, 2 if args.smooth_order is None else args.smooth_order,
                                                           args.smooth_taper or "gauss")
+    ConfigDemo.floor = None if args.floor is None else (args.floor, 6.0 if args.floor_contact_cm is None else args.floor_contact_cm,
+                                                        0.0 if args.floor_margin_cm is None else args.floor_margin_cm)
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

@@ -199,6 +199,10 @@ class PosePC:
         nf = len(dec["npts"])
         self.frame_pts_, self.frame_npts_ = dec["pts"], np.asarray(dec["npts"], dtype=np.int64)
         self.frame_key_, self.frame_imu_, self.frame_R_ = dec["key"], dec["imu"], dec["R"]
+        # the floor of every frame, in the frame of its own joints (after _decode's sign rule), and the recorded contact flags: column 0
+        # belongs to joint 15, column 1 to joint 19 (dense inference's floor figures read them; nothing else does)
+        self.frame_ground_ = np.asarray(dec["ground"], dtype=np.float32).reshape(nf, 4)
+        self.frame_contact_ = np.asarray(dec["foot"]).reshape(nf, 2, 2)[:, :, 1].astype(np.uint8)
         self.frame_rec_ = np.repeat(np.arange(len(dec["snip_len"]), dtype=np.int64), np.asarray(dec["snip_len"], dtype=np.int64))
         self.frame_bones_ = np.asarray(dec["bones"])
         self.frame_packed_ = (np.asarray(packed, dtype=np.float32).reshape(nf, self.pc_no, 6) if self._keep_frames else None)
@@ -532,6 +536,23 @@ class DenseWindows(DensePlan):
         self.width = {name: self.src[name].shape[1] for name in self.src}
         self.bone_set = np.asarray(dataset.frame_bones_, dtype=np.float32).reshape(-1, 3).copy()     # host: src["skl"] row 0 as [20, 3]
         self._out, self._zero_idx = {}, {}
+        self._dataset, self._floor = dataset, None
+
+    def floor(self):
+        """-> (ground [F, 4], contact [F, 2]): every frame's floor plane and contact flags as fp32 device tensors, uploaded on the first
+        call (dense inference's floor figures; a pass without them never calls this and uploads nothing)."""
+        import torch
+        if self._floor is None:
+            ds = self._dataset
+            if getattr(ds, "frame_ground_", None) is None or getattr(ds, "frame_contact_", None) is None:
+                raise ValueError("DenseWindows.floor needs the loader's frame_ground_ and frame_contact_")
+            ground, contact = np.asarray(ds.frame_ground_), np.asarray(ds.frame_contact_)
+            if ground.shape != (self.F, 4) or contact.shape != (self.F, 2):
+                raise ValueError("DenseWindows.floor: frame_ground_ %s and frame_contact_ %s do not belong to %d frames"
+                                 % (ground.shape, contact.shape, self.F))
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+            self._floor = (up(ground), up(contact))
+        return self._floor
 
     def frame_index(self, index):
         """Host: the frame numbers [len(index) * T] of the windows ``index``."""

@@ -719,6 +719,92 @@ def smooth_bones(src, seg, weights, order, walk, lengths, dst, moved=None, fallb
     return dst
 
 
+FLOOR_W = 22                # floor_math.h FLOOR_W: mmego_floor_stats' columns, 11 per foot
+
+
+def _floor_rows(t, name, rows, C, device, who, packed=False):
+    """One row tensor of the floor launches, checked on the HOST: an fp32 device tensor [rows, >= C] on ``device`` with unit column
+    stride and a row stride of at least its width (``packed``: exactly [rows, C], contiguous).  -> its row stride."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+        raise ValueError("%s: %s is a 2-D fp32 device tensor" % (who, name))
+    if device is not None and t.device != device:
+        raise ValueError("%s: %s lies on %s, the rows on %s" % (who, name, t.device, device))
+    if rows is not None and t.shape[0] != rows:
+        raise ValueError("%s: %s has %d rows for %d" % (who, name, t.shape[0], rows))
+    if t.shape[0] < 1 or (t.shape[1] != C if packed else t.shape[1] < C):
+        raise ValueError("%s: %s is %s, wanted at least one row of %s%d columns" % (who, name, tuple(t.shape), "" if packed else ">= ", C))
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or (packed and not t.is_contiguous()):
+        raise ValueError("%s: %s needs unit column stride and %s" % (who, name, "packed rows" if packed else "rows that do not overlap"))
+    return max(t.stride(0), t.shape[1])
+
+
+def _floor_seg(seg, rows, device, who):
+    """seg of the floor launches: one int32 per row, a host array (uploaded) or a contiguous device tensor."""
+    import numpy as np
+    if isinstance(seg, np.ndarray):
+        if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) != rows:
+            raise ValueError("%s: seg is one int32 per row (%d), got %s %s" % (who, rows, seg.dtype, seg.shape))
+        return torch.as_tensor(np.ascontiguousarray(seg)).to(device)
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 1 and seg.numel() == rows
+            and seg.is_contiguous() and seg.device == device):
+        raise ValueError("%s: seg is one contiguous int32 per row (%d), a host array or a tensor on the rows' device" % (who, rows))
+    return seg
+
+
+def _floor_metres(v, name, who, zero_ok):
+    import math
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+        raise ValueError("%s: %s is a finite number of metres %s 0, got %r" % (who, name, ">=" if zero_ok else ">", v))
+    return float(v)
+
+
+def floor_stats(lo, tgt, ground, contact, seg, H, out):
+    """out [rows, FLOOR_W] = the floor figures of both feet of every row (mmego_floor_stats; the columns are in the header): lo
+    [rows, >= 24] the predicted lower joints, tgt [rows, >= 63] the 21-joint target, ground [rows, 4] the planes and contact [rows, 2]
+    the recorded flags (fp32, packed), seg [rows] int32 (a host array or a device tensor; < 0: the row writes zeros), H > 0 the contact
+    height in metres.  Everything is checked on the host first (ValueError).  The column sums are ops.colsum's."""
+    who = "floor_stats"
+    ldl = _floor_rows(lo, "lo", None, 24, None, who)
+    rows, dev = lo.shape[0], lo.device
+    ldt = _floor_rows(tgt, "tgt", rows, 63, dev, who)
+    _floor_rows(ground, "ground", rows, 4, dev, who, packed=True)
+    _floor_rows(contact, "contact", rows, 2, dev, who, packed=True)
+    _floor_rows(out, "out", rows, FLOOR_W, dev, who, packed=True)
+    seg = _floor_seg(seg, rows, dev, who)
+    H = _floor_metres(H, "H (the contact height)", who, zero_ok=False)
+    hip.call("floor_stats", lo, ldl, tgt, ldt, ground, contact, seg, rows, H, out)
+    return out
+
+
+def floor_clamp(src, ground, seg, margin, dst, lifted=None, fallback=None):
+    """dst[:, :24] = the lower-joint rows src [rows, >= 24] with every leg raised whose foot or ankle lies under ``margin`` metres above
+    the row's plane (mmego_floor_clamp; the two-bone solve is in the header): bone lengths and the foot bone's vector are kept, hips
+    and legs above the floor keep their bits, rows with seg < 0 too.  dst is src itself or shares no byte with it.  lifted [rows] fp32
+    (optional): the larger lift of the two legs; fallback [rows] int32 (optional): the legs that fell back.  Everything is checked on
+    the host first (ValueError)."""
+    who = "floor_clamp"
+    lds = _floor_rows(src, "src", None, 24, None, who)
+    rows, dev = src.shape[0], src.device
+    ldd = _floor_rows(dst, "dst", rows, 24, dev, who)
+    _floor_rows(ground, "ground", rows, 4, dev, who, packed=True)
+    seg = _floor_seg(seg, rows, dev, who)
+    margin = _floor_metres(margin, "margin", who, zero_ok=True)
+    s0, d0 = src.data_ptr(), dst.data_ptr()
+    same = s0 == d0 and lds == ldd
+    if not same and s0 < d0 + 4 * ((rows - 1) * ldd + 24) and d0 < s0 + 4 * ((rows - 1) * lds + 24):
+        raise ValueError("%s: dst overlaps src without being it" % who)
+    if lifted is not None and not (isinstance(lifted, torch.Tensor) and lifted.is_cuda and lifted.dtype == torch.float32 and lifted.dim() == 1
+                                   and lifted.numel() == rows and lifted.is_contiguous() and lifted.device == dev):
+        raise ValueError("%s: lifted is one contiguous fp32 device word per row (%d)" % (who, rows))
+    if fallback is not None and not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32
+                                     and fallback.dim() == 1 and fallback.numel() == rows and fallback.is_contiguous()
+                                     and fallback.device == dev):
+        raise ValueError("%s: fallback is one contiguous int32 device word per row (%d)" % (who, rows))
+    hip.call("floor_clamp", src, lds, ground, seg, rows, margin, dst, ldd, lifted, fallback)
+    return dst
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

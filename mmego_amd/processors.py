@@ -894,8 +894,53 @@ def _check_smooth(smooth):
     return int(H), int(order), taper
 
 
+FLOOR_MODES = ("measure", "clamp")
+
+
+def _check_floor(floor):
+    """floor = (mode, contact_cm, margin_cm) of dense_infer, or None.  -> (mode, contact height, margin), the two in plain floats."""
+    if floor is None:
+        return None
+    if not (isinstance(floor, (tuple, list)) and len(floor) == 3):
+        raise ValueError("floor: (mode, contact_cm, margin_cm), got %r" % (floor,))
+    mode, contact_cm, margin_cm = floor
+    if mode not in FLOOR_MODES:
+        raise ValueError("floor: mode %r is not one of %s" % (mode, ", ".join(FLOOR_MODES)))
+    for name, v, zero_ok in (("contact_cm", contact_cm, False), ("margin_cm", margin_cm, True)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+            raise ValueError("floor: %s is a finite number of centimetres %s 0, got %r" % (name, ">=" if zero_ok else ">", v))
+    return mode, float(contact_cm), float(margin_cm)
+
+
+FLOOR_KEYS = ("foot_height_err_cm", "penetration_rate", "penetration_cm", "contact_precision", "contact_recall", "hover_cm")
+FLOOR_TARGET_KEYS = ("target_penetration_rate", "target_penetration_cm", "target_contact_precision", "target_contact_recall")
+
+
+def _floor_summary(sums, n, prefix="", target=False):
+    """The floor figures from the column sums [22] of ops.floor_stats over ``n`` rows that count: every key of FLOOR_KEYS pooled over
+    both feet under ``prefix`` + key, and per foot as a pair (joint 15, joint 19) under ``prefix`` + key + "_per_foot"; None where a
+    denominator is 0.  ``target``: FLOOR_TARGET_KEYS as well, the recorded skeleton's own figures (never prefixed)."""
+    s = np.asarray(sums, dtype=np.float64).reshape(2, 11)
+    ratio = lambda a, b, scale=1.0: None if b == 0 else float(a) / float(b) * scale
+
+    def figures(c, rows):
+        out = {"foot_height_err_cm": ratio(c[0], rows, 100.0), "penetration_rate": ratio(c[2], rows), "penetration_cm": ratio(c[1], c[2], 100.0),
+               "contact_precision": ratio(c[4], c[3]), "contact_recall": ratio(c[4], c[5]), "hover_cm": ratio(c[6], c[5], 100.0)}
+        tgt = {"target_penetration_rate": ratio(c[8], rows), "target_penetration_cm": ratio(c[7], c[8], 100.0),
+               "target_contact_precision": ratio(c[10], c[9]), "target_contact_recall": ratio(c[10], c[5])}
+        return out, tgt
+
+    pooled, feet = figures(s.sum(axis=0), 2 * n), [figures(s[k], n) for k in (0, 1)]
+    res = {}
+    for i, (keys, pre) in enumerate(((FLOOR_KEYS, prefix), (FLOOR_TARGET_KEYS, ""))[:2 if target else 1]):
+        for k in keys:
+            res[pre + k] = pooled[i][k]
+            res[pre + k + "_per_foot"] = (feet[0][i][k], feet[1][i][k])
+    return res
+
+
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None):
+                pose_noise=None, imu_noise=None, smooth=None, floor=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -941,6 +986,22 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     the filter moved a frame, smooth itself and smooth_fallback, the bones that kept their own frame's direction (0 in the column
     form); the arrays gain pred_unsmoothed [F, 21, 3] and moved [F].  None (the default): no launch, no key, the bytes of the pass
     without the argument.
+    floor=(mode, contact_cm, margin_cm): the pass's notion of the ground, behind the blend and the filter.  Every frame's floor plane
+    and contact flags come from the recording (DenseWindows.floor: the plane is given in the frame of the frame's own joints, so a
+    joint's height is n . x + d), as the head pose does under --gt_head_pose.  mode "measure": ops.floor_stats on the final frames and
+    on the window rows; the summary gains, pooled over both feet and as pairs (joint 15, joint 19) under key + "_per_foot",
+    foot_height_err_cm (mean |h(prediction) - h(target)|), penetration_rate (feet under the plane per covered frame and foot),
+    penetration_cm (the mean depth over the penetrating feet), contact_precision / contact_recall of "height < contact_cm" against the
+    recorded flags, hover_cm (the mean height above the plane of the flagged feet), the same under single_ for the window rows, the
+    recorded skeleton's own target_penetration_rate, target_penetration_cm, target_contact_precision, target_contact_recall (the noise
+    floor of the plane fit), None where a denominator is 0, and floor itself; the arrays gain foot_height [F, 2] of the final frames
+    (NaN where uncovered), ground [F, 4] and foot_contact [F, 2].  mode "clamp": ops.floor_clamp first raises every leg of the final
+    lower frames whose foot or ankle lies under margin_cm, keeping the frame's own bone lengths; everything above then runs on the
+    clamped frames, the frames before the clamp keep their figures under unclamped_ (the error figures and the floor figures; and
+    unclamped_accel_cm under metrics="full"), the summary gains lift_cm (the mean lift over the lifted frames, None without one),
+    lifted_frames and floor_fallback (the legs whose target was out of reach), the arrays pred_unclamped [F, 21, 3], lifted [F] and
+    floor_fallback [F].  "clamp" under blend_space="rot" is refused (ValueError): the saved rotations would no longer produce pred.
+    None (the default): no launch, no upload, no key, the bytes of the pass without the argument.
     The figures come down in one read; the per-frame arrays in one each."""
     from .data import DenseWindows
     if metrics not in METRICS:
@@ -951,6 +1012,10 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     if blend_space == "rot" and smooth is not None:
         raise ValueError("smooth: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
                          "filtered with them; filtering rotations along time is not done here")
+    floor = _check_floor(floor)
+    if blend_space == "rot" and floor is not None and floor[0] == "clamp":
+        raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
+                         "produce pred; \"measure\" goes with every space")
     dev = base.device
     plan = DenseWindows(dataset, dev, stride, blend)
     W, T, F = plan.W, plan.T, plan.F
@@ -961,14 +1026,15 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise, smooth)
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise, smooth,
+                           floor)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
 
 
 def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None, imu_noise=None,
-                smooth=None):
+                smooth=None, floor=None):
     """dense_infer behind its argument checks: the nets are in eval mode."""
     dev = base.device
     W, T, F = plan.W, plan.T, plan.F
@@ -1042,6 +1108,17 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             else:
                 ops.smooth_frames(up_b, seg, wts, order, up_f, moved)
                 ops.smooth_frames(lo_b, seg, wts, order, lo_f)
+        clamp = floor is not None and floor[0] == "clamp"
+        if floor is not None:
+            # the ground: the plane and the flags of every frame, the segments the filter uses (covered: the recording, else none)
+            ground, contact = plan.floor()
+            if smooth is None:
+                seg = torch.as_tensor(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)).to(dev)
+            if clamp:
+                lo_u = lo_f                                        # the frames before the clamp: their figures are kept beside the clamped ones'
+                lo_f, lifted = f32(F, 24), f32(F)
+                fell_f = torch.zeros(F, dtype=torch.int32, device=dev)
+                ops.floor_clamp(lo_u, ground, seg, floor[2] / 100.0, lo_f, lifted, fell_f)
         tgt_f = plan.src["target"]                                 # [F, 63]
         cov = np.flatnonzero(plan.covered)
         Fc = len(cov)
@@ -1053,13 +1130,15 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         full = metrics == "full"
         WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
         n_log = 3 + T + (2 if blend_space is not None else 0) + (1 if rot else 0)      # (smooth: two more rows behind these)
-        log = torch.zeros((n_log + (2 if smooth is not None else 0), max(43, WA)), dtype=torch.float32, device=dev)
+        n_fl = n_log + (2 if smooth is not None else 0)            # (floor: two more rows behind these, four under the clamp)
+        log = torch.zeros((n_fl + (0 if floor is None else 4 if clamp else 2), max(43, WA)), dtype=torch.float32, device=dev)
         E = f32(Fc, 43)
         hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
         ops.colsum(E, log[0, :43])
         ops.colsum(spread_c, log[1, :1])
         # the unblended window rows: the same kernel, then by position in the window
-        tgt_w = ops.gather_rows(tgt_f, torch.as_tensor(plan.row_frame).to(dev), f32(W * T, 63))
+        row_idx = torch.as_tensor(plan.row_frame).to(dev)
+        tgt_w = ops.gather_rows(tgt_f, row_idx, f32(W * T, 63))
         Ew = f32(W * T, 43)
         hip.call("pose_errors", win_up, win_lo, tgt_w, W * T, Ew)
         ops.colsum(Ew, log[2, :43])
@@ -1086,6 +1165,23 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
             hip.call("pose_errors", up_bc, lo_bc, tgt_c, Fc, Eb)
             ops.colsum(Eb, log[n_log, :43])
             ops.colsum(moved_c, log[n_log + 1, :1])
+        if floor is not None:
+            # the feet against the plane: the final frames (an uncovered row writes zeros, so the sums are the covered frames'), the
+            # window rows with their frames' planes and flags, and under the clamp the frames before it with their error figures
+            Hc = floor[1] / 100.0
+            St, Sw = f32(F, ops.FLOOR_W), f32(W * T, ops.FLOOR_W)
+            ops.floor_stats(lo_f, tgt_f, ground, contact, seg, Hc, St)
+            ops.colsum(St, log[n_fl, :ops.FLOOR_W])
+            ground_w, contact_w = ops.gather_rows(ground, row_idx, f32(W * T, 4)), ops.gather_rows(contact, row_idx, f32(W * T, 2))
+            ops.floor_stats(win_lo, tgt_w, ground_w, contact_w, torch.zeros(W * T, dtype=torch.int32, device=dev), Hc, Sw)
+            ops.colsum(Sw, log[n_fl + 1, :ops.FLOOR_W])
+            if clamp:
+                Su, Eu = f32(F, ops.FLOOR_W), f32(Fc, 43)
+                ops.floor_stats(lo_u, tgt_f, ground, contact, seg, Hc, Su)
+                ops.colsum(Su, log[n_fl + 2, :ops.FLOOR_W])
+                lo_uc = lo_u if Fc == F else ops.gather_rows(lo_u, cidx, f32(Fc, 24))
+                hip.call("pose_errors", up_c, lo_uc, tgt_c, Fc, Eu)
+                ops.colsum(Eu, log[n_fl + 3, :43])
         if full:
             thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
             A = f32(Fc, WA)
@@ -1109,6 +1205,18 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         summary.update(_error_summary(out[n_log, :43], Fc, "unsmoothed_"))
         smooth_fallback = int(fell_s.cpu().numpy().sum()) if blend_space == "bones" else 0
         summary.update(moved_cm=float(out[n_log + 1, 0]) / Fc * 100, smooth=smooth, smooth_fallback=smooth_fallback)
+    if floor is not None:
+        summary.update(_floor_summary(out[n_fl, :ops.FLOOR_W], Fc, target=True))
+        summary.update(_floor_summary(out[n_fl + 1, :ops.FLOOR_W], W * T, "single_"))
+        summary["floor"] = (floor[0], floor[1], floor[2])
+        if clamp:
+            summary.update(_floor_summary(out[n_fl + 2, :ops.FLOOR_W], Fc, "unclamped_"))
+            summary.update(_error_summary(out[n_fl + 3, :43], Fc, "unclamped_"))
+            # (lifts and fallback counts are per-frame arrays: they come down in their one read each)
+            lifted_h, fell_h = lifted.cpu().numpy(), fell_f.cpu().numpy()
+            up_frames = int((lifted_h > 0).sum())
+            summary.update(lift_cm=None if up_frames == 0 else float(lifted_h[lifted_h > 0].astype(np.float64).mean()) * 100,
+                           lifted_frames=up_frames, floor_fallback=int(fell_h.sum()))
     if full:
         spans = [(a, b) for a, b in zip(plan.rec_off[:-1], plan.rec_off[1:]) if b - a >= T]      # the covered recordings, whole
         acc = _accel_over_sequences(dev, up_f, lo_f, tgt_f, spans)
@@ -1117,6 +1225,9 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
         if smooth is not None:
             acc = _accel_over_sequences(dev, up_b, lo_b, tgt_f, spans)
             summary["unsmoothed_accel_cm"] = None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100     # (aligned_summary's mean)
+        if clamp:
+            acc = _accel_over_sequences(dev, up_f, lo_u, tgt_f, spans)
+            summary["unclamped_accel_cm"] = None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100
         summary["single_accel_cm"] = None
         if plan.stride == T:
             # the reference's windows of a recording are its last len // T windows: consecutive rows of the window tensors
@@ -1148,7 +1259,27 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, me
                       win_R=win_R)
     if smooth is not None:
         arrays.update(pred_unsmoothed=pred_b, moved=moved.cpu().numpy())
+    if floor is not None:
+        ground_h, contact_h = ground.cpu().numpy(), contact.cpu().numpy()
+        arrays.update(foot_height=foot_heights(lo_h[:, [3, 7]], ground_h, plan.covered != 0), ground=ground_h, foot_contact=contact_h)
+        if clamp:
+            pred_u = pred.copy()
+            pred_u[:, list(base.cfg.lower_joint_map)] = lo_u.cpu().numpy().reshape(F, 8, 3)
+            pred_u[plan.covered == 0] = np.nan
+            arrays.update(pred_unclamped=pred_u, lifted=lifted_h, floor_fallback=fell_h)
     return summary, arrays
+
+
+def foot_heights(feet, ground, covered):
+    """Heights [F, 2] (float32, from float64) of the feet [F, 2, 3] above the planes ground [F, 4], n . x + d with n normalised; NaN
+    where ``covered`` is false or the plane has no normal (|n| <= 1e-6)."""
+    g = np.asarray(ground, dtype=np.float64)
+    norm = np.linalg.norm(g[:, :3], axis=1)
+    ok = np.asarray(covered, dtype=bool) & (norm > 1e-6)
+    safe = np.where(norm > 1e-6, norm, 1.0)
+    h = (np.einsum("fki,fi->fk", np.asarray(feet, dtype=np.float64), g[:, :3]) + g[:, 3:4]) / safe[:, None]
+    h[~ok] = np.nan
+    return h.astype(np.float32)
 
 
 DENSE_SAVED = ("pred", "covered", "spread", "recording", "frame_in_recording", "target")      # --save_pred: the per-frame arrays of the file
@@ -1176,6 +1307,9 @@ class Evaluator(_Base):
         space = getattr(cfg, "blend_space", None)
         smooth = getattr(cfg, "smooth", None)
         more_args = {} if smooth is None else dict(smooth=smooth)
+        floor = getattr(cfg, "floor", None)
+        if floor is not None:
+            more_args["floor"] = floor
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space,
                                 pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg), **more_args)
@@ -1208,6 +1342,11 @@ class Evaluator(_Base):
             if smooth is not None:
                 more.update(pred_unsmoothed=arrays["pred_unsmoothed"], moved=arrays["moved"], smooth_window=np.int64(smooth[0]),
                             smooth_order=np.int64(smooth[1]), smooth_taper=np.asarray(smooth[2]))
+            if floor is not None:
+                more.update(foot_height=arrays["foot_height"], ground=arrays["ground"], foot_contact=arrays["foot_contact"],
+                            floor_mode=np.asarray(floor[0]), floor_contact_cm=np.float64(floor[1]), floor_margin_cm=np.float64(floor[2]))
+                if floor[0] == "clamp":
+                    more.update(pred_unclamped=arrays["pred_unclamped"], lifted=arrays["lifted"], floor_fallback=arrays["floor_fallback"])
             if noise is not None:
                 more.update(pose_noise_deg=np.float64(noise[0]), pose_noise_t=np.float64(noise[1]), pose_noise_seed=np.int64(noise[2]))
             if imu_noise is not None:
@@ -1226,6 +1365,20 @@ class Evaluator(_Base):
                 s["moved_cm"], s["smooth"][0], s["smooth"][1], s["smooth"][2], s["smooth_fallback"]))
             if self._metrics() == "full":
                 print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
+        if floor is not None:
+            print("Foot Height Error(cm): {} (joint 15: {}, joint 19: {}; single-window {})".format(
+                s["foot_height_err_cm"], *s["foot_height_err_cm_per_foot"], s["single_foot_height_err_cm"]))
+            print("Floor Penetration: rate {} depth(cm) {} (target: rate {} depth {}; single-window: rate {} depth {})".format(
+                s["penetration_rate"], s["penetration_cm"], s["target_penetration_rate"], s["target_penetration_cm"],
+                s["single_penetration_rate"], s["single_penetration_cm"]))
+            print("Foot Contact by height < {:g} cm: precision {} recall {} (target: precision {} recall {})".format(
+                floor[1], s["contact_precision"], s["contact_recall"], s["target_contact_precision"], s["target_contact_recall"]))
+            print("Contact Hover(cm): {}".format(s["hover_cm"]))
+            if floor[0] == "clamp":
+                print("Unclamped Error(cm): all {} lower {} (penetration rate {} depth(cm) {})".format(
+                    s["unclamped_all_cm"], s["unclamped_lower_cm"], s["unclamped_penetration_rate"], s["unclamped_penetration_cm"]))
+                print("Floor Clamp: {} of {} frames lifted, mean lift(cm) {}, unreachable legs {} (margin {:g} cm)".format(
+                    s["lifted_frames"], s["covered_frames"], s["lift_cm"], s["floor_fallback"], floor[2]))
         return s
 
     def _print_aligned(self, s):
