@@ -156,7 +156,7 @@ int mmego_pack_frames(void* stream, const float* pts, const long long* frame_off
  * output, bit for bit. */
 int mmego_pack_frames_noise(void* stream, const float* pts, const long long* frame_off, const long long* frame_idx, long nout,
                             int pc_no, int max_n, float keep_p, unsigned long long seed, float sigma_xyz, float sigma_v, float* out);
-/* Head-pose noise (pose_noise.hip; train_step.StageStep under pose_noise_deg / pose_noise_t, processors._epoch_eval and dense_infer under
+/* Head-pose noise (pose_noise.hip; train_step.StageStep under pose_noise_deg / pose_noise_t, processors._epoch_eval and dense.dense_infer under
  * pose_noise): row i = 0 .. n-1 of the head poses R [n][3][3] (row-major) and t [n][3] perturbed into R_out, t_out.  seed_word is ONE
  * int64 word ON THE DEVICE, read by the kernel: a launch captured into a HIP graph sees the word the host wrote before the replay (the
  * convention of mmego_seed_take / mmego_lstm_dropout).  ids (int64 on the device, may be NULL) gives every row its draw number
@@ -178,7 +178,7 @@ int mmego_pack_frames_noise(void* stream, const float* pts, const long long* fra
  * than R_out == R or t_out == t exactly (a thread reads its row before it writes it); R_out overlapping t_out. */
 int mmego_pose_jitter(void* stream, const float* R, const float* t, long n, double sigma_deg, double sigma_t,
                       const long long* seed_word, const long long* ids, float* R_out, float* t_out);
-/* IMU sensor noise and bias (imu_noise.hip; train_step.ImuStep / StageStep under imu_noise, processors._epoch_eval and dense_infer under
+/* IMU sensor noise and bias (imu_noise.hip; train_step.ImuStep / StageStep under imu_noise, processors._epoch_eval and dense.dense_infer under
  * imu_noise): the IMU samples imu [n_rows][S][15] that IMU_Net reads perturbed into out.  A row is one frame, n_rows = B T rows in B
  * windows of T (row i belongs to window i / T), a frame has S samples, a sample is 15 floats: the orientation O [3][3] row-major
  * (channels 0 .. 8), the accelerometer (9 .. 11), the gyroscope (12 .. 14).  Every sample gets WHITE noise of its own and the BIAS of its
@@ -207,7 +207,7 @@ int mmego_imu_jitter(void* stream, const float* imu, long n_rows, int T, int S,
                      double bias_rot_deg, double bias_acc, double bias_gyro,
                      const long long* seed_word, const long long* row_ids, const long long* win_ids,
                      float* out);
-/* Dense inference (blend.hip; processors.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
+/* Dense inference (blend.hip; dense.dense_infer): every frame's row blended from the rows of the overlapping windows that cover it.
  * src [nrows][C] contiguous; the cover of frame f = 0 .. F-1 is the CSR list k in [cov_off[f], cov_off[f+1]) (int64 offsets) of source
  * rows cov_row[k] (int32) with weights cov_w[k]:
  *   dst[f, c] = (sum_k w_k src[row_k, c]) / (sum_k w_k), c < C; the columns of dst[f] (row stride ldd) beyond C are not touched;
@@ -226,7 +226,7 @@ int mmego_blend_windows(void* stream, const float* src, long nrows, int C, const
  * One workgroup per phase: its rows are dealt round-robin to 16 waves, each sums its share in ascending order in double, the 16
  * partial sums are added in wave order, one float store (two launches give the same bits; no workspace, no atomics). */
 int mmego_colsum_phase(void* stream, const float* X, long ldx, long rows, int C, int period, float* out, long ldo);
-/* The same blend with every bone's length kept (blend_bones.hip; processors.dense_infer under blend_space="bones").  src [nrows][3 J]
+/* The same blend with every bone's length kept (blend_bones.hip; dense.dense_infer under blend_space="bones").  src [nrows][3 J]
  * holds rigid skeletons of J joints (3-vectors x_j) and the cover is mmego_blend_windows'; bones [NB][2] (int32, on the device) lists
  * (child, parent) joint numbers in walk order -- every joint a child at most once, every parent a root (a joint that is no bone's child)
  * or an earlier bone's child -- and bone_len [NB] (float, on the device) the lengths L_b.  Per frame, with its valid entries k (those
@@ -253,7 +253,7 @@ int mmego_blend_bones(void* stream, const float* src, long nrows, int J, const l
  * Refused: null pointers, n < 1 or >= 2^26, J outside [1, 21], NB outside [1, J - 1], ldx < 3 J, ldo < NB. */
 int mmego_bone_length_dev(void* stream, const float* X, long ldx, long n, int J, const int* bones, const float* bone_len, int NB,
                           float* out, long ldo);
-/* The blend in ROTATION space (blend_rot.hip; processors.dense_infer under blend_space="rot"): every bone's world-frame rotation
+/* The blend in ROTATION space (blend_rot.hip; dense.dense_infer under blend_space="rot"): every bone's world-frame rotation
  * averaged over the cover, the nets' forward kinematics run once on the averages.  src [nrows][3 J] and the cover are
  * mmego_blend_bones'; q [nrows][NQ][9] holds the rotations the net predicted for every row (row-major 3 x 3, head frame), Rh [nrows][9]
  * the head rotation every row was run with (the head-to-world transform is p <- Rh^T p + t); bones [NB][2] (int32, on the device) is
@@ -294,7 +294,7 @@ int mmego_bone_length_dev(void* stream, const float* X, long ldx, long n, int J,
 int mmego_blend_rot(void* stream, const float* src, long nrows, int J, const float* q, int NQ, const float* Rh,
                     const long long* cov_off, const int* cov_row, const float* cov_w, long F, const int* bones, const int* rot_idx,
                     const float* body, int NB, float* dst, long ldd, float* quat, float* spread, float* rot_spread, int* fallback);
-/* Dense inference's temporal smoothing (smooth.hip; processors.dense_infer with smooth=(H, order, taper)): a zero-phase local-polynomial
+/* Dense inference's temporal smoothing (smooth.hip; dense.dense_infer with smooth=(H, order, taper)): a zero-phase local-polynomial
  * filter along the frames.  src [F][C] (row stride lds), seg [F] (int32) the segment of every frame (-1: none), w [2 H + 1] (float,
  * positive and finite; the host makes the taper, ops.smooth_frames checks it) the weights of the taps k = -H .. H.  Per frame f:
  *   tap k is VALID when 0 <= f + k < F and seg[f + k] == seg[f] >= 0; n of them;
@@ -312,7 +312,7 @@ int mmego_blend_rot(void* stream, const float* src, long nrows, int J, const flo
  * outside [1, 31], D outside [0, 2], moved with C % 3 != 0, dst rows that overlap the src rows (the filter cannot run in place). */
 int mmego_smooth_frames(void* stream, const float* src, long lds, long F, int C, const int* seg, const float* w, int H, int D,
                         float* dst, long ldd, float* moved);
-/* The same filter with every bone's length kept (processors.dense_infer under blend_space="bones"): src [F][3 J] holds skeletons of J
+/* The same filter with every bone's length kept (dense.dense_infer under blend_space="bones"): src [F][3 J] holds skeletons of J
  * joints, bones [NB][2] and bone_len [NB] are mmego_blend_bones' walk table and lengths.  Per frame, with n, deg and c_k as above:
  *   n <= 1: the row bit for bit, moved 0, fallback 0;   otherwise
  *   a root r:            pos_r = sum_k c_k x_kr, mmego_smooth_frames' own arithmetic: those columns carry the same bits;
@@ -328,7 +328,7 @@ int mmego_smooth_frames(void* stream, const float* src, long lds, long F, int C,
  * The caller answers for the bone list (ops.smooth_bones checks it on the host); a bone that names a joint outside [0, J) is left out. */
 int mmego_smooth_bones(void* stream, const float* src, long lds, long F, int J, const int* seg, const float* w, int H, int D,
                        const int* bones, const float* bone_len, int NB, float* dst, long ldd, float* moved, int* fallback);
-/* Dense inference's floor (floor.hip; processors.dense_infer with floor=(mode, contact_cm, margin_cm)).  Both kernels read rows of the 8
+/* Dense inference's floor (floor.hip; dense.dense_infer with floor=(mode, contact_cm, margin_cm)).  Both kernels read rows of the 8
  * lower joints, [rows][24]: local joints 0..3 are the global joints 12..15, local 4..7 the global 16..19, so the legs are (hip, knee,
  * ankle, foot) = (0, 1, 2, 3) and (4, 5, 6, 7) and the feet local 3 and 7.  ground [rows][4] is every row's plane (a, b, c, d) in the
  * frame of the row's own joints; with n = (a, b, c), nh = n / |n| and dh = d / |n| the height of a point is h(x) = nh . x + dh, in double.

@@ -89,7 +89,7 @@ class Config(_Common):
 class ConfigDemo(_Common):
     Idx = 1
     batch_per_action = 3
-    dense = False               # --dense: sliding-window inference over whole recordings (processors.dense_infer)
+    dense = False               # --dense: sliding-window inference over whole recordings (dense.dense_infer)
     stride = None               # --stride: frames between window starts (None: frame_no // 2)
     blend = "mean"              # --blend: mean or triangle
     blend_space = None          # --blend_space: joints, bones or rot (None: joints, without the bone-length figures)

@@ -1,4 +1,4 @@
-// Dense inference (processors.dense_infer): every frame's pose blended from the overlapping windows that cover it, and the per-row
+// Dense inference (dense.dense_infer): every frame's pose blended from the overlapping windows that cover it, and the per-row
 // error table of all windows folded by position in the window.  Both kernels are memory-bound gathers of whole rows of at most 64
 // floats: one lane per column, so a row is one coalesced read of the wave; no atomics, every sum in a fixed order (two launches give
 // the same bits), double inside, one float store.  The arithmetic per column is blend_math.h; the recipe is the comment of the two

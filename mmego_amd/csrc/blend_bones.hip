@@ -1,4 +1,4 @@
-// Dense inference's bone-length-preserving blend (processors.dense_infer, blend_space="bones"): every frame's skeleton from the window
+// Dense inference's bone-length-preserving blend (dense.dense_infer, blend_space="bones"): every frame's skeleton from the window
 // rows that cover it, its roots blended as mmego_blend_windows blends them, every bone's DIRECTION blended over the cover, set to the
 // body's bone length and laid along the kinematic tree -- rotation about a bone's own axis moves no joint, so directions are all a
 // rigid blend of joints needs.  And the check of the result: every row's deviation from the bone lengths.  Like blend.hip a memory-bound
@@ -8,6 +8,7 @@
 // points in include/mmego_hip.h, tests/bone_blend_ref.py restates it in numpy.
 #include "common.h"
 #include "bone_blend_math.h"
+#include "skeleton_walk.h"
 
 #define BB_WAVES 4                       // one wave per output frame, four per workgroup (no barrier: a wave behind F leaves)
 
@@ -24,12 +25,8 @@ __global__ __launch_bounds__(64 * BB_WAVES) void blend_bones_kernel(const float*
   const int C = 3 * J;
   const bool joint = lane < J;
   const int j = joint ? lane : 0;        // (the lanes behind the row re-read joint 0 and store nothing)
-  // this lane's bone: the one whose child it is (a bone that names a joint outside the row is left out: its child stays a root)
-  int mine = -1, parent = -1;
-  for (int b = 0; b < NB; ++b) {
-    const int c = bones[2 * b], p = bones[2 * b + 1];
-    if (c == j && p >= 0 && p < J && p != c) mine = b, parent = p;
-  }
+  int mine, parent;                      // this lane's bone: the one whose child it is
+  sw_lane_bone(bones, NB, J, lane, &mine, &parent);
   double s[3], best[3], u[3] = {0.0, 0.0, 0.0}, pos[3] = {0.0, 0.0, 0.0}, W;
   int n;
   long one;
@@ -45,15 +42,9 @@ __global__ __launch_bounds__(64 * BB_WAVES) void blend_bones_kernel(const float*
       double ws;
       for (int i = 0; i < 3; ++i) pos[i] = bl_blend_col(src, nrows, C, cov_row, cov_w, k0, k1, 3 * j + i, &ws);
     }
-    for (int b = 0; b < NB; ++b) {       // the walk: bone b's child from its parent, parents before children
-      const int p = bones[2 * b + 1];
-      if (p < 0 || p >= J) continue;     // (the same for every lane)
-      const double p0 = shfl_d(pos[0], p), p1 = shfl_d(pos[1], p), p2 = shfl_d(pos[2], p);
-      if (joint && b == mine) pos[0] = p0 + L * u[0], pos[1] = p1 + L * u[1], pos[2] = p2 + L * u[2];
-    }
+    sw_walk(bones, NB, J, mine, L, u, pos);
   }
-  if (joint)
-    for (int i = 0; i < 3; ++i) dst[f * ldd + 3 * lane + i] = (float)pos[i];
+  sw_store(dst + f * ldd, J, lane, pos);
   if (spread) {
     double q = 0.0;
     if (joint)
@@ -61,10 +52,7 @@ __global__ __launch_bounds__(64 * BB_WAVES) void blend_bones_kernel(const float*
     q = wave_sum_d(q);
     if (lane == 0) spread[f] = bl_spread(q, W, C);   // (no entry, or weights that sum to zero: 0)
   }
-  if (fallback) {
-    const int count = __popcll(__ballot(joint && fell));
-    if (lane == 0) fallback[f] = count;
-  }
+  if (fallback) sw_count(fallback + f, lane, mine >= 0 && fell);
 }
 
 __global__ __launch_bounds__(256) void bone_length_dev_kernel(const float* __restrict__ X, long ldx, long n, int J,

@@ -1,4 +1,4 @@
-// Dense inference's blend in rotation space (processors.dense_infer, blend_space="rot"): every frame's skeleton from the ROTATIONS the
+// Dense inference's blend in rotation space (dense.dense_infer, blend_space="rot"): every frame's skeleton from the ROTATIONS the
 // nets predicted for it in the windows that cover it.  Per bone the world-frame rotations Rh^T q of the cover are averaged -- the
 // weighted chordal mean, the proper rotation nearest their weighted sum, whose quaternion is the top eigenvector of a symmetric 4 x 4
 // matrix (quat_eig.h) -- and the nets' own forward kinematics lays the rest bones along the averaged rotations from the vector-blended
@@ -9,6 +9,7 @@
 // entry point in include/mmego_hip.h, tests/rot_blend_ref.py restates it in numpy by another method (SVD).
 #include "common.h"
 #include "rot_blend_math.h"
+#include "skeleton_walk.h"
 
 #define BR_WAVES 4                       // one wave per output frame, four per workgroup (no barrier: a wave behind F leaves)
 
@@ -28,13 +29,10 @@ __global__ __launch_bounds__(64 * BR_WAVES) void blend_rot_kernel(const float* _
   const int C = 3 * J;
   const bool joint = lane < J;
   const int j = joint ? lane : 0;        // (the lanes behind the row re-read joint 0 and store nothing)
-  // this lane's bone: the one whose child it is (a bone that names a joint outside the row, or a rotation outside the NQ of a row,
-  // is left out: its child stays a root)
-  int mine = -1, ri = -1;
-  for (int b = 0; b < NB; ++b) {
-    const int c = bones[2 * b], p = bones[2 * b + 1], r = rot_idx[b];
-    if (joint && c == j && p >= 0 && p < J && p != c && r >= 0 && r < NQ) mine = b, ri = r;
-  }
+  int mine, parent;                      // this lane's bone: the one whose child it is; one whose rotation lies outside the NQ of a
+  sw_lane_bone(bones, NB, J, lane, &mine, &parent);      // row is left out as well: its child stays a root
+  int ri = mine >= 0 ? rot_idx[mine] : -1;
+  if (ri < 0 || ri >= NQ) mine = ri = -1;
   double S[9], best[9], Q[9], qm[4] = {0.0, 0.0, 0.0, 0.0}, lay[3] = {0.0, 0.0, 0.0}, pos[3] = {0.0, 0.0, 0.0}, W;
   int n;
   long one;
@@ -53,15 +51,9 @@ __global__ __launch_bounds__(64 * BR_WAVES) void blend_rot_kernel(const float* _
       double ws;
       for (int i = 0; i < 3; ++i) pos[i] = bl_blend_col(src, nrows, C, cov_row, cov_w, k0, k1, 3 * j + i, &ws);
     }
-    for (int b = 0; b < NB; ++b) {       // the walk: bone b's child from its parent, parents before children
-      const int p = bones[2 * b + 1];
-      if (p < 0 || p >= J) continue;     // (the same for every lane)
-      const double p0 = shfl_d(pos[0], p), p1 = shfl_d(pos[1], p), p2 = shfl_d(pos[2], p);
-      if (b == mine) pos[0] = p0 + lay[0], pos[1] = p1 + lay[1], pos[2] = p2 + lay[2];
-    }
+    sw_walk(bones, NB, J, mine, 1.0, lay, pos);      // (1.0 * x rounds to x, and fma(1.0, x, p) as p + x does)
   }
-  if (joint)
-    for (int i = 0; i < 3; ++i) dst[f * ldd + 3 * lane + i] = (float)pos[i];
+  sw_store(dst + f * ldd, J, lane, pos);
   if (mine >= 0)                         // (no cover: the zero quaternion)
     reinterpret_cast<float4*>(quat)[f * NB + mine] = make_float4((float)qm[0], (float)qm[1], (float)qm[2], (float)qm[3]);
   if (spread) {
@@ -77,10 +69,7 @@ __global__ __launch_bounds__(64 * BR_WAVES) void blend_rot_kernel(const float* _
     s = wave_sum_d(s);
     if (lane == 0) rot_spread[f] = br_rot_spread(s, W, NB);       // (a frame covered once has nothing to disagree with: 0)
   }
-  if (fallback) {
-    const int count = __popcll(__ballot(mine >= 0 && fell));
-    if (lane == 0) fallback[f] = count;
-  }
+  if (fallback) sw_count(fallback + f, lane, mine >= 0 && fell);
 }
 
 extern "C" int mmego_blend_rot(void* stream, const float* src, long nrows, int J, const float* q, int NQ, const float* Rh,

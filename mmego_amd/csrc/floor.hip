@@ -1,4 +1,4 @@
-// Dense inference's notion of the ground (processors.dense_infer, floor=(mode, contact_cm, margin_cm)): every frame of a recording
+// Dense inference's notion of the ground (dense.dense_infer, floor=(mode, contact_cm, margin_cm)): every frame of a recording
 // carries the floor plane in the frame of its own joints, so the height of a joint is n . x + d and needs no head pose.
 // mmego_floor_stats turns the two feet of a lower-joint row into 22 per-row figures (penetration, contact by height against the recorded
 // flags, the same for the target as the noise floor) that ops.colsum sums; mmego_floor_clamp raises a leg whose foot or ankle lies

@@ -1,4 +1,4 @@
-// Dense inference's last stage (processors.dense_infer, smooth=(H, order, taper)): a zero-phase local-polynomial filter along time over
+// Dense inference's last stage (dense.dense_infer, smooth=(H, order, taper)): a zero-phase local-polynomial filter along time over
 // every recording's stitched frames -- frame f's row becomes the value at f of the weighted least-squares polynomial of degree <= 2
 // through the rows f-H .. f+H of its own segment.  In the column form every column is filtered on its own; in the bones form the roots
 // are, and every bone's DIRECTION is filtered, set to the body's bone length and laid along the kinematic tree, as blend_bones.hip
@@ -11,6 +11,7 @@
 // the recipe is the comment of the two entry points in include/mmego_hip.h, tests/smooth_ref.py restates it in numpy by another route.
 #include "common.h"
 #include "smooth_math.h"
+#include "skeleton_walk.h"
 
 #define SM_WAVES 4                       // one wave per output frame, four per workgroup (no barrier: a wave behind F leaves)
 
@@ -85,12 +86,8 @@ __global__ __launch_bounds__(64 * SM_WAVES) void smooth_bones_kernel(const float
     if (fallback && lane == 0) fallback[f] = 0;
     return;
   }
-  // this lane's bone: the one whose child it is (a bone that names a joint outside the row is left out: its child stays a root)
-  int mine = -1, parent = -1;
-  for (int b = 0; b < NB; ++b) {
-    const int c = bones[2 * b], p = bones[2 * b + 1];
-    if (c == j && p >= 0 && p < J && p != c) mine = b, parent = p;
-  }
+  int mine, parent;                      // this lane's bone: the one whose child it is
+  sw_lane_bone(bones, NB, J, lane, &mine, &parent);
   // a root: its three columns, as mmego_smooth_frames sums them; a bone's child: s = sum_k c_k (x_child - x_parent)
   double s[3] = {0.0, 0.0, 0.0}, u[3] = {0.0, 0.0, 0.0}, pos[3] = {0.0, 0.0, 0.0};
   for (int t = 0; t <= 2 * H; ++t) {     // (the mask is the same in every lane: the whole wave shuffles or none of it)
@@ -110,14 +107,8 @@ __global__ __launch_bounds__(64 * SM_WAVES) void smooth_bones_kernel(const float
                             (double)own[3 * j + 2] - (double)own[3 * parent + 2]};     // the frame's own bone (tap 0): the fallback
     fell = bb_direction(s, best, 1.0, L, u);                                            // (the coefficients sum to 1)
   }
-  for (int b = 0; b < NB; ++b) {         // the walk: bone b's child from its parent, parents before children
-    const int p = bones[2 * b + 1];
-    if (p < 0 || p >= J) continue;       // (the same for every lane)
-    const double p0 = shfl_d(pos[0], p), p1 = shfl_d(pos[1], p), p2 = shfl_d(pos[2], p);
-    if (joint && b == mine) pos[0] = p0 + L * u[0], pos[1] = p1 + L * u[1], pos[2] = p2 + L * u[2];
-  }
-  if (joint)
-    for (int i = 0; i < 3; ++i) dst[f * ldd + 3 * lane + i] = (float)pos[i];
+  sw_walk(bones, NB, J, mine, L, u, pos);
+  sw_store(dst + f * ldd, J, lane, pos);
   if (moved) {
     double q = 0.0;
     if (joint)
@@ -128,10 +119,7 @@ __global__ __launch_bounds__(64 * SM_WAVES) void smooth_bones_kernel(const float
     q = wave_sum_d(q);
     if (lane == 0) moved[f] = sm_moved(q, 3 * J);
   }
-  if (fallback) {
-    const int count = __popcll(__ballot(joint && fell));
-    if (lane == 0) fallback[f] = count;
-  }
+  if (fallback) sw_count(fallback + f, lane, mine >= 0 && fell);
 }
 
 // true where the F rows of n columns at a (row stride lda) and at b (row stride ldb) share a byte

@@ -1,0 +1,517 @@
+"""Dense inference (`main.py --infer --dense`, not in the reference): dense_infer, whose docstring is the contract, the stages of its pass
+(_dense_pass drives them; their figures land in ONE device log with named rows), and what Evaluator.eval_dense prints and writes."""
+import types
+
+import numpy as np
+import torch
+
+from . import blocks, hip, ops, skeleton
+from .config import IMU_NOISE_FLAGS
+from .data import DenseWindows
+from .evaluation import (METRICS, PCK_THRESHOLDS_CM, _accel_over_sequences, _error_summary, _jitter_imu, _jitter_pose, aligned_summary,
+                         imu_noise_key, imu_noise_line, pose_noise_key, pose_noise_line, print_aligned, print_reference)
+from .train_step import call_upper
+
+BLEND_SPACES, SMOOTH_TAPERS, FLOOR_MODES = ("joints", "bones", "rot"), ("box", "gauss"), ("measure", "clamp")
+FLOOR_KEYS = ("foot_height_err_cm", "penetration_rate", "penetration_cm", "contact_precision", "contact_recall", "hover_cm")
+FLOOR_TARGET_KEYS = ("target_penetration_rate", "target_penetration_cm", "target_contact_precision", "target_contact_recall")
+DENSE_SAVED = ("pred", "covered", "spread", "recording", "frame_in_recording", "target")      # --save_pred: the per-frame arrays of the file
+FIGURE_ROWS = ("blend", "spread", "single", "position", "bone_dev", "single_bone_dev", "rot_spread", "unsmoothed", "moved", "floor",
+               "single_floor", "unclamped_floor", "unclamped")
+
+
+def bone_lengths(bone_set):
+    """L_b = float32(|body_b|), the norm taken in float64, of a bone set [20, 3] (row 0 of DenseWindows.src["skl"]): the lengths every
+    predicted skeleton has, both nets placing a child at parent + q . body_b with q orthonormal.  -> (upper [14], lower [6])."""
+    L = np.linalg.norm(np.asarray(bone_set, dtype=np.float64).reshape(-1, 3), axis=1).astype(np.float32)
+    return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
+
+
+def smooth_weights(H, taper):
+    """The tap weights w[2 H + 1] (float32, k = -H .. H) of dense inference's temporal filter (ops.smooth_frames): "box" ones, "gauss"
+    exp(-2 k^2 / H^2) -- a Gaussian of sigma H / 2, 0.135 at the window's ends -- computed in float64 and rounded once."""
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= ops.SMOOTH_MAX_H:
+        raise ValueError("smooth: the half-width is an integer number of frames in [1, %d], got %r" % (ops.SMOOTH_MAX_H, H))
+    if taper not in SMOOTH_TAPERS:
+        raise ValueError("smooth: taper %r is not one of %s" % (taper, ", ".join(SMOOTH_TAPERS)))
+    k = np.arange(-int(H), int(H) + 1, dtype=np.float64)
+    return (np.ones(len(k)) if taper == "box" else np.exp(-2.0 * k * k / float(H * H))).astype(np.float32)
+
+
+def _check_smooth(smooth):
+    """smooth = (H, order, taper) of dense_infer, or None.  -> the tuple with plain ints."""
+    if smooth is None:
+        return None
+    if not (isinstance(smooth, (tuple, list)) and len(smooth) == 3):
+        raise ValueError("smooth: (H, order, taper), got %r" % (smooth,))
+    H, order, taper = smooth
+    smooth_weights(H, taper)
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
+        raise ValueError("smooth: order (the polynomial's degree) is 0, 1 or 2, got %r" % (order,))
+    return int(H), int(order), taper
+
+
+def _check_floor(floor):
+    """floor = (mode, contact_cm, margin_cm) of dense_infer, or None.  -> (mode, contact height, margin), the two in plain floats."""
+    if floor is None:
+        return None
+    if not (isinstance(floor, (tuple, list)) and len(floor) == 3):
+        raise ValueError("floor: (mode, contact_cm, margin_cm), got %r" % (floor,))
+    mode, contact_cm, margin_cm = floor
+    if mode not in FLOOR_MODES:
+        raise ValueError("floor: mode %r is not one of %s" % (mode, ", ".join(FLOOR_MODES)))
+    for name, v, zero_ok in (("contact_cm", contact_cm, False), ("margin_cm", margin_cm, True)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+            raise ValueError("floor: %s is a finite number of centimetres %s 0, got %r" % (name, ">=" if zero_ok else ">", v))
+    return mode, float(contact_cm), float(margin_cm)
+
+
+def _floor_summary(sums, n, prefix="", target=False):
+    """The floor figures from the column sums [22] of ops.floor_stats over ``n`` rows that count: every key of FLOOR_KEYS pooled over
+    both feet under ``prefix`` + key, and per foot as a pair (joint 15, joint 19) under ``prefix`` + key + "_per_foot"; None where a
+    denominator is 0.  ``target``: FLOOR_TARGET_KEYS as well, the recorded skeleton's own figures (never prefixed)."""
+    s = np.asarray(sums, dtype=np.float64).reshape(2, 11)
+    ratio = lambda a, b, scale=1.0: None if b == 0 else float(a) / float(b) * scale
+
+    def figures(c, rows):
+        out = {"foot_height_err_cm": ratio(c[0], rows, 100.0), "penetration_rate": ratio(c[2], rows), "penetration_cm": ratio(c[1], c[2], 100.0),
+               "contact_precision": ratio(c[4], c[3]), "contact_recall": ratio(c[4], c[5]), "hover_cm": ratio(c[6], c[5], 100.0)}
+        tgt = {"target_penetration_rate": ratio(c[8], rows), "target_penetration_cm": ratio(c[7], c[8], 100.0),
+               "target_contact_precision": ratio(c[10], c[9]), "target_contact_recall": ratio(c[10], c[5])}
+        return out, tgt
+
+    pooled, feet = figures(s.sum(axis=0), 2 * n), [figures(s[k], n) for k in (0, 1)]
+    res = {}
+    for i, (keys, pre) in enumerate(((FLOOR_KEYS, prefix), (FLOOR_TARGET_KEYS, ""))[:2 if target else 1]):
+        for k in keys:
+            res[pre + k] = pooled[i][k]
+            res[pre + k + "_per_foot"] = (feet[0][i][k], feet[1][i][k])
+    return res
+
+
+def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
+                pose_noise=None, imu_noise=None, smooth=None, floor=None):
+    """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
+    data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
+    grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
+    (mmego_blend_windows), and the reference's error kernels run on the blended frames and on the unblended window rows.
+    -> (summary, arrays).  summary: all_cm, upper_cm, lower_cm, rot_deg, per_joint_cm of the blend as means over the covered frames; the
+    same under single_ for the window rows; position_cm [T] the mean 21-joint error by position in the window (mmego_colsum_phase);
+    spread_cm the mean disagreement of the windows about a frame; windows, frames, covered_frames, max_cover.  metrics="full": also
+    aligned_summary's keys for the covered blended frames, with accel_cm taken PER RECORDING over its stitched blended frames (the first
+    figure that sees window seams), and single_accel_cm for the stitched reference windows when stride == frame_no (else None).
+    arrays (host): pred [F, 21, 3] (lower overwrites the shared hips; NaN where covered == 0), covered, spread, recording,
+    frame_in_recording, target; the two nets' blended joints before assembly, upper [F, 15, 3] and lower [F, 8, 3] (zeros where uncovered);
+    and, still on the device, win_up [W T, 45], win_lo [W T, 24] and the plan itself.
+    blend_space: "joints" blends the 3-vectors of every joint independently (the launches above); "bones" blends every bone's DIRECTION
+    over the cover, sets it to the body's bone length and walks the kinematic tree from the vector-blended roots (mmego_blend_bones with
+    skeleton.WALK_UPPER / WALK_LOWER and bone_lengths of the campaign's bone set): the frames stay rigid skeletons, as every window's
+    prediction is, and everything downstream runs on them unchanged.  None (the default) is "joints".  Given explicitly, either value
+    adds to the summary bone_dev_cm, the mean over the covered frames and the 20 bones of | |bone| - L_b | on the blended rows (upper 14
+    from the upper rows, lower 6 from the lower rows; mmego_bone_length_dev), single_bone_dev_cm, the same over the window rows,
+    degenerate_bones, the bones that took mmego_blend_bones' fallback (0 for "joints"), and blend_space; and to the arrays fallback [F].
+    "rot" blends in rotation space (mmego_blend_rot): both nets' rotations q and the head rotation R every row ran with (after any pose
+    noise) are kept per window row, every bone's world rotation R^T q is averaged over the cover (the weighted chordal mean), and the
+    nets' forward kinematics lays the rest bones of the campaign's bone set along the averages from the vector-blended roots -- rigid
+    frames as under "bones", with the twist about every bone kept.  The summary gains rot_spread_deg, the mean over the covered frames
+    of the windows' RMS rotational distance from the mean over the 14 upper bones, and degenerate_bones counts mmego_blend_rot's
+    fallback; the arrays gain rot [F, 20, 4], the unit quaternions (w, x, y, z) of the blended WORLD rotations in BONES_ALL order (NaN
+    where uncovered), rot_spread [F] in radians, bone_vectors [20, 3] -- pred's bones are rot applied to bone_vectors -- and, still on
+    the device, win_q_up [W T, 14, 9], win_q_lo [W T, 6, 9] and win_R [W T, 9]; none of these is allocated in another space.  "rot"
+    with smooth is refused (ValueError): the rotations would not be filtered with the positions.
+    pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
+    whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
+    pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
+    imu_noise=(six sigmas, seed): every window row's IMU samples are perturbed before IMU_Net reads them (ops.imu_jitter), under ONE key
+    for the whole pass (imu_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as row_ids and the plan's window
+    number as win_ids: a frame keeps its white noise in every window that serves it, a bias belongs to its window -- overlapping windows
+    see one frame under different offsets, as separately started estimators would -- and the result does not depend on batch_size.
+    smooth=(H, order, taper): the pass's last stage, a zero-phase local-polynomial filter along time over every recording's stitched
+    blended frames (ops.smooth_frames; under blend_space="bones" ops.smooth_bones with the walk tables and bone lengths of the blend, so
+    the frames stay rigid): frame f becomes the value at f of the weighted least-squares polynomial of degree ``order`` (0, 1, 2) through
+    the frames f - H .. f + H of its own recording, weights smooth_weights(H, taper); uncovered frames take no part and stay as they
+    are.  Everything above then runs on the smoothed frames unchanged, and the blended frames' figures are kept beside them: the summary
+    gains unsmoothed_all_cm, unsmoothed_upper_cm, unsmoothed_lower_cm, unsmoothed_rot_deg, unsmoothed_per_joint_cm (and
+    unsmoothed_accel_cm under metrics="full"), moved_cm, the mean over the covered frames of the RMS distance over the upper joints that
+    the filter moved a frame, smooth itself and smooth_fallback, the bones that kept their own frame's direction (0 in the column
+    form); the arrays gain pred_unsmoothed [F, 21, 3] and moved [F].  None (the default): no launch, no key, the bytes of the pass
+    without the argument.
+    floor=(mode, contact_cm, margin_cm): the pass's notion of the ground, behind the blend and the filter.  Every frame's floor plane
+    and contact flags come from the recording (DenseWindows.floor: the plane is given in the frame of the frame's own joints, so a
+    joint's height is n . x + d), as the head pose does under --gt_head_pose.  mode "measure": ops.floor_stats on the final frames and
+    on the window rows; the summary gains, pooled over both feet and as pairs (joint 15, joint 19) under key + "_per_foot",
+    foot_height_err_cm (mean |h(prediction) - h(target)|), penetration_rate (feet under the plane per covered frame and foot),
+    penetration_cm (the mean depth over the penetrating feet), contact_precision / contact_recall of "height < contact_cm" against the
+    recorded flags, hover_cm (the mean height above the plane of the flagged feet), the same under single_ for the window rows, the
+    recorded skeleton's own target_penetration_rate, target_penetration_cm, target_contact_precision, target_contact_recall (the noise
+    floor of the plane fit), None where a denominator is 0, and floor itself; the arrays gain foot_height [F, 2] of the final frames
+    (NaN where uncovered), ground [F, 4] and foot_contact [F, 2].  mode "clamp": ops.floor_clamp first raises every leg of the final
+    lower frames whose foot or ankle lies under margin_cm, keeping the frame's own bone lengths; everything above then runs on the
+    clamped frames, the frames before the clamp keep their figures under unclamped_ (the error figures and the floor figures; and
+    unclamped_accel_cm under metrics="full"), the summary gains lift_cm (the mean lift over the lifted frames, None without one),
+    lifted_frames and floor_fallback (the legs whose target was out of reach), the arrays pred_unclamped [F, 21, 3], lifted [F] and
+    floor_fallback [F].  "clamp" under blend_space="rot" is refused (ValueError): the saved rotations would no longer produce pred.
+    None (the default): no launch, no upload, no key, the bytes of the pass without the argument.
+    The figures come down in one read; the per-frame arrays in one each."""
+    if metrics not in METRICS:
+        raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
+    if blend_space is not None and blend_space not in BLEND_SPACES:
+        raise ValueError("blend_space: %r is not one of %s" % (blend_space, ", ".join(BLEND_SPACES)))
+    smooth = _check_smooth(smooth)
+    if blend_space == "rot" and smooth is not None:
+        raise ValueError("smooth: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
+                         "filtered with them; filtering rotations along time is not done here")
+    floor = _check_floor(floor)
+    if blend_space == "rot" and floor is not None and floor[0] == "clamp":
+        raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
+                         "produce pred; \"measure\" goes with every space")
+    plan = DenseWindows(dataset, base.device, stride, blend)
+    if plan.W == 0:
+        raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, plan.T))
+    nets = [n for n in (imu_net, upper_net, lower_net) if n is not None]
+    was_training = [n.training for n in nets]
+    for n in nets:
+        n.eval()
+    try:
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size),
+                           dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise))
+    finally:
+        for n, tr in zip(nets, was_training):
+            n.train(tr)
+
+
+def figure_rows(T):
+    """The device figure log's layout: row name -> row index, "position" -> the slice of its T rows (one per position in the window);
+    T + 12 rows whichever options are on (a row whose option is off is neither written nor read); writers and readers index by name."""
+    p = FIGURE_ROWS.index("position")
+    return {name: slice(p, p + T) if i == p else i + (T - 1) * (i > p) for i, name in enumerate(FIGURE_ROWS)}
+
+
+def _f32(dev, *shape):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _run_windows(base, plan, imu_net, upper_net, lower_net, batch_size, pose_noise, imu_noise, rot):
+    """IMU -> Upper -> Lower over the plan's windows.  -> {win_up, win_lo}, every row on the device; ``rot``: and win_q_up, win_q_lo, win_R."""
+    dev, W, T = base.device, plan.W, plan.T
+    win = dict(win_up=_f32(dev, W * T, 45), win_lo=_f32(dev, W * T, 24))
+    if rot:
+        win.update(win_q_up=_f32(dev, W * T, 14, 9), win_q_lo=_f32(dev, W * T, 6, 9), win_R=_f32(dev, W * T, 9))
+    state = {}
+    if imu_noise is not None and imu_net is None:
+        raise ValueError("imu_noise perturbs what IMU_Net reads: this pass takes the head pose from the recording")
+    if imu_noise is not None:
+        win_no = torch.arange(W, dtype=torch.int64, device=dev)                                        # [W]: the plan's window numbers
+    if pose_noise is not None or imu_noise is not None:
+        row_frame = torch.as_tensor(np.ascontiguousarray(plan.row_frame, dtype=np.int64)).to(dev)      # [W T]: every row's frame
+    for s in range(0, W, batch_size):
+        idx = np.arange(s, min(s + batch_size, W))
+        b = plan.gather(idx)                                   # fresh copies: the nets transform `data` in place (Q1)
+        B = len(idx)
+        if B not in state:
+            state[B] = (torch.zeros((6, B, 64), device=dev), torch.zeros((6, B, 64), device=dev))
+        h0, c0 = state[B]
+        tgt, body, imu = b["target"], b["skl"], b["imu"]
+        if imu_noise is not None:
+            imu = _jitter_imu(state, imu, imu_noise, imu_noise_key(imu_noise[1], 0, 0), row_ids=row_frame[s * T:(s + B) * T],
+                              win_ids=win_no[s:s + B])
+        R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
+        if pose_noise is not None:
+            R, t = _jitter_pose(state, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, 0), ids=row_frame[s * T:(s + B) * T])
+        up, q_up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[:2]
+        lo, q_lo = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
+        rows = {"win_up": up, "win_lo": lo, "win_q_up": q_up, "win_q_lo": q_lo, "win_R": R}      # (R after any pose noise: what the row ran with)
+        for name, dst in win.items():
+            part = dst[s * T:(s + B) * T]
+            part.copy_(rows[name].reshape(part.shape))
+    return win
+
+
+def _blend(plan, win, space):
+    """Every frame from its windows.  -> up, lo, spread; a space: lengths; "bones", "rot": fell [2, F]; "rot": quat_*, rot_spread, bone_vectors."""
+    dev, F, win_up, win_lo = plan.device, plan.F, win["win_up"], win["win_lo"]
+    b = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), spread=_f32(dev, F),
+                              fell=torch.zeros((2, F), dtype=torch.int32, device=dev) if space in ("bones", "rot") else None,
+                              lengths=None if space is None else bone_lengths(plan.bone_set))
+    if space == "bones":
+        ops.blend_bones(win_up, plan, skeleton.WALK_UPPER, b.lengths[0], b.up, b.spread, b.fell[0])
+        ops.blend_bones(win_lo, plan, skeleton.WALK_LOWER, b.lengths[1], b.lo, None, b.fell[1])
+    elif space == "rot":
+        b.quat_up, b.quat_lo, b.rot_spread = _f32(dev, F, 14, 4), _f32(dev, F, 6, 4), _f32(dev, F)
+        body = b.bone_vectors = np.ascontiguousarray(np.asarray(plan.bone_set, dtype=np.float32).reshape(20, 3))
+        ops.blend_rot(win_up, win["win_q_up"], win["win_R"], plan, skeleton.WALK_UPPER, skeleton.ROT_UPPER, body[list(skeleton.WALK_UPPER_ROWS)],
+                      b.up, b.quat_up, b.spread, b.rot_spread, b.fell[0])
+        ops.blend_rot(win_lo, win["win_q_lo"], win["win_R"], plan, skeleton.WALK_LOWER, skeleton.ROT_LOWER, body[list(skeleton.WALK_LOWER_ROWS)],
+                      b.lo, b.quat_lo, None, None, b.fell[1])
+    else:
+        ops.blend_windows(win_up, plan, b.up, b.spread)
+        ops.blend_windows(win_lo, plan, b.lo)
+    return b
+
+
+def _smooth(up, lo, seg, smooth, lengths):
+    """The filter along time.  -> up, lo, moved [F], fell ([2, F] int32 in the bones form, ``lengths`` given; else None)."""
+    (H, order, taper), dev, F = smooth, up.device, up.shape[0]
+    wts = smooth_weights(H, taper)
+    s = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), moved=_f32(dev, F),
+                              fell=None if lengths is None else torch.zeros((2, F), dtype=torch.int32, device=dev))
+    if lengths is not None:
+        ops.smooth_bones(up, seg, wts, order, skeleton.WALK_UPPER, lengths[0], s.up, s.moved, s.fell[0])
+        ops.smooth_bones(lo, seg, wts, order, skeleton.WALK_LOWER, lengths[1], s.lo, None, s.fell[1])
+    else:
+        ops.smooth_frames(up, seg, wts, order, s.up, s.moved)
+        ops.smooth_frames(lo, seg, wts, order, s.lo)
+    return s
+
+
+def _clamp(lo, ground, seg, margin):
+    """The floor clamp on the lower rows.  -> lo, lifted [F], fell [F] int32."""
+    dev, F = lo.device, lo.shape[0]
+    c = types.SimpleNamespace(lo=_f32(dev, F, 24), lifted=_f32(dev, F), fell=torch.zeros(F, dtype=torch.int32, device=dev))
+    ops.floor_clamp(lo, ground, seg, margin, c.lo, c.lifted, c.fell)
+    return c
+
+
+def _error_figures(up, lo, tgt, out):
+    """The 43 column sums of mmego_pose_errors over rows with their targets, into the log row ``out``.  -> the per-row table."""
+    E = _f32(tgt.device, tgt.shape[0], 43)
+    hip.call("pose_errors", up, lo, tgt, tgt.shape[0], E)
+    ops.colsum(E, out[:43])
+    return E
+
+
+def _floor_figures(lo, tgt, ground, contact, seg, H, out):
+    """The column sums of ops.floor_stats over lower rows (a row whose seg is < 0 writes zeros), into the log row ``out``."""
+    S = _f32(lo.device, lo.shape[0], ops.FLOOR_W)
+    ops.floor_stats(lo, tgt, ground, contact, seg, H, S)
+    ops.colsum(S, out[:ops.FLOOR_W])
+
+
+def _accel_cm(up, lo, tgt, spans):
+    """A frame set's acceleration error over its stitched recordings in cm (aligned_summary's mean); None without a span of 3 frames."""
+    acc = _accel_over_sequences(tgt.device, up, lo, tgt, spans)
+    return None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100
+
+
+def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
+    """Every figure's launches into the named rows of ONE device log, its one device -> host read, and the summary read back under the
+    same names.  b, sm, cl: what blend, filter and clamp returned (None: did not run); sets: the frame sets (up, lo) by their prefix."""
+    dev, W, T, F, space, floor = plan.device, plan.W, plan.T, plan.F, opt["blend_space"], opt["floor"]
+    win_up, win_lo, tgt_f, (up_f, lo_f) = win["win_up"], win["win_lo"], plan.src["target"], sets[""]
+    cov = np.flatnonzero(plan.covered)
+    Fc, cidx = len(cov), None if len(cov) == F else torch.as_tensor(cov).to(dev)
+    # a per-frame tensor's covered rows (zero rows never enter a mean): the tensor itself when every frame is covered
+    rows = lambda x: x.view(F, -1) if cidx is None else ops.gather_rows(x.view(F, -1), cidx, _f32(dev, Fc, x[0].numel()))
+    full = opt["metrics"] == "full"
+    WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
+    row = figure_rows(T)
+    log = torch.zeros((T + len(FIGURE_ROWS) - 1, max(43, WA)), dtype=torch.float32, device=dev)
+    up_c, lo_c, tgt_c = rows(up_f), rows(lo_f), rows(tgt_f)
+    _error_figures(up_c, lo_c, tgt_c, log[row["blend"]])
+    ops.colsum(rows(b.spread), log[row["spread"], :1])
+    row_idx = torch.as_tensor(plan.row_frame).to(dev)
+    tgt_w = ops.gather_rows(tgt_f, row_idx, _f32(dev, W * T, 63))
+    Ew = _error_figures(win_up, win_lo, tgt_w, log[row["single"]])
+    ops.colsum_phase(Ew, T, log[row["position"], :43])
+    if space is not None:
+        D, Dw = _f32(dev, Fc, 20), _f32(dev, W * T, 20)
+        for up, lo, dst in ((up_c, lo_c, D), (win_up, win_lo, Dw)):
+            ops.bone_length_dev(up, skeleton.WALK_UPPER, b.lengths[0], dst[:, :14])
+            ops.bone_length_dev(lo, skeleton.WALK_LOWER, b.lengths[1], dst[:, 14:])
+        ops.colsum(D, log[row["bone_dev"], :20])
+        ops.colsum(Dw, log[row["single_bone_dev"], :20])
+    if space == "rot":
+        ops.colsum(rows(b.rot_spread), log[row["rot_spread"], :1])
+    if sm is not None:                                             # the frames before the filter, and how far it moved a frame
+        _error_figures(rows(sets["unsmoothed_"][0]), rows(sets["unsmoothed_"][1]), tgt_c, log[row["unsmoothed"]])
+        ops.colsum(rows(sm.moved), log[row["moved"], :1])
+    if floor is not None:
+        # the final frames, the window rows with their frames' planes and flags, the frames before the clamp (their upper rows: the final)
+        Hc, (ground, contact) = floor[1] / 100.0, plan.floor()
+        _floor_figures(lo_f, tgt_f, ground, contact, seg, Hc, log[row["floor"]])
+        ground_w, contact_w = ops.gather_rows(ground, row_idx, _f32(dev, W * T, 4)), ops.gather_rows(contact, row_idx, _f32(dev, W * T, 2))
+        _floor_figures(win_lo, tgt_w, ground_w, contact_w, torch.zeros(W * T, dtype=torch.int32, device=dev), Hc, log[row["single_floor"]])
+        if cl is not None:
+            _floor_figures(sets["unclamped_"][1], tgt_f, ground, contact, seg, Hc, log[row["unclamped_floor"]])
+            _error_figures(up_c, rows(sets["unclamped_"][1]), tgt_c, log[row["unclamped"]])
+    if full:
+        thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
+        A, alog = _f32(dev, Fc, WA), torch.zeros(WA, dtype=torch.float32, device=dev)
+        ops.pose_errors_aligned(up_c.view(Fc, 15, 3), lo_c.view(Fc, 8, 3), tgt_c.view(Fc, 21, 3), thr, A)
+        ops.colsum(A, alog)
+    out = log.cpu().numpy().astype(np.float64)                     # the figures' one device -> host read
+    s = _error_summary(out[row["blend"], :43], Fc)
+    s.update(_error_summary(out[row["single"], :43], W * T, "single_"))
+    s.update(position_cm=out[row["position"], :21].mean(axis=1) / W * 100, spread_cm=float(out[row["spread"], 0]) / Fc * 100, windows=W,
+             frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=plan.blend, frame_no=T)
+    if space is not None:
+        s.update(bone_dev_cm=float(out[row["bone_dev"], :20].mean()) / Fc * 100,
+                 single_bone_dev_cm=float(out[row["single_bone_dev"], :20].mean()) / (W * T) * 100,
+                 degenerate_bones=int(arrays["fallback"].sum()), blend_space=space)
+    if space == "rot":
+        s["rot_spread_deg"] = float(np.degrees(out[row["rot_spread"], 0] / Fc))
+    if sm is not None:
+        s.update(_error_summary(out[row["unsmoothed"], :43], Fc, "unsmoothed_"), moved_cm=float(out[row["moved"], 0]) / Fc * 100,
+                 smooth=opt["smooth"], smooth_fallback=0 if sm.fell is None else int(sm.fell.cpu().numpy().sum()))
+    if floor is not None:
+        s.update(_floor_summary(out[row["floor"], :ops.FLOOR_W], Fc, target=True))
+        s.update(_floor_summary(out[row["single_floor"], :ops.FLOOR_W], W * T, "single_"), floor=tuple(floor))
+    if cl is not None:
+        s.update(_floor_summary(out[row["unclamped_floor"], :ops.FLOOR_W], Fc, "unclamped_"))
+        s.update(_error_summary(out[row["unclamped"], :43], Fc, "unclamped_"))
+        lifted = arrays["lifted"]
+        s.update(lift_cm=float(lifted[lifted > 0].astype(np.float64).mean()) * 100 if (lifted > 0).any() else None,
+                 lifted_frames=int((lifted > 0).sum()), floor_fallback=int(arrays["floor_fallback"].sum()))
+    if full:
+        spans = [(a, e) for a, e in zip(plan.rec_off[:-1], plan.rec_off[1:]) if e - a >= T]      # the covered recordings, whole
+        s.update(aligned_summary(np.concatenate([alog.cpu().numpy().astype(np.float64) / Fc, np.full(21, np.nan)])[None], 21))
+        for prefix, (up, lo) in sets.items():                      # (accel_cm: per recording, not per minibatch)
+            s[prefix + "accel_cm"] = _accel_cm(up, lo, tgt_f, spans)
+        s["single_accel_cm"] = None
+        if plan.stride == T:
+            first = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="left")
+            last = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="right")
+            n_ref = (plan.rec_off[1:] - plan.rec_off[:-1]) // T
+            acc = _accel_over_sequences(dev, win_up, win_lo, tgt_w, [((l - n) * T, l * T) for f, l, n in zip(first, last, n_ref) if l > f])
+            s["single_accel_cm"] = None if acc is None else float(acc.mean()) * 100
+    return s
+
+
+def _assemble(cfg, upper, lower, covered):
+    """pred [F, 21, 3] from host rows [F, 15, 3] and [F, 8, 3]: lower overwrites the shared hips (Demo_test.py:121-123), NaN uncovered."""
+    pred = np.zeros((len(upper), 21, 3), dtype=np.float32)
+    pred[:, list(cfg.upper_joint_map)] = upper
+    pred[:, list(cfg.lower_joint_map)] = lower
+    pred[covered == 0] = np.nan
+    return pred
+
+
+def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor):
+    """dense_infer's arrays: every per-frame array down in one read, the window rows and the plan still on the device."""
+    F, covered = plan.F, plan.covered
+    host = lambda x, J: x.cpu().numpy().reshape(F, J, 3)
+    up_h, lo_h = host(sets[""][0], 15), host(sets[""][1], 8)
+    arrays = dict(pred=_assemble(cfg, up_h, lo_h, covered), covered=covered.astype(np.int32), spread=b.spread.cpu().numpy(),
+                  recording=plan.frame_rec, frame_in_recording=plan.frame_in_recording,
+                  target=plan.src["target"].cpu().numpy().reshape(F, 21, 3), upper=up_h, lower=lo_h, plan=plan, **win)
+    if b.lengths is not None:                                      # (an explicit space; "joints" has no fallback: zeros)
+        arrays["fallback"] = np.zeros(F, dtype=np.int32) if b.fell is None else b.fell.cpu().numpy().sum(axis=0, dtype=np.int32)
+    if "win_R" in win:                                             # ("rot")
+        quats = np.concatenate([b.quat_up.cpu().numpy(), b.quat_lo.cpu().numpy()], axis=1)      # [F, 20, 4] in BONES_ALL order
+        quats[covered == 0] = np.nan
+        arrays.update(rot=quats, rot_spread=b.rot_spread.cpu().numpy(), bone_vectors=b.bone_vectors)
+    if sm is not None:
+        arrays.update(pred_unsmoothed=_assemble(cfg, host(sets["unsmoothed_"][0], 15), host(sets["unsmoothed_"][1], 8), covered),
+                      moved=sm.moved.cpu().numpy())
+    if floor is not None:
+        ground, contact = (x.cpu().numpy() for x in plan.floor())
+        arrays.update(foot_height=foot_heights(lo_h[:, [3, 7]], ground, covered != 0), ground=ground, foot_contact=contact)
+    if cl is not None:
+        arrays.update(pred_unclamped=_assemble(cfg, up_h, host(sets["unclamped_"][1], 8), covered), lifted=cl.lifted.cpu().numpy(),
+                      floor_fallback=cl.fell.cpu().numpy())
+    return arrays
+
+
+def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
+    """dense_infer behind its argument checks: the nets are in eval mode.  opt: dense_infer's keywords from ``metrics`` on, by name."""
+    space, smooth, floor = opt["blend_space"], opt["smooth"], opt["floor"]
+    with torch.no_grad():
+        win = _run_windows(base, plan, imu_net, upper_net, lower_net, batch_size, opt["pose_noise"], opt["imu_noise"], space == "rot")
+        b = _blend(plan, win, space)
+        sets, sm, cl, seg = {"": (b.up, b.lo)}, None, None, None   # the frame sets by the prefix of their figures: "" the final ones
+        if smooth is not None or floor is not None:                # a covered frame's segment is its recording, an uncovered one has none
+            seg = torch.as_tensor(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)).to(base.device)
+        if smooth is not None:
+            sm = _smooth(b.up, b.lo, seg, smooth, b.lengths if space == "bones" else None)
+            sets = {"": (sm.up, sm.lo), "unsmoothed_": sets[""]}
+        if floor is not None and floor[0] == "clamp":
+            cl = _clamp(sets[""][1], plan.floor()[0], seg, floor[2] / 100.0)
+            sets.update({"": (sets[""][0], cl.lo), "unclamped_": sets[""]})
+        arrays = _host_arrays(base.cfg, plan, win, b, sm, cl, sets, floor)
+        summary = _figures(plan, win, b, sm, cl, sets, seg, arrays, opt)
+    blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
+    return summary, arrays
+
+
+def foot_heights(feet, ground, covered):
+    """Heights [F, 2] (float32, from float64) of the feet [F, 2, 3] above the planes ground [F, 4], n . x + d with n normalised; NaN
+    where ``covered`` is false or the plane has no normal (|n| <= 1e-6)."""
+    g = np.asarray(ground, dtype=np.float64)
+    norm = np.linalg.norm(g[:, :3], axis=1)
+    ok = np.asarray(covered, dtype=bool) & (norm > 1e-6)
+    safe = np.where(norm > 1e-6, norm, 1.0)
+    h = (np.einsum("fki,fi->fk", np.asarray(feet, dtype=np.float64), g[:, :3]) + g[:, 3:4]) / safe[:, None]
+    h[~ok] = np.nan
+    return h.astype(np.float32)
+
+
+def print_summary(s, opt, saved=None):
+    """What `--infer --dense` prints: the reference's five lines first; ``saved``: where the per-frame skeletons were written."""
+    space, smooth, floor, full = opt["blend_space"], opt["smooth"], opt["floor"], opt["metrics"] == "full"
+    print_reference(s)
+    print("Single-window (unblended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+        s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
+    print("Error by window position(cm): {}".format(s["position_cm"]))
+    print("Window Disagreement(cm): {}".format(s["spread_cm"]))
+    if space is not None:
+        print("Bone Length Deviation(cm): blended {} single-window {} (degenerate bones {})".format(
+            s["bone_dev_cm"], s["single_bone_dev_cm"], s["degenerate_bones"]))
+    if space == "rot":
+        print("Window Rotational Disagreement(°): {}".format(s["rot_spread_deg"]))
+    print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
+        s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
+    if full:
+        print_aligned(s)
+        print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
+    if saved:
+        print("Per-frame skeletons saved in {}".format(saved))
+    if opt["pose_noise"] is not None:
+        print(pose_noise_line(opt["pose_noise"]))
+    if opt["imu_noise"] is not None:
+        print(imu_noise_line(opt["imu_noise"]))
+    if smooth is not None:
+        print("Unsmoothed (blended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+            s["unsmoothed_all_cm"], s["unsmoothed_upper_cm"], s["unsmoothed_lower_cm"], s["unsmoothed_rot_deg"]))
+        print("Smoothing Displacement(cm): {} (window +-{} frames, order {}, {}; degenerate bones {})".format(
+            s["moved_cm"], s["smooth"][0], s["smooth"][1], s["smooth"][2], s["smooth_fallback"]))
+        if full:
+            print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
+    if floor is not None:
+        print("Foot Height Error(cm): {} (joint 15: {}, joint 19: {}; single-window {})".format(
+            s["foot_height_err_cm"], *s["foot_height_err_cm_per_foot"], s["single_foot_height_err_cm"]))
+        print("Floor Penetration: rate {} depth(cm) {} (target: rate {} depth {}; single-window: rate {} depth {})".format(
+            s["penetration_rate"], s["penetration_cm"], s["target_penetration_rate"], s["target_penetration_cm"],
+            s["single_penetration_rate"], s["single_penetration_cm"]))
+        print("Foot Contact by height < {:g} cm: precision {} recall {} (target: precision {} recall {})".format(
+            floor[1], s["contact_precision"], s["contact_recall"], s["target_contact_precision"], s["target_contact_recall"]))
+        print("Contact Hover(cm): {}".format(s["hover_cm"]))
+        if floor[0] == "clamp":
+            print("Unclamped Error(cm): all {} lower {} (penetration rate {} depth(cm) {})".format(
+                s["unclamped_all_cm"], s["unclamped_lower_cm"], s["unclamped_penetration_rate"], s["unclamped_penetration_cm"]))
+            print("Floor Clamp: {} of {} frames lifted, mean lift(cm) {}, unreachable legs {} (margin {:g} cm)".format(
+                s["lifted_frames"], s["covered_frames"], s["lift_cm"], s["floor_fallback"], floor[2]))
+
+
+def saved_arrays(s, arrays, opt):
+    """The dictionary `--save_pred` writes (np.savez): DENSE_SAVED and the plan's three settings, then what every option adds."""
+    space, smooth, floor = opt["blend_space"], opt["smooth"], opt["floor"]
+    keep = lambda *names: {k: arrays[k] for k in names}
+    d = dict(stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]), **keep(*DENSE_SAVED))
+    if space is not None:
+        d.update(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
+    if space == "rot":
+        d.update(keep("rot", "rot_spread", "bone_vectors"))
+    if smooth is not None:
+        d.update(keep("pred_unsmoothed", "moved"), smooth_window=np.int64(smooth[0]), smooth_order=np.int64(smooth[1]),
+                 smooth_taper=np.asarray(smooth[2]))
+    if floor is not None:
+        d.update(keep("foot_height", "ground", "foot_contact"), floor_mode=np.asarray(floor[0]), floor_contact_cm=np.float64(floor[1]),
+                 floor_margin_cm=np.float64(floor[2]))
+        if floor[0] == "clamp":
+            d.update(keep("pred_unclamped", "lifted", "floor_fallback"))
+    if opt["pose_noise"] is not None:
+        deg, t, seed = opt["pose_noise"]
+        d.update(pose_noise_deg=np.float64(deg), pose_noise_t=np.float64(t), pose_noise_seed=np.int64(seed))
+    if opt["imu_noise"] is not None:
+        d.update({flag: np.float64(v) for flag, v in zip(IMU_NOISE_FLAGS, opt["imu_noise"][0])}, imu_noise_seed=np.int64(opt["imu_noise"][1]))
+    return d

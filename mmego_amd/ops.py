@@ -6,6 +6,7 @@ or ``W.t()``) -- the element strides go straight to the kernel.
 """
 import os as _os
 
+import numpy as np
 import torch
 
 from . import hip
@@ -430,13 +431,54 @@ def pose_accel_errors(upper, lower, target, Acc):
 
 
 BLEND_MAX_C = 64            # blend.hip BL_MAX_C: one lane per column
+BONES_MAX_J = 21            # blend_bones.hip BB_MAX_J: one lane per joint
+SMOOTH_MAX_H = 31           # smooth.hip SM_MAX_H: one lane per tap, 2 H + 1 <= 63
+FLOOR_W = 22                # floor_math.h FLOOR_W: mmego_floor_stats' columns, 11 per foot
+
+
+def _per_row(t, name, rows, dtype, device, who, kind=ValueError):
+    """An optional per-row output: None, or one contiguous ``dtype`` word per row on the rows' device (``kind``: raised by anything else)."""
+    if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+        raise kind("%s: %s is a %s device tensor" % (who, name, dtype))
+    if t is not None and (t.dim() != 1 or t.numel() != rows or not t.is_contiguous() or t.device != device):
+        raise ValueError("%s: %s is one contiguous %s word per row (%d), on the rows' device" % (who, name, dtype, rows))
+
+
+def _seg_on(seg, rows, device, who):
+    """seg of the filter and the floor launches: one int32 per row, a host array (uploaded) or a contiguous tensor on the rows' device."""
+    if isinstance(seg, np.ndarray):
+        if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) != rows:
+            raise ValueError("%s: seg is one int32 per row (%d), got %s %s" % (who, rows, seg.dtype, seg.shape))
+        return torch.as_tensor(np.ascontiguousarray(seg)).to(device)
+    if not (isinstance(seg, torch.Tensor) and seg.dtype == torch.int32 and seg.dim() == 1 and seg.numel() == rows and seg.is_contiguous()
+            and seg.device == device):
+        raise ValueError("%s: seg is one contiguous int32 per row (%d), a host array or a tensor on the rows' device" % (who, rows))
+    return seg
+
+
+def _rows_overlap(a, lda, b, ldb, rows, C):
+    """True where the ``rows`` rows of C floats at tensor a (row stride lda) and at tensor b (row stride ldb) share a byte."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + 4 * ((rows - 1) * ldb + C) and b0 < a0 + 4 * ((rows - 1) * lda + C)
+
+
+_tables_dev = {}         # (_upload_once's cache)
+
+
+def _upload_once(device, *tables):
+    """Host tables (numpy) on the device, uploaded once per content and device (cleared at 64 entries); an empty one as one zero row."""
+    key = tuple((a.dtype.str, a.shape, a.tobytes()) for a in tables) + (str(device),)
+    if key not in _tables_dev:
+        if len(_tables_dev) >= 64:
+            _tables_dev.clear()
+        _tables_dev[key] = tuple(torch.as_tensor(a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)).to(device) for a in tables)
+    return _tables_dev[key]
 
 
 def _cover_on(cover, nrows, device):
     """The CSR cover (a data.DenseWindows / data.DensePlan, or its three host arrays cov_off, cov_row, cov_w) checked on the HOST against
     a source of ``nrows`` rows -- offsets ascending from 0 to the list's length, every row in [0, nrows) -- and uploaded (a plan object
     keeps its device copies).  -> (off, row, w, F)."""
-    import numpy as np
     plan = cover if hasattr(cover, "cov_off") else None
     off, row, w = (plan.cov_off, plan.cov_row, plan.cov_w) if plan is not None else cover
     off, row, w = np.asarray(off), np.asarray(row), np.asarray(w)
@@ -467,10 +509,9 @@ def blend_windows(src, cover, dst, spread=None):
     off, row, w, F = _cover_on(cover, nrows, src.device)
     if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
         raise ValueError("blend_windows: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
-    if spread is not None:
-        _chk(spread, 1)
-        if spread.numel() != F or not spread.is_contiguous() or C % 3:
-            raise ValueError("blend_windows: spread is one contiguous float per frame, of rows of 3-vectors")
+    _per_row(spread, "spread", F, torch.float32, src.device, "blend_windows", kind=TypeError)
+    if spread is not None and C % 3:
+        raise ValueError("blend_windows: spread is one contiguous float per frame, of rows of 3-vectors")
     hip.call("blend_windows", src, nrows, C, off, row, w, F, dst, max(dst.stride(0), C), spread)
     return dst
 
@@ -489,16 +530,10 @@ def colsum_phase(X, period, out):
     return out
 
 
-BONES_MAX_J = 21            # blend_bones.hip BB_MAX_J: one lane per joint
-
-_bones_dev = {}
-
-
 def _bones_on(bones, bone_len, J, device, who):
     """The walk table ((child, parent) per bone, host integers) and the bone lengths checked on the HOST for rows of J joints -- every
     joint a child at most once, every parent a root or an earlier bone's child (so there is no cycle), the lengths finite and positive
     -- and uploaded once per table and device.  -> (bones int32 [NB, 2], bone_len fp32 [NB], NB)."""
-    import numpy as np
     b = np.asarray(bones)
     L = np.asarray(bone_len.detach().cpu() if isinstance(bone_len, torch.Tensor) else bone_len)
     if b.size == 0:
@@ -520,15 +555,7 @@ def _bones_on(bones, bone_len, J, device, who):
     L = L.astype(np.float32)
     if len(L) and not (np.isfinite(L).all() and (L > 0).all()):
         raise ValueError("%s: bone lengths have to be finite and positive" % who)
-    b = np.ascontiguousarray(b, dtype=np.int32)
-    key = (b.tobytes(), L.tobytes(), J, str(device))
-    dev = _bones_dev.get(key)
-    if dev is None:
-        if len(_bones_dev) >= 64:
-            _bones_dev.clear()
-        one = lambda a: torch.as_tensor(a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)).to(device)     # (no bone: still an address)
-        dev = _bones_dev[key] = (one(b), one(L))
-    return dev + (len(b),)
+    return _upload_once(device, np.ascontiguousarray(b, dtype=np.int32), L) + (len(b),)
 
 
 def blend_bones(src, cover, bones, bone_len, dst, spread=None, fallback=None):
@@ -547,14 +574,8 @@ def blend_bones(src, cover, bones, bone_len, dst, spread=None, fallback=None):
     off, row, w, F = _cover_on(cover, nrows, src.device)
     if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
         raise ValueError("blend_bones: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
-    if spread is not None:
-        _chk(spread, 1)
-        if spread.numel() != F or not spread.is_contiguous():
-            raise ValueError("blend_bones: spread is one contiguous float per frame")
-    if fallback is not None:
-        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
-                and fallback.numel() == F and fallback.is_contiguous()):
-            raise ValueError("blend_bones: fallback is one contiguous int32 device word per frame")
+    _per_row(spread, "spread", F, torch.float32, src.device, "blend_bones", kind=TypeError)
+    _per_row(fallback, "fallback", F, torch.int32, src.device, "blend_bones")
     hip.call("blend_bones", src, nrows, C // 3, off, row, w, F, bd, ld, NB, dst, max(dst.stride(0), C), spread, fallback)
     return dst
 
@@ -573,9 +594,6 @@ def bone_length_dev(X, bones, bone_len, out):
     return out
 
 
-_rot_dev = {}
-
-
 def blend_rot(src, q, Rh, cover, bones, rot_idx, body, dst, quat, spread=None, rot_spread=None, fallback=None):
     """dst[f, :3 J] = the blend in rotation space of the rows that cover frame f (mmego_blend_rot; the recipe is in the header): per bone
     the weighted chordal mean of the world rotations Rh^T q of the cover, the roots as blend_windows blends them, the rest bones ``body``
@@ -587,7 +605,6 @@ def blend_rot(src, q, Rh, cover, bones, rot_idx, body, dst, quat, spread=None, r
     (optional) the bones per frame whose mean was degenerate.  Every tensor is contiguous float32 on src's device.  Cover, bones,
     rot_idx and body are checked on the host first; a refused call leaves every output untouched.  dst may be wider than 3 J: its other
     columns stay."""
-    import numpy as np
     _chk(src, 2)
     dst = _rows(dst)
     nrows, C = src.shape
@@ -620,30 +637,13 @@ def blend_rot(src, q, Rh, cover, bones, rot_idx, body, dst, quat, spread=None, r
         raise ValueError("blend_rot: dst is %s for %d frames of %d columns" % (tuple(dst.shape), F, C))
     if quat.numel() != F * NB * 4 or quat.shape[0] != F or quat.data_ptr() % 16:
         raise ValueError("blend_rot: quat is [%d, %d, 4], 16-byte aligned, got %s" % (F, NB, tuple(quat.shape)))
-    for name, t in (("spread", spread), ("rot_spread", rot_spread)):
-        if t is not None:
-            _chk(t, 1)
-            if t.numel() != F or not t.is_contiguous() or t.device != src.device:
-                raise ValueError("blend_rot: %s is one contiguous float per frame" % name)
-    if fallback is not None:
-        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
-                and fallback.numel() == F and fallback.is_contiguous()):
-            raise ValueError("blend_rot: fallback is one contiguous int32 device word per frame")
-    ri = np.ascontiguousarray(ri, dtype=np.int32)
-    key = (ri.tobytes(), bv.tobytes(), str(src.device))
-    rd = _rot_dev.get(key)
-    if rd is None:
-        if len(_rot_dev) >= 64:
-            _rot_dev.clear()
-        rd = _rot_dev[key] = (torch.as_tensor(ri).to(src.device), torch.as_tensor(bv).to(src.device))
+    _per_row(spread, "spread", F, torch.float32, src.device, "blend_rot", kind=TypeError)
+    _per_row(rot_spread, "rot_spread", F, torch.float32, src.device, "blend_rot", kind=TypeError)
+    _per_row(fallback, "fallback", F, torch.int32, src.device, "blend_rot")
+    rd = _upload_once(src.device, np.ascontiguousarray(ri, dtype=np.int32), bv)
     hip.call("blend_rot", src, nrows, C // 3, q, NQ, Rh, off, row, w, F, bd, rd[0], rd[1], NB, dst, max(dst.stride(0), C), quat, spread,
              rot_spread, fallback)
     return dst
-
-
-SMOOTH_MAX_H = 31           # smooth.hip SM_MAX_H: one lane per tap, 2 H + 1 <= 63
-
-_smooth_w_dev = {}
 
 
 def _smooth_on(src, seg, weights, order, dst, moved, C_max, who):
@@ -651,7 +651,6 @@ def _smooth_on(src, seg, weights, order, dst, moved, C_max, who):
     weight table (host floats: odd length 2 H + 1 with H in [1, 31], every weight finite and > 0; uploaded once per table and device),
     order in {0, 1, 2}, seg (an int32 host array or device tensor of length F; a host array is uploaded), moved (optional): one
     contiguous float per frame, of rows of 3-vectors.  -> (seg, w, H, order, F, C, lds, ldd)."""
-    import numpy as np
     src, dst = _rows(src), _rows(dst)
     F, C = src.shape
     if F < 1 or not 1 <= C <= C_max or (F > 1 and src.stride(0) < C):
@@ -659,8 +658,7 @@ def _smooth_on(src, seg, weights, order, dst, moved, C_max, who):
     if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
         raise ValueError("%s: dst is %s for %d frames of %d columns" % (who, tuple(dst.shape), F, C))
     lds, ldd = max(src.stride(0), C), max(dst.stride(0), C)
-    s0, d0 = src.data_ptr(), dst.data_ptr()
-    if s0 < d0 + 4 * ((F - 1) * ldd + C) and d0 < s0 + 4 * ((F - 1) * lds + C):
+    if _rows_overlap(src, lds, dst, ldd, F, C):
         raise ValueError("%s: dst overlaps src; the filter reads the rows around the one it writes and cannot run in place" % who)
     wt = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights)
     if wt.ndim != 1 or wt.dtype.kind != "f" or len(wt) % 2 == 0 or not 1 <= len(wt) // 2 <= SMOOTH_MAX_H:
@@ -670,31 +668,18 @@ def _smooth_on(src, seg, weights, order, dst, moved, C_max, who):
         raise ValueError("%s: every weight has to be finite and > 0" % who)
     if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
         raise ValueError("%s: order (the polynomial's degree) is 0, 1 or 2, got %r" % (who, order))
-    if isinstance(seg, np.ndarray):
-        if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) != F:
-            raise ValueError("%s: seg is one int32 per frame (%d), got %s %s" % (who, F, seg.dtype, seg.shape))
-        seg = torch.as_tensor(np.ascontiguousarray(seg)).to(src.device)
-    elif not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 1 and seg.numel() == F
-              and seg.is_contiguous()):
-        raise ValueError("%s: seg is one contiguous int32 per frame (%d), a host array or a device tensor" % (who, F))
-    if moved is not None:
-        _chk(moved, 1)
-        if moved.numel() != F or not moved.is_contiguous() or C % 3:
-            raise ValueError("%s: moved is one contiguous float per frame, of rows of 3-vectors" % who)
-    key = (wt.tobytes(), str(src.device))
-    wd = _smooth_w_dev.get(key)
-    if wd is None:
-        if len(_smooth_w_dev) >= 64:
-            _smooth_w_dev.clear()
-        wd = _smooth_w_dev[key] = torch.as_tensor(wt).to(src.device)
-    return seg, wd, len(wt) // 2, int(order), F, C, lds, ldd
+    seg = _seg_on(seg, F, src.device, who)
+    _per_row(moved, "moved", F, torch.float32, src.device, who, kind=TypeError)
+    if moved is not None and C % 3:
+        raise ValueError("%s: moved is one contiguous float per frame, of rows of 3-vectors" % who)
+    return seg, _upload_once(src.device, wt)[0], len(wt) // 2, int(order), F, C, lds, ldd
 
 
 def smooth_frames(src, seg, weights, order, dst, moved=None):
     """dst[f, :C] = the zero-phase local-polynomial filter of the rows of src [F, C <= 64] along the frames (mmego_smooth_frames; the
     recipe is in the header): the weighted least-squares polynomial of degree min(order, valid taps - 1) through the rows f - H .. f + H
     of frame f's own segment, evaluated at f.  ``seg`` [F] int32 names every frame's segment (-1: none; such a frame, and one alone in
-    its segment, keeps its row bit for bit); ``weights`` the 2 H + 1 tap weights (host floats, processors.smooth_weights); ``order`` 0, 1
+    its segment, keeps its row bit for bit); ``weights`` the 2 H + 1 tap weights (host floats, dense.smooth_weights); ``order`` 0, 1
     or 2.  moved [F] (optional, C % 3 == 0): the RMS distance over the joints between the filtered and the source row.  Everything is
     checked on the host first (ValueError); dst must not overlap src, and may be wider than C: its other columns stay."""
     seg, w, H, order, F, C, lds, ldd = _smooth_on(src, seg, weights, order, dst, moved, BLEND_MAX_C, "smooth_frames")
@@ -711,15 +696,9 @@ def smooth_bones(src, seg, weights, order, walk, lengths, dst, moved=None, fallb
         raise ValueError("smooth_bones needs rows of 3-vectors, got %s" % (tuple(src.shape),))
     seg, w, H, order, F, C, lds, ldd = _smooth_on(src, seg, weights, order, dst, moved, 3 * BONES_MAX_J, "smooth_bones")
     bd, ld, NB = _bones_on(walk, lengths, C // 3, src.device, "smooth_bones")
-    if fallback is not None:
-        if not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32 and fallback.dim() == 1
-                and fallback.numel() == F and fallback.is_contiguous()):
-            raise ValueError("smooth_bones: fallback is one contiguous int32 device word per frame")
+    _per_row(fallback, "fallback", F, torch.int32, src.device, "smooth_bones")
     hip.call("smooth_bones", src, lds, F, C // 3, seg, w, H, order, bd, ld, NB, dst, ldd, moved, fallback)
     return dst
-
-
-FLOOR_W = 22                # floor_math.h FLOOR_W: mmego_floor_stats' columns, 11 per foot
 
 
 def _floor_rows(t, name, rows, C, device, who, packed=False):
@@ -738,23 +717,8 @@ def _floor_rows(t, name, rows, C, device, who, packed=False):
     return max(t.stride(0), t.shape[1])
 
 
-def _floor_seg(seg, rows, device, who):
-    """seg of the floor launches: one int32 per row, a host array (uploaded) or a contiguous device tensor."""
-    import numpy as np
-    if isinstance(seg, np.ndarray):
-        if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) != rows:
-            raise ValueError("%s: seg is one int32 per row (%d), got %s %s" % (who, rows, seg.dtype, seg.shape))
-        return torch.as_tensor(np.ascontiguousarray(seg)).to(device)
-    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 1 and seg.numel() == rows
-            and seg.is_contiguous() and seg.device == device):
-        raise ValueError("%s: seg is one contiguous int32 per row (%d), a host array or a tensor on the rows' device" % (who, rows))
-    return seg
-
-
 def _floor_metres(v, name, who, zero_ok):
-    import math
-    import numbers
-    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
         raise ValueError("%s: %s is a finite number of metres %s 0, got %r" % (who, name, ">=" if zero_ok else ">", v))
     return float(v)
 
@@ -771,7 +735,7 @@ def floor_stats(lo, tgt, ground, contact, seg, H, out):
     _floor_rows(ground, "ground", rows, 4, dev, who, packed=True)
     _floor_rows(contact, "contact", rows, 2, dev, who, packed=True)
     _floor_rows(out, "out", rows, FLOOR_W, dev, who, packed=True)
-    seg = _floor_seg(seg, rows, dev, who)
+    seg = _seg_on(seg, rows, dev, who)
     H = _floor_metres(H, "H (the contact height)", who, zero_ok=False)
     hip.call("floor_stats", lo, ldl, tgt, ldt, ground, contact, seg, rows, H, out)
     return out
@@ -788,19 +752,13 @@ def floor_clamp(src, ground, seg, margin, dst, lifted=None, fallback=None):
     rows, dev = src.shape[0], src.device
     ldd = _floor_rows(dst, "dst", rows, 24, dev, who)
     _floor_rows(ground, "ground", rows, 4, dev, who, packed=True)
-    seg = _floor_seg(seg, rows, dev, who)
+    seg = _seg_on(seg, rows, dev, who)
     margin = _floor_metres(margin, "margin", who, zero_ok=True)
-    s0, d0 = src.data_ptr(), dst.data_ptr()
-    same = s0 == d0 and lds == ldd
-    if not same and s0 < d0 + 4 * ((rows - 1) * ldd + 24) and d0 < s0 + 4 * ((rows - 1) * lds + 24):
+    same = src.data_ptr() == dst.data_ptr() and lds == ldd
+    if not same and _rows_overlap(src, lds, dst, ldd, rows, 24):
         raise ValueError("%s: dst overlaps src without being it" % who)
-    if lifted is not None and not (isinstance(lifted, torch.Tensor) and lifted.is_cuda and lifted.dtype == torch.float32 and lifted.dim() == 1
-                                   and lifted.numel() == rows and lifted.is_contiguous() and lifted.device == dev):
-        raise ValueError("%s: lifted is one contiguous fp32 device word per row (%d)" % (who, rows))
-    if fallback is not None and not (isinstance(fallback, torch.Tensor) and fallback.is_cuda and fallback.dtype == torch.int32
-                                     and fallback.dim() == 1 and fallback.numel() == rows and fallback.is_contiguous()
-                                     and fallback.device == dev):
-        raise ValueError("%s: fallback is one contiguous int32 device word per row (%d)" % (who, rows))
+    _per_row(lifted, "lifted", rows, torch.float32, dev, who)
+    _per_row(fallback, "fallback", rows, torch.int32, dev, who)
     hip.call("floor_clamp", src, lds, ground, seg, rows, margin, dst, ldd, lifted, fallback)
     return dst
 

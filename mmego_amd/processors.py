@@ -16,9 +16,12 @@ import types
 import numpy as np
 import torch
 
-from . import blocks, hip, ops, skeleton
-from .config import IMU_NOISE_FLAGS, Config, ConfigDemo
-from .data import DeviceArrays, FrameStore, PosePC, _mix64, batch_indices
+from . import blocks, dense, hip, ops
+from .config import Config, ConfigDemo
+from .data import DeviceArrays, FrameStore, PosePC, batch_indices
+from .dense import dense_infer
+from .evaluation import (METRICS, PCK_THRESHOLDS_CM, _jitter_imu, _jitter_pose, aligned_summary, imu_noise_key, imu_noise_line, imu_noise_of,
+                         pose_noise_key, pose_noise_line, pose_noise_of, print_aligned, print_reference)
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam, LrSchedule, describe_decay, lr_schedule_of, resolve_no_decay
 from .nets_local import UpperNetwlocal
@@ -31,79 +34,6 @@ _TRAIN_DIR = os.environ.get("MMEGO_TRAIN_DIR") or os.path.join(os.path.dirname(_
 
 
 UPPER_VARIANTS = {"global": UpperNet, "wlocal": UpperNetwlocal}          # --upper_variant -> the class behind "Upper_Net"
-METRICS = ("reference", "full")                                          # --metrics
-PCK_THRESHOLDS_CM = (5.0, 10.0, 15.0)                                    # --metrics full: PCK of the absolute joint errors
-
-
-POSE_NOISE_SALT = 0x504F5345                                             # the head-pose draws' stream among what _mix64 derives from --seed
-
-
-def pose_noise_key(seed, epoch, minibatch, rank=None):
-    """The key of one minibatch's head-pose draw (--pose_noise_deg / --pose_noise_t): a pure function of (seed, epoch, minibatch number
-    [, rank]), so --resume continues the sequence with no saved state and the ranks of a data-parallel run draw differently.  rank None:
-    the evaluation passes' key, which has no rank.  -> the 63 bits mmego_pose_jitter's int64 device word takes."""
-    words = (int(seed), int(epoch), int(minibatch)) + (() if rank is None else (int(rank),))
-    return _mix64(*words, POSE_NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
-
-
-def pose_noise_of(cfg):
-    """(deg, t, seed) of a run's --pose_noise_deg / --pose_noise_t (a missing sigma: 0.0; a missing --seed: 0, as --point_noise treats
-    it), or None without the flags."""
-    deg, t = getattr(cfg, "pose_noise_deg", None), getattr(cfg, "pose_noise_t", None)
-    if deg is None and t is None:
-        return None
-    return (0.0 if deg is None else float(deg), 0.0 if t is None else float(t), int(getattr(cfg, "seed", None) or 0))
-
-
-def pose_noise_line(pose_noise):
-    return "Head Pose Noise: rotation {} deg per axis, translation {} m, seed {}".format(*pose_noise)
-
-
-def _jitter_pose(scratch, R, t, pose_noise, key, ids=None):
-    """An evaluation minibatch's head pose perturbed out of place (buffers and the device word kept in ``scratch`` per shape)."""
-    R, t = R.contiguous(), t.contiguous()
-    slot = ("pose_noise",) + tuple(R.shape)
-    if slot not in scratch:
-        scratch[slot] = (torch.empty_like(R), torch.empty_like(t), torch.zeros(1, dtype=torch.int64, device=R.device))
-    R_n, t_n, word = scratch[slot]
-    word.fill_(int(key))
-    return ops.pose_jitter(R, t, pose_noise[0], pose_noise[1], word, R_n, t_n, ids=ids)
-
-
-IMU_NOISE_SALT = 0x494D554E                                              # the IMU draws' stream among what _mix64 derives from --seed
-
-
-def imu_noise_key(seed, epoch, minibatch, rank=None):
-    """The key of one minibatch's IMU noise and bias draws (--imu_noise_* / --imu_bias_*): pose_noise_key's construction under a salt of
-    its own, so a run with both options draws the two independently.  -> the 63 bits mmego_imu_jitter's int64 device word takes."""
-    words = (int(seed or 0), int(epoch), int(minibatch)) + (() if rank is None else (int(rank),))
-    return _mix64(*words, IMU_NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
-
-
-def imu_noise_of(cfg):
-    """((noise_rot_deg, noise_acc, noise_gyro, bias_rot_deg, bias_acc, bias_gyro), seed) of a run's --imu_noise_* / --imu_bias_* (a
-    missing sigma: 0.0; a missing --seed: 0), or None without the flags."""
-    given = [getattr(cfg, flag, None) for flag in IMU_NOISE_FLAGS]
-    if all(v is None for v in given):
-        return None
-    return tuple(0.0 if v is None else float(v) for v in given), int(getattr(cfg, "seed", None) or 0)
-
-
-def imu_noise_line(imu_noise):
-    sig, seed = imu_noise
-    return ("IMU Noise: white rotation {} deg per axis, accelerometer {}, gyroscope {}; bias rotation {} deg per axis, accelerometer {}, "
-            "gyroscope {}; seed {}").format(*sig, seed)
-
-
-def _jitter_imu(scratch, imu, imu_noise, key, row_ids=None, win_ids=None):
-    """An evaluation minibatch's IMU samples [B, T, S, 15] perturbed out of place (buffer and device word kept in ``scratch`` per shape)."""
-    imu = imu.contiguous()
-    slot = ("imu_noise",) + tuple(imu.shape)
-    if slot not in scratch:
-        scratch[slot] = (torch.empty_like(imu), torch.zeros(1, dtype=torch.int64, device=imu.device))
-    out, word = scratch[slot]
-    word.fill_(int(key))
-    return ops.imu_jitter(imu, imu_noise[0], word, out, row_ids=row_ids, win_ids=win_ids)
 
 
 def upper_variant_of(state_dict):
@@ -784,29 +714,6 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
     return out
 
 
-def aligned_summary(m, J):
-    """The --metrics full figures from _epoch_eval's columns behind the reference's (m [n_minibatches, 3 J + 3 + nthr + J]): means over
-    minibatches of per-minibatch means, lengths in cm.  J = 21: the three joint errors also as means over the upper and the lower joint
-    map of the one 21-joint fit."""
-    nthr = len(PCK_THRESHOLDS_CM)
-    errs = {"root_rel_cm": m[:, :J], "rigid_cm": m[:, J:2 * J], "pa_cm": m[:, 2 * J:3 * J]}
-    s = {}
-    for name, blk in errs.items():
-        s[name] = float(np.mean(blk.mean(axis=1))) * 100
-        if J == 21:
-            s[name[:-3] + "_upper_cm"] = float(np.mean(blk[:, list(Config.upper_joint_map)].mean(axis=1))) * 100
-            s[name[:-3] + "_lower_cm"] = float(np.mean(blk[:, list(Config.lower_joint_map)].mean(axis=1))) * 100
-    s["align_rot_deg"] = float(np.mean(m[:, 3 * J]))
-    s["align_shift_cm"] = float(np.mean(m[:, 3 * J + 1])) * 100
-    s["pa_scale"] = float(np.mean(m[:, 3 * J + 2]))
-    s["pck"] = {c: float(np.mean(m[:, 3 * J + 3 + k])) for k, c in enumerate(PCK_THRESHOLDS_CM)}
-    acc = m[:, 3 * J + 3 + nthr:]
-    s["accel_cm"] = None if np.isnan(acc).any() else float(np.mean(acc.mean(axis=1))) * 100
-    s["per_joint_root_rel_cm"] = errs["root_rel_cm"].mean(axis=0) * 100
-    s["per_joint_pa_cm"] = errs["pa_cm"].mean(axis=0) * 100
-    return s
-
-
 def metrics_line(s):
     """One line of the --metrics full figures (the trainers' extra line per epoch)."""
     acc = "n/a" if s["accel_cm"] is None else "%.4f" % s["accel_cm"]
@@ -835,456 +742,6 @@ def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuf
     return (eval_loss, np.asarray([eval_loss / cfg.joint_num_lower]), float(np.mean(accu_l)), float(np.mean(accu_lo)), accu_ll, angle_ll), summary
 
 
-def _error_summary(sums, n, prefix=""):
-    """The reference's five figures from the 43 column sums of mmego_pose_errors over n rows (float64), keys prefixed."""
-    m = sums / n
-    return {prefix + "all_cm": float(m[:21].mean()) * 100, prefix + "upper_cm": float(m[41]) * 100, prefix + "lower_cm": float(m[42]) * 100,
-            prefix + "rot_deg": float(m[21:41].mean()), prefix + "per_joint_cm": m[:21] * 100}
-
-
-def _accel_over_sequences(dev, up, lo, tgt, spans):
-    """Acceleration error over sequences of different lengths: one mmego_pose_accel_errors launch (B = 1, T = its length) per span
-    [r0, r1) of the row tensors up [., 45], lo [., 24], tgt [., 63]; spans shorter than 3 rows have no second difference and are left
-    out.  -> the mean over ALL interior frames (every sequence weighs by its length - 2) per joint, float64 [21] in metres, or None."""
-    spans = [(int(r0), int(r1)) for r0, r1 in spans if r1 - r0 >= 3]
-    if not spans:
-        return None
-    Acc = torch.empty((len(spans), 21), dtype=torch.float32, device=dev)
-    for i, (r0, r1) in enumerate(spans):
-        n = r1 - r0
-        ops.pose_accel_errors(up[r0:r1].view(1, n, 15, 3), lo[r0:r1].view(1, n, 8, 3), tgt[r0:r1].view(1, n, 21, 3), Acc[i:i + 1])
-    wt = np.asarray([r1 - r0 - 2 for r0, r1 in spans], dtype=np.float64)
-    return (Acc.cpu().numpy().astype(np.float64) * wt[:, None]).sum(axis=0) / wt.sum()
-
-
-BLEND_SPACES = ("joints", "bones", "rot")
-
-
-def bone_lengths(bone_set):
-    """L_b = float32(|body_b|), the norm taken in float64, of a bone set [20, 3] (row 0 of DenseWindows.src["skl"]): the lengths every
-    predicted skeleton has, both nets placing a child at parent + q . body_b with q orthonormal.  -> (upper [14], lower [6])."""
-    L = np.linalg.norm(np.asarray(bone_set, dtype=np.float64).reshape(-1, 3), axis=1).astype(np.float32)
-    return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
-
-
-SMOOTH_TAPERS = ("box", "gauss")
-
-
-def smooth_weights(H, taper):
-    """The tap weights w[2 H + 1] (float32, k = -H .. H) of dense inference's temporal filter (ops.smooth_frames): "box" ones, "gauss"
-    exp(-2 k^2 / H^2) -- a Gaussian of sigma H / 2, 0.135 at the window's ends -- computed in float64 and rounded once."""
-    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= ops.SMOOTH_MAX_H:
-        raise ValueError("smooth: the half-width is an integer number of frames in [1, %d], got %r" % (ops.SMOOTH_MAX_H, H))
-    if taper not in SMOOTH_TAPERS:
-        raise ValueError("smooth: taper %r is not one of %s" % (taper, ", ".join(SMOOTH_TAPERS)))
-    k = np.arange(-int(H), int(H) + 1, dtype=np.float64)
-    return (np.ones(len(k)) if taper == "box" else np.exp(-2.0 * k * k / float(H * H))).astype(np.float32)
-
-
-def _check_smooth(smooth):
-    """smooth = (H, order, taper) of dense_infer, or None.  -> the tuple with plain ints."""
-    if smooth is None:
-        return None
-    if not (isinstance(smooth, (tuple, list)) and len(smooth) == 3):
-        raise ValueError("smooth: (H, order, taper), got %r" % (smooth,))
-    H, order, taper = smooth
-    smooth_weights(H, taper)
-    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
-        raise ValueError("smooth: order (the polynomial's degree) is 0, 1 or 2, got %r" % (order,))
-    return int(H), int(order), taper
-
-
-FLOOR_MODES = ("measure", "clamp")
-
-
-def _check_floor(floor):
-    """floor = (mode, contact_cm, margin_cm) of dense_infer, or None.  -> (mode, contact height, margin), the two in plain floats."""
-    if floor is None:
-        return None
-    if not (isinstance(floor, (tuple, list)) and len(floor) == 3):
-        raise ValueError("floor: (mode, contact_cm, margin_cm), got %r" % (floor,))
-    mode, contact_cm, margin_cm = floor
-    if mode not in FLOOR_MODES:
-        raise ValueError("floor: mode %r is not one of %s" % (mode, ", ".join(FLOOR_MODES)))
-    for name, v, zero_ok in (("contact_cm", contact_cm, False), ("margin_cm", margin_cm, True)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
-            raise ValueError("floor: %s is a finite number of centimetres %s 0, got %r" % (name, ">=" if zero_ok else ">", v))
-    return mode, float(contact_cm), float(margin_cm)
-
-
-FLOOR_KEYS = ("foot_height_err_cm", "penetration_rate", "penetration_cm", "contact_precision", "contact_recall", "hover_cm")
-FLOOR_TARGET_KEYS = ("target_penetration_rate", "target_penetration_cm", "target_contact_precision", "target_contact_recall")
-
-
-def _floor_summary(sums, n, prefix="", target=False):
-    """The floor figures from the column sums [22] of ops.floor_stats over ``n`` rows that count: every key of FLOOR_KEYS pooled over
-    both feet under ``prefix`` + key, and per foot as a pair (joint 15, joint 19) under ``prefix`` + key + "_per_foot"; None where a
-    denominator is 0.  ``target``: FLOOR_TARGET_KEYS as well, the recorded skeleton's own figures (never prefixed)."""
-    s = np.asarray(sums, dtype=np.float64).reshape(2, 11)
-    ratio = lambda a, b, scale=1.0: None if b == 0 else float(a) / float(b) * scale
-
-    def figures(c, rows):
-        out = {"foot_height_err_cm": ratio(c[0], rows, 100.0), "penetration_rate": ratio(c[2], rows), "penetration_cm": ratio(c[1], c[2], 100.0),
-               "contact_precision": ratio(c[4], c[3]), "contact_recall": ratio(c[4], c[5]), "hover_cm": ratio(c[6], c[5], 100.0)}
-        tgt = {"target_penetration_rate": ratio(c[8], rows), "target_penetration_cm": ratio(c[7], c[8], 100.0),
-               "target_contact_precision": ratio(c[10], c[9]), "target_contact_recall": ratio(c[10], c[5])}
-        return out, tgt
-
-    pooled, feet = figures(s.sum(axis=0), 2 * n), [figures(s[k], n) for k in (0, 1)]
-    res = {}
-    for i, (keys, pre) in enumerate(((FLOOR_KEYS, prefix), (FLOOR_TARGET_KEYS, ""))[:2 if target else 1]):
-        for k in keys:
-            res[pre + k] = pooled[i][k]
-            res[pre + k + "_per_foot"] = (feet[0][i][k], feet[1][i][k])
-    return res
-
-
-def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None, floor=None):
-    """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
-    data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
-    grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
-    (mmego_blend_windows), and the reference's error kernels run on the blended frames and on the unblended window rows.
-    -> (summary, arrays).  summary: all_cm, upper_cm, lower_cm, rot_deg, per_joint_cm of the blend as means over the covered frames; the
-    same under single_ for the window rows; position_cm [T] the mean 21-joint error by position in the window (mmego_colsum_phase);
-    spread_cm the mean disagreement of the windows about a frame; windows, frames, covered_frames, max_cover.  metrics="full": also
-    aligned_summary's keys for the covered blended frames, with accel_cm taken PER RECORDING over its stitched blended frames (the first
-    figure that sees window seams), and single_accel_cm for the stitched reference windows when stride == frame_no (else None).
-    arrays (host): pred [F, 21, 3] (lower overwrites the shared hips; NaN where covered == 0), covered, spread, recording,
-    frame_in_recording, target; the two nets' blended joints before assembly, upper [F, 15, 3] and lower [F, 8, 3] (zeros where uncovered);
-    and, still on the device, win_up [W T, 45], win_lo [W T, 24] and the plan itself.
-    blend_space: "joints" blends the 3-vectors of every joint independently (the launches above); "bones" blends every bone's DIRECTION
-    over the cover, sets it to the body's bone length and walks the kinematic tree from the vector-blended roots (mmego_blend_bones with
-    skeleton.WALK_UPPER / WALK_LOWER and bone_lengths of the campaign's bone set): the frames stay rigid skeletons, as every window's
-    prediction is, and everything downstream runs on them unchanged.  None (the default) is "joints".  Given explicitly, either value
-    adds to the summary bone_dev_cm, the mean over the covered frames and the 20 bones of | |bone| - L_b | on the blended rows (upper 14
-    from the upper rows, lower 6 from the lower rows; mmego_bone_length_dev), single_bone_dev_cm, the same over the window rows,
-    degenerate_bones, the bones that took mmego_blend_bones' fallback (0 for "joints"), and blend_space; and to the arrays fallback [F].
-    "rot" blends in rotation space (mmego_blend_rot): both nets' rotations q and the head rotation R every row ran with (after any pose
-    noise) are kept per window row, every bone's world rotation R^T q is averaged over the cover (the weighted chordal mean), and the
-    nets' forward kinematics lays the rest bones of the campaign's bone set along the averages from the vector-blended roots -- rigid
-    frames as under "bones", with the twist about every bone kept.  The summary gains rot_spread_deg, the mean over the covered frames
-    of the windows' RMS rotational distance from the mean over the 14 upper bones, and degenerate_bones counts mmego_blend_rot's
-    fallback; the arrays gain rot [F, 20, 4], the unit quaternions (w, x, y, z) of the blended WORLD rotations in BONES_ALL order (NaN
-    where uncovered), rot_spread [F] in radians, bone_vectors [20, 3] -- pred's bones are rot applied to bone_vectors -- and, still on
-    the device, win_q_up [W T, 14, 9], win_q_lo [W T, 6, 9] and win_R [W T, 9]; none of these is allocated in another space.  "rot"
-    with smooth is refused (ValueError): the rotations would not be filtered with the positions.
-    pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
-    whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
-    pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
-    imu_noise=(six sigmas, seed): every window row's IMU samples are perturbed before IMU_Net reads them (ops.imu_jitter), under ONE key
-    for the whole pass (imu_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as row_ids and the plan's window
-    number as win_ids: a frame keeps its white noise in every window that serves it, a bias belongs to its window -- overlapping windows
-    see one frame under different offsets, as separately started estimators would -- and the result does not depend on batch_size.
-    smooth=(H, order, taper): the pass's last stage, a zero-phase local-polynomial filter along time over every recording's stitched
-    blended frames (ops.smooth_frames; under blend_space="bones" ops.smooth_bones with the walk tables and bone lengths of the blend, so
-    the frames stay rigid): frame f becomes the value at f of the weighted least-squares polynomial of degree ``order`` (0, 1, 2) through
-    the frames f - H .. f + H of its own recording, weights smooth_weights(H, taper); uncovered frames take no part and stay as they
-    are.  Everything above then runs on the smoothed frames unchanged, and the blended frames' figures are kept beside them: the summary
-    gains unsmoothed_all_cm, unsmoothed_upper_cm, unsmoothed_lower_cm, unsmoothed_rot_deg, unsmoothed_per_joint_cm (and
-    unsmoothed_accel_cm under metrics="full"), moved_cm, the mean over the covered frames of the RMS distance over the upper joints that
-    the filter moved a frame, smooth itself and smooth_fallback, the bones that kept their own frame's direction (0 in the column
-    form); the arrays gain pred_unsmoothed [F, 21, 3] and moved [F].  None (the default): no launch, no key, the bytes of the pass
-    without the argument.
-    floor=(mode, contact_cm, margin_cm): the pass's notion of the ground, behind the blend and the filter.  Every frame's floor plane
-    and contact flags come from the recording (DenseWindows.floor: the plane is given in the frame of the frame's own joints, so a
-    joint's height is n . x + d), as the head pose does under --gt_head_pose.  mode "measure": ops.floor_stats on the final frames and
-    on the window rows; the summary gains, pooled over both feet and as pairs (joint 15, joint 19) under key + "_per_foot",
-    foot_height_err_cm (mean |h(prediction) - h(target)|), penetration_rate (feet under the plane per covered frame and foot),
-    penetration_cm (the mean depth over the penetrating feet), contact_precision / contact_recall of "height < contact_cm" against the
-    recorded flags, hover_cm (the mean height above the plane of the flagged feet), the same under single_ for the window rows, the
-    recorded skeleton's own target_penetration_rate, target_penetration_cm, target_contact_precision, target_contact_recall (the noise
-    floor of the plane fit), None where a denominator is 0, and floor itself; the arrays gain foot_height [F, 2] of the final frames
-    (NaN where uncovered), ground [F, 4] and foot_contact [F, 2].  mode "clamp": ops.floor_clamp first raises every leg of the final
-    lower frames whose foot or ankle lies under margin_cm, keeping the frame's own bone lengths; everything above then runs on the
-    clamped frames, the frames before the clamp keep their figures under unclamped_ (the error figures and the floor figures; and
-    unclamped_accel_cm under metrics="full"), the summary gains lift_cm (the mean lift over the lifted frames, None without one),
-    lifted_frames and floor_fallback (the legs whose target was out of reach), the arrays pred_unclamped [F, 21, 3], lifted [F] and
-    floor_fallback [F].  "clamp" under blend_space="rot" is refused (ValueError): the saved rotations would no longer produce pred.
-    None (the default): no launch, no upload, no key, the bytes of the pass without the argument.
-    The figures come down in one read; the per-frame arrays in one each."""
-    from .data import DenseWindows
-    if metrics not in METRICS:
-        raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
-    if blend_space is not None and blend_space not in BLEND_SPACES:
-        raise ValueError("blend_space: %r is not one of %s" % (blend_space, ", ".join(BLEND_SPACES)))
-    smooth = _check_smooth(smooth)
-    if blend_space == "rot" and smooth is not None:
-        raise ValueError("smooth: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
-                         "filtered with them; filtering rotations along time is not done here")
-    floor = _check_floor(floor)
-    if blend_space == "rot" and floor is not None and floor[0] == "clamp":
-        raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
-                         "produce pred; \"measure\" goes with every space")
-    dev = base.device
-    plan = DenseWindows(dataset, dev, stride, blend)
-    W, T, F = plan.W, plan.T, plan.F
-    if W == 0:
-        raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, T))
-    nets = [n for n in (imu_net, upper_net, lower_net) if n is not None]
-    was_training = [n.training for n in nets]
-    for n in nets:
-        n.eval()
-    try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), blend, metrics, blend_space, pose_noise, imu_noise, smooth,
-                           floor)
-    finally:
-        for n, tr in zip(nets, was_training):
-            n.train(tr)
-
-
-def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, blend, metrics, blend_space=None, pose_noise=None, imu_noise=None,
-                smooth=None, floor=None):
-    """dense_infer behind its argument checks: the nets are in eval mode."""
-    dev = base.device
-    W, T, F = plan.W, plan.T, plan.F
-    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    win_up, win_lo = f32(W * T, 45), f32(W * T, 24)
-    rot = blend_space == "rot"
-    if rot:                                                        # every window row's rotations and the head rotation it ran with
-        win_q_up, win_q_lo, win_R = f32(W * T, 14, 9), f32(W * T, 6, 9), f32(W * T, 9)
-    with torch.no_grad():
-        state = {}
-        if imu_noise is not None and imu_net is None:
-            raise ValueError("imu_noise perturbs what IMU_Net reads: this pass takes the head pose from the recording")
-        if imu_noise is not None:
-            win_no = torch.arange(W, dtype=torch.int64, device=dev)                                        # [W]: the plan's window numbers
-        if pose_noise is not None or imu_noise is not None:
-            row_frame = torch.as_tensor(np.ascontiguousarray(plan.row_frame, dtype=np.int64)).to(dev)      # [W T]: every row's frame
-        for s in range(0, W, batch_size):
-            idx = np.arange(s, min(s + batch_size, W))
-            b = plan.gather(idx)                                   # fresh copies: the nets transform `data` in place (Q1)
-            B = len(idx)
-            if B not in state:
-                state[B] = (torch.zeros((6, B, 64), device=dev), torch.zeros((6, B, 64), device=dev))
-            h0, c0 = state[B]
-            tgt, body = b["target"], b["skl"]
-            imu = b["imu"]
-            if imu_noise is not None:
-                imu = _jitter_imu(state, imu, imu_noise, imu_noise_key(imu_noise[1], 0, 0), row_ids=row_frame[s * T:(s + B) * T],
-                                  win_ids=win_no[s:s + B])
-            R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
-            if pose_noise is not None:
-                R, t = _jitter_pose(state, R, t, pose_noise, pose_noise_key(pose_noise[2], 0, 0), ids=row_frame[s * T:(s + B) * T])
-            up, q_up = call_upper(upper_net, b["data"], h0, c0, body, R, t)[:2]
-            lo, q_lo = lower_net(up.clone(), b["data"], h0, h0, h0, h0, body, R, t)     # x already transformed once (Q1)
-            win_up[s * T:(s + B) * T].copy_(up.reshape(B * T, 45))
-            win_lo[s * T:(s + B) * T].copy_(lo.reshape(B * T, 24))
-            if rot:
-                win_q_up[s * T:(s + B) * T].copy_(q_up.reshape(B * T, 14, 9))
-                win_q_lo[s * T:(s + B) * T].copy_(q_lo.reshape(B * T, 6, 9))
-                win_R[s * T:(s + B) * T].copy_(R.reshape(B * T, 9))           # (after any pose noise: what the row was run with)
-        # every frame from its windows
-        up_f, lo_f, spread = f32(F, 45), f32(F, 24), f32(F)
-        if blend_space is not None:
-            L_up, L_lo = bone_lengths(plan.bone_set)
-        if blend_space == "bones":
-            fell = torch.zeros((2, F), dtype=torch.int32, device=dev)
-            ops.blend_bones(win_up, plan, skeleton.WALK_UPPER, L_up, up_f, spread, fell[0])
-            ops.blend_bones(win_lo, plan, skeleton.WALK_LOWER, L_lo, lo_f, None, fell[1])
-        elif rot:
-            fell = torch.zeros((2, F), dtype=torch.int32, device=dev)
-            quat_up, quat_lo, rot_spread = f32(F, 14, 4), f32(F, 6, 4), f32(F)
-            bone_vectors = np.ascontiguousarray(np.asarray(plan.bone_set, dtype=np.float32).reshape(20, 3))
-            ops.blend_rot(win_up, win_q_up, win_R, plan, skeleton.WALK_UPPER, skeleton.ROT_UPPER, bone_vectors[list(skeleton.WALK_UPPER_ROWS)],
-                          up_f, quat_up, spread, rot_spread, fell[0])
-            ops.blend_rot(win_lo, win_q_lo, win_R, plan, skeleton.WALK_LOWER, skeleton.ROT_LOWER, bone_vectors[list(skeleton.WALK_LOWER_ROWS)],
-                          lo_f, quat_lo, None, None, fell[1])
-        else:
-            ops.blend_windows(win_up, plan, up_f, spread)
-            ops.blend_windows(win_lo, plan, lo_f)
-        if smooth is not None:
-            # along time, recording by recording: a frame's segment is its recording, an uncovered frame has none
-            H, order, taper = smooth
-            up_b, lo_b = up_f, lo_f                                # the blended frames: their figures are kept beside the smoothed ones'
-            seg = np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)
-            seg = torch.as_tensor(seg).to(dev)
-            wts = smooth_weights(H, taper)
-            up_f, lo_f, moved = f32(F, 45), f32(F, 24), f32(F)
-            if blend_space == "bones":
-                fell_s = torch.zeros((2, F), dtype=torch.int32, device=dev)
-                ops.smooth_bones(up_b, seg, wts, order, skeleton.WALK_UPPER, L_up, up_f, moved, fell_s[0])
-                ops.smooth_bones(lo_b, seg, wts, order, skeleton.WALK_LOWER, L_lo, lo_f, None, fell_s[1])
-            else:
-                ops.smooth_frames(up_b, seg, wts, order, up_f, moved)
-                ops.smooth_frames(lo_b, seg, wts, order, lo_f)
-        clamp = floor is not None and floor[0] == "clamp"
-        if floor is not None:
-            # the ground: the plane and the flags of every frame, the segments the filter uses (covered: the recording, else none)
-            ground, contact = plan.floor()
-            if smooth is None:
-                seg = torch.as_tensor(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)).to(dev)
-            if clamp:
-                lo_u = lo_f                                        # the frames before the clamp: their figures are kept beside the clamped ones'
-                lo_f, lifted = f32(F, 24), f32(F)
-                fell_f = torch.zeros(F, dtype=torch.int32, device=dev)
-                ops.floor_clamp(lo_u, ground, seg, floor[2] / 100.0, lo_f, lifted, fell_f)
-        tgt_f = plan.src["target"]                                 # [F, 63]
-        cov = np.flatnonzero(plan.covered)
-        Fc = len(cov)
-        up_c, lo_c, tgt_c, spread_c = up_f, lo_f, tgt_f, spread.view(F, 1)
-        if Fc < F:                                                 # zero rows never enter a mean
-            cidx = torch.as_tensor(cov).to(dev)
-            up_c, lo_c, tgt_c = (ops.gather_rows(x, cidx, f32(Fc, x.shape[1])) for x in (up_f, lo_f, tgt_f))
-            spread_c = ops.gather_rows(spread.view(F, 1), cidx, f32(Fc, 1))
-        full = metrics == "full"
-        WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
-        n_log = 3 + T + (2 if blend_space is not None else 0) + (1 if rot else 0)      # (smooth: two more rows behind these)
-        n_fl = n_log + (2 if smooth is not None else 0)            # (floor: two more rows behind these, four under the clamp)
-        log = torch.zeros((n_fl + (0 if floor is None else 4 if clamp else 2), max(43, WA)), dtype=torch.float32, device=dev)
-        E = f32(Fc, 43)
-        hip.call("pose_errors", up_c, lo_c, tgt_c, Fc, E)
-        ops.colsum(E, log[0, :43])
-        ops.colsum(spread_c, log[1, :1])
-        # the unblended window rows: the same kernel, then by position in the window
-        row_idx = torch.as_tensor(plan.row_frame).to(dev)
-        tgt_w = ops.gather_rows(tgt_f, row_idx, f32(W * T, 63))
-        Ew = f32(W * T, 43)
-        hip.call("pose_errors", win_up, win_lo, tgt_w, W * T, Ew)
-        ops.colsum(Ew, log[2, :43])
-        ops.colsum_phase(Ew, T, log[3:3 + T, :43])
-        if blend_space is not None:
-            # deviation from the body's bone lengths, blended frames and window rows: columns 0..19 of two more rows of the log
-            D, Dw = f32(Fc, 20), f32(W * T, 20)
-            ops.bone_length_dev(up_c, skeleton.WALK_UPPER, L_up, D[:, :14])
-            ops.bone_length_dev(lo_c, skeleton.WALK_LOWER, L_lo, D[:, 14:])
-            ops.bone_length_dev(win_up, skeleton.WALK_UPPER, L_up, Dw[:, :14])
-            ops.bone_length_dev(win_lo, skeleton.WALK_LOWER, L_lo, Dw[:, 14:])
-            ops.colsum(D, log[3 + T, :20])
-            ops.colsum(Dw, log[4 + T, :20])
-        if rot:
-            rot_spread_c = rot_spread.view(F, 1) if Fc == F else ops.gather_rows(rot_spread.view(F, 1), cidx, f32(Fc, 1))
-            ops.colsum(rot_spread_c, log[5 + T, :1])
-        if smooth is not None:
-            # the blended frames before the filter: the same error kernel; and how far the filter moved a frame
-            up_bc, lo_bc, moved_c = up_b, lo_b, moved.view(F, 1)
-            if Fc < F:
-                up_bc, lo_bc = (ops.gather_rows(x, cidx, f32(Fc, x.shape[1])) for x in (up_b, lo_b))
-                moved_c = ops.gather_rows(moved.view(F, 1), cidx, f32(Fc, 1))
-            Eb = f32(Fc, 43)
-            hip.call("pose_errors", up_bc, lo_bc, tgt_c, Fc, Eb)
-            ops.colsum(Eb, log[n_log, :43])
-            ops.colsum(moved_c, log[n_log + 1, :1])
-        if floor is not None:
-            # the feet against the plane: the final frames (an uncovered row writes zeros, so the sums are the covered frames'), the
-            # window rows with their frames' planes and flags, and under the clamp the frames before it with their error figures
-            Hc = floor[1] / 100.0
-            St, Sw = f32(F, ops.FLOOR_W), f32(W * T, ops.FLOOR_W)
-            ops.floor_stats(lo_f, tgt_f, ground, contact, seg, Hc, St)
-            ops.colsum(St, log[n_fl, :ops.FLOOR_W])
-            ground_w, contact_w = ops.gather_rows(ground, row_idx, f32(W * T, 4)), ops.gather_rows(contact, row_idx, f32(W * T, 2))
-            ops.floor_stats(win_lo, tgt_w, ground_w, contact_w, torch.zeros(W * T, dtype=torch.int32, device=dev), Hc, Sw)
-            ops.colsum(Sw, log[n_fl + 1, :ops.FLOOR_W])
-            if clamp:
-                Su, Eu = f32(F, ops.FLOOR_W), f32(Fc, 43)
-                ops.floor_stats(lo_u, tgt_f, ground, contact, seg, Hc, Su)
-                ops.colsum(Su, log[n_fl + 2, :ops.FLOOR_W])
-                lo_uc = lo_u if Fc == F else ops.gather_rows(lo_u, cidx, f32(Fc, 24))
-                hip.call("pose_errors", up_c, lo_uc, tgt_c, Fc, Eu)
-                ops.colsum(Eu, log[n_fl + 3, :43])
-        if full:
-            thr = torch.tensor([c / 100.0 for c in PCK_THRESHOLDS_CM], dtype=torch.float32, device=dev)
-            A = f32(Fc, WA)
-            ops.pose_errors_aligned(up_c.view(Fc, 15, 3), lo_c.view(Fc, 8, 3), tgt_c.view(Fc, 21, 3), thr, A)
-            alog = torch.zeros(WA, dtype=torch.float32, device=dev)
-            ops.colsum(A, alog)
-    out = log.cpu().numpy().astype(np.float64)                     # the figures' one device -> host read
-    summary = _error_summary(out[0, :43], Fc)
-    summary.update(_error_summary(out[2, :43], W * T, "single_"))
-    summary["position_cm"] = out[3:3 + T, :21].mean(axis=1) / W * 100
-    summary["spread_cm"] = float(out[1, 0]) / Fc * 100
-    summary.update(windows=W, frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=blend, frame_no=T)
-    if blend_space is not None:
-        # (the fallback counts are integers per frame: they come down with the per-frame arrays, in their one read)
-        fallback = fell.cpu().numpy().sum(axis=0, dtype=np.int32) if blend_space in ("bones", "rot") else np.zeros(F, dtype=np.int32)
-        summary.update(bone_dev_cm=float(out[3 + T, :20].mean()) / Fc * 100, single_bone_dev_cm=float(out[4 + T, :20].mean()) / (W * T) * 100,
-                       degenerate_bones=int(fallback.sum()), blend_space=blend_space)
-    if rot:
-        summary["rot_spread_deg"] = float(np.degrees(out[5 + T, 0] / Fc))
-    if smooth is not None:
-        summary.update(_error_summary(out[n_log, :43], Fc, "unsmoothed_"))
-        smooth_fallback = int(fell_s.cpu().numpy().sum()) if blend_space == "bones" else 0
-        summary.update(moved_cm=float(out[n_log + 1, 0]) / Fc * 100, smooth=smooth, smooth_fallback=smooth_fallback)
-    if floor is not None:
-        summary.update(_floor_summary(out[n_fl, :ops.FLOOR_W], Fc, target=True))
-        summary.update(_floor_summary(out[n_fl + 1, :ops.FLOOR_W], W * T, "single_"))
-        summary["floor"] = (floor[0], floor[1], floor[2])
-        if clamp:
-            summary.update(_floor_summary(out[n_fl + 2, :ops.FLOOR_W], Fc, "unclamped_"))
-            summary.update(_error_summary(out[n_fl + 3, :43], Fc, "unclamped_"))
-            # (lifts and fallback counts are per-frame arrays: they come down in their one read each)
-            lifted_h, fell_h = lifted.cpu().numpy(), fell_f.cpu().numpy()
-            up_frames = int((lifted_h > 0).sum())
-            summary.update(lift_cm=None if up_frames == 0 else float(lifted_h[lifted_h > 0].astype(np.float64).mean()) * 100,
-                           lifted_frames=up_frames, floor_fallback=int(fell_h.sum()))
-    if full:
-        spans = [(a, b) for a, b in zip(plan.rec_off[:-1], plan.rec_off[1:]) if b - a >= T]      # the covered recordings, whole
-        acc = _accel_over_sequences(dev, up_f, lo_f, tgt_f, spans)
-        m = np.concatenate([alog.cpu().numpy().astype(np.float64) / Fc, np.full(21, np.nan) if acc is None else acc])[None]
-        summary.update(aligned_summary(m, 21))
-        if smooth is not None:
-            acc = _accel_over_sequences(dev, up_b, lo_b, tgt_f, spans)
-            summary["unsmoothed_accel_cm"] = None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100     # (aligned_summary's mean)
-        if clamp:
-            acc = _accel_over_sequences(dev, up_f, lo_u, tgt_f, spans)
-            summary["unclamped_accel_cm"] = None if acc is None else float(np.mean(acc[None].mean(axis=1))) * 100
-        summary["single_accel_cm"] = None
-        if plan.stride == T:
-            # the reference's windows of a recording are its last len // T windows: consecutive rows of the window tensors
-            first = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="left")
-            last = np.searchsorted(plan.recording, np.arange(len(plan.rec_off) - 1), side="right")
-            n_ref = (plan.rec_off[1:] - plan.rec_off[:-1]) // T
-            acc = _accel_over_sequences(dev, win_up, win_lo, tgt_w, [((l - n) * T, l * T) for f, l, n in zip(first, last, n_ref) if l > f])
-            summary["single_accel_cm"] = None if acc is None else float(acc.mean()) * 100
-    blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
-    up_h, lo_h = up_f.cpu().numpy().reshape(F, 15, 3), lo_f.cpu().numpy().reshape(F, 8, 3)
-    pred = np.zeros((F, 21, 3), dtype=np.float32)
-    pred[:, list(base.cfg.upper_joint_map)] = up_h
-    pred[:, list(base.cfg.lower_joint_map)] = lo_h                 # lower overwrites the shared hips (Demo_test.py:121-123)
-    pred[plan.covered == 0] = np.nan
-    if smooth is not None:
-        pred_b = np.zeros((F, 21, 3), dtype=np.float32)
-        pred_b[:, list(base.cfg.upper_joint_map)] = up_b.cpu().numpy().reshape(F, 15, 3)
-        pred_b[:, list(base.cfg.lower_joint_map)] = lo_b.cpu().numpy().reshape(F, 8, 3)
-        pred_b[plan.covered == 0] = np.nan
-    arrays = dict(pred=pred, covered=plan.covered.astype(np.int32), spread=spread.cpu().numpy(), recording=plan.frame_rec,
-                  frame_in_recording=plan.frame_in_recording, target=tgt_f.cpu().numpy().reshape(F, 21, 3),
-                  upper=up_h, lower=lo_h, win_up=win_up, win_lo=win_lo, plan=plan)
-    if blend_space is not None:
-        arrays["fallback"] = fallback
-    if rot:
-        quats = np.concatenate([quat_up.cpu().numpy(), quat_lo.cpu().numpy()], axis=1)      # [F, 20, 4] in BONES_ALL order
-        quats[plan.covered == 0] = np.nan
-        arrays.update(rot=quats, rot_spread=rot_spread.cpu().numpy(), bone_vectors=bone_vectors, win_q_up=win_q_up, win_q_lo=win_q_lo,
-                      win_R=win_R)
-    if smooth is not None:
-        arrays.update(pred_unsmoothed=pred_b, moved=moved.cpu().numpy())
-    if floor is not None:
-        ground_h, contact_h = ground.cpu().numpy(), contact.cpu().numpy()
-        arrays.update(foot_height=foot_heights(lo_h[:, [3, 7]], ground_h, plan.covered != 0), ground=ground_h, foot_contact=contact_h)
-        if clamp:
-            pred_u = pred.copy()
-            pred_u[:, list(base.cfg.lower_joint_map)] = lo_u.cpu().numpy().reshape(F, 8, 3)
-            pred_u[plan.covered == 0] = np.nan
-            arrays.update(pred_unclamped=pred_u, lifted=lifted_h, floor_fallback=fell_h)
-    return summary, arrays
-
-
-def foot_heights(feet, ground, covered):
-    """Heights [F, 2] (float32, from float64) of the feet [F, 2, 3] above the planes ground [F, 4], n . x + d with n normalised; NaN
-    where ``covered`` is false or the plane has no normal (|n| <= 1e-6)."""
-    g = np.asarray(ground, dtype=np.float64)
-    norm = np.linalg.norm(g[:, :3], axis=1)
-    ok = np.asarray(covered, dtype=bool) & (norm > 1e-6)
-    safe = np.where(norm > 1e-6, norm, 1.0)
-    h = (np.einsum("fki,fi->fk", np.asarray(feet, dtype=np.float64), g[:, :3]) + g[:, 3:4]) / safe[:, None]
-    h[~ok] = np.nan
-    return h.astype(np.float32)
-
-
-DENSE_SAVED = ("pred", "covered", "spread", "recording", "frame_in_recording", "target")      # --save_pred: the per-frame arrays of the file
-
-
 class Evaluator(_Base):
     """`python main.py --infer` (reference Processor/Test/Demo_test.MMEgo.eval_model)."""
 
@@ -1304,94 +761,16 @@ class Evaluator(_Base):
         self.model.load(cfg.model_lower_path)
         self.model.eval()
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
-        space = getattr(cfg, "blend_space", None)
-        smooth = getattr(cfg, "smooth", None)
-        more_args = {} if smooth is None else dict(smooth=smooth)
-        floor = getattr(cfg, "floor", None)
-        if floor is not None:
-            more_args["floor"] = floor
+        opt = dict(metrics=self._metrics(), blend_space=getattr(cfg, "blend_space", None), smooth=getattr(cfg, "smooth", None),
+                   floor=getattr(cfg, "floor", None), pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg))
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
-                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, metrics=self._metrics(), blend_space=space,
-                                pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg), **more_args)
-        print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
-        print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
-        print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
-        print("Average Joint Rotation Error(°): {}".format(s["rot_deg"]))
-        print("Per Joint Localization Error(cm): {}".format(s["per_joint_cm"]))
-        print("Single-window (unblended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
-            s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
-        print("Error by window position(cm): {}".format(s["position_cm"]))
-        print("Window Disagreement(cm): {}".format(s["spread_cm"]))
-        if space is not None:
-            print("Bone Length Deviation(cm): blended {} single-window {} (degenerate bones {})".format(
-                s["bone_dev_cm"], s["single_bone_dev_cm"], s["degenerate_bones"]))
-        if space == "rot":
-            print("Window Rotational Disagreement(°): {}".format(s["rot_spread_deg"]))
-        print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
-            s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
-        if self._metrics() == "full":
-            self._print_aligned(s)
-            print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
+                                batch_size=getattr(cfg, "dense_batch_size", None) or 64, **opt)
         self.last_metrics = s
         path = getattr(cfg, "save_pred", None)
-        noise, imu_noise = pose_noise_of(cfg), imu_noise_of(cfg)
         if path:
-            more = {} if space is None else dict(blend_space=np.asarray(space), degenerate_bones=np.int64(s["degenerate_bones"]))
-            if space == "rot":
-                more.update(rot=arrays["rot"], rot_spread=arrays["rot_spread"], bone_vectors=arrays["bone_vectors"])
-            if smooth is not None:
-                more.update(pred_unsmoothed=arrays["pred_unsmoothed"], moved=arrays["moved"], smooth_window=np.int64(smooth[0]),
-                            smooth_order=np.int64(smooth[1]), smooth_taper=np.asarray(smooth[2]))
-            if floor is not None:
-                more.update(foot_height=arrays["foot_height"], ground=arrays["ground"], foot_contact=arrays["foot_contact"],
-                            floor_mode=np.asarray(floor[0]), floor_contact_cm=np.float64(floor[1]), floor_margin_cm=np.float64(floor[2]))
-                if floor[0] == "clamp":
-                    more.update(pred_unclamped=arrays["pred_unclamped"], lifted=arrays["lifted"], floor_fallback=arrays["floor_fallback"])
-            if noise is not None:
-                more.update(pose_noise_deg=np.float64(noise[0]), pose_noise_t=np.float64(noise[1]), pose_noise_seed=np.int64(noise[2]))
-            if imu_noise is not None:
-                more.update({flag: np.float64(v) for flag, v in zip(IMU_NOISE_FLAGS, imu_noise[0])}, imu_noise_seed=np.int64(imu_noise[1]))
-            np.savez(path, stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]),
-                     **{k: arrays[k] for k in DENSE_SAVED}, **more)
-            print("Per-frame skeletons saved in {}".format(path))
-        if noise is not None:
-            print(pose_noise_line(noise))
-        if imu_noise is not None:
-            print(imu_noise_line(imu_noise))
-        if smooth is not None:
-            print("Unsmoothed (blended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
-                s["unsmoothed_all_cm"], s["unsmoothed_upper_cm"], s["unsmoothed_lower_cm"], s["unsmoothed_rot_deg"]))
-            print("Smoothing Displacement(cm): {} (window +-{} frames, order {}, {}; degenerate bones {})".format(
-                s["moved_cm"], s["smooth"][0], s["smooth"][1], s["smooth"][2], s["smooth_fallback"]))
-            if self._metrics() == "full":
-                print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
-        if floor is not None:
-            print("Foot Height Error(cm): {} (joint 15: {}, joint 19: {}; single-window {})".format(
-                s["foot_height_err_cm"], *s["foot_height_err_cm_per_foot"], s["single_foot_height_err_cm"]))
-            print("Floor Penetration: rate {} depth(cm) {} (target: rate {} depth {}; single-window: rate {} depth {})".format(
-                s["penetration_rate"], s["penetration_cm"], s["target_penetration_rate"], s["target_penetration_cm"],
-                s["single_penetration_rate"], s["single_penetration_cm"]))
-            print("Foot Contact by height < {:g} cm: precision {} recall {} (target: precision {} recall {})".format(
-                floor[1], s["contact_precision"], s["contact_recall"], s["target_contact_precision"], s["target_contact_recall"]))
-            print("Contact Hover(cm): {}".format(s["hover_cm"]))
-            if floor[0] == "clamp":
-                print("Unclamped Error(cm): all {} lower {} (penetration rate {} depth(cm) {})".format(
-                    s["unclamped_all_cm"], s["unclamped_lower_cm"], s["unclamped_penetration_rate"], s["unclamped_penetration_cm"]))
-                print("Floor Clamp: {} of {} frames lifted, mean lift(cm) {}, unreachable legs {} (margin {:g} cm)".format(
-                    s["lifted_frames"], s["covered_frames"], s["lift_cm"], s["floor_fallback"], floor[2]))
+            np.savez(path, **dense.saved_arrays(s, arrays, opt))
+        dense.print_summary(s, opt, saved=path)
         return s
-
-    def _print_aligned(self, s):
-        for name, parts in (("Root-relative", "root_rel"), ("Rigid-aligned", "rigid"), ("Procrustes-aligned (PA-MPJPE)", "pa")):
-            print("{} Joint Error(cm): {} (upper {}, lower {})".format(name, s[parts + "_cm"], s[parts + "_upper_cm"], s[parts + "_lower_cm"]))
-        print("Alignment Rotation(°): {}".format(s["align_rot_deg"]))
-        print("Alignment Shift(cm): {}".format(s["align_shift_cm"]))
-        print("Procrustes Scale: {}".format(s["pa_scale"]))
-        for c, v in s["pck"].items():
-            print("PCK@{:g}cm: {}".format(c, v))
-        print("Acceleration Error(cm/frame^2): {}".format(s["accel_cm"]))
-        print("Per Joint Root-relative Error(cm): {}".format(s["per_joint_root_rel_cm"]))
-        print("Per Joint Procrustes-aligned Error(cm): {}".format(s["per_joint_pa_cm"]))
 
     def eval_model(self):
         self.model.load(self.cfg.model_lower_path)
@@ -1399,14 +778,10 @@ class Evaluator(_Base):
         noise, imu_noise = pose_noise_of(self.cfg), imu_noise_of(self.cfg)
         out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics(),
                                pose_noise=noise, imu_noise=imu_noise)
-        print("Average Joint Localization Error(cm): {}".format(s["all_cm"]))
-        print("Average UpperBody Joint Localization Error(cm): {}".format(s["upper_cm"]))
-        print("Average LowerBody Joint Localization Error(cm): {}".format(s["lower_cm"]))
-        print("Average Joint Rotation Error(°): {}".format(s["rot_deg"]))
-        print("Per Joint Localization Error(cm): {}".format(s["per_joint_cm"]))
+        print_reference(s)
         if self._metrics() == "full":
             self.last_metrics = s
-            self._print_aligned(s)
+            print_aligned(s)
         if noise is not None:
             print(pose_noise_line(noise))
         if imu_noise is not None:

@@ -1,4 +1,4 @@
-"""What the bone-length-preserving blend of dense inference (processors.dense_infer(blend_space="bones"): --infer --dense --blend_space
+"""What the bone-length-preserving blend of dense inference (dense.dense_infer(blend_space="bones"): --infer --dense --blend_space
 bones) costs and changes, in ONE process:
 
   python scripts/bench_dense_bones.py OUT.json
@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from bench_frame_store import rounds, synthetic_frames  # noqa: E402
-from mmego_amd import hip, nets, ops, processors, skeleton  # noqa: E402
+from mmego_amd import dense, hip, nets, ops, processors, skeleton  # noqa: E402
 from mmego_amd.config import ConfigDemo  # noqa: E402
 from mmego_amd.data import DensePlan, PosePC  # noqa: E402
 
@@ -125,17 +125,17 @@ def main(path):
     ds = PosePC(train=False, vis=True, batch_length=T, root=os.path.join(ROOT, "scripts"), keep_frames=True)
     res["frames"] = int(len(ds.frame_npts_))
 
-    def dense(stride, **more):
+    def timed_pass(stride, **more):
         def s():
             t0 = time.perf_counter()
-            processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
+            dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
             return time.perf_counter() - t0
         return s
     timers = {}
     for stride in (5, 1):
-        timers["stride %d, no argument" % stride] = dense(stride)
-        timers["stride %d, joints" % stride] = dense(stride, blend_space="joints")
-        timers["stride %d, bones" % stride] = dense(stride, blend_space="bones")
+        timers["stride %d, no argument" % stride] = timed_pass(stride)
+        timers["stride %d, joints" % stride] = timed_pass(stride, blend_space="joints")
+        timers["stride %d, bones" % stride] = timed_pass(stride, blend_space="bones")
     for t in timers.values():
         t()
     res["pass_s"] = rounds(timers, 5)
@@ -153,7 +153,7 @@ def main(path):
     for blend in ("mean", "triangle"):
         for stride in (10, 5, 1):
             for space in ("joints", "bones"):
-                s, _ = processors.dense_infer(base, None, up, lo, ds, stride, blend=blend, batch_size=B, metrics="full", blend_space=space)
+                s, _ = dense.dense_infer(base, None, up, lo, ds, stride, blend=blend, batch_size=B, metrics="full", blend_space=space)
                 res["effect_synthetic"]["%s stride %d %s" % (blend, stride, space)] = {
                     k: round(float(s[k]), 5) for k in ("bone_dev_cm", "single_bone_dev_cm", "all_cm", "upper_cm", "lower_cm", "rot_deg",
                                                        "spread_cm", "accel_cm", "root_rel_cm", "pa_cm")}

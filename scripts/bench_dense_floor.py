@@ -1,4 +1,4 @@
-"""What the floor option of dense inference (processors.dense_infer(floor=(mode, contact_cm, margin_cm)): --infer --dense --floor M) costs,
+"""What the floor option of dense inference (dense.dense_infer(floor=(mode, contact_cm, margin_cm)): --infer --dense --floor M) costs,
 in ONE process:
 
   python scripts/bench_dense_floor.py OUT.json
@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import floor_ref as fref  # noqa: E402
 from bench_dense_bones import chains_us, golden, load  # noqa: E402
 from bench_frame_store import rounds, synthetic_frames  # noqa: E402
-from mmego_amd import hip, nets, ops, processors  # noqa: E402
+from mmego_amd import dense, hip, nets, ops, processors  # noqa: E402
 from mmego_amd.config import ConfigDemo  # noqa: E402
 from mmego_amd.data import PosePC  # noqa: E402
 
@@ -77,14 +77,14 @@ def main(path):
     ds.frame_contact_ = np.random.default_rng(1).integers(0, 2, (F, 2)).astype(np.uint8)
     res["frames"] = int(F)
 
-    def dense(**more):
+    def timed_pass(**more):
         def s():
             t0 = time.perf_counter()
-            processors.dense_infer(base, None, up, lo, ds, 5, batch_size=B, **more)
+            dense.dense_infer(base, None, up, lo, ds, 5, batch_size=B, **more)
             return time.perf_counter() - t0
         return s
-    timers = {"stride 5, no argument": dense(), "stride 5, floor measure": dense(floor=("measure", 6, 0)),
-              "stride 5, floor clamp": dense(floor=("clamp", 6, 0))}
+    timers = {"stride 5, no argument": timed_pass(), "stride 5, floor measure": timed_pass(floor=("measure", 6, 0)),
+              "stride 5, floor clamp": timed_pass(floor=("clamp", 6, 0))}
     for t in timers.values():
         t()
     res["pass_s"] = rounds(timers, 5)
@@ -93,7 +93,7 @@ def main(path):
     for k in ("measure", "clamp"):
         res["pass_s"]["floor %s / no argument" % k] = round(res["pass_s"]["stride 5, floor %s" % k]["median"] / base_s["median"], 4)
     print("pass_s", res["pass_s"])
-    s, _ = processors.dense_infer(base, None, up, lo, ds, 5, batch_size=B, floor=("clamp", 6, 0))
+    s, _ = dense.dense_infer(base, None, up, lo, ds, 5, batch_size=B, floor=("clamp", 6, 0))
     res["clamp_synthetic"] = {"note": "pretrained weights on random clouds against random targets: the figures show the mechanics, not accuracy",
                               **{k: s[k] for k in ("covered_frames", "lifted_frames", "lift_cm", "floor_fallback", "penetration_rate",
                                                    "unclamped_penetration_rate", "unclamped_penetration_cm", "all_cm", "unclamped_all_cm")}}

@@ -1,4 +1,4 @@
-"""What dense inference (processors.dense_infer: --infer --dense) costs and shows, in ONE process, three rounds, medians:
+"""What dense inference (dense.dense_infer: --infer --dense) costs and shows, in ONE process, three rounds, medians:
 
   python scripts/bench_dense_infer.py OUT.json
 
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from bench_frame_store import rounds, synthetic_frames  # noqa: E402
-from mmego_amd import hip, nets, ops, processors  # noqa: E402
+from mmego_amd import dense, hip, nets, ops, processors  # noqa: E402
 from mmego_amd.config import ConfigDemo  # noqa: E402
 from mmego_amd.data import ArraySplit, DensePlan, DenseWindows, PosePC  # noqa: E402
 from mmego_amd.train_step import call_upper  # noqa: E402
@@ -73,10 +73,10 @@ def main(path):
                      "alternating, three rounds, medians; launches: device events around one launch, 20 after 3"}
 
     # (a) the pass
-    def dense(stride):
+    def timed_pass(stride):
         def s():
             t0 = time.perf_counter()
-            processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B)
+            dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B)
             return time.perf_counter() - t0
         return s
 
@@ -93,7 +93,7 @@ def main(path):
         torch.cuda.synchronize()
         return time.perf_counter() - t0
     timers = {"evaluate_full B=1": plain(1), "evaluate_full B=64": plain(B)}
-    timers.update({"dense stride %d" % s: dense(s) for s in (20, 10, 5, 1)})
+    timers.update({"dense stride %d" % s: timed_pass(s) for s in (20, 10, 5, 1)})
     timers["plan + upload (stride 1)"] = plan_only
     for t in timers.values():
         t()                                                        # (warm: every minibatch size's first launches, the device copies)
@@ -155,11 +155,11 @@ def main(path):
     res["blend_against_single_synthetic"] = {}
     for blend in ("mean", "triangle"):
         for stride in (10, 5, 1):
-            s, _ = processors.dense_infer(base, None, up, lo, ds, stride, blend=blend, batch_size=B, metrics="full")
+            s, _ = dense.dense_infer(base, None, up, lo, ds, stride, blend=blend, batch_size=B, metrics="full")
             res["blend_against_single_synthetic"]["%s stride %d" % (blend, stride)] = {
                 "blended_all_cm": round(s["all_cm"], 4), "single_all_cm": round(s["single_all_cm"], 4), "spread_cm": round(s["spread_cm"], 4),
                 "accel_cm": round(s["accel_cm"], 4), "position_cm": [round(float(v), 4) for v in s["position_cm"]]}
-    s, _ = processors.dense_infer(base, None, up, lo, ds, T, batch_size=B, metrics="full")
+    s, _ = dense.dense_infer(base, None, up, lo, ds, T, batch_size=B, metrics="full")
     res["blend_against_single_synthetic"]["mean stride 20"] = {
         "blended_all_cm": round(s["all_cm"], 4), "single_all_cm": round(s["single_all_cm"], 4), "accel_cm": round(s["accel_cm"], 4),
         "single_accel_cm (stitched reference windows)": round(s["single_accel_cm"], 4)}

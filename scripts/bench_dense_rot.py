@@ -1,4 +1,4 @@
-"""What dense inference's blend in rotation space (processors.dense_infer(blend_space="rot"): --infer --dense --blend_space rot) costs
+"""What dense inference's blend in rotation space (dense.dense_infer(blend_space="rot"): --infer --dense --blend_space rot) costs
 beside the bone-direction blend, in ONE process:
 
   python scripts/bench_dense_rot.py OUT.json
@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from bench_frame_store import rounds, synthetic_frames  # noqa: E402
-from mmego_amd import hip, nets, ops, processors, skeleton  # noqa: E402
+from mmego_amd import dense, hip, nets, ops, processors, skeleton  # noqa: E402
 from mmego_amd.config import ConfigDemo  # noqa: E402
 from mmego_amd.data import DensePlan, PosePC  # noqa: E402
 
@@ -141,16 +141,16 @@ def main(path):
     ds = PosePC(train=False, vis=True, batch_length=T, root=os.path.join(ROOT, "scripts"), keep_frames=True)
     res["frames"] = int(len(ds.frame_npts_))
 
-    def dense(stride, **more):
+    def timed_pass(stride, **more):
         def s():
             t0 = time.perf_counter()
-            processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
+            dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
             return time.perf_counter() - t0
         return s
     timers = {}
     for stride in (5, 1):
-        timers["stride %d, bones" % stride] = dense(stride, blend_space="bones")
-        timers["stride %d, rot" % stride] = dense(stride, blend_space="rot")
+        timers["stride %d, bones" % stride] = timed_pass(stride, blend_space="bones")
+        timers["stride %d, rot" % stride] = timed_pass(stride, blend_space="rot")
     for t in timers.values():
         t()
     res["pass_s"] = rounds(timers, 5)
@@ -173,7 +173,7 @@ def main(path):
         inside.clear()
         ops.blend_rot = timed
         try:
-            processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B, blend_space="rot")
+            dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B, blend_space="rot")
         finally:
             ops.blend_rot = real
         torch.cuda.synchronize()
@@ -186,7 +186,7 @@ def main(path):
     res["figures_synthetic"] = {"note": "pretrained weights on random clouds: the error figures show the mechanics, not accuracy"}
     for stride in (10, 5, 1):
         for space in ("bones", "rot"):
-            s, _ = processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B, blend_space=space)
+            s, _ = dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B, blend_space=space)
             keys = ("bone_dev_cm", "single_bone_dev_cm", "all_cm", "upper_cm", "lower_cm", "rot_deg", "spread_cm") + (("rot_spread_deg",) if space == "rot" else ())
             res["figures_synthetic"]["stride %d %s" % (stride, space)] = dict({k: round(float(s[k]), 5) for k in keys},
                                                                             degenerate_bones=s["degenerate_bones"])

@@ -1,4 +1,4 @@
-"""What the temporal filter of dense inference (processors.dense_infer(smooth=(H, order, taper)): --infer --dense --smooth H) costs and
+"""What the temporal filter of dense inference (dense.dense_infer(smooth=(H, order, taper)): --infer --dense --smooth H) costs and
 changes, in ONE process:
 
   python scripts/bench_dense_smooth.py OUT.json
@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from bench_dense_bones import chains_us, golden, load  # noqa: E402
 from bench_frame_store import rounds, synthetic_frames  # noqa: E402
-from mmego_amd import hip, nets, ops, processors, skeleton  # noqa: E402
+from mmego_amd import dense, hip, nets, ops, processors, skeleton  # noqa: E402
 from mmego_amd.config import ConfigDemo  # noqa: E402
 from mmego_amd.data import DensePlan, PosePC  # noqa: E402
 
@@ -66,7 +66,7 @@ def main(path):
     forms = {"blend_windows C = 45 with spread (stride-1 plan)": lambda: hip.call("blend_windows", win_up, n, 45, off, row, w, F, dst[45], 45, spread),
              "blend_windows C = 24 (stride-1 plan)": lambda: hip.call("blend_windows", win_lo, n, 24, off, row, w, F, dst[24], 24, None)}
     for H in HS:
-        wd = torch.as_tensor(processors.smooth_weights(H, "gauss")).to(dev)
+        wd = torch.as_tensor(dense.smooth_weights(H, "gauss")).to(dev)
 
         def add(H=H, wd=wd):
             forms["smooth_frames C = 45 with moved, H = %d" % H] = lambda: hip.call("smooth_frames", src[45], 45, F, 45, seg, wd, H, 2, dst[45], 45, moved)
@@ -87,18 +87,18 @@ def main(path):
     ds = PosePC(train=False, vis=True, batch_length=T, root=os.path.join(ROOT, "scripts"), keep_frames=True)
     res["frames"] = int(len(ds.frame_npts_))
 
-    def dense(stride, **more):
+    def timed_pass(stride, **more):
         def s():
             t0 = time.perf_counter()
-            processors.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
+            dense.dense_infer(base, None, up, lo, ds, stride, batch_size=B, **more)
             return time.perf_counter() - t0
         return s
     timers = {}
     for stride in (5, 1):
-        timers["stride %d, no argument" % stride] = dense(stride)
-        timers["stride %d, smooth" % stride] = dense(stride, smooth=(8, 2, "gauss"))
-        timers["stride %d, bones" % stride] = dense(stride, blend_space="bones")
-        timers["stride %d, bones, smooth" % stride] = dense(stride, blend_space="bones", smooth=(8, 2, "gauss"))
+        timers["stride %d, no argument" % stride] = timed_pass(stride)
+        timers["stride %d, smooth" % stride] = timed_pass(stride, smooth=(8, 2, "gauss"))
+        timers["stride %d, bones" % stride] = timed_pass(stride, blend_space="bones")
+        timers["stride %d, bones, smooth" % stride] = timed_pass(stride, blend_space="bones", smooth=(8, 2, "gauss"))
     for t in timers.values():
         t()
     res["pass_s"] = rounds(timers, 5)
@@ -117,10 +117,10 @@ def main(path):
     for space in ("joints", "bones"):
         for H in HS:
             for order in (0, 1, 2):
-                s, _ = processors.dense_infer(base, None, up, lo, ds, 5, batch_size=B, metrics="full", blend_space=space, smooth=(H, order, "gauss"))
+                s, _ = dense.dense_infer(base, None, up, lo, ds, 5, batch_size=B, metrics="full", blend_space=space, smooth=(H, order, "gauss"))
                 res["effect_synthetic"]["%s H %d order %d gauss" % (space, H, order)] = dict(
                     {k: round(float(s[k]), 5) for k in keys}, smooth_fallback=s["smooth_fallback"])
-        s, _ = processors.dense_infer(base, None, up, lo, ds, 5, batch_size=B, metrics="full", blend_space=space, smooth=(8, 2, "box"))
+        s, _ = dense.dense_infer(base, None, up, lo, ds, 5, batch_size=B, metrics="full", blend_space=space, smooth=(8, 2, "box"))
         res["effect_synthetic"]["%s H 8 order 2 box" % space] = dict({k: round(float(s[k]), 5) for k in keys}, smooth_fallback=s["smooth_fallback"])
     print("effect_synthetic", res["effect_synthetic"])
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

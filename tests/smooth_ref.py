@@ -8,7 +8,7 @@ TINY = 1e-9
 
 
 def weights(H, taper):
-    """box: ones; gauss: exp(-2 k^2 / H^2), rounded to float32 (what processors.smooth_weights returns)."""
+    """box: ones; gauss: exp(-2 k^2 / H^2), rounded to float32 (what dense.smooth_weights returns)."""
     k = np.arange(-H, H + 1, dtype=np.float64)
     return (np.ones(2 * H + 1) if taper == "box" else np.exp(-2.0 * k * k / (H * H))).astype(np.float32)
 

@@ -113,10 +113,10 @@ def test_the_bone_list_is_checked_on_the_host():
 
 
 def test_bone_lengths_of_the_bone_set():
-    from mmego_amd import processors
+    from mmego_amd import dense
     rng = np.random.default_rng(0)
     body = rng.normal(0, 0.3, (20, 3)).astype(np.float32)
-    up, lo = processors.bone_lengths(body)
+    up, lo = dense.bone_lengths(body)
     want = np.sqrt((body.astype(np.float64) ** 2).sum(axis=1)).astype(np.float32)
     assert up.dtype == np.float32 and np.array_equal(up, want[:14]) and np.array_equal(lo, want[14:])
 

@@ -37,7 +37,7 @@ def _d(dev, a):
 
 
 def _body(rng, nb):
-    """A random bone set [nb, 3] with lengths in (0.05, 0.55) m, and L_b = float32(|body_b|) as processors.bone_lengths takes it."""
+    """A random bone set [nb, 3] with lengths in (0.05, 0.55) m, and L_b = float32(|body_b|) as dense.bone_lengths takes it."""
     u = rng.normal(size=(nb, 3))
     body = (u / np.linalg.norm(u, axis=1, keepdims=True) * rng.uniform(0.05, 0.55, (nb, 1))).astype(np.float32)
     return body, np.linalg.norm(body.astype(np.float64), axis=1).astype(np.float32)

@@ -1,4 +1,4 @@
-"""GPU: dense inference with the bone-length-preserving blend (processors.dense_infer(blend_space="bones"), `main.py --infer --dense
+"""GPU: dense inference with the bone-length-preserving blend (dense.dense_infer(blend_space="bones"), `main.py --infer --dense
 --blend_space bones`) on the synthetic Sample_data tree of tests/test_dense_infer_gpu.py: recordings of 23, 20, 7 and 41 frames
 (frame_no = 20), nets from torch.manual_seed, the recorded head pose.
 
@@ -53,7 +53,7 @@ class _World:
 def world(tmp_path_factory):
     """The tree, its PosePC with the per-frame clouds, seeded nets, and the dense passes the tests share (each computed once)."""
     assert torch.cuda.is_available()
-    from mmego_amd import nets, processors
+    from mmego_amd import dense, nets, processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
     w = _World()
@@ -74,14 +74,14 @@ def world(tmp_path_factory):
     w.up, w.lo = nets.UpperNet().to(w.dev).eval(), nets.LowerNet(64).to(w.dev).eval()
     torch.save(w.up.state_dict(), w.tmp / "upper.pth")
     torch.save(w.lo.state_dict(), w.tmp / "lower.pth")
-    w.L_up, w.L_lo = processors.bone_lengths(np.asarray(w.ds.frame_bones_, dtype=np.float32).reshape(-1, 3))
+    w.L_up, w.L_lo = dense.bone_lengths(np.asarray(w.ds.frame_bones_, dtype=np.float32).reshape(-1, 3))
     w.runs = {}
 
     def run(blend, space):
         key = (blend, space)
         if key not in w.runs:
             more = {} if space is None else dict(blend_space=space)
-            s, a = processors.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, blend=blend, batch_size=4, **more)
+            s, a = dense.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, blend=blend, batch_size=4, **more)
             a = dict(a, win_up_h=a["win_up"].cpu().numpy(), win_lo_h=a["win_lo"].cpu().numpy())
             w.runs[key] = (s, a)
         return w.runs[key]
@@ -166,9 +166,9 @@ def test_summary_figures(world, blend):
 
 
 def test_an_unknown_blend_space_is_refused(world):
-    from mmego_amd import processors
+    from mmego_amd import dense
     with pytest.raises(ValueError, match="blend_space"):
-        processors.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rotations")
+        dense.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rotations")
 
 
 def _run(args, env):

@@ -1,4 +1,4 @@
-"""GPU: dense inference (processors.dense_infer, `main.py --infer --dense`) on a tiny synthetic Sample_data tree with the .mat keys of
+"""GPU: dense inference (dense.dense_infer, `main.py --infer --dense`) on a tiny synthetic Sample_data tree with the .mat keys of
 tests/test_cli_gpu.py but recordings of 23, 20, 7 and 41 frames (frame_no = 20): one with a head window, one that is exactly a window, one
 too short for any, one with two reference windows and a frame left over.  Nets from torch.manual_seed, the recorded head pose.
 
@@ -53,7 +53,7 @@ class _World:
 def world(tmp_path_factory):
     """The tree, its PosePC with the per-frame clouds, seeded nets, and the dense passes the tests share (each computed once)."""
     assert torch.cuda.is_available()
-    from mmego_amd import nets, processors
+    from mmego_amd import dense, nets, processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
     w = _World()
@@ -79,7 +79,7 @@ def world(tmp_path_factory):
     def run(stride, blend="mean", batch_size=4, metrics="reference"):
         key = (stride, blend, batch_size, metrics)
         if key not in w.runs:
-            s, a = processors.dense_infer(w.base, None, w.up, w.lo, w.ds, stride, blend=blend, batch_size=batch_size, metrics=metrics)
+            s, a = dense.dense_infer(w.base, None, w.up, w.lo, w.ds, stride, blend=blend, batch_size=batch_size, metrics=metrics)
             a = dict(a, win_up_h=a["win_up"].cpu().numpy(), win_lo_h=a["win_lo"].cpu().numpy())
             w.runs[key] = (s, a)
         return w.runs[key]

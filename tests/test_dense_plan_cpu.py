@@ -179,3 +179,17 @@ def test_dense_options_reach_the_config():
                 setattr(c, k, v)
             elif k in c.__dict__:
                 delattr(c, k)
+
+
+@pytest.mark.parametrize("T", [1, 3, 20, 64])
+def test_the_figure_log_has_one_named_row_per_figure(T):
+    """dense.figure_rows: the names are unique, their rows disjoint, "position" spans exactly T rows and every other name one, and the
+    rows fill 0 .. T + 12 -- whichever options a pass runs with."""
+    from mmego_amd import dense
+    assert len(set(dense.FIGURE_ROWS)) == len(dense.FIGURE_ROWS) == 13
+    rows = dense.figure_rows(T)
+    assert list(rows) == list(dense.FIGURE_ROWS)
+    taken = {name: list(range(r.start, r.stop)) if isinstance(r, slice) else [r] for name, r in rows.items()}
+    assert len(taken["position"]) == T and all(len(v) == 1 for name, v in taken.items() if name != "position")
+    every = sorted(r for v in taken.values() for r in v)
+    assert every == list(range(T + 12))                 # disjoint, no gap, T + 12 in all

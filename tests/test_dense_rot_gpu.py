@@ -1,4 +1,4 @@
-"""GPU: dense inference with the blend in rotation space (processors.dense_infer(blend_space="rot"), `main.py --infer --dense
+"""GPU: dense inference with the blend in rotation space (dense.dense_infer(blend_space="rot"), `main.py --infer --dense
 --blend_space rot`) on a synthetic Sample_data tree like that of tests/test_dense_bones_gpu.py: recordings of 23, 20, 7 and 41 frames
 (frame_no = 20), nets from torch.manual_seed, the recorded head pose -- here with every R_btc a PROPER rotation, as a recording's is
 (asserted on the head rotations the rows ran with).
@@ -61,7 +61,7 @@ class _World:
 def world(tmp_path_factory):
     """The tree, its PosePC with the per-frame clouds, seeded nets, and the dense passes the tests share (each computed once)."""
     assert torch.cuda.is_available()
-    from mmego_amd import nets, processors
+    from mmego_amd import dense, nets, processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
     w = _World()
@@ -90,7 +90,7 @@ def world(tmp_path_factory):
         key = (blend, space, stride, tag)
         if key not in w.runs:
             more = {} if space is None else dict(blend_space=space)
-            s, a = processors.dense_infer(w.base, None, w.up, w.lo, w.ds, stride, blend=blend, batch_size=4, **more)
+            s, a = dense.dense_infer(w.base, None, w.up, w.lo, w.ds, stride, blend=blend, batch_size=4, **more)
             a = dict(a)
             for k in ("win_up", "win_lo", "win_q_up", "win_q_lo", "win_R"):
                 if k in a:
@@ -215,9 +215,9 @@ def test_summary_figures(world, blend):
 
 
 def test_rot_with_smooth_is_refused(world):
-    from mmego_amd import processors
+    from mmego_amd import dense
     with pytest.raises(ValueError, match="would not be filtered"):
-        processors.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rot", smooth=(3, 2, "gauss"))
+        dense.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rot", smooth=(3, 2, "gauss"))
 
 
 def _run(args, env):

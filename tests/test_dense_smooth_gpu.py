@@ -1,4 +1,4 @@
-"""GPU: dense inference with its temporal filter (processors.dense_infer(smooth=(H, order, taper)), `main.py --infer --dense --smooth H`)
+"""GPU: dense inference with its temporal filter (dense.dense_infer(smooth=(H, order, taper)), `main.py --infer --dense --smooth H`)
 on the synthetic Sample_data tree of tests/test_dense_infer_gpu.py: recordings of 23, 20, 7 and 41 frames (frame_no = 20), nets from
 torch.manual_seed, the recorded head pose.
 
@@ -30,7 +30,7 @@ SMOOTH = (2, 2, "gauss")
 def world(tmp_path_factory):
     """The tree, its PosePC with the per-frame clouds, seeded nets, and the dense passes the tests share (each computed once)."""
     assert torch.cuda.is_available()
-    from mmego_amd import nets, processors
+    from mmego_amd import dense, nets, processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
     w = _World()
@@ -51,7 +51,7 @@ def world(tmp_path_factory):
     w.up, w.lo = nets.UpperNet().to(w.dev).eval(), nets.LowerNet(64).to(w.dev).eval()
     torch.save(w.up.state_dict(), w.tmp / "upper.pth")
     torch.save(w.lo.state_dict(), w.tmp / "lower.pth")
-    w.L_up, w.L_lo = processors.bone_lengths(np.asarray(w.ds.frame_bones_, dtype=np.float32).reshape(-1, 3))
+    w.L_up, w.L_lo = dense.bone_lengths(np.asarray(w.ds.frame_bones_, dtype=np.float32).reshape(-1, 3))
     w.runs = {}
 
     def run(space=None, metrics="reference", **more):
@@ -59,7 +59,7 @@ def world(tmp_path_factory):
         if key not in w.runs:
             if space is not None:
                 more = dict(more, blend_space=space)
-            w.runs[key] = processors.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, batch_size=4, metrics=metrics, **more)
+            w.runs[key] = dense.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, batch_size=4, metrics=metrics, **more)
         return w.runs[key]
 
     w.run = run
@@ -93,7 +93,7 @@ def test_smooth_none_is_the_call_without_the_argument(world):
 
 @pytest.mark.parametrize("space", [None, "bones"])
 def test_smoothed_frames_against_the_restatement(world, space):
-    from mmego_amd import processors
+    from mmego_amd import dense
     s0, a0 = world.run(space, "full")
     s, a = world.run(space, "full", smooth=SMOOTH)
     cov = a["covered"] > 0
@@ -111,7 +111,7 @@ def test_smoothed_frames_against_the_restatement(world, space):
     assert set(a) - set(a0) == {"pred_unsmoothed", "moved"} and s["smooth"] == SMOOTH and s["smooth_fallback"] == 0
     # the smoothed frames: the restatement on the blended ones, recording by recording
     seg, w = _seg(a), sref.weights(SMOOTH[0], SMOOTH[2])
-    assert np.array_equal(w, processors.smooth_weights(SMOOTH[0], SMOOTH[2]))
+    assert np.array_equal(w, dense.smooth_weights(SMOOTH[0], SMOOTH[2]))
     if space == "bones":
         up64, moved64, fb_up = sref.smooth_bones(a0["upper"].reshape(F, 45), seg, w, SMOOTH[1], bref.UPPER_WALK, world.L_up)
         lo64, _, fb_lo = sref.smooth_bones(a0["lower"].reshape(F, 24), seg, w, SMOOTH[1], bref.LOWER_WALK, world.L_lo)
@@ -156,10 +156,10 @@ def test_bones_stay_rigid_under_the_filter(world):
 
 
 def test_a_bad_smooth_argument_is_refused(world):
-    from mmego_amd import processors
+    from mmego_amd import dense
     for bad in ((0, 2, "gauss"), (32, 2, "gauss"), (2, 3, "gauss"), (2, 2, "hann"), (2, 2)):
         with pytest.raises(ValueError, match="smooth"):
-            processors.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, smooth=bad)
+            dense.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, smooth=bad)
 
 
 def test_command_line(world):

@@ -126,21 +126,21 @@ def test_other_values_are_refused(capsys, monkeypatch):
 
 
 def test_the_floor_argument_is_checked():
-    from mmego_amd import processors
-    assert processors._check_floor(None) is None
-    assert processors._check_floor(("clamp", 6, np.float32(0.5))) == ("clamp", 6.0, 0.5)
+    from mmego_amd import dense
+    assert dense._check_floor(None) is None
+    assert dense._check_floor(("clamp", 6, np.float32(0.5))) == ("clamp", 6.0, 0.5)
     for bad in (("clamp", 6), ("snap", 6, 0), ("measure", 0, 0), ("measure", -1, 0), ("measure", 6, -1), ("measure", float("nan"), 0),
                 ("measure", 6, float("inf")), ("measure", True, 0), ("measure", "6", 0), "measure"):
         with pytest.raises(ValueError, match="floor"):
-            processors._check_floor(bad)
+            dense._check_floor(bad)
 
 
 def test_summary_arithmetic():
-    from mmego_amd import processors
+    from mmego_amd import dense
     sums = np.zeros(22)
     sums[:11] = [0.30, 0.04, 2, 5, 4, 6, 0.12, 0.01, 1, 6, 5]          # foot 0 over 10 rows
     sums[11:] = [0.10, 0.00, 0, 0, 0, 0, 0.00, 0.00, 0, 0, 0]          # foot 1: nothing penetrates, nothing low, nothing flagged
-    s = processors._floor_summary(sums, 10, "x_", target=True)
+    s = dense._floor_summary(sums, 10, "x_", target=True)
     assert s["x_foot_height_err_cm_per_foot"] == (pytest.approx(3.0), pytest.approx(1.0)) and s["x_foot_height_err_cm"] == pytest.approx(2.0)
     assert s["x_penetration_rate_per_foot"] == (0.2, 0.0) and s["x_penetration_rate"] == 0.1
     assert s["x_penetration_cm_per_foot"] == (pytest.approx(2.0), None) and s["x_penetration_cm"] == pytest.approx(2.0)
@@ -148,8 +148,8 @@ def test_summary_arithmetic():
     assert s["x_hover_cm_per_foot"] == (pytest.approx(2.0), None)
     assert s["target_penetration_rate"] == 0.05 and s["target_penetration_cm"] == pytest.approx(1.0)
     assert s["target_contact_precision"] == pytest.approx(5 / 6) and s["target_contact_recall"] == pytest.approx(5 / 6)
-    assert not any(k.startswith("target_") for k in processors._floor_summary(sums, 10, "single_"))
-    assert set(processors._floor_summary(sums, 10)) == {k + t for k in processors.FLOOR_KEYS for t in ("", "_per_foot")}
+    assert not any(k.startswith("target_") for k in dense._floor_summary(sums, 10, "single_"))
+    assert set(dense._floor_summary(sums, 10)) == {k + t for k in dense.FLOOR_KEYS for t in ("", "_per_foot")}
 
 
 def test_the_entry_points_are_declared_as_ops_calls_them():

@@ -250,7 +250,7 @@ def world(tmp_path_factory):
     """The tree, its PosePC with the per-frame clouds, seeded nets; after a first pass the floor of every frame is set to z = the median
     predicted foot height (about half the feet then lie under it) and the flags are drawn at random.  The passes are computed once."""
     assert torch.cuda.is_available()
-    from mmego_amd import nets, processors
+    from mmego_amd import dense, nets, processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
     w = _World()
@@ -279,7 +279,7 @@ def world(tmp_path_factory):
         if key not in w.runs:
             if space is not None:
                 more = dict(more, blend_space=space)
-            w.runs[key] = processors.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, batch_size=4, metrics=metrics, **more)
+            w.runs[key] = dense.dense_infer(w.base, None, w.up, w.lo, w.ds, 3, batch_size=4, metrics=metrics, **more)
         return w.runs[key]
 
     w.run = run
@@ -337,7 +337,7 @@ def test_floor_none_is_the_call_without_the_argument(world):
 
 @pytest.mark.parametrize("space", [None, "rot"])
 def test_measure_against_float64(world, space):
-    from mmego_amd import processors
+    from mmego_amd import dense
     s0, a0 = world.run(space)
     s, a = world.run(space, floor=("measure", 6, 0))
     cov = a["covered"] > 0
@@ -359,9 +359,9 @@ def test_measure_against_float64(world, space):
     win = a["win_lo"].cpu().numpy().reshape(-1, 8, 3)
     rf = plan.row_frame
     want_w, _ = _figures(win[:, [3, 7]], a["target"][rf][:, [15, 19]], a["ground"][rf], a["foot_contact"][rf], 0.06)
-    _hold(s, want_w, "single_", processors.FLOOR_KEYS)
-    assert set(s) - set(s0) == ({p + k + t for p in ("", "single_") for k in processors.FLOOR_KEYS for t in ("", "_per_foot")}
-                                | {k + t for k in processors.FLOOR_TARGET_KEYS for t in ("", "_per_foot")} | {"floor"})
+    _hold(s, want_w, "single_", dense.FLOOR_KEYS)
+    assert set(s) - set(s0) == ({p + k + t for p in ("", "single_") for k in dense.FLOOR_KEYS for t in ("", "_per_foot")}
+                                | {k + t for k in dense.FLOOR_TARGET_KEYS for t in ("", "_per_foot")} | {"floor"})
 
 
 @pytest.mark.parametrize("smooth", [None, (2, 2, "gauss")])
@@ -410,11 +410,11 @@ def test_clamp_under_bones_keeps_the_bone_lengths(world):
 
 
 def test_clamp_under_rot_is_refused(world):
-    from mmego_amd import processors
+    from mmego_amd import dense
     with pytest.raises(ValueError, match="floor"):
-        processors.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rot", floor=("clamp", 6, 0))
+        dense.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, blend_space="rot", floor=("clamp", 6, 0))
     with pytest.raises(ValueError, match="floor"):
-        processors.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, floor=("snap", 6, 0))
+        dense.dense_infer(world.base, None, world.up, world.lo, world.ds, 3, floor=("snap", 6, 0))
 
 
 def test_command_line(world):

@@ -110,7 +110,7 @@ def test_the_key_is_a_pure_function_of_its_words():
 
 
 def test_imu_jitter_is_declared_as_ops_calls_it():
-    from mmego_amd import hip, ops, train_step, processors
+    from mmego_amd import dense, hip, ops, processors, train_step
     proto = hip.parse_header()["mmego_imu_jitter"]
     assert [n for _, n in proto] == ["stream", "imu", "n_rows", "T", "S", "noise_rot_deg", "noise_acc", "noise_gyro", "bias_rot_deg",
                                      "bias_acc", "bias_gyro", "seed_word", "row_ids", "win_ids", "out"]
@@ -121,7 +121,7 @@ def test_imu_jitter_is_declared_as_ops_calls_it():
     assert all(sig[n].default is None for n in ("T", "row_ids", "win_ids"))
     for step in (train_step.StageStep, train_step.ImuStep):
         assert inspect.signature(step.__init__).parameters["imu_noise"].default is None
-    for fn in (processors._epoch_eval, processors.evaluate_full, processors.dense_infer):
+    for fn in (processors._epoch_eval, processors.evaluate_full, dense.dense_infer):
         assert inspect.signature(fn).parameters["imu_noise"].default is None
 
 

@@ -108,6 +108,7 @@ def dense(world):
     from mmego_amd import processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
+    from mmego_amd.dense import dense_infer
     np.random.seed(3)
     ds = PosePC(train=False, vis=True, keep_frames=True, batch_length=T, root=world.data)
     keep = ConfigDemo.gt_head_pose
@@ -121,7 +122,7 @@ def dense(world):
 
     def fresh(batch_size, noise):
         more = {} if noise is None else dict(imu_noise=noise)
-        return processors.dense_infer(base, world.imu, world.up, world.lo, ds, 3, batch_size=batch_size, **more)
+        return dense_infer(base, world.imu, world.up, world.lo, ds, 3, batch_size=batch_size, **more)
 
     def run(batch_size, noise):
         if (batch_size, noise) not in d.runs:
@@ -135,7 +136,7 @@ def test_dense_inference_does_not_depend_on_the_minibatch(world, dense):
     """Twice the same arrays; the same skeletons at two minibatch sizes (the draw numbers are the row's global frame and the plan's window,
     not their places in the minibatch), within the project's 2e-5 m for two minibatch sizes; and other skeletons than the noise-free
     pass's."""
-    from mmego_amd import processors
+    from mmego_amd.dense import dense_infer
     s4, a4 = dense.run(4, NOISE)
     s4b, a4b = dense.fresh(4, NOISE)
     for k in ("pred", "upper", "lower", "spread"):
@@ -152,7 +153,7 @@ def test_dense_inference_does_not_depend_on_the_minibatch(world, dense):
     print("IMU noise moved a joint by up to %.3g m" % moved)
     assert moved > 1e-4 and set(s0) == set(s4) and set(a0) == set(a4)
     with pytest.raises(ValueError, match="imu_noise"):
-        processors.dense_infer(dense.base, None, world.up, world.lo, dense.ds, 3, batch_size=4, imu_noise=NOISE)
+        dense_infer(dense.base, None, world.up, world.lo, dense.ds, 3, batch_size=4, imu_noise=NOISE)
 
 
 def _infer(world, argv):

@@ -99,7 +99,7 @@ def test_the_key_is_a_pure_function_of_its_words():
 
 
 def test_pose_jitter_is_declared_as_ops_calls_it():
-    from mmego_amd import hip, ops, train_step, processors
+    from mmego_amd import dense, hip, ops, processors, train_step
     proto = hip.parse_header()["mmego_pose_jitter"]
     assert [n for _, n in proto] == ["stream", "R", "t", "n", "sigma_deg", "sigma_t", "seed_word", "ids", "R_out", "t_out"]
     assert [c for c, _ in proto] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double, ctypes.c_double,
@@ -108,7 +108,7 @@ def test_pose_jitter_is_declared_as_ops_calls_it():
     assert inspect.signature(ops.pose_jitter).parameters["ids"].default is None
     step = inspect.signature(train_step.StageStep.__init__).parameters
     assert step["pose_noise_deg"].default is None and step["pose_noise_t"].default is None
-    for fn in (processors._epoch_eval, processors.evaluate_full, processors.dense_infer):
+    for fn in (processors._epoch_eval, processors.evaluate_full, dense.dense_infer):
         assert inspect.signature(fn).parameters["pose_noise"].default is None
 
 

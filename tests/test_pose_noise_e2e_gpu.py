@@ -99,6 +99,7 @@ def dense(world):
     from mmego_amd import processors
     from mmego_amd.config import ConfigDemo
     from mmego_amd.data import PosePC
+    from mmego_amd.dense import dense_infer
     np.random.seed(3)
     ds = PosePC(train=False, vis=True, keep_frames=True, batch_length=T, root=world.data)
     keep = ConfigDemo.gt_head_pose
@@ -112,7 +113,7 @@ def dense(world):
 
     def fresh(batch_size, noise):
         more = {} if noise is None else dict(pose_noise=noise)
-        return processors.dense_infer(base, None, world.up, world.lo, ds, 3, batch_size=batch_size, **more)
+        return dense_infer(base, None, world.up, world.lo, ds, 3, batch_size=batch_size, **more)
 
     def run(batch_size, noise):
         if (batch_size, noise) not in d.runs:

@@ -36,8 +36,8 @@ def test_blend_space_rot_reaches_the_config():
                 setattr(c, k, v)
             elif k in c.__dict__:
                 delattr(c, k)
-    from mmego_amd import processors
-    assert processors.BLEND_SPACES == ("joints", "bones", "rot")
+    from mmego_amd import dense
+    assert dense.BLEND_SPACES == ("joints", "bones", "rot")
 
 
 def test_blend_space_rot_needs_dense(capsys, monkeypatch):

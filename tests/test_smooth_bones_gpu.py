@@ -119,7 +119,7 @@ def test_smooth_bones_against_the_restatement(dev, tree, F):
 def test_the_column_form_shortens_bones_and_the_bones_form_does_not(dev):
     """Through ops, with the project's walk tables: a skeleton whose bones turn by a tenth of a radian a frame, under a wide moving
     average.  The column filter shortens the bones by centimetres; the bones form keeps them."""
-    from mmego_amd import ops, processors, skeleton
+    from mmego_amd import dense, ops, skeleton
     rng = np.random.default_rng(17)
     for walk, J in ((skeleton.WALK_UPPER, 15), (skeleton.WALK_LOWER, 8)):
         bones = [tuple(b) for b in walk.tolist()]
@@ -135,7 +135,7 @@ def test_the_column_form_shortens_bones_and_the_bones_form_does_not(dev):
                 fast[f, c] = fast[f, p] + float(l) * d
         srcd = _d(dev, fast.reshape(F, 3 * J).astype(np.float32))
         seg = np.zeros(F, np.int32)
-        w = processors.smooth_weights(8, "gauss")
+        w = dense.smooth_weights(8, "gauss")
         rigid, plain = (torch.full((F, 3 * J), SENT, dtype=torch.float32, device=dev) for _ in range(2))
         fb = torch.full((F,), -7, dtype=torch.int32, device=dev)
         ops.smooth_bones(srcd, seg, w, 0, walk, L, rigid, None, fb)
@@ -154,7 +154,7 @@ def test_a_bone_that_reverses_between_two_frames_keeps_its_own_direction(dev):
     bone (bone 0 of the upper walk: head 14 -> joint 3, L = 0.25) points along +x in frame 0 and -x in frame 1, from heads at multiples
     of 0.25, so the filtered vector is exactly zero: each frame keeps its own direction from the filtered head, counts one fallback, and
     the joints below stay rigid."""
-    from mmego_amd import ops, processors
+    from mmego_amd import dense, ops
     J, bones = TREES["upper"]
     rng = np.random.default_rng(11)
     body, _ = _body(rng, len(bones))
@@ -169,7 +169,7 @@ def test_a_bone_that_reverses_between_two_frames_keeps_its_own_direction(dev):
     src = np.stack([a.ravel(), b.ravel()]).astype(np.float32)
     assert np.array_equal(src[0, 9:12] - src[0, 42:45], [0.25, 0, 0]) and np.array_equal(src[1, 9:12] - src[1, 42:45], [-0.25, 0, 0])
     seg = np.array([4, 4], np.int32)
-    w = processors.smooth_weights(1, "box")
+    w = dense.smooth_weights(1, "box")
     dst = torch.full((2, 45), SENT, dtype=torch.float32, device=dev)
     mv = torch.full((2,), SENT, dtype=torch.float32, device=dev)
     fb = torch.full((2,), -7, dtype=torch.int32, device=dev)
@@ -188,14 +188,14 @@ def test_a_bone_that_reverses_between_two_frames_keeps_its_own_direction(dev):
 
 
 def test_refusals_leave_the_outputs_alone(dev):
-    from mmego_amd import hip, ops, processors
+    from mmego_amd import dense, hip, ops
     J, bones = TREES["upper"]
     rng = np.random.default_rng(5)
     _, L = _body(rng, len(bones))
     F = 9
     src = _d(dev, slow_rows(rng, F, J, bones, L))
     seg = np.zeros(F, np.int32)
-    w = processors.smooth_weights(2, "gauss")
+    w = dense.smooth_weights(2, "gauss")
     dst = torch.full((F, 45), SENT, dtype=torch.float32, device=dev)
     mv = torch.full((F,), SENT, dtype=torch.float32, device=dev)
     fb = torch.full((F,), -7, dtype=torch.int32, device=dev)

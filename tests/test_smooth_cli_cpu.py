@@ -1,5 +1,5 @@
 """CPU: --smooth / --smooth_order / --smooth_taper on the command line (defaults, refusals, what reaches ConfigDemo), the weight tables
-of processors.smooth_weights, the check of dense_infer's smooth argument, and the two entry points' declarations."""
+of dense.smooth_weights, the check of dense_infer's smooth argument, and the two entry points' declarations."""
 import numpy as np
 import pytest
 
@@ -67,9 +67,9 @@ def test_other_values_are_refused(capsys, monkeypatch):
 
 
 def test_weight_tables():
-    from mmego_amd import processors
+    from mmego_amd import dense
     for H in (1, 2, 8, 31):
-        box, gauss = processors.smooth_weights(H, "box"), processors.smooth_weights(H, "gauss")
+        box, gauss = dense.smooth_weights(H, "box"), dense.smooth_weights(H, "gauss")
         assert box.dtype == np.float32 and gauss.dtype == np.float32 and box.shape == gauss.shape == (2 * H + 1,)
         assert np.array_equal(box, np.ones(2 * H + 1, np.float32))
         k = np.arange(-H, H + 1, dtype=np.float64)
@@ -78,16 +78,16 @@ def test_weight_tables():
         assert np.array_equal(box, sref.weights(H, "box")) and np.array_equal(gauss, sref.weights(H, "gauss"))
     for H, taper in ((0, "box"), (32, "box"), (2.0, "box"), (True, "box"), (4, "hann")):
         with pytest.raises(ValueError, match="smooth"):
-            processors.smooth_weights(H, taper)
+            dense.smooth_weights(H, taper)
 
 
 def test_the_smooth_argument_is_checked():
-    from mmego_amd import processors
-    assert processors._check_smooth(None) is None
-    assert processors._check_smooth((np.int64(3), 2, "box")) == (3, 2, "box")
+    from mmego_amd import dense
+    assert dense._check_smooth(None) is None
+    assert dense._check_smooth((np.int64(3), 2, "box")) == (3, 2, "box")
     for bad in ((3, 2), (0, 2, "box"), (32, 2, "box"), (3, 3, "box"), (3, -1, "box"), (3, 1.0, "box"), (3, 2, "hann"), "gauss", 3):
         with pytest.raises(ValueError, match="smooth"):
-            processors._check_smooth(bad)
+            dense._check_smooth(bad)
 
 
 def test_the_entry_points_are_declared_as_ops_calls_them():

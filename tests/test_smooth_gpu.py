@@ -131,12 +131,12 @@ def test_a_segment_does_not_see_its_neighbours(dev):
 
 
 def test_refusals_leave_the_outputs_alone(dev):
-    from mmego_amd import hip, ops, processors
+    from mmego_amd import dense, hip, ops
     rng = np.random.default_rng(3)
     F, C = 20, 45
     src = _d(dev, rng.normal(0.0, 0.7, (F, C)).astype(np.float32))
     seg = np.zeros(F, np.int32)
-    w = processors.smooth_weights(3, "gauss")
+    w = dense.smooth_weights(3, "gauss")
     dst = torch.full((F, C), SENT, dtype=torch.float32, device=dev)
     mv = torch.full((F,), SENT, dtype=torch.float32, device=dev)
     both = torch.full((2 * F, C), SENT, dtype=torch.float32, device=dev)
