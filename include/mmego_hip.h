@@ -426,6 +426,11 @@ int mmego_lstm64_backward(void* stream, int B, int T, const float* dout, long do
                           const float* gates1, const float* cst0, const float* cst1, const float* c0_0,
                           const float* c0_1, const float* whh0, const float* whh1, float* dgates0, float* dgates1,
                           long dgs);
+/* Batch rows per workgroup (4 or 16) that the four lstm64 calls take at batch size B on the current device: 4-row workgroups
+ * (v_mfma_f32_4x4x1_16B_f32) while the 16-row grid, 2 x ceil(B/16) workgroups, covers at most half of the CUs, 16-row
+ * ones (v_mfma_f32_16x16x4_f32) from there on.  The two forms add the terms of every product in the same order: the same bits.
+ * All launches of one B take the same form.  MMEGO_LSTM64_ROWS=4|16 in the environment forces one. */
+int mmego_lstm64_rows(int B);
 
 /* The two calls above for n <= 4 INDEPENDENT stacks' layers in ONE launch (grid z = stack; descs: n host structs whose fields are the
  * argument lists above, in order).  All stacks share B and T and the options (stashes for all or none, dropout for all or none).

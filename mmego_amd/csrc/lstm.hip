@@ -9,11 +9,14 @@
 //                     one XCD (its L2 then holds 1/8 of W_hh).
 //  lstm64_fwd/bwd     whole-sequence persistent kernels for the three H=64 BiLSTMs of Upper_Net /
 //                     Lower_Net (Upper_Net.py:333, Lower_Net.py:91): batch rows are independent through
-//                     the recurrence, so a workgroup keeps W_hh (64 KB) in LDS, 16 rows of h in LDS and c
-//                     in registers and walks all T steps with no inter-workgroup traffic.
+//                     the recurrence, so a workgroup keeps W_hh in registers, 16 or 4 rows of h in LDS and c
+//                     in registers and walks all T steps with no inter-workgroup traffic.  16 rows per
+//                     workgroup on v_mfma_f32_16x16x4_f32 where that fills the chip, 4 rows on
+//                     v_mfma_f32_4x4x1_16B_f32 for small batches (ROWS below; l64_rows chooses).
 #include "common.h"
 #include "lstm_cell.h"
 #include <stddef.h>
+#include <stdlib.h>
 #include <string.h>
 
 // ---------------------------------------------------------------------------------------------
@@ -61,63 +64,174 @@ typedef float __attribute__((address_space(1)))* l64_gptr;
 typedef f32x4 __attribute__((address_space(1)))* l64_gptr4;
 typedef const f32x4 __attribute__((address_space(1)))* l64_gcptr4;
 
-// FULL: B is a multiple of the 16 rows of a workgroup, so every `live` test is a compile-time true; STASH / DROP: the backward
+// ROWS: the batch rows of a workgroup, 16 or 4.  One step of a 16-row workgroup is 64 v_mfma_f32_16x16x4_f32 per wave at 32 cycles
+// each: 2048 cycles of one CU's matrix pipe that no schedule inside the CU shortens, on 2 B/16 workgroups (8 of 256 CUs at B = 64).
+// Rows are independent through the recurrence, so small batches take 4-row workgroups instead: the same step is 64
+// v_mfma_f32_4x4x1_16B_f32 per wave at 8 cycles each (512 cycles) on four times as many CUs.  The launchers choose (l64_rows).
+//
+// Who owns what.  ROWS = 16: lane (fq, fr) of wave w owns hidden unit 16 w + fr and rows 4 fq .. 4 fq + 3 (the 16x16 accumulator
+// layout).  ROWS = 4: lane 4 b + r of wave w owns hidden unit 16 w + b and row r, ONE cell per lane.  Either way element (k, row) of
+// the h tile is at k * ROWS + row -- for ROWS = 4 that is the thread index, and an operand read is 64 consecutive words: no bank
+// conflict in either direction (the backward's gate-gradient tile: L64BwdProd<ROWS>::at).
+template <int ROWS>
+struct L64Map {
+  static_assert(ROWS == 16 || ROWS == 4, "rows of a workgroup");
+  static constexpr int RPL = ROWS / 4;        // rows (cells) per lane
+  static __device__ __forceinline__ int unit(int wave, int lane) { return wave * 16 + (ROWS == 16 ? (lane & 15) : (lane >> 2)); }
+  static __device__ __forceinline__ int row0(int lane) { return ROWS == 16 ? (lane >> 4) * 4 : (lane & 3); }   // this lane's first row
+};
+
+// One k of the 4-row product: D[block b][row i][column c] += A[ABID][row i] * B[b][c] -- the four rows of block ABID's A operand go
+// to all 16 blocks (CBSZ = 4), so ONE register holds 16 k's of the h tile (lane 4 a + i: row i of k = a) and an h value is read from
+// LDS once, not once per block.  (The broadcast fields are immediates: a template argument, not a loop variable.)
+template <int ABID>
+__device__ __forceinline__ f32x4 l64_mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, ABID, 0); }
+// ONE accumulator chain, in a fixed order of the k's: the order in which the 16-row form's v_mfma_f32_16x16x4_f32 chain takes them
+// (an instruction adds its four k's one after the other, each one fused multiply-add, as a 4x4x1 instruction adds its one), so that
+// the two forms give the same bits.  X(a) expands to the instructions of block a.
+#define L64_X16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+
+// a[i] of lane q of a quad  <->  a[q] of lane i: two rounds of pairwise exchanges by DPP quad permutes (no LDS, no wait)
+__device__ __forceinline__ float l64_quad_perm_b1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)); }  // [1,0,3,2]
+__device__ __forceinline__ float l64_quad_perm_4e(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)); }  // [2,3,0,1]
+__device__ __forceinline__ void l64_quad_transpose(float (&a)[4], int lane) {
+  const bool o1 = lane & 1, o2 = lane & 2;
+#pragma unroll
+  for (int r = 0; r < 4; r += 2) {
+    const float x = a[r], y = a[r + 1], got = l64_quad_perm_b1(o1 ? x : y);
+    a[r] = o1 ? got : x;
+    a[r + 1] = o1 ? y : got;
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const float x = a[q], y = a[q + 2], got = l64_quad_perm_4e(o2 ? x : y);
+    a[q] = o2 ? got : x;
+    a[q + 2] = o2 ? y : got;
+  }
+}
+
+// The recurrent product of the forward step, h_{t-1} . W_hh^T for this lane's cells: W_hh stationary in 64 registers per lane, loaded
+// straight from global memory (no W_hh tile in LDS, no staging pass); run() reads the h tile and leaves pre[gate][cell].
+template <int ROWS>
+struct L64FwdProd;
+template <>
+struct L64FwdProd<16> {
+  // at MFMA step s lane quad fq takes k = 16 fq + s (for h and W_hh alike: any k order is valid as long as both operands agree),
+  // so the 16 values of a gate are 4 contiguous 16-B loads
+  float wreg[16][4];
+  __device__ __forceinline__ void load(const float* W, int wave, int lane) {
+    const int fq = lane >> 4, j = wave * 16 + (lane & 15);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float* wrow = W + (g * 64 + j) * 64 + 16 * fq;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + 4 * q);
+        wreg[4 * q + 0][g] = v.x; wreg[4 * q + 1][g] = v.y; wreg[4 * q + 2][g] = v.z; wreg[4 * q + 3][g] = v.w;
+      }
+    }
+  }
+  __device__ __forceinline__ void run(const float* hs, int lane, float (&pre)[4][4]) const {
+    const int fr = lane & 15, fq = lane >> 4;
+    f32x4 acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float hk[16];                    // all 16 operand reads in flight before the first MFMA (they were issued in pairs, each
+#pragma unroll                       // pair followed by its own wait: eight LDS latencies per step)
+    for (int k4 = 0; k4 < 16; ++k4) hk[k4] = hs[(16 * fq + k4) * 16 + fr];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k4 = 0; k4 < 16; ++k4) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(hk[k4], wreg[k4][g], acc[g], 0, 0, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) pre[g][reg] = acc[g][reg];
+  }
+};
+template <>
+struct L64FwdProd<4> {
+  // B operand: lane 4 b + g holds the column of (unit 16 w + b, gate g), one W_hh row of 64 k's (16 contiguous 16-B loads); A
+  // operand register v: k = 16 v + a in block a.  The instruction's 64 columns are this wave's 16 units x 4 gates, so the gates of a
+  // k share ONE instruction.  The 16-row form's chain of a gate takes k = 16 fq + s, fq = 0 .. 3 inside instruction s = 0 .. 15:
+  // here that is block a = s of register v = fq, a outside and v inside, on one accumulator -- the same sum in the same order, the
+  // same bits.  The result has the four rows of a (unit, gate) in one lane; the cell wants the four gates of a (unit, row): a 4 x 4
+  // transpose inside each lane quad.
+  float wreg[64];
+  __device__ __forceinline__ void load(const float* W, int wave, int lane) {
+    const float* wrow = W + ((lane & 3) * 64 + wave * 16 + (lane >> 2)) * 64;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + 4 * q);
+      wreg[4 * q + 0] = v.x; wreg[4 * q + 1] = v.y; wreg[4 * q + 2] = v.z; wreg[4 * q + 3] = v.w;
+    }
+  }
+  __device__ __forceinline__ void run(const float* hs, int lane, float (&pre)[4][1]) const {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    float hk[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) hk[v] = hs[64 * v + lane];
+    __builtin_amdgcn_sched_barrier(0);
+#define L64_FWD_K(A_)                                                                                                       \
+  s = l64_mfma4<A_>(hk[0], wreg[A_], s); s = l64_mfma4<A_>(hk[1], wreg[16 + A_], s); s = l64_mfma4<A_>(hk[2], wreg[32 + A_], s); \
+  s = l64_mfma4<A_>(hk[3], wreg[48 + A_], s);
+    L64_X16(L64_FWD_K)
+#undef L64_FWD_K
+    float a[4] = {s.x, s.y, s.z, s.w};
+    l64_quad_transpose(a, lane);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pre[g][0] = a[g];
+  }
+};
+
+// FULL: B is a multiple of the ROWS rows of a workgroup, so every `live` test is a compile-time true; STASH / DROP: the backward
 // stashes (gates, cell states, h_{t-1}: all or none) / the fused inter-layer dropout.  Template parameters so that the step loop is
 // straight-line code.  That matters more than it looks: with loads and stores predicated row by row (an s_cbranch_execz around
 // each) and run-time branches on the optional outputs, the compiler could not count the outstanding memory operations across
 // the loop and put ONE s_waitcnt vmcnt(0) into every step -- which waits for the previous step's ~28 stores per lane to be
 // acknowledged, not only for the prefetched inputs (2.26 us per step; 1.96 us now).
-template <bool FULL, bool STASH, bool DROP>
+template <bool FULL, bool STASH, bool DROP, int ROWS>
 __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* hs = smem;              // [64 k][16 rows]
+  using Map = L64Map<ROWS>;
+  constexpr int R = Map::RPL;    // cells of this lane: rows rl .. rl + R - 1 of hidden unit j
+  float* hs = smem;              // [64 k][ROWS rows]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = blockIdx.y, r0 = blockIdx.x * 16;
+  const int d = blockIdx.y, r0 = blockIdx.x * ROWS;
   const int B = p.B, T = p.T;
-  const float* W = p.whh[d];
-  const int fr = lane & 15, fq = lane >> 4;
-  const int j = wave * 16 + fr;  // hidden unit of this lane
-  float creg[4], hreg[4], bh[4];
+  const int j = Map::unit(wave, lane), rl = Map::row0(lane);
+  float creg[R], hreg[R], bh[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) bh[g] = p.bhh[d] ? p.bhh[d][g * 64 + j] : 0.f;
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    int row = r0 + fq * 4 + reg;
+  for (int reg = 0; reg < R; ++reg) {
+    int row = r0 + rl + reg;
     bool ok = row < B;
     creg[reg] = (ok && p.c0[d]) ? p.c0[d][row * 64 + j] : 0.f;
     hreg[reg] = (ok && p.h0[d]) ? p.h0[d][row * 64 + j] : 0.f;
-    hs[j * 16 + fq * 4 + reg] = hreg[reg];
+    hs[j * ROWS + rl + reg] = hreg[reg];
   }
   __syncthreads();
-  // This lane's W_hh operand fragments stay in registers for the whole sequence, loaded straight from global memory: at
-  // MFMA step s lane quad fq takes k = 16 fq + s (for h and W_hh alike: any k order is valid as long as both operands agree),
-  // so the 16 values of a gate are 4 contiguous 16-B loads.  No W_hh tile in LDS, no staging pass.
-  float wreg[16][4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float* wrow = W + (g * 64 + j) * 64 + 16 * fq;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + 4 * q);
-      wreg[4 * q + 0][g] = v.x; wreg[4 * q + 1][g] = v.y; wreg[4 * q + 2][g] = v.z; wreg[4 * q + 3][g] = v.w;
-    }
-  }
+  L64FwdProd<ROWS> prod;         // W_hh: stationary in registers for the whole sequence
+  prod.load(p.whh[d], wave, lane);
 
   // The input projections do not depend on the recurrence: step s+1's values are fetched while step s computes, so
   // their latency (the longest thing in a step otherwise) is off the critical path.  All addresses advance by a
   // per-step stride from bases computed once (the address arithmetic used to outweigh the MFMAs).
-  float xp[4][4], xpn[4][4];
+  float xp[4][R], xpn[4][R];
   constexpr bool stash = STASH, keep_h = STASH, drop = DROP;
   const unsigned dkey = drop ? dropout_key(p.seed_ctr[0], p.salt) : 0u;
   const float keep_scale = drop ? 1.0f / (1.0f - p.drop_p) : 1.0f;
   const int t_first = d == 0 ? 0 : T - 1;
   const long dir = d == 0 ? 1 : -1;
-  l64_gcptr xq[4];
-  l64_gptr oq[4], hq[4], gq[4], cq[4];
-  bool live[4];
+  l64_gcptr xq[R];
+  l64_gptr oq[R], hq[R], gq[R], cq[R];
+  bool live[R];
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int row = r0 + fq * 4 + reg;
+  for (int reg = 0; reg < R; ++reg) {
+    const int row = r0 + rl + reg;
     live[reg] = FULL || row < B;
     const long rt = (long)(live[reg] ? row : 0) * T + t_first;
     xq[reg] = (l64_gcptr)(p.xproj[d] + rt * p.xs + j);
@@ -131,7 +245,7 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
              cstep = dir * (long)B * 64;
 #define L64_LOAD_XP(DST)                                                                            \
   do {                                                                                              \
-    _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) {                                           \
+    _Pragma("unroll") for (int reg = 0; reg < R; ++reg) {                                           \
       _Pragma("unroll") for (int g = 0; g < 4; ++g) DST[g][reg] = (FULL || live[reg]) ? xq[reg][g * 64] : 0.f; \
       xq[reg] += xstep;                                                                             \
     }                                                                                               \
@@ -141,37 +255,27 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
     // (unconditional: past the last step the previous address is loaded again -- no branch around the prefetch)
     if (s + 1 >= T) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) xq[reg] -= xstep;
+      for (int reg = 0; reg < R; ++reg) xq[reg] -= xstep;
     }
     L64_LOAD_XP(xpn);
     if (keep_h) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
+      for (int reg = 0; reg < R; ++reg) {
         if (FULL || live[reg]) *hq[reg] = hreg[reg];
         hq[reg] += hstep;
       }
     }
-    f32x4 acc[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float hk[16];                    // all 16 operand reads in flight before the first MFMA (they were issued in pairs, each
-#pragma unroll                       // pair followed by its own wait: eight LDS latencies per step)
-    for (int k4 = 0; k4 < 16; ++k4) hk[k4] = hs[(16 * fq + k4) * 16 + fr];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k4 = 0; k4 < 16; ++k4) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(hk[k4], wreg[k4][g], acc[g], 0, 0, 0);
-    }
+    float acc[4][R];                 // h_{t-1} . W_hh^T of this lane's cells, per gate
+    prod.run(hs, lane, acc);
     L64_LDS_BARRIER();  // everyone has finished reading hs for this step
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
+    for (int reg = 0; reg < R; ++reg) {
       const LstmCell u = lstm_cell_fwd(acc[0][reg] + (xp[0][reg] + bh[0]), acc[1][reg] + (xp[1][reg] + bh[1]),
                                        acc[2][reg] + (xp[2][reg] + bh[2]), acc[3][reg] + (xp[3][reg] + bh[3]), creg[reg]);
       const float cn = u.c, hn = u.h;
       creg[reg] = cn;
       hreg[reg] = hn;
-      hs[j * 16 + fq * 4 + reg] = hn;
+      hs[j * ROWS + rl + reg] = hn;
       if (FULL || live[reg]) {
         *oq[reg] = hn;
         if (drop) {
@@ -193,13 +297,13 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) xp[g][reg] = xpn[g][reg];
+      for (int reg = 0; reg < R; ++reg) xp[g][reg] = xpn[g][reg];
     L64_LDS_BARRIER();
   }
 #undef L64_LOAD_XP
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    int row = r0 + fq * 4 + reg;
+  for (int reg = 0; reg < R; ++reg) {
+    int row = r0 + rl + reg;
     if (row < B) {
       if (p.hn[d]) p.hn[d][row * 64 + j] = hreg[reg];
       if (p.cn[d]) p.cn[d][row * 64 + j] = creg[reg];
@@ -207,16 +311,31 @@ __device__ __forceinline__ void lstm64_fwd_body(const Lstm64P& p) {
   }
 }
 
-template <bool FULL, bool STASH, bool DROP>
-__global__ __launch_bounds__(256) void lstm64_fwd_kernel(Lstm64P p) { lstm64_fwd_body<FULL, STASH, DROP>(p); }
+template <bool FULL, bool STASH, bool DROP, int ROWS>
+__global__ __launch_bounds__(256) void lstm64_fwd_kernel(Lstm64P p) { lstm64_fwd_body<FULL, STASH, DROP, ROWS>(p); }
 
 // Several INDEPENDENT stacks' layers in one launch (grid z = stack): UpperNetwlocal's global and anchor BiLSTM(64) stacks have the same
 // shape and no data in common (Net/Upper_Net.py:333-339 and :208-216) -- one after the other each layer was 8 workgroups on a 256-CU
 // chip, twice.
 #define L64_MAX_MULTI 4
 struct Lstm64Multi { Lstm64P p[L64_MAX_MULTI]; };
-template <bool FULL, bool STASH, bool DROP>
-__global__ __launch_bounds__(256) void lstm64_fwd_multi_kernel(Lstm64Multi m) { lstm64_fwd_body<FULL, STASH, DROP>(m.p[blockIdx.z]); }
+template <bool FULL, bool STASH, bool DROP, int ROWS>
+__global__ __launch_bounds__(256) void lstm64_fwd_multi_kernel(Lstm64Multi m) { lstm64_fwd_body<FULL, STASH, DROP, ROWS>(m.p[blockIdx.z]); }
+
+// Rows per workgroup at batch size B: 4 while the 16-row grid -- 2 directions x ceil(B / 16) workgroups -- covers at most half of
+// the chip's CUs (B <= 1024 on 256 CUs), 16 from there on: a large batch fills the chip with 16-row workgroups already (config 5's
+// B = 2048: 256 of them) and four times the launch width buys it nothing.  Measured (scripts/bench_lstm64_rows.py, T = 8, forward /
+// backward us per launch, 4-row against 16-row): B = 512 10.4 / 8.8 against 19.8 / 19.1; B = 1024 (two 4-row workgroups per CU) 15.8 /
+// 12.9 against 21.1 / 20.1; B = 2048 (four per CU) 24.8 / 21.2 against 21.9 / 21.5.  A function of B and the device alone -- not of
+// T, the options or the number of stacks of a _multi launch -- so that every launch of one shape takes the same form and sums in the
+// same order.  MMEGO_LSTM64_ROWS = 4 | 16 forces one form (A/B runs and the tests; read per call: the tests switch it).
+static int l64_rows(int B) {
+  const char* env = getenv("MMEGO_LSTM64_ROWS");
+  const int forced = env ? atoi(env) : 0;
+  if (forced == 4 || forced == 16) return forced;
+  return 2 * cdiv(B, 16) * 2 <= mmego_cu_count() ? 4 : 16;
+}
+extern "C" int mmego_lstm64_rows(int B) { return B > 0 ? l64_rows(B) : MMEGO_EBADARG; }
 
 extern "C" int mmego_lstm64_forward(void* stream, int B, int T, const float* xproj0, const float* xproj1, long xs,
                                     const float* whh0, const float* whh1, const float* bhh0, const float* bhh1,
@@ -242,14 +361,16 @@ extern "C" int mmego_lstm64_forward(void* stream, int B, int T, const float* xpr
   p.hprev[0] = hprev0; p.hprev[1] = hprev1;
   p.B = B; p.T = T;
   p.drop_y = drop_y; p.drop_mask = drop_mask; p.drop_p = drop_p; p.seed_ctr = seed_ctr; p.salt = (unsigned)salt;
-  size_t lds = (size_t)(64 * 16) * sizeof(float);            // h tile only: W_hh lives in registers
-  const bool full = B % 16 == 0, st_ = gates0 != nullptr, dr = drop_mask != nullptr;
+  const int rows = l64_rows(B);
+  size_t lds = (size_t)(64 * rows) * sizeof(float);          // h tile only: W_hh lives in registers
+  const bool full = B % rows == 0, st_ = gates0 != nullptr, dr = drop_mask != nullptr;
   MMEGO_REQUIRE((hprev0 != nullptr) == st_ && (hprev1 != nullptr) == st_ && (gates1 != nullptr) == st_);   // stashes: all or none
-#define L64_FWD_LAUNCH(F_, S_, D_)                                                                                    \
-  do {                                                                                                                \
-    if (int e = mmego_allow_lds<lstm64_fwd_kernel<F_, S_, D_>>(lds)) return e;                                        \
-    hipLaunchKernelGGL((lstm64_fwd_kernel<F_, S_, D_>), dim3(cdiv(B, 16), 2), dim3(256), lds, (hipStream_t)stream, p); \
+#define L64_FWD_LAUNCH_R(F_, S_, D_, R_)                                                                                     \
+  do {                                                                                                                       \
+    if (int e = mmego_allow_lds<lstm64_fwd_kernel<F_, S_, D_, R_>>(lds)) return e;                                           \
+    hipLaunchKernelGGL((lstm64_fwd_kernel<F_, S_, D_, R_>), dim3(cdiv(B, R_), 2), dim3(256), lds, (hipStream_t)stream, p);   \
   } while (0)
+#define L64_FWD_LAUNCH(F_, S_, D_) do { if (rows == 4) L64_FWD_LAUNCH_R(F_, S_, D_, 4); else L64_FWD_LAUNCH_R(F_, S_, D_, 16); } while (0)
   if (full) {
     if (st_ && dr) L64_FWD_LAUNCH(true, true, true);
     else if (st_) L64_FWD_LAUNCH(true, true, false);
@@ -262,6 +383,7 @@ extern "C" int mmego_lstm64_forward(void* stream, int B, int T, const float* xpr
     else L64_FWD_LAUNCH(false, false, false);
   }
 #undef L64_FWD_LAUNCH
+#undef L64_FWD_LAUNCH_R
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -277,92 +399,25 @@ struct Lstm64BwdP {
   X(P, D, dout) X(P, D, dos) X(P, D, gates) X(P, D, cst) X(P, D, c0) X(P, D, whh) X(P, D, dgates) X(P, D, dgs) X(P, D, B) X(P, D, T)
 L64_SAME_LAYOUT(Lstm64BwdP, MmegoLstm64Bwd, L64_BWD_FIELDS);
 
-// FULL as in lstm64_fwd_kernel: straight-line step loop (no row predicates, the prefetch unconditional, loads from explicit
-// global pointers), so the compiler counts its waits instead of draining the memory pipe every step.
-template <bool FULL>
-__device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* dgs = smem;              // [256 n][16 rows]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = blockIdx.y, r0 = blockIdx.x * 16;
-  const int B = p.B, T = p.T;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int j = wave * 16 + fr;
-  // W_hh as this lane's 64 MFMA operands (row n = 4*i + fq, column 16*wave + fr), straight from global memory with all
-  // loads in flight (the LDS copy it replaces was a rolled loop of 16 dependent global -> LDS round trips per launch)
+// The recurrent product of the backward step, dh_rec[row][k] = sum_n dgates[row][n] * W_hh[n][k] over the 256 gate columns n, from the
+// gate-gradient tile dgs [256 n][ROWS] in LDS; W_hh stationary in 64 registers per lane, straight from global memory with all loads in
+// flight.  run() follows the barrier behind the tile's stores; take() follows the step's closing barrier and leaves dh[cell].
+template <int ROWS>
+struct L64BwdProd;
+template <>
+struct L64BwdProd<16> {
+  static constexpr int LDS_FLOATS = 256 * 16;
+  static __device__ __forceinline__ int at(int n, int row) { return n * 16 + row; }      // where (n, row) of the tile lies
+  // this wave owns k in [16 w, 16 w + 16): operand i is row n = 4 i + fq, column 16 w + fr
   float wreg[64];
-  {
-    const float* W = p.whh[d] + fq * 64 + wave * 16 + fr;
+  f32x4 dh4;
+  __device__ __forceinline__ void load(const float* Whh, int wave, int lane) {
+    const float* W = Whh + (lane >> 4) * 64 + wave * 16 + (lane & 15);
 #pragma unroll
     for (int i = 0; i < 64; ++i) wreg[i] = W[i * 256];
   }
-  float dcreg[4] = {0.f, 0.f, 0.f, 0.f};
-  f32x4 dhrec = {0.f, 0.f, 0.f, 0.f};
-
-  // Everything a step reads from memory (incoming dh, saved gates, cell states) is independent of the recurrence: the
-  // next step's values are fetched while this step computes.  c_{t-1} of this step is c_t of the next one.
-  float gin[4][6], gnx[4][6];        // per row: dh_in, i, f, g, o, c_prev
-  float ccur[4];
-  const l64_gcptr g_gates = (l64_gcptr)p.gates[d], g_dout = (l64_gcptr)p.dout, g_cst = (l64_gcptr)p.cst[d];
-  const bool has_c0 = p.c0[d] != nullptr;
-  const l64_gcptr g_c0 = has_c0 ? (l64_gcptr)p.c0[d] : g_cst;      // (a valid address either way: the value is masked below)
-#define L64_LOAD_BWD(DST, step)                                                                                \
-  do {                                                                                                         \
-    const int tq_ = d == 0 ? (step) : T - 1 - (step);                                                          \
-    const int tp_ = d == 0 ? tq_ - 1 : tq_ + 1;                                                                \
-    _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) {                                                      \
-      const int row_ = r0 + fq * 4 + reg;                                                                      \
-      if (FULL || row_ < B) {                                                                                  \
-        const f32x4 gv_ = *(l64_gcptr4)(g_gates + ((long)tq_ * B + row_) * 256 + 4 * j);                       \
-        DST[reg][0] = g_dout[((long)row_ * T + tq_) * p.dos + d * 64 + j];                                     \
-        DST[reg][1] = gv_.x; DST[reg][2] = gv_.y; DST[reg][3] = gv_.z; DST[reg][4] = gv_.w;                    \
-        const l64_gcptr cp_ = ((step) > 0) ? g_cst + ((long)tp_ * B + row_) * 64 + j : g_c0 + (long)row_ * 64 + j; \
-        const float cv_ = *cp_;                                                                                \
-        DST[reg][5] = ((step) > 0 || has_c0) ? cv_ : 0.f;                                                      \
-      } else {                                                                                                 \
-        _Pragma("unroll") for (int q = 0; q < 6; ++q) DST[reg][q] = 0.f;                                       \
-      }                                                                                                        \
-    }                                                                                                          \
-  } while (0)
-  L64_LOAD_BWD(gin, T - 1);
-  {
-    const int tl = d == 0 ? T - 1 : 0;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      int row = r0 + fq * 4 + reg;
-      ccur[reg] = (FULL || row < B) ? g_cst[((long)tl * B + row) * 64 + j] : 0.f;
-    }
-  }
-  for (int s = T - 1; s >= 0; --s) {
-    const int tt = d == 0 ? s : T - 1 - s;
-    const int sn = s > 0 ? s - 1 : 0;          // (unconditional prefetch: the last step loads step 0's values again)
-    L64_LOAD_BWD(gnx, sn);
-    float dg4[4][4];
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      int row = r0 + fq * 4 + reg;
-      if (FULL || row < B) {
-        float dh = gin[reg][0] + dhrec[reg];
-        float gi = gin[reg][1], gf = gin[reg][2], gg = gin[reg][3], go = gin[reg][4];
-        const LstmCellGrad o = lstm_cell_bwd(gi, gf, gg, go, fast_tanh(ccur[reg]), gin[reg][5], dcreg[reg], dh);   // (tanh: the forward's fast form)
-        dg4[0][reg] = o.di;
-        dg4[1][reg] = o.df;
-        dg4[2][reg] = o.dg;
-        dg4[3][reg] = o.dout;
-        dcreg[reg] = o.dcprev;
-        l64_gptr dst = (l64_gptr)p.dgates[d] + ((long)row * T + tt) * p.dgs + j;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) dst[g * 64] = dg4[g][reg];
-      } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) dg4[g][reg] = 0.f;
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) dgs[(g * 64 + j) * 16 + fq * 4 + reg] = dg4[g][reg];
-      ccur[reg] = gin[reg][5];
-    }
-    L64_LDS_BARRIER();
-    // dh_rec[row][k] = sum_n dgates[row][n] * W_hh[n][k]; this wave owns k in [16*wave, 16*wave+16)
+  __device__ __forceinline__ void run(float* dgs, int wave, int lane) {
+    const int fr = lane & 15, fq = lane >> 4;
     // four accumulator chains (a dependent 16x16x4 MFMA can issue every 32 cycles, an independent one every 8) and the
     // operand reads in groups of 16 ahead of their MFMAs (fixed summation order: (a0 + a1) + (a2 + a3))
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f}, a3 = {0.f, 0.f, 0.f, 0.f};
@@ -380,22 +435,160 @@ __device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
         a3 = __builtin_amdgcn_mfma_f32_16x16x4f32(dk[u + 3], wreg[nb + u + 3], a3, 0, 0, 0);
       }
     }
-    dhrec = (a0 + a1) + (a2 + a3);
+    dh4 = (a0 + a1) + (a2 + a3);
+  }
+  __device__ __forceinline__ void take(const float* dgs, int wave, int lane, float (&dh)[4]) const {
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) dh[reg] = dh4[reg];
+  }
+};
+template <>
+struct L64BwdProd<4> {
+  // One 4x4x1 instruction is 4 rows x 64 columns x one n, and the step has 64 output columns k in all: a wave cannot own a quarter of
+  // the k's without leaving 48 of its 64 columns idle.  So every wave takes ALL 64 k's (lane = k) and a quarter of the sum, and the
+  // four partial sums meet in LDS.  The quarter of wave w is accumulator chain w of the 16-row form -- the n's with (n mod 16) / 4 = w,
+  // in rising order on one accumulator -- and dh of a cell is (p0 + p1) + (p2 + p3) as there: the same bits.  Register v, block a:
+  // n = 16 (4 v + a / 4) + 4 w + a mod 4.  The tile keeps a wave's 64 n's together (at(): 272 words per wave, 16 past 256, so that the
+  // two hidden-unit groups of a 32-lane store group land on different bank halves): operand reads are 64 consecutive words.
+  // Partial sums: wave w's rows at part[w][row][k], rows 72 words apart: a ds_read_b32 is served in two groups of 32 lanes over 32
+  // banks, and the 32 cells of a group (4 rows x 8 units) then read row * 8 + unit, 32 different banks.
+  static constexpr int WLDS = 272, PART = 4 * WLDS, PLD = 72, LDS_FLOATS = PART + 4 * 4 * PLD;
+  static __device__ __forceinline__ int at(int n, int row) { return ((n & 15) >> 2) * WLDS + (4 * (n >> 4) + (n & 3)) * 4 + row; }
+  float wreg[64];
+  __device__ __forceinline__ void load(const float* Whh, int wave, int lane) {
+    const float* W = Whh + (long)(4 * wave) * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) wreg[i] = W[(16 * (i >> 2) + (i & 3)) * 64];
+  }
+  __device__ __forceinline__ void run(float* dgs, int wave, int lane) {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    float dk[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) dk[v] = dgs[WLDS * wave + 64 * v + lane];
+    __builtin_amdgcn_sched_barrier(0);
+#define L64_BWD_K(A_) s = l64_mfma4<A_>(dk[V_], wreg[16 * V_ + A_], s);
+#define V_ 0
+    L64_X16(L64_BWD_K)
+#undef V_
+#define V_ 1
+    L64_X16(L64_BWD_K)
+#undef V_
+#define V_ 2
+    L64_X16(L64_BWD_K)
+#undef V_
+#define V_ 3
+    L64_X16(L64_BWD_K)
+#undef V_
+#undef L64_BWD_K
+    float* part = dgs + PART + wave * (4 * PLD) + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[i * PLD] = s[i];
+  }
+  __device__ __forceinline__ void take(const float* dgs, int wave, int lane, float (&dh)[1]) const {
+    const float* part = dgs + PART + (lane & 3) * PLD + wave * 16 + (lane >> 2);
+    const float p0 = part[0], p1 = part[4 * PLD], p2 = part[8 * PLD], p3 = part[12 * PLD];
+    dh[0] = (p0 + p1) + (p2 + p3);
+  }
+};
+
+// FULL as in lstm64_fwd_kernel: straight-line step loop (no row predicates, the prefetch unconditional, loads from explicit
+// global pointers), so the compiler counts its waits instead of draining the memory pipe every step.
+template <bool FULL, int ROWS>
+__device__ __forceinline__ void lstm64_bwd_body(const Lstm64BwdP& p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  using Map = L64Map<ROWS>;
+  constexpr int R = Map::RPL;
+  float* dgs = smem;              // [256 n][ROWS rows] (+ the 4-row form's partial sums)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = blockIdx.y, r0 = blockIdx.x * ROWS;
+  const int B = p.B, T = p.T;
+  const int j = Map::unit(wave, lane), rl = Map::row0(lane);
+  L64BwdProd<ROWS> prod;
+  prod.load(p.whh[d], wave, lane);
+  float dcreg[R], dhrec[R];
+#pragma unroll
+  for (int reg = 0; reg < R; ++reg) dcreg[reg] = dhrec[reg] = 0.f;
+
+  // Everything a step reads from memory (incoming dh, saved gates, cell states) is independent of the recurrence: the
+  // next step's values are fetched while this step computes.  c_{t-1} of this step is c_t of the next one.
+  float gin[R][6], gnx[R][6];        // per row: dh_in, i, f, g, o, c_prev
+  float ccur[R];
+  const l64_gcptr g_gates = (l64_gcptr)p.gates[d], g_dout = (l64_gcptr)p.dout, g_cst = (l64_gcptr)p.cst[d];
+  const bool has_c0 = p.c0[d] != nullptr;
+  const l64_gcptr g_c0 = has_c0 ? (l64_gcptr)p.c0[d] : g_cst;      // (a valid address either way: the value is masked below)
+#define L64_LOAD_BWD(DST, step)                                                                                \
+  do {                                                                                                         \
+    const int tq_ = d == 0 ? (step) : T - 1 - (step);                                                          \
+    const int tp_ = d == 0 ? tq_ - 1 : tq_ + 1;                                                                \
+    _Pragma("unroll") for (int reg = 0; reg < R; ++reg) {                                                      \
+      const int row_ = r0 + rl + reg;                                                                          \
+      if (FULL || row_ < B) {                                                                                  \
+        const f32x4 gv_ = *(l64_gcptr4)(g_gates + ((long)tq_ * B + row_) * 256 + 4 * j);                       \
+        DST[reg][0] = g_dout[((long)row_ * T + tq_) * p.dos + d * 64 + j];                                     \
+        DST[reg][1] = gv_.x; DST[reg][2] = gv_.y; DST[reg][3] = gv_.z; DST[reg][4] = gv_.w;                    \
+        const l64_gcptr cp_ = ((step) > 0) ? g_cst + ((long)tp_ * B + row_) * 64 + j : g_c0 + (long)row_ * 64 + j; \
+        const float cv_ = *cp_;                                                                                \
+        DST[reg][5] = ((step) > 0 || has_c0) ? cv_ : 0.f;                                                      \
+      } else {                                                                                                 \
+        _Pragma("unroll") for (int q = 0; q < 6; ++q) DST[reg][q] = 0.f;                                       \
+      }                                                                                                        \
+    }                                                                                                          \
+  } while (0)
+  L64_LOAD_BWD(gin, T - 1);
+  {
+    const int tl = d == 0 ? T - 1 : 0;
+#pragma unroll
+    for (int reg = 0; reg < R; ++reg) {
+      int row = r0 + rl + reg;
+      ccur[reg] = (FULL || row < B) ? g_cst[((long)tl * B + row) * 64 + j] : 0.f;
+    }
+  }
+  for (int s = T - 1; s >= 0; --s) {
+    const int tt = d == 0 ? s : T - 1 - s;
+    const int sn = s > 0 ? s - 1 : 0;          // (unconditional prefetch: the last step loads step 0's values again)
+    L64_LOAD_BWD(gnx, sn);
+    float dg4[4][R];
+#pragma unroll
+    for (int reg = 0; reg < R; ++reg) {
+      int row = r0 + rl + reg;
+      if (FULL || row < B) {
+        float dh = gin[reg][0] + dhrec[reg];
+        float gi = gin[reg][1], gf = gin[reg][2], gg = gin[reg][3], go = gin[reg][4];
+        const LstmCellGrad o = lstm_cell_bwd(gi, gf, gg, go, fast_tanh(ccur[reg]), gin[reg][5], dcreg[reg], dh);   // (tanh: the forward's fast form)
+        dg4[0][reg] = o.di;
+        dg4[1][reg] = o.df;
+        dg4[2][reg] = o.dg;
+        dg4[3][reg] = o.dout;
+        dcreg[reg] = o.dcprev;
+        l64_gptr dst = (l64_gptr)p.dgates[d] + ((long)row * T + tt) * p.dgs + j;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dst[g * 64] = dg4[g][reg];
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dg4[g][reg] = 0.f;
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) dgs[L64BwdProd<ROWS>::at(g * 64 + j, rl + reg)] = dg4[g][reg];
+      ccur[reg] = gin[reg][5];
+    }
+    L64_LDS_BARRIER();
+    prod.run(dgs, wave, lane);
     __builtin_amdgcn_sched_barrier(0);       // (keep the copy of the prefetched values at the end of the step: see the forward kernel)
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
+    for (int reg = 0; reg < R; ++reg)
 #pragma unroll
       for (int q = 0; q < 6; ++q) gin[reg][q] = gnx[reg][q];
     L64_LDS_BARRIER();
+    prod.take(dgs, wave, lane, dhrec);
   }
 #undef L64_LOAD_BWD
 }
 
-template <bool FULL>
-__global__ __launch_bounds__(256) void lstm64_bwd_kernel(Lstm64BwdP p) { lstm64_bwd_body<FULL>(p); }
+template <bool FULL, int ROWS>
+__global__ __launch_bounds__(256) void lstm64_bwd_kernel(Lstm64BwdP p) { lstm64_bwd_body<FULL, ROWS>(p); }
 struct Lstm64BwdMulti { Lstm64BwdP p[L64_MAX_MULTI]; };
-template <bool FULL>
-__global__ __launch_bounds__(256) void lstm64_bwd_multi_kernel(Lstm64BwdMulti m) { lstm64_bwd_body<FULL>(m.p[blockIdx.z]); }
+template <bool FULL, int ROWS>
+__global__ __launch_bounds__(256) void lstm64_bwd_multi_kernel(Lstm64BwdMulti m) { lstm64_bwd_body<FULL, ROWS>(m.p[blockIdx.z]); }
 
 extern "C" int mmego_lstm64_backward(void* stream, int B, int T, const float* dout, long dos, const float* gates0,
                                      const float* gates1, const float* cst0, const float* cst1, const float* c0_0,
@@ -411,9 +604,14 @@ extern "C" int mmego_lstm64_backward(void* stream, int B, int T, const float* do
   p.whh[0] = whh0; p.whh[1] = whh1;
   p.dgates[0] = dgates0; p.dgates[1] = dgates1; p.dgs = dgs;
   p.B = B; p.T = T;
-  const size_t lds = (size_t)(256 * 16) * sizeof(float);
-  if (B % 16 == 0) hipLaunchKernelGGL(lstm64_bwd_kernel<true>, dim3(cdiv(B, 16), 2), dim3(256), lds, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(lstm64_bwd_kernel<false>, dim3(cdiv(B, 16), 2), dim3(256), lds, (hipStream_t)stream, p);
+#define L64_BWD_LAUNCH(K_, R_, Z_, P_)                                                                                              \
+  do {                                                                                                                              \
+    const size_t lds = (size_t)L64BwdProd<R_>::LDS_FLOATS * sizeof(float);                                                          \
+    if (B % R_ == 0) hipLaunchKernelGGL((K_<true, R_>), dim3(cdiv(B, R_), 2, Z_), dim3(256), lds, (hipStream_t)stream, P_);         \
+    else hipLaunchKernelGGL((K_<false, R_>), dim3(cdiv(B, R_), 2, Z_), dim3(256), lds, (hipStream_t)stream, P_);                    \
+  } while (0)
+  if (l64_rows(B) == 4) L64_BWD_LAUNCH(lstm64_bwd_kernel, 4, 1, p);
+  else L64_BWD_LAUNCH(lstm64_bwd_kernel, 16, 1, p);
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -438,9 +636,11 @@ extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const MmegoLstm64
     m.p[i] = l64_param<Lstm64P>(p);
   }
   for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = m.p[0];
-  const size_t lds = (size_t)(64 * 16) * sizeof(float);
-  const bool full = B % 16 == 0;
-#define L64_FWDM_LAUNCH(F_, S_, D_) hipLaunchKernelGGL((lstm64_fwd_multi_kernel<F_, S_, D_>), dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m)
+  const int rows = l64_rows(B);
+  const size_t lds = (size_t)(64 * rows) * sizeof(float);
+  const bool full = B % rows == 0;
+#define L64_FWDM_LAUNCH_R(F_, S_, D_, R_) hipLaunchKernelGGL((lstm64_fwd_multi_kernel<F_, S_, D_, R_>), dim3(cdiv(B, R_), 2, n), dim3(256), lds, (hipStream_t)stream, m)
+#define L64_FWDM_LAUNCH(F_, S_, D_) do { if (rows == 4) L64_FWDM_LAUNCH_R(F_, S_, D_, 4); else L64_FWDM_LAUNCH_R(F_, S_, D_, 16); } while (0)
   if (full) {
     if (st_ && dr) L64_FWDM_LAUNCH(true, true, true);
     else if (st_) L64_FWDM_LAUNCH(true, true, false);
@@ -453,6 +653,7 @@ extern "C" int mmego_lstm64_forward_multi(void* stream, int n, const MmegoLstm64
     else L64_FWDM_LAUNCH(false, false, false);
   }
 #undef L64_FWDM_LAUNCH
+#undef L64_FWDM_LAUNCH_R
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }
@@ -470,9 +671,9 @@ extern "C" int mmego_lstm64_backward_multi(void* stream, int n, const MmegoLstm6
     m.p[i] = l64_param<Lstm64BwdP>(p);
   }
   for (int i = n; i < L64_MAX_MULTI; ++i) m.p[i] = m.p[0];
-  const size_t lds = (size_t)(256 * 16) * sizeof(float);
-  if (B % 16 == 0) hipLaunchKernelGGL(lstm64_bwd_multi_kernel<true>, dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m);
-  else hipLaunchKernelGGL(lstm64_bwd_multi_kernel<false>, dim3(cdiv(B, 16), 2, n), dim3(256), lds, (hipStream_t)stream, m);
+  if (l64_rows(B) == 4) L64_BWD_LAUNCH(lstm64_bwd_multi_kernel, 4, n, m);
+  else L64_BWD_LAUNCH(lstm64_bwd_multi_kernel, 16, n, m);
+#undef L64_BWD_LAUNCH
   MMEGO_LAUNCH_CHECK();
   return MMEGO_OK;
 }

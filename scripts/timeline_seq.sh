@@ -7,6 +7,7 @@ rm -rf "$out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace -d "$out/trace" -o bench -- python3 "$root/bench.py" --steps 6 --warmup 2 --trace-only --sequential > "$out/trace.log" 2>&1
 db=$(find "$out/trace" -name "*.db" | head -1)
-python3 "$root/scripts/trace_timeline.py" "$db" > "$out/timeline.txt"
+# (a step ends with its second Adam launch: the default marker, the persistent projection GEMM, is no longer part of the step)
+python3 "$root/scripts/trace_timeline.py" "$db" --marker adam_step_kernel --per-step 2 > "$out/timeline.txt"
 rm -rf "$out/trace"
 tail -3 "$out/timeline.txt"
