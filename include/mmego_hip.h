@@ -67,6 +67,8 @@ int mmego_gemm_group(void* stream, int n, const MmegoGemmDesc* descs);
 /* ---- BatchNorm and row-wise helpers (bn.hip) ----------------------------------------------------
  * Train-mode statistics of X[rows, C] (+ running-stat update with torch semantics: momentum, unbiased
  * running var) -> mean, invstd, a = gamma*invstd, b = beta, so that y = (x-mean)*a + b.
+ * running_mean and running_var: both given, or both NULL (no update); every other pointer is required (here, in
+ * mmego_bn_finalize and in the pair form).  rows == 1: the running variance takes the biased value, 0.
  * partial_ws: 3*C*mmego_colstats_nblk(rows) floats.   Replaces native_batch_norm (train) of
  * Upper_Net.py:253-255,282-284, Lower_Net.py:51-53, GCN.py:106,117,136,310. */
 int mmego_colstats_nblk(long rows);

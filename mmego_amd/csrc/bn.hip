@@ -439,6 +439,7 @@ extern "C" int mmego_bn_train_stats(void* stream, const float* X, long ldx, long
                                     const float* beta, float* running_mean, float* running_var, float momentum,
                                     float eps, float* partial_ws, float* mean, float* invstd, float* a, float* b) {
   MMEGO_REQUIRE(X && rows > 0 && C > 0 && partial_ws && mean && invstd && a && b);
+  MMEGO_REQUIRE(gamma && beta && (running_mean == nullptr) == (running_var == nullptr));    // (bn_finalize_kernel reads all four)
   hipStream_t st = (hipStream_t)stream;
   const long RPB = rows_per_block(rows);
   int nblk = cdiv(rows, RPB);
@@ -494,7 +495,7 @@ extern "C" int mmego_bn_train_stats_pair(void* stream, long rows, int C, float* 
 extern "C" int mmego_bn_eval_affine(void* stream, int C, const float* gamma, const float* beta,
                                     const float* running_mean, const float* running_var, float eps, float* mean,
                                     float* invstd, float* a, float* b) {
-  MMEGO_REQUIRE(C > 0 && gamma && beta && running_mean && running_var);
+  MMEGO_REQUIRE(C > 0 && gamma && beta && running_mean && running_var && mean && invstd && a && b);
   hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, C, gamma, beta,
                      running_mean, running_var, eps, mean, invstd, a, b);
   MMEGO_LAUNCH_CHECK();
@@ -514,7 +515,8 @@ extern "C" int mmego_bn_fold_linear(void* stream, const float* W, const float* b
 extern "C" int mmego_affine_act(void* stream, const float* X1, long ld1, const float* m1, const float* a1,
                                 const float* b1, const float* X2, long ld2, const float* m2, const float* a2,
                                 const float* b2, float* Y, long ldy, long rows, int C, int relu) {
-  MMEGO_REQUIRE(X1 && Y && rows > 0 && C > 0);
+  MMEGO_REQUIRE(X1 && Y && rows > 0 && C > 0 && m1 && a1 && b1);
+  MMEGO_REQUIRE(!X2 || (m2 && a2 && b2));
   hipLaunchKernelGGL(affine_act_kernel, dim3(ew_blocks(rows * C)), dim3(256), 0, (hipStream_t)stream, X1, ld1, m1, a1,
                      b1, X2, ld2, m2, a2, b2, Y, ldy, rows, C, relu);
   MMEGO_LAUNCH_CHECK();

@@ -824,7 +824,8 @@ def test_input_gradient_product_in_k_slabs_on_320x256_tiles(dev, rows, In, K):
 def test_colsum_of_long_wide_tensors(dev, rows, C, ld, off):
     """ops.colsum on > 1024 rows: the 128 x 64 16-byte-load partial kernel (r06; aligned tensors of >= 4096 rows and >= 256 columns: the
     first two shapes -- the second with ragged last row block and column tile) and the 16-row-block kernel (unaligned row stride; narrow)
-    against float64, with the copy in out2 and accumulation."""
+    against float64, with the copy in out2 and accumulation.
+    (tests/test_bn_kernels_gpu.py holds every path of mmego_colsum, the short one too, to per-column bounds.)"""
     from mmego_amd import ops
     g = torch.Generator().manual_seed(rows + C)
     buf = torch.randn(rows, ld, generator=g).to(dev)
