@@ -330,6 +330,39 @@ int mmego_smooth_frames(void* stream, const float* src, long lds, long F, int C,
  * The caller answers for the bone list (ops.smooth_bones checks it on the host); a bone that names a joint outside [0, J) is left out. */
 int mmego_smooth_bones(void* stream, const float* src, long lds, long F, int J, const int* seg, const float* w, int H, int D,
                        const int* bones, const float* bone_len, int NB, float* dst, long ldd, float* moved, int* fallback);
+/* The same filter in ROTATION space (smooth.hip; dense.dense_infer under blend_space="rot" with rot_smooth=(H, order, taper)): every
+ * bone's world rotation filtered along the frames, the forward kinematics run once on the filtered rotations.  src [F][3 J] (row stride
+ * lds) holds the rigid frames mmego_blend_rot wrote, quat [F][NB][4] its unit quaternions (w, x, y, z), the world rotation of bone b of
+ * frame f, 16-byte aligned; seg, w, H, D as for mmego_smooth_frames; bones [NB][2] and body [NB][3] are mmego_blend_rot's walk table and
+ * rest bone vectors.  Per frame, with the valid taps, n, deg and c_k exactly as for mmego_smooth_frames (the same function, the same bits):
+ *   n <= 1: dst[f, :3 J] = src[f] bit for bit, quat_out[f] = quat[f] bit for bit, moved, rot_moved and fallback 0;   otherwise
+ *   a root r:            pos_r = sum_k c_k x_kr, mmego_smooth_frames' own arithmetic: those columns carry the same bits;
+ *   bone b = (c, p):     A_k = the rotation matrix of (double) quat[f + k][b] (even in the quaternion: its sign does not matter);
+ *                        S = sum_k c_k A_k over the valid taps, ascending k;  W = sum_k |c_k|, the same order;
+ *                        Qbar_b = the proper rotation that maximises tr(Q^T S), by mmego_blend_rot's 4 x 4 eigenproblem and Jacobi
+ *                        sweeps: for D = 0 the weighted chordal mean of the neighbouring frames' rotations, for D = 1, 2 the local
+ *                        polynomial of the matrix entries projected onto the rotations (c_k can be negative);  where the two largest
+ *                        eigenvalues lie no more than 1e-9 W apart -- the FALLBACK, counted in fallback[f] -- the quaternion, by the
+ *                        same route, of A_0, the frame's own rotation;  canonical sign: the first non-zero component is positive;
+ *                        an input that is unit only up to fp32 rounding is projected by the mean itself;
+ *                        pos_c = pos_p + Qbar_b body_b, the bones taken in their listed order;
+ *   dst[f, 3 j + i] = (float) pos_j[i] in one store; the columns of dst[f] (row stride ldd) beyond 3 J are not touched;
+ *   quat_out[f, b] = (float4) the quaternion of Qbar_b: one 16-byte store;
+ *   moved[f] (may be NULL) as mmego_smooth_frames', of pos before its rounding against src[f];
+ *   rot_moved[f] (may be NULL) = sqrt(sum_b theta_b^2 / NB) in radians, theta_b the angle of Qbar_b^T A_0 taken as mmego_blend_rot's
+ *                        rot_spread takes it: how far the filter turned the frame's bones;
+ *   fallback[f] (int32, may be NULL) = the number of bones of the frame that took the fallback.
+ * Every filtered bone has the length |body_b| up to the rounding of its two endpoints, and quat_out laid over body from dst's roots gives
+ * dst.  All arithmetic in double from the fp32 inputs, no atomics, no LDS, sums in a fixed order: two launches give the same bits.  One
+ * wave per frame; lane = tap for the coefficients, then lane = joint (the bone whose child it is): one 16-byte load per bone and tap,
+ * nine accumulators and one Jacobi solve per lane, the parent's position handed over by wave shuffles.  Refused: a null src, quat, seg,
+ * w, bones, body, dst or quat_out, F < 1 or >= 2^31, J outside [2, 21], NB outside [1, J - 1], lds or ldd < 3 J, H outside [1, 31], D
+ * outside [0, 2], a quat or quat_out that is not 16-byte aligned, dst rows that overlap the src rows, quat_out overlapping quat.  The
+ * caller answers for the bone list (ops.smooth_rot checks it on the host); a bone that names a joint outside [0, J) is left out: its
+ * child stays a root and its quaternion is not written. */
+int mmego_smooth_rot(void* stream, const float* src, long lds, long F, int J, const float* quat, int NB, const int* seg, const float* w,
+                     int H, int D, const int* bones, const float* body, float* dst, long ldd, float* quat_out, float* moved,
+                     float* rot_moved, int* fallback);
 /* Dense inference's floor (floor.hip; dense.dense_infer with floor=(mode, contact_cm, margin_cm)).  Both kernels read rows of the 8
  * lower joints, [rows][24]: local joints 0..3 are the global joints 12..15, local 4..7 the global 16..19, so the legs are (hip, knee,
  * ankle, foot) = (0, 1, 2, 3) and (4, 5, 6, 7) and the feet local 3 and 7.  ground [rows][4] is every row's plane (a, b, c, d) in the

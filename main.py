@@ -5,6 +5,7 @@
                  --log_dir IDX --load_IMU_path P --load_Upper_path P --load_Lower_path P]
   python main.py --infer [--vis | --dense [--stride S --blend {mean,triangle} --blend_space {joints,bones,rot} --save_pred PATH]]
   python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
+  python main.py --infer --dense --blend_space rot --rot_smooth H [--rot_smooth_order {0,1,2} --rot_smooth_taper {box,gauss}]
   python main.py --infer --dense --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
@@ -36,7 +37,11 @@ by position in the window and the windows' disagreement are printed, and PATH re
 blends bone directions and keeps the body's bone lengths, so that a blended frame is a rigid skeleton again; --blend_space rot averages
 the world rotations both nets predicted for every bone over the windows and runs the nets' forward kinematics once on the averages --
 rigid frames too, with the twist about every bone kept -- prints the windows' rotational disagreement in degrees and adds a unit
-quaternion per bone and frame (rot), rot_spread and the rest bones (bone_vectors) to PATH; it does not go with --smooth; --smooth H [--smooth_order D
+quaternion per bone and frame (rot), rot_spread and the rest bones (bone_vectors) to PATH; it does not go with --smooth but has a filter
+of its own, --rot_smooth H [--rot_smooth_order D --rot_smooth_taper {box,gauss}]: every bone's world rotation is filtered along time on the
+device -- the proper rotation nearest the local polynomial of degree D of the rotations over +-H frames, the chordal mean at D = 0 -- and the
+skeleton is laid along the filtered rotations, so the saved rot still produces pred; the blended frames' figures, the displacement, the
+mean turn and the rotational jitter before and after the filter are printed; --smooth H [--smooth_order D
 --smooth_taper {box,gauss}] then filters every recording's stitched frames along time on the device, a zero-phase local polynomial of
 degree D over +-H frames -- of bone directions under --blend_space bones -- and prints the blended frames' figures and the mean
 displacement beside the smoothed ones'; --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M] reads every frame's recorded
@@ -212,7 +217,8 @@ def build_parser():
                         "chordal mean -- and the nets' forward kinematics run once on the averages: rigid frames with the twist about every "
                         "bone kept; one more line gives the windows' rotational disagreement in degrees, and --save_pred's file gains rot "
                         "[F, 20, 4], a unit quaternion (w, x, y, z) per bone and frame in the world frame, rot_spread [F] and bone_vectors "
-                        "[20, 3], the rest bones: rot applied to bone_vectors from pred's roots gives pred.  Not with --smooth).  Given, any "
+                        "[20, 3], the rest bones: rot applied to bone_vectors from pred's roots gives pred.  Not with --smooth; --rot_smooth "
+                        "filters the rotations along time).  Given, any "
                         "value prints one more line, the blended and single-window deviation from the bone "
                         "lengths, and adds blend_space and degenerate_bones to --save_pred's file")
     p.add_argument("--save_pred", type=str,
@@ -229,6 +235,19 @@ def build_parser():
                    help="--smooth: degree of the local polynomial (default 2; 0 is a weighted moving average)")
     p.add_argument("--smooth_taper", type=str, choices=["box", "gauss"], default=None,
                    help="--smooth: weights of the frames of the window -- box (ones) or gauss (default: exp(-2 k^2 / H^2), sigma H / 2)")
+    p.add_argument("--rot_smooth", type=int, metavar="H",
+                   help="--dense --blend_space rot: filter every bone's blended world rotation along time on the device -- with --smooth's "
+                        "taps and weights over the frames f-H .. f+H of the same recording, H in [1, 31], the proper rotation nearest the "
+                        "local polynomial of the rotation matrices (order 0: the weighted chordal mean of the neighbouring frames) -- and "
+                        "lay the rest bones along the filtered rotations from the filtered roots: rigid frames whose saved rot still "
+                        "produces pred (off by default).  The figures above are then the filtered frames'; more lines give the blended "
+                        "frames' error, the displacement with the mean turn, the rotational jitter before and after the filter and "
+                        "(--metrics full) the unsmoothed acceleration error, and --save_pred's file gains pred_unsmoothed, rot_unsmoothed, "
+                        "moved, rot_moved, rot_smooth_window, rot_smooth_order, rot_smooth_taper")
+    p.add_argument("--rot_smooth_order", type=int, choices=[0, 1, 2], default=None,
+                   help="--rot_smooth: degree of the local polynomial (default 2; 0 is the weighted chordal mean)")
+    p.add_argument("--rot_smooth_taper", type=str, choices=["box", "gauss"], default=None,
+                   help="--rot_smooth: weights of the frames of the window -- box or gauss (default), as --smooth_taper")
     p.add_argument("--floor", type=str, choices=["measure", "clamp"], default=None,
                    help="--dense: hold the saved feet against every frame's recorded floor plane (given in the frame of the frame's own "
                         "joints; it comes from the recording, as the head pose does under --gt_head_pose) and the recorded foot-contact "
@@ -248,7 +267,16 @@ def build_parser():
 
 
 def check_dense(parser, args):
-    """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred, the --smooth and the --floor flags belong to it."""
+    """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred, the --smooth, --rot_smooth and --floor flags belong to it."""
+    for flag in ("rot_smooth_order", "rot_smooth_taper"):
+        if getattr(args, flag) is not None and args.rot_smooth is None and args.dense:
+            parser.error("--%s belongs to --rot_smooth H: without --rot_smooth no rotation is filtered" % flag)
+    if args.rot_smooth is not None and not 1 <= args.rot_smooth <= 31:
+        parser.error("--rot_smooth is the filter's half-width in frames: it has to lie in [1, 31] (2 H + 1 taps fit one wave), got %d"
+                     % args.rot_smooth)
+    if args.dense and args.rot_smooth is not None and args.blend_space != "rot":
+        parser.error("--rot_smooth belongs to --dense --blend_space rot: it filters the blended rotations, which only that space keeps "
+                     "(--smooth filters the positions of the other spaces)")
     for flag in ("smooth_order", "smooth_taper"):
         if getattr(args, flag) is not None and args.smooth is None and args.dense:
             parser.error("--%s belongs to --smooth H: without --smooth nothing is filtered" % flag)
@@ -267,10 +295,10 @@ def check_dense(parser, args):
                      % args.smooth)
     if args.dense and args.blend_space == "rot" and args.smooth is not None:
         parser.error("--smooth does not go with --blend_space rot: the filter runs on joint positions, so the saved rotations would not "
-                     "be filtered with the positions (filtering rotations along time is not provided)")
+                     "be filtered with the positions (--rot_smooth H filters the rotations and lays the positions along them)")
     if not args.dense:
-        for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper", "floor", "floor_contact_cm",
-                     "floor_margin_cm"):
+        for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper", "rot_smooth", "rot_smooth_order",
+                     "rot_smooth_taper", "floor", "floor_contact_cm", "floor_margin_cm"):
             if getattr(args, flag) is not None:
                 parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % flag)
         return
@@ -559,6 +587,8 @@ def apply_overrides(args):
     ConfigDemo.save_pred, ConfigDemo.dense_batch_size, ConfigDemo.blend_space = args.save_pred, args.batch_size, args.blend_space
     ConfigDemo.smooth = None if args.smooth is None else (args.smooth, 2 if args.smooth_order is None else args.smooth_order,
                                                           args.smooth_taper or "gauss")
+    ConfigDemo.rot_smooth = None if args.rot_smooth is None else (args.rot_smooth, 2 if args.rot_smooth_order is None else args.rot_smooth_order,
+                                                                  args.rot_smooth_taper or "gauss")
     ConfigDemo.floor = None if args.floor is None else (args.floor, 6.0 if args.floor_contact_cm is None else args.floor_contact_cm,
                                                         0.0 if args.floor_margin_cm is None else args.floor_margin_cm)
     if args.imu_precision is not None:

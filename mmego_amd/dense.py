@@ -27,27 +27,29 @@ def bone_lengths(bone_set):
     return L[list(skeleton.WALK_UPPER_ROWS)], L[list(skeleton.WALK_LOWER_ROWS)]
 
 
-def smooth_weights(H, taper):
+def smooth_weights(H, taper, who="smooth"):
     """The tap weights w[2 H + 1] (float32, k = -H .. H) of dense inference's temporal filter (ops.smooth_frames): "box" ones, "gauss"
-    exp(-2 k^2 / H^2) -- a Gaussian of sigma H / 2, 0.135 at the window's ends -- computed in float64 and rounded once."""
+    exp(-2 k^2 / H^2) -- a Gaussian of sigma H / 2, 0.135 at the window's ends -- computed in float64 and rounded once.  ``who``: the
+    argument a refusal names."""
     if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= ops.SMOOTH_MAX_H:
-        raise ValueError("smooth: the half-width is an integer number of frames in [1, %d], got %r" % (ops.SMOOTH_MAX_H, H))
+        raise ValueError("%s: the half-width is an integer number of frames in [1, %d], got %r" % (who, ops.SMOOTH_MAX_H, H))
     if taper not in SMOOTH_TAPERS:
-        raise ValueError("smooth: taper %r is not one of %s" % (taper, ", ".join(SMOOTH_TAPERS)))
+        raise ValueError("%s: taper %r is not one of %s" % (who, taper, ", ".join(SMOOTH_TAPERS)))
     k = np.arange(-int(H), int(H) + 1, dtype=np.float64)
     return (np.ones(len(k)) if taper == "box" else np.exp(-2.0 * k * k / float(H * H))).astype(np.float32)
 
 
-def _check_smooth(smooth):
-    """smooth = (H, order, taper) of dense_infer, or None.  -> the tuple with plain ints."""
+def _check_smooth(smooth, who="smooth"):
+    """smooth = (H, order, taper) of dense_infer (``who``: smooth or rot_smooth, the name a refusal carries), or None.  -> the tuple
+    with plain ints."""
     if smooth is None:
         return None
     if not (isinstance(smooth, (tuple, list)) and len(smooth) == 3):
-        raise ValueError("smooth: (H, order, taper), got %r" % (smooth,))
+        raise ValueError("%s: (H, order, taper), got %r" % (who, smooth))
     H, order, taper = smooth
-    smooth_weights(H, taper)
+    smooth_weights(H, taper, who)
     if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= order <= 2:
-        raise ValueError("smooth: order (the polynomial's degree) is 0, 1 or 2, got %r" % (order,))
+        raise ValueError("%s: order (the polynomial's degree) is 0, 1 or 2, got %r" % (who, order))
     return int(H), int(order), taper
 
 
@@ -90,7 +92,7 @@ def _floor_summary(sums, n, prefix="", target=False):
 
 
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None, floor=None):
+                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -118,7 +120,7 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     fallback; the arrays gain rot [F, 20, 4], the unit quaternions (w, x, y, z) of the blended WORLD rotations in BONES_ALL order (NaN
     where uncovered), rot_spread [F] in radians, bone_vectors [20, 3] -- pred's bones are rot applied to bone_vectors -- and, still on
     the device, win_q_up [W T, 14, 9], win_q_lo [W T, 6, 9] and win_R [W T, 9]; none of these is allocated in another space.  "rot"
-    with smooth is refused (ValueError): the rotations would not be filtered with the positions.
+    with smooth is refused (ValueError): the rotations would not be filtered with the positions; rot_smooth filters them.
     pose_noise=(deg, t, seed): every window row's head pose is perturbed before the nets see it (ops.pose_jitter), under ONE key for the
     whole pass (pose_noise_key(seed, 0, 0)) with the row's GLOBAL frame number (plan.row_frame) as its draw number: a frame carries one
     pose error in every window that serves it, as a per-frame estimator's error would, and the result does not depend on batch_size.
@@ -152,6 +154,22 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     lifted_frames and floor_fallback (the legs whose target was out of reach), the arrays pred_unclamped [F, 21, 3], lifted [F] and
     floor_fallback [F].  "clamp" under blend_space="rot" is refused (ValueError): the saved rotations would no longer produce pred.
     None (the default): no launch, no upload, no key, the bytes of the pass without the argument.
+    rot_smooth=(H, order, taper), under blend_space="rot" only (ValueError in any other space): the filter along time in ROTATION
+    space, behind the blend where smooth sits (ops.smooth_rot, once per net with the walk tables and rest bones of the blend).  With
+    smooth's taps, weights and coefficients c_k, every bone's world rotation of frame f becomes the proper rotation nearest
+    sum_k c_k A_k over the frames f - H .. f + H of its own recording -- at order 0 the weighted chordal mean of the neighbouring
+    frames, at order 1 and 2 the local polynomial of the matrix entries projected onto the rotations -- the roots are filtered as
+    smooth filters them, and the forward kinematics lays the rest bones along the filtered rotations: rigid frames, and rot applied to
+    bone_vectors from pred's roots still gives pred.  Everything above then runs on the filtered frames unchanged (floor "measure"
+    too; "clamp" and smooth stay refused under "rot").  The summary gains the unsmoothed_ figures and moved_cm as under smooth,
+    rot_moved_deg, the mean over the covered frames of the RMS angle over the 14 upper bones that the filter turned a frame,
+    rot_smooth itself, rot_smooth_fallback, the bones of both nets that kept their own frame's rotation, and rot_jitter_deg /
+    unsmoothed_rot_jitter_deg: over the frames f whose neighbours f - 1, f + 1 are covered frames of the same recording and over the
+    20 bones, the mean angle in degrees of D1^T D2 with D1 = Q_{f-1}^T Q_f and D2 = Q_f^T Q_{f+1} -- the rotational counterpart of
+    the acceleration error, which needs no ground truth; computed on the host in float64 from the arrays' quaternions, None without
+    such a frame.  The arrays gain pred_unsmoothed [F, 21, 3], rot_unsmoothed [F, 20, 4] (NaN where uncovered), moved [F] and rot_moved
+    [F] in radians; rot and pred are the filtered ones.  None (the default): no launch, no allocation, no key, the bytes of the pass
+    without the argument.
     The figures come down in one read; the per-frame arrays in one each."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
@@ -160,11 +178,15 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     smooth = _check_smooth(smooth)
     if blend_space == "rot" and smooth is not None:
         raise ValueError("smooth: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
-                         "filtered with them; filtering rotations along time is not done here")
+                         "filtered with them; rot_smooth filters the rotations along time and lays the positions along them")
+    rot_smooth = _check_smooth(rot_smooth, "rot_smooth")
+    if rot_smooth is not None and blend_space != "rot":
+        raise ValueError("rot_smooth: the filter runs on the blended rotations, which only blend_space=\"rot\" keeps, got blend_space=%r; "
+                         "smooth filters the positions of the other spaces" % (blend_space,))
     floor = _check_floor(floor)
     if blend_space == "rot" and floor is not None and floor[0] == "clamp":
         raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
-                         "produce pred; \"measure\" goes with every space")
+                         "produce pred (with or without rot_smooth); \"measure\" goes with every space")
     plan = DenseWindows(dataset, base.device, stride, blend)
     if plan.W == 0:
         raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, plan.T))
@@ -174,7 +196,8 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
         n.eval()
     try:
         return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size),
-                           dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise))
+                           dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise,
+                                rot_smooth=rot_smooth))
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
@@ -253,7 +276,7 @@ def _smooth(up, lo, seg, smooth, lengths):
     """The filter along time.  -> up, lo, moved [F], fell ([2, F] int32 in the bones form, ``lengths`` given; else None)."""
     (H, order, taper), dev, F = smooth, up.device, up.shape[0]
     wts = smooth_weights(H, taper)
-    s = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), moved=_f32(dev, F),
+    s = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), moved=_f32(dev, F), rot_moved=None,
                               fell=None if lengths is None else torch.zeros((2, F), dtype=torch.int32, device=dev))
     if lengths is not None:
         ops.smooth_bones(up, seg, wts, order, skeleton.WALK_UPPER, lengths[0], s.up, s.moved, s.fell[0])
@@ -262,6 +285,44 @@ def _smooth(up, lo, seg, smooth, lengths):
         ops.smooth_frames(up, seg, wts, order, s.up, s.moved)
         ops.smooth_frames(lo, seg, wts, order, s.lo)
     return s
+
+
+def _smooth_rot(b, seg, rot_smooth):
+    """The filter along time in rotation space, on what _blend returned under "rot".  -> up, lo, quat_up, quat_lo, moved [F],
+    rot_moved [F], fell [2, F] int32."""
+    (H, order, taper), dev, F, body = rot_smooth, b.up.device, b.up.shape[0], b.bone_vectors
+    wts = smooth_weights(H, taper, "rot_smooth")
+    s = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), quat_up=_f32(dev, F, 14, 4), quat_lo=_f32(dev, F, 6, 4),
+                              moved=_f32(dev, F), rot_moved=_f32(dev, F), fell=torch.zeros((2, F), dtype=torch.int32, device=dev))
+    ops.smooth_rot(b.up, b.quat_up, seg, wts, order, skeleton.WALK_UPPER, body[list(skeleton.WALK_UPPER_ROWS)], s.up, s.quat_up, s.moved,
+                   s.rot_moved, s.fell[0])
+    ops.smooth_rot(b.lo, b.quat_lo, seg, wts, order, skeleton.WALK_LOWER, body[list(skeleton.WALK_LOWER_ROWS)], s.lo, s.quat_lo, None, None,
+                   s.fell[1])
+    return s
+
+
+def rot_jitter_deg(quat, recording, covered):
+    """The rotational jitter of quaternions quat [F, NB, 4] (w, x, y, z) along time, in degrees and float64: over the frames f whose
+    neighbours f - 1 and f + 1 lie in the same recording, all three covered, and over the NB bones, the mean angle of D1^T D2 with
+    D1 = Q_{f-1}^T Q_f and D2 = Q_f^T Q_{f+1}, Q the rotation of the normalised quaternion -- how much the frame-to-frame turn changes
+    from one frame to the next.  None without such a frame.  Taken in quaternion algebra (a product of rotations is a product of unit
+    quaternions, and the angle of d = (w, v) is 2 atan2(|v|, |w|), in [0, pi] whatever the sign of any quaternion): three products per
+    frame and bone instead of three 3 x 3 matrix products."""
+    rec, cov = np.asarray(recording), np.asarray(covered) != 0
+    mid = np.flatnonzero(cov[1:-1] & cov[:-2] & cov[2:] & (rec[1:-1] == rec[:-2]) & (rec[1:-1] == rec[2:])) + 1
+    if len(mid) == 0:
+        return None
+    q = np.ascontiguousarray(np.moveaxis(np.asarray(quat, dtype=np.float64), -1, 0))        # [4, F, NB]: a component is contiguous
+
+    def conj_mul(a, b):                                            # conj(a) b: the quaternion of A^T B (up to the norms)
+        (aw, ax, ay, az), (bw, bx, by, bz) = a, b
+        return (aw * bw + ax * bx + ay * by + az * bz, aw * bx - ax * bw - ay * bz + az * by,
+                aw * by + ax * bz - ay * bw - az * bx, aw * bz - ax * by + ay * bx - az * bw)
+    step = conj_mul(q[:, :-1], q[:, 1:])                           # frame f to f + 1, once for every pair of neighbours
+    dw, dx, dy, dz = conj_mul([c[mid - 1] for c in step], [c[mid] for c in step])
+    # (the angle is homogeneous in d: the three quaternions' norms, 1 to float rounding, drop out of atan2's two arguments alike)
+    ang = 2.0 * np.arctan2(np.sqrt(dx * dx + dy * dy + dz * dz), np.abs(dw))
+    return float(np.degrees(ang).mean())
 
 
 def _clamp(lo, ground, seg, margin):
@@ -325,6 +386,8 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
     if sm is not None:                                             # the frames before the filter, and how far it moved a frame
         _error_figures(rows(sets["unsmoothed_"][0]), rows(sets["unsmoothed_"][1]), tgt_c, log[row["unsmoothed"]])
         ops.colsum(rows(sm.moved), log[row["moved"], :1])
+        if sm.rot_moved is not None:                               # (the rotation filter: the upper launch's mean turn beside it)
+            ops.colsum(rows(sm.rot_moved), log[row["moved"], 1:2])
     if floor is not None:
         # the final frames, the window rows with their frames' planes and flags, the frames before the clamp (their upper rows: the final)
         Hc, (ground, contact) = floor[1] / 100.0, plan.floor()
@@ -351,8 +414,14 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
     if space == "rot":
         s["rot_spread_deg"] = float(np.degrees(out[row["rot_spread"], 0] / Fc))
     if sm is not None:
-        s.update(_error_summary(out[row["unsmoothed"], :43], Fc, "unsmoothed_"), moved_cm=float(out[row["moved"], 0]) / Fc * 100,
-                 smooth=opt["smooth"], smooth_fallback=0 if sm.fell is None else int(sm.fell.cpu().numpy().sum()))
+        s.update(_error_summary(out[row["unsmoothed"], :43], Fc, "unsmoothed_"), moved_cm=float(out[row["moved"], 0]) / Fc * 100)
+        fell = 0 if sm.fell is None else int(sm.fell.cpu().numpy().sum())
+        if sm.rot_moved is None:
+            s.update(smooth=opt["smooth"], smooth_fallback=fell)
+        else:
+            s.update(rot_moved_deg=float(np.degrees(out[row["moved"], 1] / Fc)), rot_smooth=opt["rot_smooth"], rot_smooth_fallback=fell,
+                     rot_jitter_deg=rot_jitter_deg(arrays["rot"], arrays["recording"], arrays["covered"]),
+                     unsmoothed_rot_jitter_deg=rot_jitter_deg(arrays["rot_unsmoothed"], arrays["recording"], arrays["covered"]))
     if floor is not None:
         s.update(_floor_summary(out[row["floor"], :ops.FLOOR_W], Fc, target=True))
         s.update(_floor_summary(out[row["single_floor"], :ops.FLOOR_W], W * T, "single_"), floor=tuple(floor))
@@ -397,12 +466,16 @@ def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor):
     if b.lengths is not None:                                      # (an explicit space; "joints" has no fallback: zeros)
         arrays["fallback"] = np.zeros(F, dtype=np.int32) if b.fell is None else b.fell.cpu().numpy().sum(axis=0, dtype=np.int32)
     if "win_R" in win:                                             # ("rot")
-        quats = np.concatenate([b.quat_up.cpu().numpy(), b.quat_lo.cpu().numpy()], axis=1)      # [F, 20, 4] in BONES_ALL order
-        quats[covered == 0] = np.nan
-        arrays.update(rot=quats, rot_spread=b.rot_spread.cpu().numpy(), bone_vectors=b.bone_vectors)
+        def quats(q):                                              # [F, 20, 4] in BONES_ALL order
+            q = np.concatenate([q.quat_up.cpu().numpy(), q.quat_lo.cpu().numpy()], axis=1)
+            q[covered == 0] = np.nan
+            return q
+        arrays.update(rot=quats(b if sm is None else sm), rot_spread=b.rot_spread.cpu().numpy(), bone_vectors=b.bone_vectors)
     if sm is not None:
         arrays.update(pred_unsmoothed=_assemble(cfg, host(sets["unsmoothed_"][0], 15), host(sets["unsmoothed_"][1], 8), covered),
                       moved=sm.moved.cpu().numpy())
+        if sm.rot_moved is not None:
+            arrays.update(rot_unsmoothed=quats(b), rot_moved=sm.rot_moved.cpu().numpy())
     if floor is not None:
         ground, contact = (x.cpu().numpy() for x in plan.floor())
         arrays.update(foot_height=foot_heights(lo_h[:, [3, 7]], ground, covered != 0), ground=ground, foot_contact=contact)
@@ -414,15 +487,18 @@ def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor):
 
 def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
     """dense_infer behind its argument checks: the nets are in eval mode.  opt: dense_infer's keywords from ``metrics`` on, by name."""
-    space, smooth, floor = opt["blend_space"], opt["smooth"], opt["floor"]
+    space, smooth, floor, rot_smooth = opt["blend_space"], opt["smooth"], opt["floor"], opt["rot_smooth"]
     with torch.no_grad():
         win = _run_windows(base, plan, imu_net, upper_net, lower_net, batch_size, opt["pose_noise"], opt["imu_noise"], space == "rot")
         b = _blend(plan, win, space)
         sets, sm, cl, seg = {"": (b.up, b.lo)}, None, None, None   # the frame sets by the prefix of their figures: "" the final ones
-        if smooth is not None or floor is not None:                # a covered frame's segment is its recording, an uncovered one has none
+        if smooth is not None or floor is not None or rot_smooth is not None:      # a covered frame's segment is its recording, an uncovered one has none
             seg = torch.as_tensor(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)).to(base.device)
         if smooth is not None:
             sm = _smooth(b.up, b.lo, seg, smooth, b.lengths if space == "bones" else None)
+            sets = {"": (sm.up, sm.lo), "unsmoothed_": sets[""]}
+        if rot_smooth is not None:                                 # (never both: smooth is refused under "rot", rot_smooth elsewhere)
+            sm = _smooth_rot(b, seg, rot_smooth)
             sets = {"": (sm.up, sm.lo), "unsmoothed_": sets[""]}
         if floor is not None and floor[0] == "clamp":
             cl = _clamp(sets[""][1], plan.floor()[0], seg, floor[2] / 100.0)
@@ -448,6 +524,7 @@ def foot_heights(feet, ground, covered):
 def print_summary(s, opt, saved=None):
     """What `--infer --dense` prints: the reference's five lines first; ``saved``: where the per-frame skeletons were written."""
     space, smooth, floor, full = opt["blend_space"], opt["smooth"], opt["floor"], opt["metrics"] == "full"
+    rot_smooth = opt.get("rot_smooth")
     print_reference(s)
     print("Single-window (unblended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
         s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
@@ -476,6 +553,14 @@ def print_summary(s, opt, saved=None):
             s["moved_cm"], s["smooth"][0], s["smooth"][1], s["smooth"][2], s["smooth_fallback"]))
         if full:
             print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
+    if rot_smooth is not None:
+        print("Unsmoothed (blended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+            s["unsmoothed_all_cm"], s["unsmoothed_upper_cm"], s["unsmoothed_lower_cm"], s["unsmoothed_rot_deg"]))
+        print("Rotation Smoothing: displacement(cm) {} mean turn(°) {} (window +-{} frames, order {}, {}; degenerate bones {})".format(
+            s["moved_cm"], s["rot_moved_deg"], s["rot_smooth"][0], s["rot_smooth"][1], s["rot_smooth"][2], s["rot_smooth_fallback"]))
+        print("Rotational Jitter(°/frame^2): {} (blended {})".format(s["rot_jitter_deg"], s["unsmoothed_rot_jitter_deg"]))
+        if full:
+            print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
     if floor is not None:
         print("Foot Height Error(cm): {} (joint 15: {}, joint 19: {}; single-window {})".format(
             s["foot_height_err_cm"], *s["foot_height_err_cm_per_foot"], s["single_foot_height_err_cm"]))
@@ -494,7 +579,7 @@ def print_summary(s, opt, saved=None):
 
 def saved_arrays(s, arrays, opt):
     """The dictionary `--save_pred` writes (np.savez): DENSE_SAVED and the plan's three settings, then what every option adds."""
-    space, smooth, floor = opt["blend_space"], opt["smooth"], opt["floor"]
+    space, smooth, floor, rot_smooth = opt["blend_space"], opt["smooth"], opt["floor"], opt.get("rot_smooth")
     keep = lambda *names: {k: arrays[k] for k in names}
     d = dict(stride=np.int64(s["stride"]), blend=np.asarray(s["blend"]), frame_no=np.int64(s["frame_no"]), **keep(*DENSE_SAVED))
     if space is not None:
@@ -504,6 +589,9 @@ def saved_arrays(s, arrays, opt):
     if smooth is not None:
         d.update(keep("pred_unsmoothed", "moved"), smooth_window=np.int64(smooth[0]), smooth_order=np.int64(smooth[1]),
                  smooth_taper=np.asarray(smooth[2]))
+    if rot_smooth is not None:
+        d.update(keep("pred_unsmoothed", "rot_unsmoothed", "moved", "rot_moved"), rot_smooth_window=np.int64(rot_smooth[0]),
+                 rot_smooth_order=np.int64(rot_smooth[1]), rot_smooth_taper=np.asarray(rot_smooth[2]))
     if floor is not None:
         d.update(keep("foot_height", "ground", "foot_contact"), floor_mode=np.asarray(floor[0]), floor_contact_cm=np.float64(floor[1]),
                  floor_margin_cm=np.float64(floor[2]))

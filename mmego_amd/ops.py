@@ -701,6 +701,45 @@ def smooth_bones(src, seg, weights, order, walk, lengths, dst, moved=None, fallb
     return dst
 
 
+def smooth_rot(src, quat, seg, weights, order, walk, body, dst, quat_out, moved=None, rot_moved=None, fallback=None):
+    """The same filter in rotation space, for the rigid rows and quaternions blend_rot wrote (mmego_smooth_rot; the recipe is in the
+    header): src [F, 3 J] with J <= 21, quat [F, NB, 4] the unit quaternions (w, x, y, z) of every bone's world rotation.  The roots are
+    filtered as smooth_frames filters them; every bone's rotation becomes the proper rotation nearest sum_k c_k A_k over its valid taps
+    -- at order 0 the weighted chordal mean of the neighbouring frames -- and the rest bones ``body`` ([NB, 3] host floats) are laid
+    along ``walk`` ([NB, 2] host integers (child, parent), parents first; checked as blend_rot checks them).  dst [F, >= 3 J] receives
+    the rigid filtered rows, quat_out [F, NB, 4] their quaternions in canonical sign; moved [F] (optional) as smooth_frames';
+    rot_moved [F] (optional): the RMS angle over the bones, in radians, that the filter turned the frame; fallback [F] int32
+    (optional): the bones per frame whose filtered rotation had no direction and that kept the frame's own.  Everything is checked on
+    the host first; a refused call leaves every output untouched.  Neither output may overlap its input."""
+    if src.dim() == 2 and src.shape[1] % 3:
+        raise ValueError("smooth_rot needs rows of 3-vectors, got %s" % (tuple(src.shape),))
+    seg, w, H, order, F, C, lds, ldd = _smooth_on(src, seg, weights, order, dst, moved, 3 * BONES_MAX_J, "smooth_rot")
+    if C // 3 < 2:
+        raise ValueError("smooth_rot needs rows of 2 to %d 3-vectors, got %s" % (BONES_MAX_J, tuple(src.shape)))
+    for name, t in (("quat", quat), ("quat_out", quat_out)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == src.device and t.is_contiguous()):
+            raise ValueError("smooth_rot: %s is a contiguous float32 tensor on the source's device" % name)
+    bv = np.asarray(body.detach().cpu() if isinstance(body, torch.Tensor) else body)
+    if bv.ndim != 2 or bv.shape[1] != 3 or bv.dtype.kind != "f":
+        raise ValueError("smooth_rot: body is [NB, 3] floats, one rest vector per bone")
+    bv = np.ascontiguousarray(bv, dtype=np.float32)
+    if not np.isfinite(bv).all():
+        raise ValueError("smooth_rot: bone lengths have to be finite and positive")
+    bd, _, NB = _bones_on(walk, np.linalg.norm(bv.astype(np.float64), axis=1), C // 3, src.device, "smooth_rot")
+    if NB < 1:
+        raise ValueError("smooth_rot: at least one bone")
+    for name, t in (("quat", quat), ("quat_out", quat_out)):
+        if t.dim() != 3 or tuple(t.shape) != (F, NB, 4) or t.data_ptr() % 16:
+            raise ValueError("smooth_rot: %s is [%d, %d, 4], 16-byte aligned, got %s" % (name, F, NB, tuple(t.shape)))
+    if _rows_overlap(quat, 4 * NB, quat_out, 4 * NB, F, 4 * NB):
+        raise ValueError("smooth_rot: quat_out overlaps quat; the filter reads the frames around the one it writes")
+    _per_row(rot_moved, "rot_moved", F, torch.float32, src.device, "smooth_rot", kind=TypeError)
+    _per_row(fallback, "fallback", F, torch.int32, src.device, "smooth_rot")
+    hip.call("smooth_rot", src, lds, F, C // 3, quat, NB, seg, w, H, order, bd, _upload_once(src.device, bv)[0], dst, ldd, quat_out,
+             moved, rot_moved, fallback)
+    return dst
+
+
 def _floor_rows(t, name, rows, C, device, who, packed=False):
     """One row tensor of the floor launches, checked on the HOST: an fp32 device tensor [rows, >= C] on ``device`` with unit column
     stride and a row stride of at least its width (``packed``: exactly [rows, C], contiguous).  -> its row stride."""

@@ -755,14 +755,15 @@ class Evaluator(_Base):
         self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no, keep_frames=bool(getattr(cfg, "dense", False)))
 
     def eval_dense(self):
-        """`--infer --dense [--stride S --blend B --smooth H --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
+        """`--infer --dense [--stride S --blend B --smooth H --rot_smooth H --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
         (the reference's five lines for the blend first), the per-frame skeletons written when asked for.  -> the summary."""
         cfg = self.cfg
         self.model.load(cfg.model_lower_path)
         self.model.eval()
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
         opt = dict(metrics=self._metrics(), blend_space=getattr(cfg, "blend_space", None), smooth=getattr(cfg, "smooth", None),
-                   floor=getattr(cfg, "floor", None), pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg))
+                   floor=getattr(cfg, "floor", None), pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg),
+                   rot_smooth=getattr(cfg, "rot_smooth", None))
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, **opt)
         self.last_metrics = s
