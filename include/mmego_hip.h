@@ -228,6 +228,33 @@ int mmego_blend_windows(void* stream, const float* src, long nrows, int C, const
  * One workgroup per phase: its rows are dealt round-robin to 16 waves, each sums its share in ascending order in double, the 16
  * partial sums are added in wave order, one float store (two launches give the same bits; no workspace, no atomics). */
 int mmego_colsum_phase(void* stream, const float* X, long ldx, long rows, int C, int period, float* out, long ldo);
+/* The error breakdown of the evaluation passes (breakdown.hip; evaluation.breakdown_launches): a per-row table reduced by a group id
+ * per row.  X [rows][C] (row stride ldx >= C), 1 <= C <= 64, 1 <= rows < 2^24; group [rows] int32; 1 <= G <= 65535:
+ *   out[g, c] = the sum of X[r, c] over the rows r with group[r] == g, g < G, c < C; the columns of out[g] (row stride ldo >= C) beyond
+ *               C are not touched;   count[g] (count may be NULL) = the number of those rows, as a float (exact: rows < 2^24).
+ * A row whose id lies outside [0, G) belongs to no group: its values are never read into a sum (selected out, not multiplied by zero),
+ * so a NaN or an Inf there reaches no output.  A group without rows gets zeros and count 0.  The rows need not be sorted by group.
+ * One workgroup per group; the table is cut into blocks of 64 rows, dealt round-robin to the 16 waves of the workgroup; a wave adds the
+ * group's rows of its blocks in ascending row order in double, one lane per column; the 16 partial sums are added in wave order, one
+ * float store.  The order depends on (rows, G) and on which rows the group owns, on nothing else: two launches give the same bits.  No
+ * workspace, no atomics, out needs no zeroing.  Refused (non-zero, nothing launched): a null X, group or out; rows < 1 or >= 2^24; C
+ * outside [1, 64]; G outside [1, 65535]; ldx < C; ldo < C. */
+int mmego_colsum_groups(void* stream, const float* X, long ldx, long rows, int C, const int* group, int G, float* out, long ldo,
+                        float* count);
+/* Integer histograms of the non-negative values of the same kind of table, by the same kind of group id (group NULL: one group of all
+ * rows, G = 1).  The bin of a value x, with the product in fp32 and the comparisons in this order:
+ *   x is NaN or x < 0:                      not binned; counted in dropped
+ *   x * inv_width >= nbins - 1 (+Inf too):  the last bin, nbins - 1, the overflow bin (decided before any float-to-int conversion)
+ *   otherwise:                              bin (int)(x * inv_width)
+ * pool = 1: the C columns of a group's rows go into one histogram, hist [G][nbins] and dropped [G] (both int32);
+ * pool = 0: one histogram per group and column, hist [G][C][nbins] and dropped [G][C].
+ * Rows whose id lies outside [0, G) are ignored.  Counts are exact.  One workgroup per histogram: LDS integer counters (integer adds
+ * commute, so the LDS atomics keep two launches bit-equal), then plain stores of the finished histogram -- every word of hist and
+ * dropped is written, neither needs zeroing; no global atomics, no workspace.  Refused: a null X, hist or dropped; a null group with
+ * G != 1; rows < 1 or >= 2^24; C outside [1, 64]; G outside [1, 65535]; ldx < C; nbins outside [1, 4096]; pool other than 0 or 1;
+ * inv_width that is not finite and > 0. */
+int mmego_hist_groups(void* stream, const float* X, long ldx, long rows, int C, const int* group, int G, float inv_width, int nbins,
+                      int pool, int* hist, int* dropped);
 /* The same blend with every bone's length kept (blend_bones.hip; dense.dense_infer under blend_space="bones").  src [nrows][3 J]
  * holds rigid skeletons of J joints (3-vectors x_j) and the cover is mmego_blend_windows'; bones [NB][2] (int32, on the device) lists
  * (child, parent) joint numbers in walk order -- every joint a child at most once, every parent a root (a joint that is no bone's child)

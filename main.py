@@ -7,6 +7,7 @@
   python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
   python main.py --infer --dense --blend_space rot --rot_smooth H [--rot_smooth_order {0,1,2} --rot_smooth_taper {box,gauss}]
   python main.py --infer --dense --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M]
+  python main.py --infer [--dense ...] --breakdown
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -58,7 +59,12 @@ head-pose error costs -- and one "Head Pose Noise" line follows the figures), --
 and --imu_bias_rot_deg D / --imu_bias_acc S / --imu_bias_gyro S (the 20 x 15 IMU samples per frame that IMU_Net reads are perturbed on the
 device: white noise drawn per sample, and a bias that stays constant over a window, each on the orientation -- a rotation, degrees per axis
 -- the accelerometer and the gyroscope; with --train, for every --network and with --finetune_imu / --finetune_all, re-drawn every
-minibatch inside the captured step; with --infer [--dense] a sensitivity instrument, one "IMU Noise" line following the figures).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+minibatch inside the captured step; with --infer [--dense] a sensitivity instrument, one "IMU Noise" line following the figures),
+--breakdown (with --infer, with or without --dense and with every dense option: the joint error by action -- the number an action's
+directory is named by -- and by recording as plain means over each group's frames, reduced on the device by a group id per frame, and
+the distribution of the 21 joint errors from a device histogram of 0.05 cm bins: p50 / p90 / p95 / p99, the PCK area under 15 cm, every
+joint's median, the five worst recordings; printed behind every other line, and --save_pred's file gains action, by_action_*,
+by_recording_all_cm, error_hist and error_hist_bin_cm).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -263,7 +269,28 @@ def build_parser():
                         "unflagged feet of the 21 frames the test fixture stores; no claim for the full data)")
     p.add_argument("--floor_margin_cm", type=float, default=None, metavar="M",
                    help="--floor clamp: feet and ankles are raised to M cm above the floor (default 0)")
+    p.add_argument("--breakdown", action="store_true",
+                   help="--infer [--dense]: break the error down on the device -- one line per action (the number its directory is named "
+                        "by) with the mean joint, upper, lower and rotation error over the action's frames, its p50 and p90 (--metrics "
+                        "full: PA-MPJPE and root-relative error too), the five worst recordings, and the distribution of all joint errors "
+                        "from a histogram of 0.05 cm bins up to 204.75 cm: p50, p90, p95, p99, the PCK area under 15 cm and every joint's "
+                        "median.  Group figures are plain means over frames.  Printed behind every other line; --dense takes them on the "
+                        "final frames and --save_pred's file gains action, by_action_*, by_recording_all_cm, error_hist, error_hist_bin_cm")
     return p
+
+
+def check_breakdown(parser, args):
+    """--breakdown adds figures to an inference pass that compares skeletons: --infer, with or without --dense."""
+    if not args.breakdown:
+        return
+    if args.train:
+        parser.error("--breakdown does not go with --train: it breaks down an inference pass (the epochs' evaluation prints no breakdown)")
+    if not args.infer:
+        parser.error("--breakdown goes with --infer only (with or without --dense): it adds figures to that pass")
+    if args.vis:
+        parser.error("--breakdown does not go with --vis")
+    if args.network == "IMU_Net":
+        parser.error("--breakdown does not go with --network IMU_Net: stage 1 evaluates a head pose, there is no joint error to break down")
 
 
 def check_dense(parser, args):
@@ -520,6 +547,7 @@ def check_finetune(parser, args, world):
     check_dense(parser, args)
     check_pose_noise(parser, args)
     check_imu_noise(parser, args)
+    check_breakdown(parser, args)
     if not args.finetune_imu:
         if args.imu_lr is not None and not args.finetune_all:
             parser.error("--imu_lr is the IMU_Net's learning rate under --finetune_imu; without that flag the IMU_Net is frozen")
@@ -591,6 +619,7 @@ def apply_overrides(args):
                                                                   args.rot_smooth_taper or "gauss")
     ConfigDemo.floor = None if args.floor is None else (args.floor, 6.0 if args.floor_contact_cm is None else args.floor_contact_cm,
                                                         0.0 if args.floor_margin_cm is None else args.floor_margin_cm)
+    ConfigDemo.breakdown = bool(args.breakdown)
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

@@ -93,7 +93,7 @@ class PosePC:
         if not vis:
             order = np.arange(n)
             np.random.RandomState(Config.dataset_random_seed).shuffle(order)    # same permutation as shuffling each array
-            for name in ("data_ti_", "data_key_", "skl_", "ground_", "foot_contact_", "imu_", "R_R0R_", "t_R0R_", "win_start_"):
+            for name in ("data_ti_", "data_key_", "skl_", "ground_", "foot_contact_", "imu_", "R_R0R_", "t_R0R_", "win_start_", "win_rec_"):
                 setattr(self, name, getattr(self, name)[order])
         cut = int(n * 0.8)
         self.split_cut = n if vis else cut              # windows [0, split_cut) of the arrays train, the rest test
@@ -173,10 +173,10 @@ class PosePC:
         dec = self._decode()
         win = {k: [] for k in ("ti", "key", "imu", "skl", "ground", "foot", "R", "t", "RtW")}
         bones = [b for b in dec["bones"]]
-        packed, starts = [], []                          # every frame's packed cloud; every window's first frame (global number)
+        packed, starts, win_rec = [], [], []             # every frame's packed cloud; every window's first frame (global number) and recording
         f0 = 0                                           # first frame of the snippet in the packed arrays
         p0 = 0                                           # first point of that frame in dec["pts"]
-        for count in dec["snip_len"]:
+        for rec_no, count in enumerate(dec["snip_len"]):
             rec = {k: [] for k in ("ti", "key", "imu", "ground", "foot", "R", "t", "RtW")}
             for f in range(f0, f0 + int(count)):
                 n = int(dec["npts"][f])
@@ -190,6 +190,7 @@ class PosePC:
             L = self.frame_no
             while len(rec["ti"]) >= L:
                 starts.append(f0 - int(count) + len(rec["ti"]) - L)
+                win_rec.append(rec_no)
                 for k in rec:
                     win[k].append(rec[k][-L:])
                     rec[k] = rec[k][:-L]
@@ -207,6 +208,18 @@ class PosePC:
         self.frame_bones_ = np.asarray(dec["bones"])
         self.frame_packed_ = (np.asarray(packed, dtype=np.float32).reshape(nf, self.pc_no, 6) if self._keep_frames else None)
         self.win_start_ = np.asarray(starts, dtype=np.int64)
+        # where every recording comes from (recording r is list_snippets(root)[r], as in frame_rec_): the integer its action directory is
+        # named by and the snippet's position among that directory's entries (None where the decoded frames are not this tree's); and
+        # every window's recording, in data_ti_'s order
+        try:
+            snippets = list_snippets(self.root)
+            names = sorted(os.listdir(self.root), key=lambda name: int(name))
+        except (OSError, ValueError):                    # (frames decoded elsewhere, served under a root that is no Sample_data tree)
+            snippets, names = [], []
+        known = len(snippets) == len(dec["snip_len"]) > 0
+        self.rec_action_ = np.asarray([int(names[a]) for a, _, _ in snippets], dtype=np.int64) if known else None
+        self.rec_snippet_ = np.asarray([j for _, j, _ in snippets], dtype=np.int64) if known else None
+        self.win_rec_ = np.asarray(win_rec, dtype=np.int64)
         print("data load end")
         return tuple(np.asarray(win[k]) for k in ("ti", "key", "imu", "skl", "ground", "foot", "R", "t", "RtW"))
 
@@ -537,6 +550,10 @@ class DenseWindows(DensePlan):
         self.bone_set = np.asarray(dataset.frame_bones_, dtype=np.float32).reshape(-1, 3).copy()     # host: src["skl"] row 0 as [20, 3]
         self._out, self._zero_idx = {}, {}
         self._dataset, self._floor = dataset, None
+        # every recording's action (the integer its directory is named by), for the error breakdown; None from a loader without it
+        act = getattr(dataset, "rec_action_", None)
+        self.rec_action = None if act is None else np.asarray(act, dtype=np.int64)
+        self.rec_snippet = None if act is None else np.asarray(dataset.rec_snippet_, dtype=np.int64)
 
     def floor(self):
         """-> (ground [F, 4], contact [F, 2]): every frame's floor plane and contact flags as fp32 device tensors, uploaded on the first

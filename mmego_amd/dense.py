@@ -8,8 +8,9 @@ import torch
 from . import blocks, hip, ops, skeleton
 from .config import IMU_NOISE_FLAGS
 from .data import DenseWindows
-from .evaluation import (METRICS, PCK_THRESHOLDS_CM, _accel_over_sequences, _error_summary, _jitter_imu, _jitter_pose, aligned_summary,
-                         imu_noise_key, imu_noise_line, pose_noise_key, pose_noise_line, print_aligned, print_reference)
+from .evaluation import (METRICS, PCK_THRESHOLDS_CM, Breakdown, _accel_over_sequences, _error_summary, _jitter_imu, _jitter_pose,
+                         aligned_summary, check_breakdown, imu_noise_key, imu_noise_line, pose_noise_key, pose_noise_line, print_aligned,
+                         print_breakdown, print_reference)
 from .train_step import call_upper
 
 BLEND_SPACES, SMOOTH_TAPERS, FLOOR_MODES = ("joints", "bones", "rot"), ("box", "gauss"), ("measure", "clamp")
@@ -92,7 +93,7 @@ def _floor_summary(sums, n, prefix="", target=False):
 
 
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None):
+                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None, breakdown=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -170,7 +171,15 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     such a frame.  The arrays gain pred_unsmoothed [F, 21, 3], rot_unsmoothed [F, 20, 4] (NaN where uncovered), moved [F] and rot_moved
     [F] in radians; rot and pred are the filtered ones.  None (the default): no launch, no allocation, no key, the bytes of the pass
     without the argument.
-    The figures come down in one read; the per-frame arrays in one each."""
+    breakdown=(bin_cm, nbins) (evaluation.BREAKDOWN_BINS is --breakdown's): the error of the FINAL frames -- behind blend, filter and
+    clamp -- by action, by recording and as a distribution (evaluation.Breakdown's launches: mmego_colsum_groups over the per-frame
+    error table, the group of a frame its action or its recording where covered != 0 and -1 elsewhere; mmego_hist_groups over the 21
+    joint errors).  The summary gains evaluation.breakdown_summary's keys -- by_action, by_recording, percentiles_cm,
+    percentile_clipped, beyond, per_joint_median_cm, pck_auc, breakdown; all group figures plain means over the group's covered frames,
+    as this pass's own figures are; an action or a recording without a covered frame carries None -- and the arrays action [F] (int64,
+    the number the frame's action directory is named by).  None (the default): no launch, no allocation, the bytes of the pass without
+    the argument.
+    The figures come down in one read (the histograms of breakdown in one more); the per-frame arrays in one each."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
     if blend_space is not None and blend_space not in BLEND_SPACES:
@@ -184,10 +193,13 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
         raise ValueError("rot_smooth: the filter runs on the blended rotations, which only blend_space=\"rot\" keeps, got blend_space=%r; "
                          "smooth filters the positions of the other spaces" % (blend_space,))
     floor = _check_floor(floor)
+    breakdown = check_breakdown(breakdown)
     if blend_space == "rot" and floor is not None and floor[0] == "clamp":
         raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
                          "produce pred (with or without rot_smooth); \"measure\" goes with every space")
     plan = DenseWindows(dataset, base.device, stride, blend)
+    if breakdown is not None and plan.rec_action is None:
+        raise ValueError("breakdown: the loader has no rec_action_ / rec_snippet_ (a data.PosePC has); there is nothing to group by")
     if plan.W == 0:
         raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, plan.T))
     nets = [n for n in (imu_net, upper_net, lower_net) if n is not None]
@@ -197,7 +209,7 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     try:
         return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size),
                            dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise,
-                                rot_smooth=rot_smooth))
+                                rot_smooth=rot_smooth, breakdown=breakdown))
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
@@ -366,9 +378,15 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
     full = opt["metrics"] == "full"
     WA = ops.pose_errors_aligned_width(21, len(PCK_THRESHOLDS_CM)) if full else 0
     row = figure_rows(T)
-    log = torch.zeros((T + len(FIGURE_ROWS) - 1, max(43, WA)), dtype=torch.float32, device=dev)
+    bd, log_shape = None, (T + len(FIGURE_ROWS) - 1, max(43, WA))
+    if opt.get("breakdown") is not None:                           # the grouped sums live behind the log, in the same buffer and read
+        bd = Breakdown(opt["breakdown"], np.where(plan.covered != 0, plan.frame_rec, -1), plan.rec_action, plan.rec_snippet, full, dev)
+        buf = torch.zeros(log_shape[0] * log_shape[1] + bd.floats(), dtype=torch.float32, device=dev)
+        log = buf[:log_shape[0] * log_shape[1]].view(log_shape)
+    else:
+        log = torch.zeros(log_shape, dtype=torch.float32, device=dev)
     up_c, lo_c, tgt_c = rows(up_f), rows(lo_f), rows(tgt_f)
-    _error_figures(up_c, lo_c, tgt_c, log[row["blend"]])
+    E = _error_figures(up_c, lo_c, tgt_c, log[row["blend"]])
     ops.colsum(rows(b.spread), log[row["spread"], :1])
     row_idx = torch.as_tensor(plan.row_frame).to(dev)
     tgt_w = ops.gather_rows(tgt_f, row_idx, _f32(dev, W * T, 63))
@@ -402,7 +420,18 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
         A, alog = _f32(dev, Fc, WA), torch.zeros(WA, dtype=torch.float32, device=dev)
         ops.pose_errors_aligned(up_c.view(Fc, 15, 3), lo_c.view(Fc, 8, 3), tgt_c.view(Fc, 21, 3), thr, A)
         ops.colsum(A, alog)
-    out = log.cpu().numpy().astype(np.float64)                     # the figures' one device -> host read
+    if bd is not None:
+        # the tables over ALL frames (an uncovered frame's row is in no group, whatever it holds): the ones above where every frame is covered
+        if cidx is not None:
+            E = _f32(dev, F, 43)
+            hip.call("pose_errors", up_f, lo_f, tgt_f, F, E)
+            if full:
+                A = ops.pose_errors_aligned(up_f.view(F, 15, 3), lo_f.view(F, 8, 3), tgt_f.view(F, 21, 3), thr, _f32(dev, F, WA))
+        hists = bd.launch(E, A if full else None, buf[log.numel():])
+        host = buf.cpu().numpy().astype(np.float64)                # the figures' one device -> host read
+        out, groups = host[:log.numel()].reshape(log_shape), bd.summary(host[log.numel():], hists.cpu().numpy())
+    else:
+        out = log.cpu().numpy().astype(np.float64)                 # the figures' one device -> host read
     s = _error_summary(out[row["blend"], :43], Fc)
     s.update(_error_summary(out[row["single"], :43], W * T, "single_"))
     s.update(position_cm=out[row["position"], :21].mean(axis=1) / W * 100, spread_cm=float(out[row["spread"], 0]) / Fc * 100, windows=W,
@@ -443,6 +472,8 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
             n_ref = (plan.rec_off[1:] - plan.rec_off[:-1]) // T
             acc = _accel_over_sequences(dev, win_up, win_lo, tgt_w, [((l - n) * T, l * T) for f, l, n in zip(first, last, n_ref) if l > f])
             s["single_accel_cm"] = None if acc is None else float(acc.mean()) * 100
+    if bd is not None:
+        s.update(groups)
     return s
 
 
@@ -455,7 +486,7 @@ def _assemble(cfg, upper, lower, covered):
     return pred
 
 
-def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor):
+def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor, breakdown=None):
     """dense_infer's arrays: every per-frame array down in one read, the window rows and the plan still on the device."""
     F, covered = plan.F, plan.covered
     host = lambda x, J: x.cpu().numpy().reshape(F, J, 3)
@@ -482,6 +513,8 @@ def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor):
     if cl is not None:
         arrays.update(pred_unclamped=_assemble(cfg, up_h, host(sets["unclamped_"][1], 8), covered), lifted=cl.lifted.cpu().numpy(),
                       floor_fallback=cl.fell.cpu().numpy())
+    if breakdown is not None:
+        arrays["action"] = plan.rec_action[plan.frame_rec]
     return arrays
 
 
@@ -503,7 +536,7 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
         if floor is not None and floor[0] == "clamp":
             cl = _clamp(sets[""][1], plan.floor()[0], seg, floor[2] / 100.0)
             sets.update({"": (sets[""][0], cl.lo), "unclamped_": sets[""]})
-        arrays = _host_arrays(base.cfg, plan, win, b, sm, cl, sets, floor)
+        arrays = _host_arrays(base.cfg, plan, win, b, sm, cl, sets, floor, opt.get("breakdown"))
         summary = _figures(plan, win, b, sm, cl, sets, seg, arrays, opt)
     blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
     return summary, arrays
@@ -575,6 +608,8 @@ def print_summary(s, opt, saved=None):
                 s["unclamped_all_cm"], s["unclamped_lower_cm"], s["unclamped_penetration_rate"], s["unclamped_penetration_cm"]))
             print("Floor Clamp: {} of {} frames lifted, mean lift(cm) {}, unreachable legs {} (margin {:g} cm)".format(
                 s["lifted_frames"], s["covered_frames"], s["lift_cm"], s["floor_fallback"], floor[2]))
+    if opt.get("breakdown") is not None:
+        print_breakdown(s)
 
 
 def saved_arrays(s, arrays, opt):
@@ -602,4 +637,12 @@ def saved_arrays(s, arrays, opt):
         d.update(pose_noise_deg=np.float64(deg), pose_noise_t=np.float64(t), pose_noise_seed=np.int64(seed))
     if opt["imu_noise"] is not None:
         d.update({flag: np.float64(v) for flag, v in zip(IMU_NOISE_FLAGS, opt["imu_noise"][0])}, imu_noise_seed=np.int64(opt["imu_noise"][1]))
+    if opt.get("breakdown") is not None:
+        a, r = s["by_action"], s["by_recording"]
+        nan = lambda x: np.asarray([np.nan if v is None else v for v in x], dtype=np.float64)
+        d.update(keep("action"), by_action_action=np.asarray(a["action"], dtype=np.int64), by_action_frames=np.asarray(a["frames"], dtype=np.int64),
+                 by_action_recordings=np.asarray(a["recordings"], dtype=np.int64),
+                 **{"by_action_" + k: nan(a[k]) for k in a if k not in ("action", "frames", "recordings")},
+                 by_recording_all_cm=nan(r["all_cm"]), by_recording_frames=np.asarray(r["frames"], dtype=np.int64),
+                 error_hist=np.asarray(s["error_hist"], dtype=np.int64), error_hist_bin_cm=np.float64(s["breakdown"][0]))
     return d

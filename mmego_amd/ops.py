@@ -530,6 +530,75 @@ def colsum_phase(X, period, out):
     return out
 
 
+GROUPS_MAX_G = 65535        # breakdown.hip BD_MAX_G: one workgroup per group
+GROUPS_MAX_ROWS = 1 << 24   # breakdown.hip: a group's row count travels as a float
+HIST_MAX_BINS = 4096        # breakdown.hip BD_MAX_BINS: one LDS counter per bin
+
+
+def is_float32(v):
+    """True where the finite float64 ``v`` is a float32 exactly."""
+    with np.errstate(over="ignore"):
+        return bool(np.isfinite(np.float32(v)) and float(np.float32(v)) == float(v))
+
+
+def _group_table(X, group, G, who):
+    """The table and the group ids of colsum_groups / hist_groups checked on the host: X [rows, C] fp32 with unit column stride, group one
+    contiguous int32 per row on X's device (or None where ``who`` allows it).  -> (X, rows, C, G)."""
+    X = _rows(X)
+    rows, C = X.shape
+    if isinstance(G, bool) or not isinstance(G, (int, np.integer)):
+        raise TypeError("%s: G is an integer number of groups, got %r" % (who, G))
+    if not 1 <= rows < GROUPS_MAX_ROWS or not 1 <= C <= BLEND_MAX_C or (rows > 1 and X.stride(0) < C):
+        raise ValueError("%s: a table of 1 to %d rows of 1 to %d columns, got %s" % (who, GROUPS_MAX_ROWS - 1, BLEND_MAX_C, tuple(X.shape)))
+    if not 1 <= G <= GROUPS_MAX_G:
+        raise ValueError("%s: G lies in [1, %d], got %d" % (who, GROUPS_MAX_G, G))
+    _per_row(group, "group", rows, torch.int32, X.device, who, kind=TypeError)
+    return X, rows, C, int(G)
+
+
+def colsum_groups(X, group, G, out, count=None):
+    """out[g, c] = the sum of X[r, c] over the rows with group[r] == g (mmego_colsum_groups: double inside, a fixed order; a row whose id
+    lies outside [0, G) is in no sum): X [rows, C <= 64], group [rows] int32 on the device, out [G, >= C] (its other columns stay), count
+    [G] fp32 (optional) the groups' row counts."""
+    if group is None:
+        raise TypeError("colsum_groups: group is an int32 device tensor")
+    X, rows, C, G = _group_table(X, group, G, "colsum_groups")
+    out = _rows(out)
+    if out.device != X.device or out.shape[0] != G or out.shape[1] < C or (G > 1 and out.stride(0) < C):
+        raise ValueError("colsum_groups: out is %s for %d groups of %d columns" % (tuple(out.shape), G, C))
+    _per_row(count, "count", G, torch.float32, X.device, "colsum_groups", kind=TypeError)
+    hip.call("colsum_groups", X, max(X.stride(0), C), rows, C, group, G, out, max(out.stride(0), C), count)
+    return out
+
+
+def hist_groups(X, group, G, inv_width, nbins, hist, dropped, pool=True):
+    """Integer histograms of the values of X [rows, C <= 64] by group (mmego_hist_groups; its comment is the binning recipe): a value x
+    lands in bin (int)(x * inv_width) -- inv_width, the bins per unit of X, has to be a float32 exactly, it is what the kernel multiplies
+    by -- the last of the ``nbins`` bins taking everything beyond, NaN and negative values counted in ``dropped``.  group None: all rows,
+    G = 1.  pool: one histogram per group, hist [G, nbins] and dropped [G]; else one per group and column, hist [G, C, nbins] and
+    dropped [G, C]; both contiguous int32 device tensors, every word of which is written."""
+    X, rows, C, G = _group_table(X, group, G, "hist_groups")
+    if group is None and G != 1:
+        raise ValueError("hist_groups: without group ids there is one group, got G = %d" % G)
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)):
+        raise TypeError("hist_groups: nbins is an integer, got %r" % (nbins,))
+    if not 1 <= nbins <= HIST_MAX_BINS:
+        raise ValueError("hist_groups: nbins lies in [1, %d], got %d" % (HIST_MAX_BINS, nbins))
+    if isinstance(inv_width, bool) or not isinstance(inv_width, (int, float, np.integer, np.floating)):
+        raise TypeError("hist_groups: inv_width is a number, got %r" % (inv_width,))
+    inv = float(inv_width)
+    if not 0.0 < inv < float("inf") or not is_float32(inv):                   # (false for NaN as well)
+        raise ValueError("hist_groups: inv_width is finite, > 0 and a float32 exactly, got %r" % (inv_width,))
+    shape = (G, int(nbins)) if pool else (G, C, int(nbins))
+    for t, name, want in ((hist, "hist", shape), (dropped, "dropped", shape[:-1])):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32):
+            raise TypeError("hist_groups: %s is an int32 device tensor" % name)
+        if tuple(t.shape) != want or not t.is_contiguous() or t.device != X.device:
+            raise ValueError("hist_groups: %s is a contiguous %s on the table's device, got %s" % (name, want, tuple(t.shape)))
+    hip.call("hist_groups", X, max(X.stride(0), C), rows, C, group, G, inv, int(nbins), int(bool(pool)), hist, dropped)
+    return hist
+
+
 def _bones_on(bones, bone_len, J, device, who):
     """The walk table ((child, parent) per bone, host integers) and the bone lengths checked on the HOST for rows of J joints -- every
     joint a child at most once, every parent a root or an earlier bone's child (so there is no cycle), the lengths finite and positive

@@ -20,8 +20,9 @@ from . import blocks, dense, hip, ops
 from .config import Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, batch_indices
 from .dense import dense_infer
-from .evaluation import (METRICS, PCK_THRESHOLDS_CM, _jitter_imu, _jitter_pose, aligned_summary, imu_noise_key, imu_noise_line, imu_noise_of,
-                         pose_noise_key, pose_noise_line, pose_noise_of, print_aligned, print_reference)
+from .evaluation import (BREAKDOWN_BINS, METRICS, PCK_THRESHOLDS_CM, Breakdown, _jitter_imu, _jitter_pose, aligned_summary, check_breakdown,
+                         dataset_groups, imu_noise_key, imu_noise_line, imu_noise_of, pose_noise_key, pose_noise_line, pose_noise_of,
+                         print_aligned, print_breakdown, print_reference)
 from .nets import IMUNet, LowerNet, UpperNet
 from .params import FusedAdam, LrSchedule, describe_decay, lr_schedule_of, resolve_no_decay
 from .nets_local import UpperNetwlocal
@@ -636,7 +637,7 @@ class LowerTrainer(_StageTrainer):
 
 
 def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics="reference", pose_noise=None,
-                imu_noise=None):
+                imu_noise=None, breakdown=None):
     """One evaluation pass with ONE host synchronisation: -> float64 array [n_minibatches, W] of per-frame MEANS per minibatch.
     lower_net None: W = 30, the columns of mmego_pose_errors_upper; else W = 45: the 43 columns of mmego_pose_errors, then the
     Lower stage's L1(sum) loss per frame and its mean joint distance.  The split is uploaded once per dataset object
@@ -648,7 +649,11 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
     pose_noise=(deg, t, seed): every minibatch's head pose is perturbed before the nets see it (ops.pose_jitter under
     pose_noise_key(seed, 0, minibatch number), rows numbered within the minibatch): what head-pose error costs in joint error.
     imu_noise=(six sigmas, seed): every minibatch's IMU samples are perturbed before IMU_Net reads them (ops.imu_jitter under
-    imu_noise_key(seed, 0, minibatch number), frames and windows numbered within the minibatch): what sensor error costs."""
+    imu_noise_key(seed, 0, minibatch number), frames and windows numbered within the minibatch): what sensor error costs.
+    breakdown=(bin_cm, nbins), with a Lower_Net only: the per-minibatch tables are slices of ONE table over all rows of the pass -- the
+    launches above write and read their slices, so every column keeps its bits -- and after the last minibatch evaluation.Breakdown's
+    launches run over it (the grouped sums behind the log, in the same read; the histograms in one further read).  -> (the array above,
+    breakdown_summary's keys).  None (the default): no launch, no allocation, the bytes of the pass without the argument."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
     if imu_noise is not None and imu_net is None:
@@ -660,7 +665,22 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
     full = metrics == "full"
     J = 15 if lower_net is None else 21
     WA = ops.pose_errors_aligned_width(J, len(PCK_THRESHOLDS_CM)) if full else 0
-    log = torch.zeros((len(todo), W + WA + (J if full else 0)), dtype=torch.float32, device=dev)
+    width = W + WA + (J if full else 0)
+    bd = E_all = A_all = None
+    if breakdown is not None:
+        if lower_net is None:
+            raise ValueError("breakdown: the figures are those of the 21 joints, so the pass needs a Lower_Net")
+        win_rec, rec_action, rec_snippet = dataset_groups(dataset)
+        T_all = int(np.shape(dataset._items[0])[1])
+        row_rec = np.repeat(win_rec[np.concatenate(todo)] if len(todo) else win_rec[:0], T_all)          # rows in the order the pass writes them
+        bd = Breakdown(breakdown, row_rec, rec_action, rec_snippet, full, dev)
+        buf = torch.zeros(len(todo) * width + bd.floats(), dtype=torch.float32, device=dev)
+        log = buf[:len(todo) * width].view(len(todo), width)
+        E_all = torch.empty((bd.rows, 43), dtype=torch.float32, device=dev)
+        A_all = torch.empty((bd.rows, WA), dtype=torch.float32, device=dev) if full else None
+    else:
+        log = torch.zeros((len(todo), width), dtype=torch.float32, device=dev)
+    row0 = 0
     frames = np.empty(len(todo), dtype=np.float64)
     seqs = np.full(len(todo), np.nan)                       # (sequences per minibatch whose acceleration error was taken)
     scratch = base.__dict__.setdefault("_eval_scratch", {})
@@ -680,6 +700,8 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
                 scratch[key] = (torch.zeros((6, B, 64), device=dev), torch.zeros((6, B, 64), device=dev),
                                 torch.empty((F, 43 if lower_net is not None else 30), dtype=torch.float32, device=dev))
             h0, c0, E = scratch[key]
+            if bd is not None:
+                E = E_all[row0:row0 + F]
             tgt, body = b["target"], b["skl"]
             imu = b["imu"] if imu_noise is None else _jitter_imu(scratch, b["imu"], imu_noise, imu_noise_key(imu_noise[1], 0, i))
             R, t = base.head_pose(imu_net, imu, b["R_R0R"], tgt)
@@ -701,17 +723,26 @@ def _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, low
                 if akey not in scratch:
                     scratch[akey] = (torch.empty((F, WA), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.float32, device=dev))
                 A, Acc = scratch[akey]
+                if bd is not None:
+                    A = A_all[row0:row0 + F]
                 ops.pose_errors_aligned(up, lo, tgt, scratch["pck_thr"], A)
                 ops.colsum(A, log[i, W:W + WA])
                 if T >= 3:
                     ops.pose_accel_errors(up, lo, tgt, Acc)
                     ops.colsum(Acc, log[i, W + WA:])
                     seqs[i] = B
-    out = log.cpu().numpy().astype(np.float64)                               # the epoch's one device -> host read
+            row0 += F
+        if bd is not None:
+            hists = bd.launch(E_all, A_all, buf[len(todo) * width:])
+    if bd is not None:
+        host = buf.cpu().numpy().astype(np.float64)                          # the epoch's one device -> host read, the grouped sums behind the log
+        out, groups = host[:len(todo) * width].reshape(len(todo), width), bd.summary(host[len(todo) * width:], hists.cpu().numpy())
+    else:
+        out = log.cpu().numpy().astype(np.float64)                           # the epoch's one device -> host read
     out[:, :W + WA] /= frames[:, None]
     out[:, W + WA:] /= seqs[:, None]
     blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
-    return out
+    return out if bd is None else (out, groups)
 
 
 def metrics_line(s):
@@ -724,14 +755,23 @@ def metrics_line(s):
 
 
 def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuffle, rng=None, metrics="reference", pose_noise=None,
-                  imu_noise=None):
+                  imu_noise=None, breakdown=None):
     """IMU -> Upper -> Lower over a data split (reference Processor/Test/Demo_test.py:71-184, Train_Lower.py:232-332); returns
     (reference-style tuple, summary dict).  Device-resident split, one host read per pass (_epoch_eval).  metrics="full": the same
     tuple and summary keys from the same launches, and the summary also holds aligned_summary's keys for the 21 joints.
-    pose_noise=(deg, t, seed), imu_noise=(six sigmas, seed): _epoch_eval's keywords."""
+    pose_noise=(deg, t, seed), imu_noise=(six sigmas, seed): _epoch_eval's keywords.
+    breakdown=(bin_cm, nbins) (evaluation.BREAKDOWN_BINS is --breakdown's), on a split that knows its recordings (a data.PosePC): the
+    summary also holds evaluation.breakdown_summary's keys -- by_action and by_recording, PLAIN means over each group's frames (the
+    figures above are means over minibatches of per-minibatch means; the two coincide where all minibatches have one size),
+    percentiles_cm, percentile_clipped, beyond, per_joint_median_cm, pck_auc of the 21 joint errors' histogram, and breakdown itself.
+    None (the default): none of these keys, the launches and bytes of the pass without the argument."""
     cfg = base.cfg
+    breakdown = check_breakdown(breakdown)
     m = _epoch_eval(base, dataset, batch_size, shuffle, rng, imu_net, upper_net, lower_net, metrics, pose_noise=pose_noise,
-                    imu_noise=imu_noise)
+                    imu_noise=imu_noise, breakdown=breakdown)
+    groups = None
+    if breakdown is not None:
+        m, groups = m
     eval_loss = float(np.mean(m[:, 43]))
     accu_l, accu_up, accu_lo = m[:, :21].mean(axis=1), m[:, 41], m[:, 42]
     accu_ll, angle_ll = m[:, :21].mean(axis=0), m[:, 21:41].mean(axis=0)
@@ -739,6 +779,8 @@ def evaluate_full(base, imu_net, upper_net, lower_net, dataset, batch_size, shuf
                    rot_deg=float(sum(angle_ll) / len(angle_ll)), per_joint_cm=accu_ll * 100)
     if metrics == "full":
         summary.update(aligned_summary(m[:, 45:], 21))
+    if groups is not None:
+        summary.update(groups)
     return (eval_loss, np.asarray([eval_loss / cfg.joint_num_lower]), float(np.mean(accu_l)), float(np.mean(accu_lo)), accu_ll, angle_ll), summary
 
 
@@ -763,7 +805,7 @@ class Evaluator(_Base):
         stride = cfg.stride if getattr(cfg, "stride", None) is not None else max(1, self.frame_no // 2)
         opt = dict(metrics=self._metrics(), blend_space=getattr(cfg, "blend_space", None), smooth=getattr(cfg, "smooth", None),
                    floor=getattr(cfg, "floor", None), pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg),
-                   rot_smooth=getattr(cfg, "rot_smooth", None))
+                   rot_smooth=getattr(cfg, "rot_smooth", None), breakdown=BREAKDOWN_BINS if getattr(cfg, "breakdown", False) else None)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, **opt)
         self.last_metrics = s
@@ -777,8 +819,9 @@ class Evaluator(_Base):
         self.model.load(self.cfg.model_lower_path)
         self.model.eval()
         noise, imu_noise = pose_noise_of(self.cfg), imu_noise_of(self.cfg)
+        breakdown = BREAKDOWN_BINS if getattr(self.cfg, "breakdown", False) else None
         out, s = evaluate_full(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, 1, False, metrics=self._metrics(),
-                               pose_noise=noise, imu_noise=imu_noise)
+                               pose_noise=noise, imu_noise=imu_noise, breakdown=breakdown)
         print_reference(s)
         if self._metrics() == "full":
             self.last_metrics = s
@@ -787,6 +830,9 @@ class Evaluator(_Base):
             print(pose_noise_line(noise))
         if imu_noise is not None:
             print(imu_noise_line(imu_noise))
+        if breakdown is not None:
+            self.last_metrics = s
+            print_breakdown(s)
         return out
 
     def eval_all_skeleton(self):
