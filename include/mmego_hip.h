@@ -429,6 +429,55 @@ int mmego_floor_stats(void* stream, const float* lo, long ldl, const float* tgt,
                       const int* seg, long rows, double H, float* out);
 int mmego_floor_clamp(void* stream, const float* src, long lds, const float* ground, const int* seg, long rows, double margin, float* dst,
                       long ldd, float* lifted, int* fallback);
+/* Dense inference's pictures (render.hip, render_math.h; mmego_amd/render.py, dense.dense_infer with render=...): a scene builder that
+ * turns every frame into a table of 2-D primitives, and a tiled rasteriser that composites such tables into 8-bit RGB images.
+ * A primitive is 12 floats: ax, ay, bx, by, r, alpha, cr, cg, cb, 0, 0, 0 -- a capsule from a to b in pixel coordinates (a disc where
+ * a == b) of radius r pixels, opacity alpha and colour (cr, cg, cb) in levels 0..255.
+ * mmego_render_raster: prims [I][P][12] (16-byte aligned) -> out (uint8), image i a W x H viewport of 3-byte pixels at
+ * out + i img_stride + y row_pitch + 3 x (bytes; whatever lies between the viewport's rows stays as it is, so two views can share one
+ * frame through the pitch).  The centre of pixel (x, y) is (x + 0.5, y + 0.5).  Per pixel, all in fp32: the colour starts at the
+ * background (bg_r, bg_g, bg_b); the image's primitives are composited in INDEX order,
+ *   d = the distance from the pixel centre to the segment ab:  t = clamp(((p - a) . (b - a)) / |b - a|^2, 0, 1), 0 where a == b,
+ *       d = |p - (a + t (b - a))|;
+ *   c = clamp(r + 0.5 - d, 0, 1) alpha;   colour += c (prim_colour - colour) per channel;
+ * the byte stored is (int)(min(max(colour, 0), 255) + 0.5f).  A primitive contributes nothing where any of its first nine floats is
+ * not finite, where alpha <= 0 or r < 0, or where |b - a|^2 overflows fp32.  The composite is continuous in every input: the order is
+ * fixed, nothing is decided by "nearest wins", there is no depth test.  One workgroup of 256 threads per (image, 32 x 32 tile): 256
+ * primitives at a time are culled against the tile's pixel centres grown by r + 0.5 and, on top, by 2^-21 of the coordinates'
+ * magnitudes -- conservative beyond the fp32 roundings of the distance, so a culled primitive's c is 0 on the tile and culling
+ * changes no byte, the survivors are compacted in index order into an LDS list (64-bit ballot, popcount prefix per wave,
+ * wave offsets through LDS), and every thread composites the list into its four horizontally adjacent pixels in registers and stores
+ * 12 bytes as three dwords; edge tiles mask their pixels.  No atomics, every byte has one owner: two launches give the same bytes.
+ * Refused: a null pointer, I < 1, I x tiles >= 2^31, P outside [0, 1024] (0 paints the background), W or H outside [16, 2048],
+ * W % 4 != 0, row_pitch < 3 W or % 4 != 0, img_stride < H row_pitch or % 4 != 0, an out that is not 4-byte aligned, prims that are
+ * not 16-byte aligned, a bg level outside [0, 255].  The caller answers for out's extent (ops.render_raster checks it on the host).
+ * mmego_render_prims: the scene of F frames, everything in the frame of the frame's own joints: pred [F][63] (row stride ldp) and tgt
+ * [F][63] (row stride ldt) the predicted and the recorded 21 joints, ground [F][4] the floor planes (height h(x), unit normal u and
+ * the rule |n| > 1e-6 as for mmego_floor_stats above), cloud [F][N][6] the radar returns (x, y, z, r, v, intensity), seg [F] int32
+ * (< 0: the frame has no prediction), cam [F][8] a 2 x 4 affine per frame, x_px = m0 p_x + m1 p_y + m2 p_z + m3 and y_px the same with
+ * m4..m7, ring [32][2] the pairs (cos, sin)(2 pi k / 32) as the host rounded them.  -> prims [F][P][12] with P = 134 + N, in this
+ * order (the layer order; bones are skeleton.BONES_ALL's 20 (parent, child) pairs):
+ *   first  count  what                                                                radius  colour        alpha
+ *   0      32     floor ring: segment k joins vertex k to vertex (k + 1) % 32 of      0.5     170,170,170   1
+ *                 foot + cos_k e1 + sin_k e2, foot = t0 - h(t0) u (t0 = target joint 0), e1 = the coordinate axis with the smallest
+ *                 |u_i| (the first on ties) minus its component along u, normalised, e2 = u x e1: a circle of 1 m in the plane
+ *   32     20     shadow: every predicted bone, both ends dropped x - h(x) u          2       60,60,60      0.35
+ *   52     20     target bones                                                        1.5     120,120,120   1
+ *   72     21     target joints (discs)                                               2.5     90,90,90      1
+ *   93     N      cloud returns (discs), (40,90,220) + s ((230,60,40) - (40,90,220)),  1.5     by Doppler    0.8
+ *                 s = clamp(0.5 + v / (2 vmax), 0, 1)
+ *   93+N   20     predicted bones, (0,170,0) + s ((230,0,0) - (0,170,0)),              2       by error      1
+ *                 s = min(e / 0.15, 1), e = |child - its target| in metres
+ *   113+N  21     predicted joints (discs), coloured the same way by their own error  3       by error      1
+ * An ABSENT primitive is twelve zeros (alpha 0: the rasteriser skips it): the ring and the shadow where the plane has no normal; the
+ * shadow, the predicted bones and joints where seg < 0 (such a frame shows the target alone); a cloud row whose x, y and z are all
+ * exactly 0 (padding).  Double inside, one float store per value; one thread per (frame, primitive), no LDS, no atomics.  Refused: a
+ * null pointer (cloud may be NULL where N == 0), F < 1 or >= 2^31, N outside [0, 890] (so P <= 1024), ldp or ldt < 63, a vmax that is
+ * not finite or not > 0, prims that are not 16-byte aligned. */
+int mmego_render_raster(void* stream, const float* prims, int I, int P, unsigned char* out, int W, int H, long row_pitch, long img_stride,
+                        int bg_r, int bg_g, int bg_b);
+int mmego_render_prims(void* stream, const float* pred, long ldp, const float* tgt, long ldt, const float* ground, const float* cloud,
+                       int N, const int* seg, const float* cam, const float* ring, long F, double vmax, float* prims);
 /* BatchNorm (train) backward through an optional ReLU mask (Ymask > 0): dgamma, dbeta, dX.
  * partial_ws: 2*C*nblk floats, c12_ws: 2*C floats. */
 int mmego_bn_backward(void* stream, const float* dY, long lddy, const float* Ymask, long ldm, const float* X, long ldx,

@@ -8,6 +8,7 @@
   python main.py --infer --dense --blend_space rot --rot_smooth H [--rot_smooth_order {0,1,2} --rot_smooth_taper {box,gauss}]
   python main.py --infer --dense --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M]
   python main.py --infer [--dense ...] --breakdown
+  python main.py --infer --dense --render DIR [--render_size PX --render_recordings 0,3,7 --render_fps N]
 
 Added flags (not in the reference): --gt_head_pose (use the recorded head pose when no IMU_Net checkpoint is
 available), --data_root, --seed, --resume (bit-exact continuation: weights, Adam moments/step, epoch, RNG states),
@@ -64,15 +65,20 @@ minibatch inside the captured step; with --infer [--dense] a sensitivity instrum
 directory is named by -- and by recording as plain means over each group's frames, reduced on the device by a group id per frame, and
 the distribution of the 21 joint errors from a device histogram of 0.05 cm bins: p50 / p90 / p95 / p99, the PCK area under 15 cm, every
 joint's median, the five worst recordings; printed behind every other line, and --save_pred's file gains action, by_action_*,
-by_recording_all_cm, error_hist and error_hist_bin_cm).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+by_recording_all_cm, error_hist and error_hist_bin_cm), --infer --dense --render DIR [--render_size PX --render_recordings LIST
+--render_fps N] (the dense pass's FINAL frames -- behind blend, filter and clamp -- drawn on the device, one animated PNG per recording in
+DIR: predicted skeleton coloured by error over the recorded one, the radar returns coloured by Doppler, the floor ring and the skeleton's
+shadow on the recorded plane, front view left and side view right in a body-fixed camera; --infer --vis is that pass at the reference's
+windows, drawn into ./vis/<Idx>/).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
 import os
+import re
 
 import torch
 
-from mmego_amd.config import IMU_NOISE_FLAGS, Config, ConfigDemo
+from mmego_amd.config import IMU_NOISE_FLAGS, RENDER_FPS, RENDER_SIZE, Config, ConfigDemo
 
 
 def build_parser():
@@ -276,7 +282,44 @@ def build_parser():
                         "from a histogram of 0.05 cm bins up to 204.75 cm: p50, p90, p95, p99, the PCK area under 15 cm and every joint's "
                         "median.  Group figures are plain means over frames.  Printed behind every other line; --dense takes them on the "
                         "final frames and --save_pred's file gains action, by_action_*, by_recording_all_cm, error_hist, error_hist_bin_cm")
+    p.add_argument("--render", type=str, metavar="DIR",
+                   help="--dense: draw the final frames of every recording that has a covered frame on the device and write one "
+                        "animated PNG per recording into DIR, rec{recording:04d}_action{A}.png: the prediction coloured by its error "
+                        "over the recorded skeleton, the radar returns coloured by Doppler velocity, a 1 m ring and the prediction's "
+                        "shadow on the recorded floor plane; front view left, side view right, in a camera fixed to the recorded body "
+                        "(off by default; not with --vis, which draws into ./vis/<Idx>/ on its own)")
+    p.add_argument("--render_size", type=int, default=None, metavar="PX",
+                   help="--render: a view is PX x PX pixels and a frame PX x 2 PX; a multiple of 4 in [64, 1024] (default 256)")
+    p.add_argument("--render_recordings", type=str, default=None, metavar="LIST",
+                   help="--render: comma-separated loader recording numbers, as --save_pred's `recording` counts them (default: all)")
+    p.add_argument("--render_fps", type=int, default=None, metavar="N", help="--render: frames per second of the animation, in [1, 100] (default 10)")
     return p
+
+
+def parse_recordings(text):
+    """--render_recordings' value "0,3,7" -> [0, 3, 7]; None where it is no comma-separated list of integers >= 0."""
+    if not re.fullmatch(r"[0-9]+(,[0-9]+)*", text):
+        return None
+    return [int(p) for p in text.split(",")]
+
+
+def check_render(parser, args):
+    """--render is a stage of --infer --dense; --render_size, --render_recordings and --render_fps belong to it."""
+    given = [flag for flag in ("render", "render_size", "render_recordings", "render_fps") if getattr(args, flag) is not None]
+    if not given:
+        return
+    if args.render is not None and args.vis:
+        parser.error("--render does not go with --vis: --vis draws every recording into ./vis/<Idx>/ on its own")
+    if not args.dense:
+        parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % given[0])
+    if args.render is None:
+        parser.error("--%s belongs to --render DIR: without --render nothing is drawn" % given[0])
+    if args.render_size is not None and not (64 <= args.render_size <= 1024 and args.render_size % 4 == 0):
+        parser.error("--render_size is a view's edge in pixels: a multiple of 4 in [64, 1024], got %d" % args.render_size)
+    if args.render_recordings is not None and parse_recordings(args.render_recordings) is None:
+        parser.error("--render_recordings is a comma-separated list of loader recording numbers >= 0 (0,3,7), got %r" % args.render_recordings)
+    if args.render_fps is not None and not 1 <= args.render_fps <= 100:
+        parser.error("--render_fps is the animation's frames per second: it has to lie in [1, 100], got %d" % args.render_fps)
 
 
 def check_breakdown(parser, args):
@@ -544,6 +587,7 @@ def check_finetune(parser, args, world):
     check_lr_schedule(parser, args)
     check_weight_decay(parser, args)
     check_frame_store(parser, args)
+    check_render(parser, args)
     check_dense(parser, args)
     check_pose_noise(parser, args)
     check_imu_noise(parser, args)
@@ -620,6 +664,11 @@ def apply_overrides(args):
     ConfigDemo.floor = None if args.floor is None else (args.floor, 6.0 if args.floor_contact_cm is None else args.floor_contact_cm,
                                                         0.0 if args.floor_margin_cm is None else args.floor_margin_cm)
     ConfigDemo.breakdown = bool(args.breakdown)
+    ConfigDemo.vis = bool(args.vis)
+    ConfigDemo.render = None if args.render is None else (
+        args.render, RENDER_SIZE if args.render_size is None else args.render_size,
+        None if args.render_recordings is None else parse_recordings(args.render_recordings),
+        RENDER_FPS if args.render_fps is None else args.render_fps)
     if args.imu_precision is not None:
         os.environ["MMEGO_IMU_PRECISION"] = args.imu_precision      # read by IMUNet.__init__
     if args.imu_train_precision is not None:

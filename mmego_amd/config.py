@@ -9,6 +9,7 @@ import torch
 from . import skeleton as sk
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RENDER_SIZE, RENDER_FPS = 256, 10      # --render_size's and --render_fps's defaults, and what --vis draws at
 # --imu_noise_* / --imu_bias_*: the six flags and configuration attributes, in the order of mmego_imu_jitter's sigmas
 IMU_NOISE_FLAGS = ("imu_noise_rot_deg", "imu_noise_acc", "imu_noise_gyro", "imu_bias_rot_deg", "imu_bias_acc", "imu_bias_gyro")
 
@@ -98,3 +99,5 @@ class ConfigDemo(_Common):
     floor = None                # --floor M [--floor_contact_cm H --floor_margin_cm C]: (M, H, C), the dense pass's floor figures / clamp (None: off)
     save_pred = None            # --save_pred: .npz of the per-frame skeletons
     dense_batch_size = None     # --batch_size under --dense: windows per minibatch (None: 64)
+    render = None               # --render DIR [--render_size PX --render_recordings LIST --render_fps N]: (DIR, PX, recordings or None, N) (None: off)
+    vis = False                 # --vis: the loader keeps the per-frame clouds, as under --dense (Evaluator.eval_all_skeleton draws them)

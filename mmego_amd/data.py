@@ -549,7 +549,7 @@ class DenseWindows(DensePlan):
         self.width = {name: self.src[name].shape[1] for name in self.src}
         self.bone_set = np.asarray(dataset.frame_bones_, dtype=np.float32).reshape(-1, 3).copy()     # host: src["skl"] row 0 as [20, 3]
         self._out, self._zero_idx = {}, {}
-        self._dataset, self._floor = dataset, None
+        self._dataset, self._floor, self._ground = dataset, None, None
         # every recording's action (the integer its directory is named by), for the error breakdown; None from a loader without it
         act = getattr(dataset, "rec_action_", None)
         self.rec_action = None if act is None else np.asarray(act, dtype=np.int64)
@@ -570,6 +570,20 @@ class DenseWindows(DensePlan):
             up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
             self._floor = (up(ground), up(contact))
         return self._floor
+
+    def ground(self):
+        """-> ground [F, 4]: every frame's floor plane alone, an fp32 device tensor (floor()'s where that was uploaded): dense inference's
+        pictures need the plane and no contact flags.  ValueError where the loader has no frame_ground_ of F rows."""
+        import torch
+        if self._floor is not None:
+            return self._floor[0]
+        if self._ground is None:
+            ground = getattr(self._dataset, "frame_ground_", None)
+            if ground is None or np.asarray(ground).shape != (self.F, 4):
+                raise ValueError("DenseWindows.ground needs the loader's frame_ground_ [%d, 4], got %s"
+                                 % (self.F, None if ground is None else np.asarray(ground).shape))
+            self._ground = torch.as_tensor(np.ascontiguousarray(ground, dtype=np.float32)).to(self.device)
+        return self._ground
 
     def frame_index(self, index):
         """Host: the frame numbers [len(index) * T] of the windows ``index``."""

@@ -1,11 +1,13 @@
 """Dense inference (`main.py --infer --dense`, not in the reference): dense_infer, whose docstring is the contract, the stages of its pass
 (_dense_pass drives them; their figures land in ONE device log with named rows), and what Evaluator.eval_dense prints and writes."""
+import os
 import types
 
 import numpy as np
 import torch
 
 from . import blocks, hip, ops, skeleton
+from . import render as render_mod
 from .config import IMU_NOISE_FLAGS
 from .data import DenseWindows
 from .evaluation import (METRICS, PCK_THRESHOLDS_CM, Breakdown, _accel_over_sequences, _error_summary, _jitter_imu, _jitter_pose,
@@ -69,6 +71,28 @@ def _check_floor(floor):
     return mode, float(contact_cm), float(margin_cm)
 
 
+def _check_render(render):
+    """render = (directory, size, recordings_or_None, fps) of dense_infer, or None.  -> the tuple with plain values, the recordings a
+    sorted tuple of distinct loader recording numbers."""
+    if render is None:
+        return None
+    if not (isinstance(render, (tuple, list)) and len(render) == 4):
+        raise ValueError("render: (directory, size, recordings or None, fps), got %r" % (render,))
+    directory, size, recs, fps = render
+    if not isinstance(directory, (str, os.PathLike)) or not str(directory):
+        raise ValueError("render: the directory is a path, got %r" % (directory,))
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 64 <= size <= 1024 or size % 4:
+        raise ValueError("render: size is a multiple of 4 in [64, 1024] pixels, got %r" % (size,))
+    if isinstance(fps, bool) or not isinstance(fps, (int, np.integer)) or not 1 <= fps <= 100:
+        raise ValueError("render: fps is an integer in [1, 100], got %r" % (fps,))
+    if recs is not None:
+        recs = list(recs)
+        if not recs or any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0 for r in recs):
+            raise ValueError("render: recordings is None (all) or a non-empty list of loader recording numbers >= 0, got %r" % (render[2],))
+        recs = tuple(sorted(set(int(r) for r in recs)))
+    return os.fspath(directory), int(size), recs, int(fps)
+
+
 def _floor_summary(sums, n, prefix="", target=False):
     """The floor figures from the column sums [22] of ops.floor_stats over ``n`` rows that count: every key of FLOOR_KEYS pooled over
     both feet under ``prefix`` + key, and per foot as a pair (joint 15, joint 19) under ``prefix`` + key + "_per_foot"; None where a
@@ -93,7 +117,7 @@ def _floor_summary(sums, n, prefix="", target=False):
 
 
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None, breakdown=None):
+                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None, breakdown=None, render=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -179,6 +203,15 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     as this pass's own figures are; an action or a recording without a covered frame carries None -- and the arrays action [F] (int64,
     the number the frame's action directory is named by).  None (the default): no launch, no allocation, the bytes of the pass without
     the argument.
+    render=(directory, size, recordings, fps): pictures of the FINAL frames -- behind blend, filter and clamp.  After the figures, every
+    recording asked for (``recordings``: loader recording numbers, None for all; a number the loader does not have is refused) that has
+    a covered frame is drawn on the device (render.render_frames: ops.render_prims and ops.render_raster, twice per chunk of frames) from
+    what the pass holds in HBM -- the final frames, the targets, every frame's packed cloud and floor plane -- as ``size`` x 2 ``size``
+    images, the front view left and the side view right, in the body-fixed camera of render.camera, and written as an animated PNG of
+    ``fps`` frames per second, rec{recording:04d}_action{A}.png in ``directory`` (created; without the loader's rec_action_ the name
+    ends behind the number), the recording's frames in order, an uncovered frame showing the target alone.  The summary gains
+    rendered_recordings and rendered_frames; pred and every other array are untouched.  None (the default): no launch, no
+    allocation, no key.
     The figures come down in one read (the histograms of breakdown in one more); the per-frame arrays in one each."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
@@ -194,6 +227,7 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
                          "smooth filters the positions of the other spaces" % (blend_space,))
     floor = _check_floor(floor)
     breakdown = check_breakdown(breakdown)
+    render = _check_render(render)
     if blend_space == "rot" and floor is not None and floor[0] == "clamp":
         raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
                          "produce pred (with or without rot_smooth); \"measure\" goes with every space")
@@ -202,6 +236,10 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
         raise ValueError("breakdown: the loader has no rec_action_ / rec_snippet_ (a data.PosePC has); there is nothing to group by")
     if plan.W == 0:
         raise ValueError("dense inference: no recording of %s has %d frames, so there is no window to run" % (dataset.root, plan.T))
+    if render is not None:
+        plan.ground()                  # (the pictures need every frame's plane: a loader without one is refused here, ahead of the pass)
+    if render is not None and render[2] is not None and render[2][-1] >= len(plan.rec_off) - 1:
+        raise ValueError("render: recording %d is not one of the loader's %d" % (render[2][-1], len(plan.rec_off) - 1))
     nets = [n for n in (imu_net, upper_net, lower_net) if n is not None]
     was_training = [n.training for n in nets]
     for n in nets:
@@ -209,7 +247,7 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     try:
         return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size),
                            dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise,
-                                rot_smooth=rot_smooth, breakdown=breakdown))
+                                rot_smooth=rot_smooth, breakdown=breakdown, render=render))
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
@@ -518,6 +556,32 @@ def _host_arrays(cfg, plan, win, b, sm, cl, sets, floor, breakdown=None):
     return arrays
 
 
+def _render(plan, up, lo, render):
+    """The pictures of the final frames (up [F, 45], lo [F, 24], on the device), one animated PNG per recording asked for that has a
+    covered frame.  -> (recordings written, frames written)."""
+    directory, size, recs, fps = render
+    dev, F = plan.device, plan.F
+    os.makedirs(directory, exist_ok=True)
+    # the 21 joints of a frame from the two nets' rows, as _assemble lays them out (the lower rows own the shared hips): upper slots
+    # 0..11 are the joints 0..11, slot 14 is joint 20; the lower slots 0..7 are the joints 12..19
+    pred = _f32(dev, F, 63)
+    ops.copy2d(up[:, :36], pred[:, :36])
+    ops.copy2d(lo, pred[:, 36:60])
+    ops.copy2d(up[:, 42:45], pred[:, 60:63])
+    seg = torch.as_tensor(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32)).to(dev)
+    ground, cloud, tgt = plan.ground(), plan.src["data"].view(F, plan.pc_no, 6), plan.src["target"]
+    done = frames = 0
+    for r in (range(len(plan.rec_off) - 1) if recs is None else recs):
+        a, e = int(plan.rec_off[r]), int(plan.rec_off[r + 1])
+        if e == a or not (plan.covered[a:e] != 0).any():
+            continue
+        img = render_mod.render_frames(pred[a:e], tgt[a:e], ground[a:e], cloud[a:e], seg[a:e], size)
+        name = "rec%04d%s.png" % (r, "" if plan.rec_action is None else "_action%d" % plan.rec_action[r])
+        render_mod.write_apng(os.path.join(directory, name), img.cpu().numpy(), fps)
+        done, frames = done + 1, frames + (e - a)
+    return done, frames
+
+
 def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
     """dense_infer behind its argument checks: the nets are in eval mode.  opt: dense_infer's keywords from ``metrics`` on, by name."""
     space, smooth, floor, rot_smooth = opt["blend_space"], opt["smooth"], opt["floor"], opt["rot_smooth"]
@@ -538,6 +602,9 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
             sets.update({"": (sets[""][0], cl.lo), "unclamped_": sets[""]})
         arrays = _host_arrays(base.cfg, plan, win, b, sm, cl, sets, floor, opt.get("breakdown"))
         summary = _figures(plan, win, b, sm, cl, sets, seg, arrays, opt)
+        if opt.get("render") is not None:
+            done, frames = _render(plan, sets[""][0], sets[""][1], opt["render"])
+            summary.update(rendered_recordings=done, rendered_frames=frames)
     blocks.seq_xcd_raise()          # (the frozen IMU_Net's persistent launches: invalid head poses must not become a reported metric)
     return summary, arrays
 
@@ -610,6 +677,8 @@ def print_summary(s, opt, saved=None):
                 s["lifted_frames"], s["covered_frames"], s["lift_cm"], s["floor_fallback"], floor[2]))
     if opt.get("breakdown") is not None:
         print_breakdown(s)
+    if opt.get("render") is not None:
+        print("Rendered: {} recordings, {} frames -> {}".format(s["rendered_recordings"], s["rendered_frames"], opt["render"][0]))
 
 
 def saved_arrays(s, arrays, opt):

@@ -871,6 +871,82 @@ def floor_clamp(src, ground, seg, margin, dst, lifted=None, fallback=None):
     return dst
 
 
+RENDER_REC, RENDER_FIXED, RENDER_MAX_P = 12, 134, 1024        # render_math.h RD_REC, RD_FIXED, RD_MAX_P
+# (cos, sin)(2 pi k / 32) of the floor ring's 32 vertices, float64 rounded once: the table mmego_render_prims is handed
+RENDER_RING = np.stack([np.cos(2.0 * np.pi * np.arange(32) / 32.0), np.sin(2.0 * np.pi * np.arange(32) / 32.0)], axis=1).astype(np.float32)
+
+
+def render_prims(pred, tgt, ground, cloud, seg, cam, vmax, prims):
+    """prims [F, 134 + N, 12] = every frame's scene as 2-D primitives in layer order (mmego_render_prims; the layers are in the header):
+    pred and tgt [F, >= 63] the predicted and the recorded joints, ground [F, 4] the planes, cloud [F, N, 6] the radar returns (N in
+    [0, 890]), seg [F] int32 (a host array or a device tensor; < 0: the frame shows the target alone), cam [F, 8] the 2 x 4 affine of
+    every frame, vmax > 0 the Doppler velocity at which the cloud's colour saturates.  Everything is checked on the host first (ValueError)."""
+    who = "render_prims"
+    ldp = _floor_rows(pred, "pred", None, 63, None, who)
+    F, dev = pred.shape[0], pred.device
+    ldt = _floor_rows(tgt, "tgt", F, 63, dev, who)
+    _floor_rows(ground, "ground", F, 4, dev, who, packed=True)
+    _floor_rows(cam, "cam", F, 8, dev, who, packed=True)
+    if F >= 2 ** 31:
+        raise ValueError("%s: %d frames do not fit the launch" % (who, F))
+    if not (isinstance(cloud, torch.Tensor) and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.dim() == 3 and cloud.device == dev
+            and cloud.shape[0] == F and cloud.shape[2] == 6 and cloud.is_contiguous()):
+        raise ValueError("%s: cloud is a contiguous fp32 tensor [%d, N, 6] on the rows' device" % (who, F))
+    N = cloud.shape[1]
+    if not 0 <= N <= RENDER_MAX_P - RENDER_FIXED:
+        raise ValueError("%s: N = %d returns per frame lie outside [0, %d]" % (who, N, RENDER_MAX_P - RENDER_FIXED))
+    seg = _seg_on(seg, F, dev, who)
+    if isinstance(vmax, bool) or not isinstance(vmax, (int, float, np.integer, np.floating)) or not np.isfinite(vmax) or not vmax > 0:
+        raise ValueError("%s: vmax is a finite velocity > 0, got %r" % (who, vmax))
+    if not (isinstance(prims, torch.Tensor) and prims.is_cuda and prims.dtype == torch.float32 and prims.device == dev and prims.is_contiguous()
+            and tuple(prims.shape) == (F, RENDER_FIXED + N, RENDER_REC) and prims.data_ptr() % 16 == 0):
+        raise ValueError("%s: prims is a contiguous fp32 tensor [%d, %d, %d] on the rows' device, 16-byte aligned"
+                         % (who, F, RENDER_FIXED + N, RENDER_REC))
+    hip.call("render_prims", pred, ldp, tgt, ldt, ground, cloud if N else None, N, seg, cam, _upload_once(dev, RENDER_RING)[0], F, float(vmax),
+             prims)
+    return prims
+
+
+def render_raster(prims, out, bg=(255, 255, 255)):
+    """out [I, H, W, 3] (uint8) = the tables prims [I, P, 12] composited in index order over the background ``bg`` (mmego_render_raster;
+    the recipe is in the header).  out may be a VIEW of a larger frame -- unit stride along the channels, 3 along x, a row pitch and an
+    image stride that are multiples of 4 bytes -- so that two views share one frame; the bytes outside the view stay.  P in [0, 1024],
+    W and H in [16, 2048], W a multiple of 4.  Everything is checked on the host first (ValueError)."""
+    who = "render_raster"
+    if not (isinstance(prims, torch.Tensor) and prims.is_cuda and prims.dtype == torch.float32 and prims.dim() == 3):
+        raise ValueError("%s: prims is a 3-D fp32 device tensor" % who)
+    I, P = prims.shape[0], prims.shape[1]
+    if I < 1 or not 0 <= P <= RENDER_MAX_P or prims.shape[2] != RENDER_REC or not prims.is_contiguous():
+        raise ValueError("%s: prims is %s, wanted contiguous [I >= 1, P in [0, %d], %d]" % (who, tuple(prims.shape), RENDER_MAX_P, RENDER_REC))
+    if prims.data_ptr() % 16:
+        raise ValueError("%s: prims is not 16-byte aligned" % who)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 4 and out.device == prims.device):
+        raise ValueError("%s: out is a 4-D uint8 tensor on the primitives' device" % who)
+    if out.shape[0] != I or out.shape[3] != 3:
+        raise ValueError("%s: out is %s for %d images of 3-byte pixels" % (who, tuple(out.shape), I))
+    H, W = out.shape[1], out.shape[2]
+    if not (16 <= W <= 2048 and 16 <= H <= 2048) or W % 4:
+        raise ValueError("%s: W = %d and H = %d have to lie in [16, 2048], W a multiple of 4" % (who, W, H))
+    stride, pitch = out.stride(0) if I > 1 else max(out.stride(0), H * out.stride(1)), out.stride(1)
+    if out.stride(3) != 1 or out.stride(2) != 3:
+        raise ValueError("%s: out's pixels are 3 adjacent bytes, a row's pixels adjacent, got strides %s" % (who, tuple(out.stride())))
+    if pitch < 3 * W or pitch % 4:
+        raise ValueError("%s: the row pitch %d is below 3 W = %d or no multiple of 4" % (who, pitch, 3 * W))
+    if stride < H * pitch or stride % 4:
+        raise ValueError("%s: the image stride %d is below H x pitch = %d or no multiple of 4" % (who, stride, H * pitch))
+    if out.data_ptr() % 4:
+        raise ValueError("%s: out is not 4-byte aligned" % who)
+    if I * ((W + 31) // 32) * ((H + 31) // 32) >= 2 ** 31:
+        raise ValueError("%s: %d images of %d x %d pixels do not fit one launch" % (who, I, W, H))
+    if not (isinstance(bg, (tuple, list)) and len(bg) == 3
+            and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 255 for v in bg)):
+        raise ValueError("%s: bg is three integer levels in [0, 255], got %r" % (who, bg))
+    if P == 0:                                                     # (an empty tensor has no address; the ABI refuses a null pointer)
+        prims = _upload_once(prims.device, np.zeros((1, RENDER_REC), dtype=np.float32))[0]
+    hip.call("render_raster", prims, I, P, out, W, H, pitch, stride, int(bg[0]), int(bg[1]), int(bg[2]))
+    return out
+
+
 def fill(t, v):
     if not t.is_contiguous():
         raise ValueError("fill needs a contiguous tensor")

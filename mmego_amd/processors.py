@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import blocks, dense, hip, ops
-from .config import Config, ConfigDemo
+from .config import RENDER_FPS, RENDER_SIZE, Config, ConfigDemo
 from .data import DeviceArrays, FrameStore, PosePC, batch_indices
 from .dense import dense_infer
 from .evaluation import (BREAKDOWN_BINS, METRICS, PCK_THRESHOLDS_CM, Breakdown, _jitter_imu, _jitter_pose, aligned_summary, check_breakdown,
@@ -794,7 +794,8 @@ class Evaluator(_Base):
         self.model_IMU = self._load_imu()
         self.Upper_net = self._new_upper(cfg.model_upper_path).eval()           # (--upper_variant)
         # (--dense: the per-frame clouds stay; nothing else about the object depends on the keyword)
-        self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no, keep_frames=bool(getattr(cfg, "dense", False)))
+        self.vis_data = PosePC(train=False, vis=True, batch_length=self.frame_no,
+                               keep_frames=bool(getattr(cfg, "dense", False) or getattr(cfg, "vis", False)))
 
     def eval_dense(self):
         """`--infer --dense [--stride S --blend B --smooth H --rot_smooth H --save_pred PATH --batch_size N]`: dense_infer over the recordings, its figures printed
@@ -806,6 +807,8 @@ class Evaluator(_Base):
         opt = dict(metrics=self._metrics(), blend_space=getattr(cfg, "blend_space", None), smooth=getattr(cfg, "smooth", None),
                    floor=getattr(cfg, "floor", None), pose_noise=pose_noise_of(cfg), imu_noise=imu_noise_of(cfg),
                    rot_smooth=getattr(cfg, "rot_smooth", None), breakdown=BREAKDOWN_BINS if getattr(cfg, "breakdown", False) else None)
+        if getattr(cfg, "render", None) is not None:               # (the key only with --render: the pass without it is untouched)
+            opt["render"] = cfg.render
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, **opt)
         self.last_metrics = s
@@ -836,7 +839,18 @@ class Evaluator(_Base):
         return out
 
     def eval_all_skeleton(self):
-        raise NotImplementedError("--vis (matplotlib animation) is outside the hot path and not provided")
+        """`--infer --vis` (reference Demo_test.MMEgo.eval_all_skeleton, whose drawing routine its Utils.py does not define): the dense
+        pass at stride = frame_no with blend "mean" -- the reference's windows plus one head window per recording -- with every recording
+        drawn on the device into ./vis/<Idx>/ at --render's defaults; prints what that dense pass prints.  -> the summary."""
+        cfg = self.cfg
+        self.model.load(cfg.model_lower_path)
+        self.model.eval()
+        opt = dict(metrics=self._metrics(), blend_space=None, smooth=None, floor=None, pose_noise=None, imu_noise=None, rot_smooth=None,
+                   breakdown=None, render=(os.path.join(".", "vis", str(cfg.Idx)), RENDER_SIZE, None, RENDER_FPS))
+        s, _ = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, self.frame_no, blend="mean", batch_size=64, **opt)
+        self.last_metrics = s
+        dense.print_summary(s, opt)
+        return s
 
 
 class ImuTrainer(_Base):
