@@ -390,6 +390,44 @@ int mmego_smooth_bones(void* stream, const float* src, long lds, long F, int J, 
 int mmego_smooth_rot(void* stream, const float* src, long lds, long F, int J, const float* quat, int NB, const int* seg, const float* w,
                      int H, int D, const int* bones, const float* body, float* dst, long ldd, float* quat_out, float* moved,
                      float* rot_moved, int* fallback);
+/* Dense inference's CAUSAL filter along time (one_euro.hip; dense.dense_infer with one_euro=(fc, beta, dc)): the one-euro filter (Casiez
+ * et al. 2012), an exponential low-pass whose cutoff rises with the joint's own filtered speed.  It never reads a frame ahead of the one
+ * it writes.  Units are per frame: fc (finite, > 0) the minimum cutoff in cycles per frame, beta (finite, >= 0) how much a joint's speed
+ * in metres per frame raises the cutoff, in 1/metre, dc (finite, > 0) the cutoff of the speed estimate in cycles per frame.
+ * src [F][3 J] (row stride lds) holds rows of J 3-vectors.  The host cuts [0, F) into R RUNS: run_off [R + 1] (int64) ascends from 0 to F,
+ * run r owns the frames [run_off[r], run_off[r + 1]); run_on [R] (int32): 0 -- the run's rows are copied to dst bit for bit, moved 0 --
+ * or non-zero -- the run is filtered.  With alpha(c) = w / (w + 1), w = 2 pi c, per filtered run and joint j, x_i the joint's 3-vector
+ * at the run's frame i, all arithmetic in double, the state (xhat, dhat) kept in double across the frames and never re-read from dst:
+ *   i = 0:   xhat_0 = x_0 (the row is copied bit for bit), dhat_0 = 0, moved 0;
+ *   i >= 1:  d = x_i - xhat_{i-1};   dhat_i = dhat_{i-1} + alpha(dc) (d - dhat_{i-1});   s = |dhat_i|, the Euclidean norm of the three
+ *            components;   a = alpha(fc + beta s);   xhat_i = xhat_{i-1} + a d;
+ *   dst[f, 3 j + t] = (float) xhat_i[t], one store per word; the columns of dst[f] (row stride ldd) beyond 3 J are not touched;
+ *   moved[f] (may be NULL) = sqrt(sum_j |xhat_ij - x_ij|^2 / J), before the rounding: mmego_smooth_frames' definition.
+ * One cutoff per joint and frame, from the joint's speed: the result does not depend on the axes of the (moving) frame the joints live
+ * in, and a constant run comes back bit for bit (d = 0 leaves both states as they are).  Every multiply-add above is one fma.
+ * One wave per run, lane = joint; sequential along the run, the rows loaded 8 frames ahead of their use; no LDS, no atomics, a fixed
+ * order: two launches give the same bits.  Refused: a null src, run_off, run_on or dst, F < 1 or >= 2^31, J outside [1, 21], lds or ldd <
+ * 3 J, R outside [1, F], fc, beta or dc not finite or out of range, dst rows that overlap the src rows.  The caller answers for the runs
+ * partitioning [0, F) (ops.one_euro checks them on the host); the kernel clips a run to [0, F). */
+int mmego_one_euro(void* stream, const float* src, long lds, long F, int J, const long long* run_off, const int* run_on, int R, double fc,
+                   double beta, double dc, float* dst, long ldd, float* moved);
+/* The same filter with every bone's length kept (dense.dense_infer under blend_space="bones"): bones [NB][2] and bone_len [NB] are
+ * mmego_blend_bones' walk table and lengths.  A copy run, and a filtered run's first frame: the row bit for bit, moved 0, fallback 0.
+ * Per filtered run and frame i >= 1:
+ *   a root r:        the recursion above on its position: the same function, the same bits as mmego_one_euro gives that joint;
+ *   bone b = (c, p): the same recursion on v_i = x_ic - x_ip (the difference formed in double) with the state vhat (vhat_0 = v_0),
+ *                    dhat, the speed |dhat| of the vector; the state keeps the UNNORMALISED vhat;
+ *                    u = vhat_i / |vhat_i| where |vhat_i| > 1e-9 L_b, else -- the FALLBACK, counted in fallback[f] -- v_i / |v_i|, the
+ *                    frame's own direction, or the zero vector where that is zero too (the bone stays on its parent);
+ *                    pos_c = pos_p + L_b u, the bones taken in their listed order;
+ *   dst[f, 3 j + t] = (float) pos_j[t];   moved[f] (may be NULL) as above against pos;   fallback[f] (int32, may be NULL) = the number
+ *   of bones of the frame that took the fallback.
+ * Every filtered bone has length L_b up to the rounding of its two endpoints.  One wave per run, lane = joint, the parent's position
+ * handed over by wave shuffles.  Refused: as mmego_one_euro, and NB outside [0, J - 1], null bones or bone_len with NB > 0.  The caller
+ * answers for the bone list (ops.one_euro_bones checks it on the host); a bone that names a joint outside [0, J) is left out. */
+int mmego_one_euro_bones(void* stream, const float* src, long lds, long F, int J, const long long* run_off, const int* run_on, int R,
+                         double fc, double beta, double dc, const int* bones, const float* bone_len, int NB, float* dst, long ldd,
+                         float* moved, int* fallback);
 /* Dense inference's floor (floor.hip; dense.dense_infer with floor=(mode, contact_cm, margin_cm)).  Both kernels read rows of the 8
  * lower joints, [rows][24]: local joints 0..3 are the global joints 12..15, local 4..7 the global 16..19, so the legs are (hip, knee,
  * ankle, foot) = (0, 1, 2, 3) and (4, 5, 6, 7) and the feet local 3 and 7.  ground [rows][4] is every row's plane (a, b, c, d) in the

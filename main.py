@@ -7,6 +7,7 @@
   python main.py --infer --dense --smooth H [--smooth_order {0,1,2} --smooth_taper {box,gauss}]
   python main.py --infer --dense --blend_space rot --rot_smooth H [--rot_smooth_order {0,1,2} --rot_smooth_taper {box,gauss}]
   python main.py --infer --dense --floor {measure,clamp} [--floor_contact_cm H --floor_margin_cm M]
+  python main.py --infer --dense --online [--lookahead L] [--one_euro FC [--one_euro_beta B --one_euro_dcutoff DC]]
   python main.py --infer [--dense ...] --breakdown
   python main.py --infer --dense --render DIR [--render_size PX --render_recordings 0,3,7 --render_fps N]
 
@@ -69,7 +70,13 @@ by_recording_all_cm, error_hist and error_hist_bin_cm), --infer --dense --render
 --render_fps N] (the dense pass's FINAL frames -- behind blend, filter and clamp -- drawn on the device, one animated PNG per recording in
 DIR: predicted skeleton coloured by error over the recorded one, the radar returns coloured by Doppler, the floor ring and the skeleton's
 shadow on the recorded plane, front view left and side view right in a body-fixed camera; --infer --vis is that pass at the reference's
-windows, drawn into ./vis/<Idx>/).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
+windows, drawn into ./vis/<Idx>/), --infer --dense --online [--lookahead L] (what a running device could have answered L frames after
+the frame: every frame is blended from the windows that had ended by then alone, the first frame_no - 1 - L frames of a recording are
+the warm-up and count as uncovered, --stride defaults to min(L + 1, frame_no // 2); not with --smooth / --rot_smooth, which read ahead)
+and --infer --dense --one_euro FC [--one_euro_beta B --one_euro_dcutoff DC] (the one-euro filter along time on the device, where
+--smooth sits: a causal low-pass per joint of minimum cutoff FC cycles per frame, raised by B per metre per frame of the joint's own
+speed, the speed estimate's cutoff DC; of bone vectors under --blend_space bones; with or without --online, not with --smooth,
+--rot_smooth or --blend_space rot).  Under `python -m torch.distributed.run --nproc-per-node N main.py --train ...` training is
 data parallel (one rank per GPU, RCCL gradient all-reduce).
 """
 import argparse
@@ -260,6 +267,28 @@ def build_parser():
                    help="--rot_smooth: degree of the local polynomial (default 2; 0 is the weighted chordal mean)")
     p.add_argument("--rot_smooth_taper", type=str, choices=["box", "gauss"], default=None,
                    help="--rot_smooth: weights of the frames of the window -- box or gauss (default), as --smooth_taper")
+    p.add_argument("--online", action="store_true",
+                   help="--dense: what a running device could have answered -- frame f is blended from the windows that had ended by "
+                        "f + --lookahead alone.  The first frame_no - 1 - L frames of every recording are the warm-up (no full window yet) "
+                        "and count as uncovered; --stride defaults to min(L + 1, frame_no // 2) and may not exceed L + 1.  Not with "
+                        "--smooth or --rot_smooth (they read H frames ahead); --one_euro is the causal filter.  One 'Online' line in "
+                        "front of the counts; --save_pred's file gains online_lookahead")
+    p.add_argument("--lookahead", type=int, default=None, metavar="L",
+                   help="--online: the latency budget in frames, in [0, frame_no - 1] (default 0: a frame is answered by the one window "
+                        "that ends at it)")
+    p.add_argument("--one_euro", type=float, default=None, metavar="FC",
+                   help="--dense: the one-euro filter (Casiez et al. 2012) along time on the device, after the blend where --smooth sits "
+                        "-- a causal exponential low-pass per joint whose cutoff is FC + B |speed| cycles per frame, so it never reads a "
+                        "frame ahead; FC finite and > 0.  Under --blend_space bones every bone's vector is filtered and the body's bone "
+                        "lengths are kept.  Three more lines give the blended frames' error, the mean displacement and (--metrics full) "
+                        "the unsmoothed acceleration error; --save_pred's file gains pred_unsmoothed, moved, one_euro_cutoff, "
+                        "one_euro_beta, one_euro_dcutoff.  Not with --smooth, --rot_smooth or --blend_space rot")
+    p.add_argument("--one_euro_beta", type=float, default=None, metavar="B",
+                   help="--one_euro: how much a joint's speed in metres per frame raises the cutoff, in 1/metre, finite and >= 0 "
+                        "(default 0: a plain exponential filter)")
+    p.add_argument("--one_euro_dcutoff", type=float, default=None, metavar="DC",
+                   help="--one_euro: cutoff of the speed estimate in cycles per frame, finite and > 0 (default 0.1: the filter's usual "
+                        "1 Hz at the recordings' 10 frames per second)")
     p.add_argument("--floor", type=str, choices=["measure", "clamp"], default=None,
                    help="--dense: hold the saved feet against every frame's recorded floor plane (given in the frame of the frame's own "
                         "joints; it comes from the recording, as the head pose does under --gt_head_pose) and the recorded foot-contact "
@@ -336,6 +365,42 @@ def check_breakdown(parser, args):
         parser.error("--breakdown does not go with --network IMU_Net: stage 1 evaluates a head pose, there is no joint error to break down")
 
 
+def check_online(parser, args):
+    """--online [--lookahead L] and --one_euro FC [--one_euro_beta B --one_euro_dcutoff DC] are stages of --infer --dense."""
+    given = (["online"] if args.online else []) + [f for f in ("lookahead", "one_euro", "one_euro_beta", "one_euro_dcutoff")
+                                                     if getattr(args, f) is not None]
+    if given and not (args.dense and args.infer):
+        parser.error("--%s belongs to --infer --dense (sliding-window inference); without --dense nothing reads it" % given[0])
+    if args.lookahead is not None and not args.online:
+        parser.error("--lookahead belongs to --online: without --online every frame is blended from all its windows")
+    if args.lookahead is not None and not 0 <= args.lookahead <= Config.frame_no - 1:
+        parser.error("--lookahead is the latency budget in frames: it has to lie in [0, %d] (frame_no - 1; %d is the offline cover), got %d"
+                     % (Config.frame_no - 1, Config.frame_no - 1, args.lookahead))
+    for flag in ("one_euro_beta", "one_euro_dcutoff"):
+        if getattr(args, flag) is not None and args.one_euro is None:
+            parser.error("--%s belongs to --one_euro FC: without --one_euro nothing is filtered" % flag)
+    finite = lambda v: v == v and abs(v) != float("inf")
+    if args.one_euro is not None and not (finite(args.one_euro) and args.one_euro > 0.0):
+        parser.error("--one_euro is the filter's minimum cutoff in cycles per frame: finite and > 0, got %r" % args.one_euro)
+    if args.one_euro_beta is not None and not (finite(args.one_euro_beta) and args.one_euro_beta >= 0.0):
+        parser.error("--one_euro_beta is the speed coefficient in 1/metre: finite and >= 0, got %r" % args.one_euro_beta)
+    if args.one_euro_dcutoff is not None and not (finite(args.one_euro_dcutoff) and args.one_euro_dcutoff > 0.0):
+        parser.error("--one_euro_dcutoff is the speed estimate's cutoff in cycles per frame: finite and > 0, got %r" % args.one_euro_dcutoff)
+    for other in ("smooth", "rot_smooth"):
+        if args.online and getattr(args, other) is not None:
+            parser.error("--online does not go with --%s: that filter reads H frames ahead of the frame it writes, which is what --online "
+                         "promises not to do (--one_euro FC filters along time without looking ahead)" % other)
+        if args.one_euro is not None and getattr(args, other) is not None:
+            parser.error("--one_euro does not go with --%s: it sits where that filter sits, and one pass runs one filter along time" % other)
+    if args.one_euro is not None and args.blend_space == "rot":
+        parser.error("--one_euro does not go with --blend_space rot: the filter runs on joint positions, so the saved rotations would "
+                     "not be filtered with the positions (a causal filter of rotations is not provided)")
+    if args.online and args.stride is not None and args.stride > (args.lookahead or 0) + 1:
+        parser.error("--stride has to lie in [1, %d] under --online --lookahead %d: frame f is served by the windows that ended by f + %d, "
+                     "so a larger stride leaves frames between windows uncovered, got %d"
+                     % ((args.lookahead or 0) + 1, args.lookahead or 0, args.lookahead or 0, args.stride))
+
+
 def check_dense(parser, args):
     """--dense is a mode of --infer; --stride, --blend, --blend_space, --save_pred, the --smooth, --rot_smooth and --floor flags belong to it."""
     for flag in ("rot_smooth_order", "rot_smooth_taper"):
@@ -366,6 +431,7 @@ def check_dense(parser, args):
     if args.dense and args.blend_space == "rot" and args.smooth is not None:
         parser.error("--smooth does not go with --blend_space rot: the filter runs on joint positions, so the saved rotations would not "
                      "be filtered with the positions (--rot_smooth H filters the rotations and lays the positions along them)")
+    check_online(parser, args)
     if not args.dense:
         for flag in ("stride", "blend", "blend_space", "save_pred", "smooth", "smooth_order", "smooth_taper", "rot_smooth", "rot_smooth_order",
                      "rot_smooth_taper", "floor", "floor_contact_cm", "floor_margin_cm"):
@@ -663,6 +729,11 @@ def apply_overrides(args):
                                                                   args.rot_smooth_taper or "gauss")
     ConfigDemo.floor = None if args.floor is None else (args.floor, 6.0 if args.floor_contact_cm is None else args.floor_contact_cm,
                                                         0.0 if args.floor_margin_cm is None else args.floor_margin_cm)
+    ConfigDemo.online = (args.lookahead or 0) if args.online else None
+    if args.online and args.stride is None:          # (what a device with that budget has to compute)
+        ConfigDemo.stride = max(1, min(ConfigDemo.online + 1, Config.frame_no // 2))
+    ConfigDemo.one_euro = None if args.one_euro is None else (args.one_euro, 0.0 if args.one_euro_beta is None else args.one_euro_beta,
+                                                              0.1 if args.one_euro_dcutoff is None else args.one_euro_dcutoff)
     ConfigDemo.breakdown = bool(args.breakdown)
     ConfigDemo.vis = bool(args.vis)
     ConfigDemo.render = None if args.render is None else (

@@ -96,6 +96,8 @@ class ConfigDemo(_Common):
     blend_space = None          # --blend_space: joints, bones or rot (None: joints, without the bone-length figures)
     smooth = None               # --smooth H [--smooth_order D --smooth_taper T]: (H, D, T), the dense pass's temporal filter (None: off)
     rot_smooth = None           # --rot_smooth H [--rot_smooth_order D --rot_smooth_taper T]: (H, D, T), the filter of the blended rotations (None: off)
+    online = None               # --online [--lookahead L]: L, the latency budget in frames of the causal window cover (None: the offline cover)
+    one_euro = None             # --one_euro FC [--one_euro_beta B --one_euro_dcutoff DC]: (FC, B, DC), the dense pass's causal filter (None: off)
     floor = None                # --floor M [--floor_contact_cm H --floor_margin_cm C]: (M, H, C), the dense pass's floor figures / clamp (None: off)
     save_pred = None            # --save_pred: .npz of the per-frame skeletons
     dense_batch_size = None     # --batch_size under --dense: windows per minibatch (None: 64)

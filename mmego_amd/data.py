@@ -483,17 +483,32 @@ class DensePlan:
       row_frame [W T] int64: the global frame of window row w T + p
       cover     of frame f, as CSR: cov_off [F + 1] int64, cov_row [nnz] int32 (rows w T + p, ascending w within a frame), cov_w [nnz]
                 fp32 (blend "mean": 1; "triangle": min(p + 1, T - p), the window's middle counts most); covered [F] the counts.
-    Every frame of a recording of at least T frames is covered, at most ceil(T / S) + 1 times."""
+    Every frame of a recording of at least T frames is covered, at most ceil(T / S) + 1 times.
+    lookahead=L, an integer in [0, T - 1] (None, the default: every array as above): the CAUSAL cover of a device that may answer for
+    frame f no later than L frames after it.  The windows do not move (starts, recording, row_frame, W); window row r of window
+    w = r // T, whose last frame is e = starts[w] + T - 1, stays in the cover of frame f only where e <= f + L, and cov_off, cov_row,
+    cov_w, covered and max_cover are those of the rows that stay, the weights those of ``blend``.  L = T - 1 is the cover above, byte
+    for byte.  The first T - 1 - L frames of every recording of at least T frames are covered by nothing -- the WARM-UP, a device has
+    no full window yet -- and ``warmup`` counts them (0 without lookahead); every later frame is covered if and only if S <= L + 1, so
+    a larger stride is refused."""
 
-    def __init__(self, lengths, T, stride, blend="mean"):
+    def __init__(self, lengths, T, stride, blend="mean", lookahead=None):
         T, S = int(T), int(stride)
         if T < 1 or not 1 <= S <= T:
             raise ValueError("dense windows: the stride has to lie in [1, %d] (a larger one leaves frames between windows uncovered), got %r"
                              % (T, stride))
         if blend not in BLENDS:
             raise ValueError("blend: %r is not one of %s" % (blend, ", ".join(BLENDS)))
+        if lookahead is not None:
+            if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or not 0 <= lookahead <= T - 1:
+                raise ValueError("dense windows: lookahead is an integer number of frames in [0, %d], got %r" % (T - 1, lookahead))
+            if S > lookahead + 1:
+                raise ValueError("dense windows: under lookahead %d a frame is served by a window that ends at most %d frames after it, "
+                                 "so a stride above %d leaves frames between windows uncovered, got %d"
+                                 % (lookahead, lookahead, lookahead + 1, S))
+            lookahead = int(lookahead)
         lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
-        self.T, self.stride, self.blend = T, S, blend
+        self.T, self.stride, self.blend, self.lookahead = T, S, blend, lookahead
         self.F = F = int(lengths.sum())
         self.rec_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
         starts, recs = [], []
@@ -512,14 +527,17 @@ class DensePlan:
         if W * T >= 2 ** 31:
             raise ValueError("dense windows: %d window rows do not fit the cover's int32 row numbers" % (W * T))
         order = np.argsort(self.row_frame, kind="stable")           # rows by frame; within a frame in row order = ascending window
+        if lookahead is not None:                                   # the rows whose window had ended by their frame + L: position p >= T - 1 - L
+            order = order[order % T >= T - 1 - lookahead]
         self.cov_row = np.ascontiguousarray(order.astype(np.int32))
-        self.covered = np.bincount(self.row_frame, minlength=F).astype(np.int64)
+        self.covered = np.bincount(self.row_frame[order], minlength=F).astype(np.int64)
         self.cov_off = np.concatenate([[0], np.cumsum(self.covered)]).astype(np.int64)
         p = self.cov_row % T
         self.cov_w = (np.ones(len(p), np.float32) if blend == "mean" else np.minimum(p + 1, T - p).astype(np.float32))
         self.max_cover = int(self.covered.max()) if F else 0
         self.frame_rec = np.repeat(np.arange(len(lengths), dtype=np.int64), lengths)
         self.frame_in_recording = np.arange(F, dtype=np.int64) - self.rec_off[:-1][self.frame_rec]
+        self.warmup = 0 if lookahead is None else int((lengths >= T).sum()) * (T - 1 - lookahead)
 
 
 class DenseWindows(DensePlan):
@@ -529,7 +547,7 @@ class DenseWindows(DensePlan):
 
     FIELDS = DeviceArrays.FIELDS
 
-    def __init__(self, dataset, device, stride, blend="mean"):
+    def __init__(self, dataset, device, stride, blend="mean", lookahead=None):
         import torch
         if getattr(dataset, "frame_packed_", None) is None:
             raise ValueError("DenseWindows needs the per-frame clouds: build the PosePC with keep_frames=True")
@@ -537,7 +555,8 @@ class DenseWindows(DensePlan):
             raise ValueError("DenseWindows serves whole recordings: build the PosePC with train=False, vis=True")
         F = len(dataset.frame_npts_)
         nrec = int(dataset.frame_rec_.max()) + 1 if F else 0
-        super().__init__(np.bincount(np.asarray(dataset.frame_rec_, dtype=np.int64), minlength=nrec), dataset.frame_no, stride, blend)
+        super().__init__(np.bincount(np.asarray(dataset.frame_rec_, dtype=np.int64), minlength=nrec), dataset.frame_no, stride, blend,
+                         lookahead=lookahead)
         self.device, self.pc_no = device, int(dataset.pc_no)
         f32 = lambda a, rows: torch.as_tensor(np.ascontiguousarray(a).reshape(rows, -1), dtype=torch.float32).to(device)
         T = self.T

@@ -71,6 +71,29 @@ def _check_floor(floor):
     return mode, float(contact_cm), float(margin_cm)
 
 
+def _check_online(online, T=None):
+    """online = L of dense_infer, the latency budget in frames, or None.  -> a plain int (T given: held to [0, T - 1])."""
+    if online is None:
+        return None
+    if isinstance(online, bool) or not isinstance(online, (int, np.integer)) or online < 0 or (T is not None and online > T - 1):
+        raise ValueError("online: the lookahead is an integer number of frames in [0, frame_no - 1]%s, got %r"
+                         % ("" if T is None else " = [0, %d]" % (T - 1), online))
+    return int(online)
+
+
+def _check_one_euro(one_euro):
+    """one_euro = (fc, beta, dc) of dense_infer, or None.  -> the tuple in plain floats."""
+    if one_euro is None:
+        return None
+    if not (isinstance(one_euro, (tuple, list)) and len(one_euro) == 3):
+        raise ValueError("one_euro: (fc, beta, dc), got %r" % (one_euro,))
+    for name, v, low in (("fc (the minimum cutoff in cycles per frame)", one_euro[0], "> 0"), ("beta", one_euro[1], ">= 0"),
+                         ("dc (the speed estimate's cutoff in cycles per frame)", one_euro[2], "> 0")):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (v == 0 and low == "> 0"):
+            raise ValueError("one_euro: %s is a finite number %s, got %r" % (name, low, v))
+    return tuple(float(v) for v in one_euro)
+
+
 def _check_render(render):
     """render = (directory, size, recordings_or_None, fps) of dense_infer, or None.  -> the tuple with plain values, the recordings a
     sorted tuple of distinct loader recording numbers."""
@@ -117,7 +140,8 @@ def _floor_summary(sums, n, prefix="", target=False):
 
 
 def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mean", batch_size=64, metrics="reference", blend_space=None,
-                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None, breakdown=None, render=None):
+                pose_noise=None, imu_noise=None, smooth=None, floor=None, rot_smooth=None, breakdown=None, render=None, online=None,
+                one_euro=None):
     """Sliding-window inference over whole recordings (not in the reference): IMU -> Upper -> Lower over the overlapping windows of
     data.DenseWindows(dataset, stride, blend), in minibatches of ``batch_size`` windows exactly as _epoch_eval runs one (eval mode, no
     grad), every window's rows kept on the device; then every frame's pose is the weighted mean of the rows that cover it
@@ -212,6 +236,23 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     ends behind the number), the recording's frames in order, an uncovered frame showing the target alone.  The summary gains
     rendered_recordings and rendered_frames; pred and every other array are untouched.  None (the default): no launch, no
     allocation, no key.
+    online=L, an integer in [0, frame_no - 1]: what a RUNNING device could have answered L frames after the frame.  Frame f is blended
+    from the windows that had ended by f + L alone (data.DensePlan's lookahead: the windows and every launch are those of the offline
+    pass, only the cover is filtered; L = frame_no - 1 is the offline cover).  The first frame_no - 1 - L frames of every recording of
+    at least frame_no frames are the WARM-UP, covered by nothing: they count as uncovered everywhere -- covered 0, pred NaN, segment
+    -1, in no mean.  stride > L + 1 would leave later frames uncovered and is refused (ValueError), and so are smooth and rot_smooth,
+    which read H frames ahead.  Everything else goes with it.  The summary gains online and warmup_frames.  None (the default): no
+    key, the bytes of the pass without the argument.
+    one_euro=(fc, beta, dc): the CAUSAL filter along time, where smooth sits -- behind the blend, in front of the floor clamp -- over
+    every maximal stretch of covered frames of one recording (ops.one_euro_runs of the segments; ops.one_euro, under
+    blend_space="bones" ops.one_euro_bones with the walk tables and bone lengths of the blend, so the frames stay rigid): the one-euro
+    filter per joint, xhat_i = xhat_{i-1} + alpha(fc + beta |dhat_i|) (x_i - xhat_{i-1}) with dhat the filtered speed (cutoff dc) and
+    alpha(c) = 2 pi c / (2 pi c + 1), all per frame; a stretch's first frame keeps its bytes, uncovered frames take no part.  It works
+    with or without online and is refused with smooth, with rot_smooth and under blend_space="rot" (ValueError).  Everything above then
+    runs on the filtered frames, and the blended frames keep their figures under unsmoothed_ exactly as under smooth (with
+    unsmoothed_accel_cm under metrics="full"); the summary gains moved_cm, one_euro itself and one_euro_fallback, the bones that took
+    their own frame's direction (0 in the column form); the arrays gain pred_unsmoothed [F, 21, 3] and moved [F].  None (the default):
+    no launch, no allocation, no key, the bytes of the pass without the argument.
     The figures come down in one read (the histograms of breakdown in one more); the per-frame arrays in one each."""
     if metrics not in METRICS:
         raise ValueError("metrics: %r is not one of %s" % (metrics, ", ".join(METRICS)))
@@ -228,10 +269,24 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     floor = _check_floor(floor)
     breakdown = check_breakdown(breakdown)
     render = _check_render(render)
+    online, one_euro = _check_online(online, getattr(dataset, "frame_no", None)), _check_one_euro(one_euro)
+    for name, given in (("smooth", smooth), ("rot_smooth", rot_smooth)):
+        if online is not None and given is not None:
+            raise ValueError("online: %s reads H frames ahead of the frame it writes, which is what online promises not to do; "
+                             "one_euro filters along time without looking ahead" % name)
+        if one_euro is not None and given is not None:
+            raise ValueError("one_euro: it sits where %s sits, and one pass runs one filter along time" % name)
+    if one_euro is not None and blend_space == "rot":
+        raise ValueError("one_euro: the filter runs on joint positions, so under blend_space=\"rot\" the saved rotations would not be "
+                         "filtered with them (a causal filter of rotations is not provided)")
+    if online is not None and int(stride) > online + 1:
+        raise ValueError("online: frame f is served by the windows that ended by f + %d, so a stride above %d leaves frames between "
+                         "windows uncovered, got %r" % (online, online + 1, stride))
     if blend_space == "rot" and floor is not None and floor[0] == "clamp":
         raise ValueError("floor: the clamp moves joint positions, so under blend_space=\"rot\" the saved rotations would no longer "
                          "produce pred (with or without rot_smooth); \"measure\" goes with every space")
-    plan = DenseWindows(dataset, base.device, stride, blend)
+    plan = DenseWindows(dataset, base.device, stride, blend) if online is None else DenseWindows(dataset, base.device, stride, blend,
+                                                                                                 lookahead=online)
     if breakdown is not None and plan.rec_action is None:
         raise ValueError("breakdown: the loader has no rec_action_ / rec_snippet_ (a data.PosePC has); there is nothing to group by")
     if plan.W == 0:
@@ -245,9 +300,13 @@ def dense_infer(base, imu_net, upper_net, lower_net, dataset, stride, blend="mea
     for n in nets:
         n.eval()
     try:
-        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size),
-                           dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise,
-                                rot_smooth=rot_smooth, breakdown=breakdown, render=render))
+        opt = dict(metrics=metrics, blend_space=blend_space, smooth=smooth, floor=floor, pose_noise=pose_noise, imu_noise=imu_noise,
+                   rot_smooth=rot_smooth, breakdown=breakdown, render=render)
+        if online is not None:
+            opt["online"] = online
+        if one_euro is not None:
+            opt["one_euro"] = one_euro
+        return _dense_pass(base, plan, imu_net, upper_net, lower_net, int(batch_size), opt)
     finally:
         for n, tr in zip(nets, was_training):
             n.train(tr)
@@ -334,6 +393,21 @@ def _smooth(up, lo, seg, smooth, lengths):
     else:
         ops.smooth_frames(up, seg, wts, order, s.up, s.moved)
         ops.smooth_frames(lo, seg, wts, order, s.lo)
+    return s
+
+
+def _one_euro(up, lo, plan, one_euro, lengths):
+    """The causal filter along time.  -> up, lo, moved [F], fell ([2, F] int32 in the bones form, ``lengths`` given; else None)."""
+    (fc, beta, dc), dev, F = one_euro, up.device, up.shape[0]
+    runs = ops.one_euro_runs(np.where(plan.covered != 0, plan.frame_rec, -1).astype(np.int32))
+    s = types.SimpleNamespace(up=_f32(dev, F, 45), lo=_f32(dev, F, 24), moved=_f32(dev, F), rot_moved=None, one_euro=True,
+                              fell=None if lengths is None else torch.zeros((2, F), dtype=torch.int32, device=dev))
+    if lengths is not None:
+        ops.one_euro_bones(up, runs, fc, beta, dc, skeleton.WALK_UPPER, lengths[0], s.up, s.moved, s.fell[0])
+        ops.one_euro_bones(lo, runs, fc, beta, dc, skeleton.WALK_LOWER, lengths[1], s.lo, None, s.fell[1])
+    else:
+        ops.one_euro(up, runs, fc, beta, dc, s.up, s.moved)
+        ops.one_euro(lo, runs, fc, beta, dc, s.lo)
     return s
 
 
@@ -474,6 +548,8 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
     s.update(_error_summary(out[row["single"], :43], W * T, "single_"))
     s.update(position_cm=out[row["position"], :21].mean(axis=1) / W * 100, spread_cm=float(out[row["spread"], 0]) / Fc * 100, windows=W,
              frames=F, covered_frames=Fc, max_cover=plan.max_cover, stride=plan.stride, blend=plan.blend, frame_no=T)
+    if opt.get("online") is not None:
+        s.update(online=opt["online"], warmup_frames=plan.warmup)
     if space is not None:
         s.update(bone_dev_cm=float(out[row["bone_dev"], :20].mean()) / Fc * 100,
                  single_bone_dev_cm=float(out[row["single_bone_dev"], :20].mean()) / (W * T) * 100,
@@ -483,7 +559,9 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
     if sm is not None:
         s.update(_error_summary(out[row["unsmoothed"], :43], Fc, "unsmoothed_"), moved_cm=float(out[row["moved"], 0]) / Fc * 100)
         fell = 0 if sm.fell is None else int(sm.fell.cpu().numpy().sum())
-        if sm.rot_moved is None:
+        if getattr(sm, "one_euro", False):
+            s.update(one_euro=opt["one_euro"], one_euro_fallback=fell)
+        elif sm.rot_moved is None:
             s.update(smooth=opt["smooth"], smooth_fallback=fell)
         else:
             s.update(rot_moved_deg=float(np.degrees(out[row["moved"], 1] / Fc)), rot_smooth=opt["rot_smooth"], rot_smooth_fallback=fell,
@@ -499,7 +577,8 @@ def _figures(plan, win, b, sm, cl, sets, seg, arrays, opt):
         s.update(lift_cm=float(lifted[lifted > 0].astype(np.float64).mean()) * 100 if (lifted > 0).any() else None,
                  lifted_frames=int((lifted > 0).sum()), floor_fallback=int(arrays["floor_fallback"].sum()))
     if full:
-        spans = [(a, e) for a, e in zip(plan.rec_off[:-1], plan.rec_off[1:]) if e - a >= T]      # the covered recordings, whole
+        warm = 0 if opt.get("online") is None else T - 1 - opt["online"]                         # (online: behind the warm-up)
+        spans = [(a + warm, e) for a, e in zip(plan.rec_off[:-1], plan.rec_off[1:]) if e - a >= T]      # the covered recordings, whole
         s.update(aligned_summary(np.concatenate([alog.cpu().numpy().astype(np.float64) / Fc, np.full(21, np.nan)])[None], 21))
         for prefix, (up, lo) in sets.items():                      # (accel_cm: per recording, not per minibatch)
             s[prefix + "accel_cm"] = _accel_cm(up, lo, tgt_f, spans)
@@ -597,6 +676,9 @@ def _dense_pass(base, plan, imu_net, upper_net, lower_net, batch_size, opt):
         if rot_smooth is not None:                                 # (never both: smooth is refused under "rot", rot_smooth elsewhere)
             sm = _smooth_rot(b, seg, rot_smooth)
             sets = {"": (sm.up, sm.lo), "unsmoothed_": sets[""]}
+        if opt.get("one_euro") is not None:                        # (refused with either filter above)
+            sm = _one_euro(b.up, b.lo, plan, opt["one_euro"], b.lengths if space == "bones" else None)
+            sets = {"": (sm.up, sm.lo), "unsmoothed_": sets[""]}
         if floor is not None and floor[0] == "clamp":
             cl = _clamp(sets[""][1], plan.floor()[0], seg, floor[2] / 100.0)
             sets.update({"": (sets[""][0], cl.lo), "unclamped_": sets[""]})
@@ -624,7 +706,7 @@ def foot_heights(feet, ground, covered):
 def print_summary(s, opt, saved=None):
     """What `--infer --dense` prints: the reference's five lines first; ``saved``: where the per-frame skeletons were written."""
     space, smooth, floor, full = opt["blend_space"], opt["smooth"], opt["floor"], opt["metrics"] == "full"
-    rot_smooth = opt.get("rot_smooth")
+    rot_smooth, online, one_euro = opt.get("rot_smooth"), opt.get("online"), opt.get("one_euro")
     print_reference(s)
     print("Single-window (unblended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
         s["single_all_cm"], s["single_upper_cm"], s["single_lower_cm"], s["single_rot_deg"]))
@@ -635,8 +717,12 @@ def print_summary(s, opt, saved=None):
             s["bone_dev_cm"], s["single_bone_dev_cm"], s["degenerate_bones"]))
     if space == "rot":
         print("Window Rotational Disagreement(°): {}".format(s["rot_spread_deg"]))
-    print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}".format(
-        s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"]))
+    if online is not None:
+        print("Online: lookahead {} frames (frame f from the windows that ended by f + {}), warm-up frames {}".format(
+            s["online"], s["online"], s["warmup_frames"]))
+    print("Dense windows: {} windows of {} frames at stride {} (blend {}), {} of {} frames covered, largest cover {}{}".format(
+        s["windows"], s["frame_no"], s["stride"], s["blend"], s["covered_frames"], s["frames"], s["max_cover"],
+        "" if online is None else ", lookahead {}, warm-up frames {}".format(s["online"], s["warmup_frames"])))
     if full:
         print_aligned(s)
         print("Single-window Acceleration Error(cm/frame^2): {}".format(s["single_accel_cm"]))
@@ -679,6 +765,13 @@ def print_summary(s, opt, saved=None):
         print_breakdown(s)
     if opt.get("render") is not None:
         print("Rendered: {} recordings, {} frames -> {}".format(s["rendered_recordings"], s["rendered_frames"], opt["render"][0]))
+    if one_euro is not None:
+        print("Unsmoothed (blended) Error(cm): all {} upper {} lower {} rotation(°) {}".format(
+            s["unsmoothed_all_cm"], s["unsmoothed_upper_cm"], s["unsmoothed_lower_cm"], s["unsmoothed_rot_deg"]))
+        print("One-Euro Filter: displacement(cm) {} (min cutoff {} beta {} speed cutoff {} per frame; degenerate bones {})".format(
+            s["moved_cm"], s["one_euro"][0], s["one_euro"][1], s["one_euro"][2], s["one_euro_fallback"]))
+        if full:
+            print("Unsmoothed Acceleration Error(cm/frame^2): {}".format(s["unsmoothed_accel_cm"]))
 
 
 def saved_arrays(s, arrays, opt):
@@ -706,6 +799,12 @@ def saved_arrays(s, arrays, opt):
         d.update(pose_noise_deg=np.float64(deg), pose_noise_t=np.float64(t), pose_noise_seed=np.int64(seed))
     if opt["imu_noise"] is not None:
         d.update({flag: np.float64(v) for flag, v in zip(IMU_NOISE_FLAGS, opt["imu_noise"][0])}, imu_noise_seed=np.int64(opt["imu_noise"][1]))
+    if opt.get("online") is not None:
+        d["online_lookahead"] = np.int64(opt["online"])
+    if opt.get("one_euro") is not None:
+        fc, beta, dc = opt["one_euro"]
+        d.update(keep("pred_unsmoothed", "moved"), one_euro_cutoff=np.float64(fc), one_euro_beta=np.float64(beta),
+                 one_euro_dcutoff=np.float64(dc))
     if opt.get("breakdown") is not None:
         a, r = s["by_action"], s["by_recording"]
         nan = lambda x: np.asarray([np.nan if v is None else v for v in x], dtype=np.float64)

@@ -809,6 +809,78 @@ def smooth_rot(src, quat, seg, weights, order, walk, body, dst, quat_out, moved=
     return dst
 
 
+def one_euro_runs(seg):
+    """The runs of the causal filter from the host int32 ``seg`` [F] (a frame's segment, -1: none): the maximal stretches of consecutive
+    frames with the same segment, which partition [0, F).  -> (run_off [R + 1] int64 ascending from 0 to F, run_on [R] int32: 1 where the
+    run's segment is >= 0 -- it is filtered --, 0 where it is an uncovered stretch -- its rows are copied)."""
+    seg = np.asarray(seg)
+    if seg.dtype != np.int32 or seg.ndim != 1 or len(seg) < 1:
+        raise ValueError("one_euro_runs: seg is one int32 per frame, at least one, got %s %s" % (seg.dtype, seg.shape))
+    first = np.concatenate([[0], np.flatnonzero(seg[1:] != seg[:-1]) + 1]).astype(np.int64)
+    return np.concatenate([first, [len(seg)]]).astype(np.int64), (seg[first] >= 0).astype(np.int32)
+
+
+def _one_euro_on(src, runs, fc, beta, dc, dst, moved, who):
+    """What the two causal-filter launches share, checked on the HOST: src [F, 3 J] and dst [F, >= 3 J] row tensors that share no byte;
+    runs = (run_off, run_on), host arrays as one_euro_runs returns them -- run_off int64 ascending from 0 to F with every run at least
+    one frame, run_on int32 one per run; fc finite > 0, beta finite >= 0, dc finite > 0; moved (optional): one contiguous float per
+    frame.  -> (run_off, run_on on the device, R, fc, beta, dc, F, C, lds, ldd)."""
+    if not (isinstance(src, torch.Tensor) and isinstance(dst, torch.Tensor) and src.is_cuda and dst.is_cuda and src.dtype == torch.float32
+            and dst.dtype == torch.float32 and src.device == dst.device):
+        raise ValueError("%s: src and dst are fp32 tensors on one device" % who)
+    if src.dim() != 2 or dst.dim() != 2 or src.stride(1) != 1 or dst.stride(1) != 1:
+        raise ValueError("%s: src and dst are row tensors with unit column stride, got %s and %s" % (who, tuple(src.shape), tuple(dst.shape)))
+    F, C = src.shape
+    if F < 1 or C % 3 or not 1 <= C // 3 <= BONES_MAX_J or (F > 1 and src.stride(0) < C):
+        raise ValueError("%s needs a source of at least one row of 1 to %d 3-vectors, got %s" % (who, BONES_MAX_J, tuple(src.shape)))
+    if dst.shape[0] != F or dst.shape[1] < C or (F > 1 and dst.stride(0) < C):
+        raise ValueError("%s: dst is %s for %d frames of %d columns" % (who, tuple(dst.shape), F, C))
+    lds, ldd = max(src.stride(0), C), max(dst.stride(0), C)
+    if _rows_overlap(src, lds, dst, ldd, F, C):
+        raise ValueError("%s: dst overlaps src; the filter reads rows ahead of the one it writes and cannot run in place" % who)
+    if not (isinstance(runs, (tuple, list)) and len(runs) == 2):
+        raise ValueError("%s: runs is (run_off, run_on), as one_euro_runs returns them" % who)
+    off, on = (np.asarray(a) for a in runs)
+    if off.dtype != np.int64 or on.dtype != np.int32 or off.ndim != 1 or on.ndim != 1 or len(off) != len(on) + 1 or len(on) < 1:
+        raise ValueError("%s: run_off is [R + 1] int64 and run_on [R] int32 with R >= 1, got %s %s and %s %s"
+                         % (who, off.dtype, off.shape, on.dtype, on.shape))
+    if off[0] != 0 or off[-1] != F or (np.diff(off) < 1).any():
+        raise ValueError("%s: run_off does not ascend from 0 to the %d frames with every run at least one frame" % (who, F))
+    par = []
+    for name, v, low in (("fc (the minimum cutoff)", fc, "> 0"), ("beta", beta, ">= 0"), ("dc (the speed estimate's cutoff)", dc, "> 0")):
+        ok = not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if not ok or v < 0 or (v == 0 and low == "> 0"):
+            raise ValueError("%s: %s is a finite number %s, got %r" % (who, name, low, v))
+        par.append(float(v))
+    _per_row(moved, "moved", F, torch.float32, src.device, who)
+    off_d, on_d = _upload_once(src.device, np.ascontiguousarray(off), np.ascontiguousarray(on))
+    return (off_d, on_d, len(on)) + tuple(par) + (F, C, lds, ldd)
+
+
+def one_euro(src, runs, fc, beta, dc, dst, moved=None):
+    """dst[f, :3 J] = the one-euro filter of the rows of src [F, 3 J] (J <= 21 3-vectors a row) along the frames (mmego_one_euro; the
+    recipe is in the header): a causal exponential low-pass per joint whose cutoff is fc + beta |dhat| cycles per frame, dhat the
+    joint's own filtered speed (cutoff dc); frame f's row depends on no later frame.  ``runs`` = (run_off, run_on) from one_euro_runs:
+    every filtered run starts from its own first frame, whose row is kept bit for bit, and a copy run keeps all its rows.  moved [F]
+    (optional): the RMS distance over the joints between the filtered and the source row.  Everything is checked on the host first
+    (ValueError); dst must not overlap src, and may be wider than 3 J: its other columns stay."""
+    off, on, R, fc, beta, dc, F, C, lds, ldd = _one_euro_on(src, runs, fc, beta, dc, dst, moved, "one_euro")
+    hip.call("one_euro", src, lds, F, C // 3, off, on, R, fc, beta, dc, dst, ldd, moved)
+    return dst
+
+
+def one_euro_bones(src, runs, fc, beta, dc, walk, lengths, dst, moved=None, fallback=None):
+    """The same filter for rows of rigid skeletons (mmego_one_euro_bones): the roots filtered as one_euro filters them, every bone's
+    vector child - parent filtered by the same recursion, set to ``lengths`` and laid along ``walk`` ([NB, 2] host integers (child,
+    parent), parents first; checked as blend_bones checks them) -- the filtered frames are rigid skeletons again.  fallback [F] int32
+    (optional): the bones per frame whose filtered vector vanished and that took the frame's own direction."""
+    off, on, R, fc, beta, dc, F, C, lds, ldd = _one_euro_on(src, runs, fc, beta, dc, dst, moved, "one_euro_bones")
+    bd, ld, NB = _bones_on(walk, lengths, C // 3, src.device, "one_euro_bones")
+    _per_row(fallback, "fallback", F, torch.int32, src.device, "one_euro_bones")
+    hip.call("one_euro_bones", src, lds, F, C // 3, off, on, R, fc, beta, dc, bd, ld, NB, dst, ldd, moved, fallback)
+    return dst
+
+
 def _floor_rows(t, name, rows, C, device, who, packed=False):
     """One row tensor of the floor launches, checked on the HOST: an fp32 device tensor [rows, >= C] on ``device`` with unit column
     stride and a row stride of at least its width (``packed``: exactly [rows, C], contiguous).  -> its row stride."""

@@ -809,6 +809,9 @@ class Evaluator(_Base):
                    rot_smooth=getattr(cfg, "rot_smooth", None), breakdown=BREAKDOWN_BINS if getattr(cfg, "breakdown", False) else None)
         if getattr(cfg, "render", None) is not None:               # (the key only with --render: the pass without it is untouched)
             opt["render"] = cfg.render
+        for key in ("online", "one_euro"):                         # (likewise)
+            if getattr(cfg, key, None) is not None:
+                opt[key] = getattr(cfg, key)
         s, arrays = dense_infer(self, self.model_IMU, self.Upper_net, self.model, self.vis_data, stride, blend=cfg.blend,
                                 batch_size=getattr(cfg, "dense_batch_size", None) or 64, **opt)
         self.last_metrics = s
